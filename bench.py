@@ -10,10 +10,14 @@ station table (tiles partition embarrassingly): weak scaling, no d
 ``python -m torch.distributed.run``, spawned before this process touches the GPU) and relays rank 0's line;
 under torchrun (WORLD_SIZE set) it is a rank.
 
-Rank 0 prints ONE JSON line (contract in the task description) carrying
+Rank 0 prints ONE JSON line carrying metric / value / unit / n_gpus / steps / warmup / ms_per_step /
+higher_is_better / scaling / vs_baseline / dtype / data / config and
   roofline      dominant kernels = the universal-kriging launches, HIP-event timed inside the library on the
-                launch stream; HBM as BASELINE.json asks, the binding fp64-vector figure next to it (``fp64``:
-                nominal = SURVEY 8d's flops, executed = factorisation + border only)
+                launch stream during the timed steps; HBM as BASELINE.json asks, the binding fp64-vector figure next
+                to it (``fp64``: nominal = SURVEY 8d's flops, executed = factorisation + border only)
+A plain run does only that: set-up, warm-up, the timed steps, ``--dump-outputs`` if given, the line.  With ``--full``
+the line also carries the records below (each a run of its own after the headline) and the oracle spot check of
+``--scaling strong``:
   daily         (N = 1) the cell-DAY producing path, timed the same way: the same tile, Tmin + Tmax, normals +
                 GWR + 10 years of daily int16 values + Tmin>=Tmax fixer, outputs resident in HBM
   configs       (N = 1) the other BASELINE.json configurations, driver-timed in the same run: ``c4_tile`` (the
@@ -26,6 +30,11 @@ Rank 0 prints ONE JSON line (contract in the task description) carrying
                 daily (streamed) path -- every rank streams its tiles' int16 days to pinned host memory, no gather
   cpu_baseline  (N = 1) the CPU oracle on bounded samples of the headline workload: all host cores (>= 64 cells
                 per thread) and one core
+
+``--dump-outputs DIR`` writes what the timed path handed its caller in its last timed step as DIR/<name>.npy (float32;
+integer arrays as float64, exactly): norm_tmin / se_tmin / ninvalid / status of rank 0's tile, or the gathered mosaic of
+``--scaling strong``.  Inputs are pure functions of the arguments (seeded generators), so two builds run with the same
+arguments can be compared output for output.
 """
 import argparse
 import glob
@@ -76,8 +85,13 @@ def uk_flops_distance(k):
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also the records beyond the headline (daily, cpu_baseline + parity, configs, the strong record of "
+                         "N > 1, the oracle spot check of --scaling strong); the --no-* / record options below apply to them")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (at most 64 MB in all)")
     ap.add_argument("--size", type=int, default=250, help="tile edge in cells (default: the C2 tile)")
     ap.add_argument("--nstns", type=int, default=10000)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -118,7 +132,29 @@ def parse():
     ap.add_argument("--strong-daily-cols", type=int, default=1000)
     ap.add_argument("--strong-daily-years", type=int, default=3)
     ap.add_argument("--dump-mosaic", default=None, help="strong mode: rank 0 writes the gathered mosaic here (.npz)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, arrays, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: ``arrays`` ({name: host array}) as ``out_dir/<name>.npy``, float32 (integer arrays as float64, which
+    holds every int32 exactly).  When they would exceed ``max_bytes`` in all, every array is replaced by the same share of
+    its elements: a fixed, seeded sample of flat indices (sorted; the same indices for arrays of the same size), 1-D."""
+    os.makedirs(out_dir, exist_ok=True)
+    conv = {k: np.asarray(v, np.float64 if np.issubdtype(np.asarray(v).dtype, np.integer) else np.float32) for k, v in arrays.items()}
+    budget = max_bytes - 4096 * len(conv)                        # (room for the .npy headers)
+    total = sum(a.nbytes for a in conv.values())
+    for k, a in conv.items():
+        if total > budget:
+            n = max(1, int(a.size * (budget / float(total))))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))
+            a = a.ravel()[idx]
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def spawn(args):
@@ -377,7 +413,7 @@ def shared_stations(env, key, build):
 # =====================================================================================================================
 # the tile farm of topowx_amd.driver on ONE fixed masked grid (strong scaling; at N = 1 the c3 / c3_strip records)
 # =====================================================================================================================
-def strip_run(env, args, steps, warmup, spot_check, full=False, fitted=False):
+def strip_run(env, args, steps, warmup, spot_check, full=False, fitted=False, dump_dir=None):
     """BASELINE.json configs[2] shape on a strip of the seed-7 masked CONUS-shaped grid: Tmin + Tmax normals + SE of
     every valid cell, tiles dealt to the ranks with driver.assign_tiles (LPT), every rank's tiles computed device-
     resident into the send buffer of ONE dist.gather (RCCL over xGMI) that assembles the four mosaics on rank 0.
@@ -472,6 +508,8 @@ def strip_run(env, args, steps, warmup, spot_check, full=False, fitted=False):
         rec["note"] = "systems counted in an untimed pass of their own; the timed pass is the code path of configs.c3"
     if env.rank == 0 and args.dump_mosaic:
         np.savez(args.dump_mosaic, **{k: v.cpu().numpy() for k, v in state["mosaic"].items()})
+    if env.rank == 0 and dump_dir:
+        dump_outputs(dump_dir, {k: v.cpu().numpy() for k, v in state["mosaic"].items()})
     if env.rank == 0 and spot_check and not args.no_cpu_baseline:
         # a 6x6 window of valid cells of the mosaic against the oracle
         from oracle import pyoracle as orc
@@ -934,7 +972,7 @@ def main():
     top_strong = scaling == "strong"
 
     if top_strong:
-        rec = strip_run(env, args, args.steps, args.warmup, spot_check=world == 1)
+        rec = strip_run(env, args, args.steps, args.warmup, spot_check=world == 1 and args.full, dump_dir=args.dump_outputs)
         if rank == 0:
             res = {"metric": "grid-cell-days interpolated/sec", "value": rec["value"],
                    "unit": "cell-months/s (normals config: one time step = one calendar month, mean + SE)",
@@ -992,6 +1030,9 @@ def main():
     ncell_ok = int((status == 0).sum())
     units_per_step = ncell_ok * 12                     # (cell, month) outputs, each mean + SE
     value = world * units_per_step * args.steps / elapsed
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"norm_tmin": d_norm.cpu().numpy(), "se_tmin": d_se.cpu().numpy(),
+                                         "ninvalid": d_ninv.cpu().numpy(), "status": status})
 
     # ---- roofline of the dominant kernels (universal kriging) ---------------------------------
     uk_ms = float(np.mean([t["uk_ms"] for t in kern]))
@@ -1060,7 +1101,7 @@ def main():
 
     import datetime as dt
     # ---- daily record: the path that produces cell-DAYS (N = 1) --------------------------------------
-    if world == 1 and not args.no_daily:
+    if args.full and world == 1 and not args.no_daily:
         res["daily"] = daily_record(env, args, base, grid, g, d_ninv, d_stat, dt.date(args.daily_year0, 1, 1),
                                     dt.date(args.daily_year0 + args.daily_years - 1, 12, 31),
                                     "C2 tile, %d years from %d" % (args.daily_years, args.daily_year0),
@@ -1068,7 +1109,7 @@ def main():
                                     daily_traffic if args.daily_years == 10 else None, traffic_src)
 
     # ---- CPU baseline: the oracle on bounded samples of the headline workload ---------------------
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import pyoracle as orc
         orc.build()
         cores = os.cpu_count() or 1
@@ -1119,7 +1160,7 @@ def main():
             pass
 
     # ---- the other BASELINE.json configurations, driver-timed in the same line (N = 1) ----------------
-    if world == 1 and not args.no_configs and (args.size == 250 or args.force_configs):
+    if args.full and world == 1 and not args.no_configs and (args.size == 250 or args.force_configs):
         want_cfg = [c for c in args.configs.split(",") if c]
         cfg = {}
         if "c2_fitted" in want_cfg:
@@ -1170,12 +1211,12 @@ def main():
         ctx = None
 
     # ---- N > 1: the tile farm on one fixed grid next to the weak headline ------------------------------
-    if world > 1 and scaling == "auto":
+    if args.full and world > 1 and scaling == "auto":
         del d_in, d_norm, d_se
         torch.cuda.empty_cache()
         rec = strip_run(env, args, args.strong_steps, 1, spot_check=False)
         rec["scaling"] = "strong"
-        rec["note"] = ("total work fixed as N grows; its N = 1 counterpart: python bench.py --configs c3_strip (same code "
+        rec["note"] = ("total work fixed as N grows; its N = 1 counterpart: python bench.py --full --configs c3_strip (same code "
                        "path as configs.c3 of the N = 1 line: topowx_amd.driver)")
         if args.strong_daily_rows > 0:
             rec["daily"] = strong_daily_run(env, args)

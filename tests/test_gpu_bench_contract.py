@@ -1,6 +1,7 @@
-"""GPU: bench.py prints ONE JSON line with the fields the driver's contract names (task description: metric / value / unit /
-n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config, plus `roofline`
-and `cpu_baseline`), on a reduced tile so that the test takes seconds.  Also the 2-rank spawn mode (fresh child processes
+"""GPU: bench.py prints ONE JSON line with the fields of its contract (metric / value / unit / n_gpus / steps / warmup /
+ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config, plus `roofline`; with --full also
+`cpu_baseline` and the other records), on a reduced tile so that the test takes seconds.  A plain run carries the headline
+alone, and --dump-outputs writes what its last timed step computed.  Also the 2-rank spawn mode (fresh child processes
 through torch.distributed.run; on a 1-GPU box the ranks share the GPU over gloo and say so)."""
 import json
 import os
@@ -24,7 +25,7 @@ def _run(*args):
 
 
 def test_bench_line_contract():
-    d = _run("--size", "64", "--nstns", "2500", "--steps", "2", "--warmup", "1", "--daily-years", "1", "--stream-tiles", "2",
+    d = _run("--full", "--size", "64", "--nstns", "2500", "--steps", "2", "--warmup", "1", "--daily-years", "1", "--stream-tiles", "2",
              "--cpu-sample", "16")
     for k, t in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
                  ("ms_per_step", float), ("higher_is_better", bool), ("scaling", str), ("dtype", str), ("data", str),
@@ -44,11 +45,41 @@ def test_bench_line_contract():
     assert dd["value"] > 0 and dd["packed_int16_vs_oracle"]["max_abs_lsb"] <= 1 and dd["stream"]["tiles"] == 2
 
 
+def test_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """Without --full the line holds the headline (and the roofline of its own timed steps) and nothing else; --steps sets
+    the timed steps; --dump-outputs writes the arrays of the last timed step, float32 / float64, identical from run to run
+    with the same arguments, and consistent with the line."""
+    import numpy as np
+    args = ("--size", "64", "--nstns", "2500", "--steps", "3", "--warmup", "1")
+    dumps = []
+    for i in range(2):
+        out = tmp_path / ("out%d" % i)
+        d = _run(*args, "--dump-outputs", str(out))
+        for k, t in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
+                     ("ms_per_step", float), ("higher_is_better", bool), ("dtype", str), ("config", dict), ("roofline", dict)):
+            assert isinstance(d[k], t), (k, d[k])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["scaling"] == "weak" and d["value"] > 0
+        assert abs(d["ms_per_step"] * 1e-3 * d["value"] - d["config"]["cells_ok"] * 12) < 1e-6 * d["value"]
+        for k in ("daily", "cpu_baseline", "configs", "strong", "parity_max_abs_degC"):
+            assert k not in d, k
+        files = sorted(p.name for p in out.iterdir())
+        assert files == ["ninvalid.npy", "norm_tmin.npy", "se_tmin.npy", "status.npy"], files
+        arr = {f[:-4]: np.load(out / f) for f in files}
+        assert sum((out / f).stat().st_size for f in files) <= 64 * 10 ** 6
+        assert all(a.dtype in (np.float32, np.float64) for a in arr.values())
+        assert arr["norm_tmin"].shape == arr["se_tmin"].shape == (12, 64, 64) and arr["status"].shape == (64, 64)
+        assert int((arr["status"] == 0).sum()) == d["config"]["cells_ok"] > 0
+        assert np.isfinite(arr["norm_tmin"][:, arr["status"] == 0]).all()
+        dumps.append(arr)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+
+
 SMALL_STRIP = ("--strip-rows", "100", "--strip-cols", "400", "--strip-tile", "50", "--strip-nstns", "2500")
 
 
 def test_bench_spawns_ranks_itself():
-    d = _run("--gpus", "2", "--size", "64", "--nstns", "2500", "--steps", "2", "--warmup", "1", "--strong-steps", "1",
+    d = _run("--full", "--gpus", "2", "--size", "64", "--nstns", "2500", "--steps", "2", "--warmup", "1", "--strong-steps", "1",
              "--strong-daily-rows", "100", "--strong-daily-cols", "200", "--strong-daily-years", "1", *SMALL_STRIP)
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["value"] > 0
     assert "daily" not in d and "cpu_baseline" not in d          # rank-0, N = 1 records only
@@ -69,13 +100,18 @@ def test_bench_strong_two_ranks_equal_one_rank(tmp_path):
     outs = []
     for n in (1, 2):
         path = str(tmp_path / ("mosaic%d.npz" % n))
-        d = _run("--gpus", str(n), "--scaling", "strong", "--steps", "1", "--warmup", "0", "--dump-mosaic", path, *SMALL_STRIP)
+        dump = tmp_path / ("dump%d" % n)
+        d = _run("--full", "--gpus", str(n), "--scaling", "strong", "--steps", "1", "--warmup", "0", "--dump-mosaic", path,
+                 "--dump-outputs", str(dump), *SMALL_STRIP)
         assert d["scaling"] == "strong" and d["n_gpus"] == n and d["value"] > 0
         s = d["strong"]
         assert s["cells_ok"] == s["cells_valid"] > 0 and len(s["tiles_per_rank"]) == n and s["gather_ms"] >= 0
         if n == 1:
             assert s["spot_check_vs_oracle"]["max_abs_degC"] < 1e-4 and s["spot_check_vs_oracle"]["fills_where_oracle_fails"]
         outs.append(np.load(path))
+        for k in outs[-1].files:                                 # --dump-outputs: the same mosaic, as float32 .npy files
+            got = np.load(dump / (k + ".npy"))
+            assert got.dtype == np.float32 and np.array_equal(got, outs[-1][k]), k
     assert sorted(outs[0].files) == ["norm_tmax", "norm_tmin", "se_tmax", "se_tmin"]
     for k in outs[0].files:
         assert outs[0][k].shape == (12, 100, 400) and np.array_equal(outs[0][k], outs[1][k]), k
@@ -85,7 +121,7 @@ def test_bench_strong_two_ranks_equal_one_rank(tmp_path):
 def test_bench_other_configs_reduced():
     """The c4_tile / c5 / c3 records of the default line, on reduced sizes (--force-configs; c3_strip = the code path of
     c3 on a small strip instead of the full configs[2] grid)."""
-    d = _run("--size", "64", "--nstns", "2500", "--steps", "1", "--warmup", "1", "--no-daily", "--cpu-sample", "16",
+    d = _run("--full", "--size", "64", "--nstns", "2500", "--steps", "1", "--warmup", "1", "--no-daily", "--cpu-sample", "16",
              "--force-configs", "--configs", "c4_tile,c5,c3_strip", "--c5-years", "1", "--c5-nstns", "2500",
              "--strong-steps", "1", *SMALL_STRIP)
     assert d["dtype"].startswith("f64") and d["roofline"]["traffic_measured_in_this_run"] is False
@@ -106,7 +142,7 @@ def test_bench_c2_fitted_and_c4_reduced():
     """The two records added in round 5, on reduced sizes: ``c2_fitted`` (the headline tile under the variograms step21 ->
     step22 fit on its own database: same systems, parity vs the oracle on the fitted table) and ``c4`` (every tile of a
     masked grid streamed with daily output: counts, per-tile times, oracle check of cells from four tiles)."""
-    d = _run("--size", "64", "--nstns", "2500", "--steps", "2", "--warmup", "1", "--no-daily", "--cpu-sample", "16",
+    d = _run("--full", "--size", "64", "--nstns", "2500", "--steps", "2", "--warmup", "1", "--no-daily", "--cpu-sample", "16",
              "--force-configs", "--configs", "c2_fitted,c4,c3_fitted", "--c4-rows", "150", "--c4-cols", "400", "--c4-years", "2",
              "--strip-tile", "50", "--strip-nstns", "2500", "--strip-rows", "100", "--strip-cols", "400")
     f = d["configs"]["c2_fitted"]

@@ -68,10 +68,10 @@ def test_rccl_one_rank_group_beside_libtwxhip():
 
 
 def test_bench_strong_line_under_a_one_rank_nccl_group():
-    """``bench.py --gpus 1 --scaling strong`` with TWX_BENCH_FORCE_PG=1: process group, barriers, the max-over-ranks reduction
+    """``bench.py --full --gpus 1 --scaling strong`` with TWX_BENCH_FORCE_PG=1: process group, barriers, the max-over-ranks reduction
     and the mosaic gather of the N > 1 path all run, over RCCL, at world 1."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_port()), TWX_BENCH_FORCE_PG="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--scaling", "strong", "--steps", "1", "--warmup", "0",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--scaling", "strong", "--steps", "1", "--warmup", "0",
                         "--strip-rows", "100", "--strip-cols", "400", "--strip-tile", "50", "--strip-nstns", "2500", "--strong-daily-rows", "0"],
                        capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]

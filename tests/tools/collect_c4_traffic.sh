@@ -5,7 +5,7 @@ set -u
 OUT=gpurun_out/prof_c4
 rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
-ARGS="--steps 1 --warmup 0 --daily-years 69 --no-cpu-baseline --no-configs --stream-tiles 0"
+ARGS="--full --steps 1 --warmup 0 --daily-years 69 --no-cpu-baseline --no-configs --stream-tiles 0"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/dfetch -o f --output-format csv -- python3 bench.py $ARGS > $OUT/dfetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/dwrite -o w --output-format csv -- python3 bench.py $ARGS > $OUT/dwrite.log 2>&1
 python3 tests/tools/reduce_profiles.py $OUT > /dev/null

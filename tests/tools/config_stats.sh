@@ -6,7 +6,7 @@ CFG=${1:-c3_fitted}; TAG=${2:-cs_$CFG}
 OUT=gpurun_out/$TAG
 rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $OUT/stats -o s --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-daily --configs $CFG --c3-steps 1 2>$OUT/stats.err | tail -1 > $OUT/bench_profiled.json
+rocprofv3 --kernel-trace --stats -d $OUT/stats -o s --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-daily --configs $CFG --c3-steps 1 2>$OUT/stats.err | tail -1 > $OUT/bench_profiled.json
 python3 - "$OUT" "$CFG" <<'PY'
 import csv, glob, json, os, sys
 out, cfg = sys.argv[1], sys.argv[2]

@@ -5,7 +5,7 @@ TAG=${1:-qsd}; shift || true
 OUT=gpurun_out/$TAG
 rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $OUT/stats -o s --output-format csv -- python3 bench.py --steps 6 --warmup 1 --no-cpu-baseline --no-configs --stream-tiles 0 "$@" 2>$OUT/stats.err | tail -1 > $OUT/bench_profiled.json
+rocprofv3 --kernel-trace --stats -d $OUT/stats -o s --output-format csv -- python3 bench.py --full --steps 6 --warmup 1 --no-cpu-baseline --no-configs --stream-tiles 0 "$@" 2>$OUT/stats.err | tail -1 > $OUT/bench_profiled.json
 python3 - "$OUT" <<'PY'
 import csv, glob, json, os, sys
 out = sys.argv[1]
