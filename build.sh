@@ -1,5 +1,5 @@
 #!/bin/bash
-# Build libtwxhip.so (gfx950) in-tree.  hipcc cross-compiles without a GPU.
+# Build libtwxhip.so and libtwxqa.so (gfx950) in-tree.  hipcc cross-compiles without a GPU.
 # The compiler's per-kernel resource remarks (VGPRs / AGPRs / scratch / LDS / occupancy) are reduced into
 # topowx_amd/libtwxhip.resources.txt: tests/test_isa_resources.py fails when a kriging / daily kernel spills or
 # outgrows the register budget its waves_per_eu tuning assumes (a compiler bump would otherwise cost 10-20 % silently).
@@ -22,4 +22,13 @@ if ! hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared -std=c++17 
 fi
 show_diagnostics "$LOG"
 python3 tests/tools/isa_resources.py "$LOG" > topowx_amd/libtwxhip.resources.txt
+# libtwxqa.so: the station QA kernels (include/twx_qa.h), a library of their own -- built second, same flags
+if ! hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared -std=c++17 -Iinclude \
+    -Rpass-analysis=kernel-resource-usage "$@" -o topowx_amd/libtwxqa.so topowx_amd/qa/twx_outlier.hip 2> "$LOG"; then
+    show_diagnostics "$LOG"
+    rm -f "$LOG"
+    exit 1
+fi
+show_diagnostics "$LOG"
+python3 tests/tools/isa_resources.py "$LOG" > topowx_amd/libtwxqa.resources.txt
 rm -f "$LOG"

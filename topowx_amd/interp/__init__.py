@@ -3,7 +3,8 @@
 Every numerical result comes from libtwxhip (HIP kernels on MI355X) through
 ``topowx_amd._lib``; there is no CPU implementation here.  ``__all__`` holds every name of the reference's four
 ``__all__`` lists (interp_tair.py:22-24, station_select.py:23, optimize.py:20-23, tiling.py:23) except ``XvalOutlier``
-(station QA upstream of the serially-complete database: out of scope).
+(step20's station outlier screen): it lives in ``topowx_amd.interp.optimize`` (fits in libtwxqa, ``topowx_amd._qalib``) and is
+not re-exported here; ``topowx_amd.step20`` drives it.
 """
 from .station_select import StationSelect  # noqa: F401
 from .interp_tair import (BuildKrigParams, GwrTairAnom, InterpTair, KrigTair, KrigTairAll,  # noqa: F401
