@@ -2,7 +2,9 @@
 csrc/twx_deflate.h).  The reference reaches that storage form through netCDF4-python's ``zlib=True`` (tiling.py:720,894,913,
 1035).  Checks: (1) zlib -- the decoder inside libhdf5 -- inflates every stream to the shuffled chunk of what the synchronous
 entry computes; (2) the GPU's bytes equal the CPU restatement's (oracle/deflate_oracle.py), byte for byte; (3) a NetCDF-4 tile
-file whose chunks were appended with H5Dwrite_chunk reads back through libhdf5 as the same int16 arrays."""
+file whose chunks were appended with H5Dwrite_chunk reads back through libhdf5 as the same int16 arrays.  Through the same entry,
+what the kernel probe (tests/test_gpu_deflate_kernels.py) cannot see -- df_launch's own carving and launch order -- at the sizes
+temperature tiles of 1 096 days never reach: day axes of 1 and 3 days, an all-masked tile, the 25 203-day production axis."""
 import zlib
 
 import numpy as np
@@ -59,17 +61,113 @@ def test_deflated_chunks_equal_the_restatement_and_inflate_to_the_daily_values(g
                 lo, hi = dorc.shuffled(chunk)
                 assert raw.size == 2 * lo.size and np.array_equal(raw[:lo.size], lo) and np.array_equal(raw[lo.size:], hi), (var, c)
                 assert np.array_equal(dorc.inflate_chunk(blob, nd, cy, cx), chunk)
-    # byte for byte against the restatement (pure Python: a few chunks)
+    # byte for byte against the restatement (pure Python: a few chunks, whatever their size)
     o = outs[0]
     for var in ("tmin", "tmax"):
         chunks = _tile_chunks(want["daily_" + var], cy, cx)
         table = dorc.tile_table(want["daily_" + var], cy, cx)         # the variable's Huffman code, from every 16th segment of every chunk
         for c in sorted({0, len(chunks) // 2, len(chunks) - 1}):
-            if chunks[c].size > 400000:
-                continue
             assert o["deflated_" + var][c] == dorc.deflate_chunk(chunks[c], table), (var, c)
     sizes = [len(b) for b in o["deflated_tmin"]]
     assert max(sizes) <= 2 * nd * cy * cx + 5 * (nd * cy * cx // dorc.SEG + nd * cy * cx // 65535 + 2) + 11       # never longer than stored
+
+
+def _stream_one_tile(ctx, grid, rows, cols, cy, cx):
+    """one tile through ctx.stream(..., deflate_chunks=(cy, cx)) -- the library's own carving and launch order (df_launch) --
+    -> {variable: [chunk streams]}"""
+    Y, X = rows.stop - rows.start, cols.stop - cols.start
+    st = ctx.stream(Y, X, daily=True, nslots=2, deflate_chunks=(cy, cx))
+    st.submit(0, grid, rows, cols)
+    o = st.wait(0)
+    got = {var: [bytes(b) for b in o["deflated_" + var]] for var in ("tmin", "tmax")}
+    st.close()
+    return got
+
+
+def _assert_streams(got, want, cy, cx, compared):
+    """every stream inflates (zlib) to its shuffled chunk; the chunks `compared(number of chunks)` names equal the restatement"""
+    from oracle import deflate_oracle as dorc
+    for var in ("tmin", "tmax"):
+        daily = want["daily_" + var]
+        chunks = _tile_chunks(daily, cy, cx)
+        assert len(got[var]) == len(chunks)
+        n = chunks[0].size
+        for c, (blob, chunk) in enumerate(zip(got[var], chunks)):
+            lo, hi = dorc.shuffled(chunk)
+            assert zlib.decompress(blob) == lo.tobytes() + hi.tobytes(), (var, c)
+            assert len(blob) <= 2 + n + 5 * -(-n // 65535) + n + 5 * -(-n // dorc.SEG) + 9, (var, c)
+        table = dorc.tile_table(daily, cy, cx)
+        for c in compared(len(chunks)):
+            assert got[var][c] == dorc.deflate_chunk(chunks[c], table), (var, c)
+
+
+def _synthetic(first, last, nstns, nrows=None, ncols=None):
+    import datetime as dt
+    from topowx_amd import _lib, synth
+    from topowx_amd.dates import get_days_metadata
+    days = get_days_metadata(dt.date(*first), dt.date(*last))
+    grid = synth.make_grid("C2", nrows=nrows, ncols=ncols) if nrows else synth.make_grid("C1")
+    ctx = _lib.Context()
+    for var, which in (("tmin", _lib.TMIN), ("tmax", _lib.TMAX)):
+        ctx.set_stations(which, synth.make_stations(grid["bbox"], nstns, 1, var, days, with_obs=True))
+    return days, grid, ctx
+
+
+@pytest.mark.parametrize("ndays", [1, 3])
+def test_a_short_day_axis_through_the_stream(ndays):
+    """Chunks shorter than a piece (N = ndays cy cx of 3 .. 12 < 64) through the library's own launch path: one segment of a
+    partial piece, most threads without a byte, every high-plane block stored (the code's description alone is longer)."""
+    days, grid, ctx = _synthetic((1981, 1, 1), (1981, 1, ndays), 300)
+    assert days.size == ndays
+    rows, cols = slice(10, 14), slice(20, 26)
+    want = ctx.interp_grid(grid, daily=True, rows=rows, cols=cols)
+    assert np.all(want["status"] == 0) and want["daily_tmin"].shape == (ndays, 4, 6)
+    for cy, cx in ((2, 2), (1, 3)):
+        assert ndays * cy * cx < 64
+        got = _stream_one_tile(ctx, grid, rows, cols, cy, cx)
+        _assert_streams(got, want, cy, cx, lambda n: range(n))
+        for var in ("tmin", "tmax"):
+            assert all(len(b) == 2 + (ndays * cy * cx + 5) * 2 + 9 for b in got[var])          # both planes stored
+    ctx.close()
+
+
+def test_an_all_masked_tile_through_the_stream(golden_case):
+    """A tile without one unmasked cell is not short-cut: its chunks are the constant fill value (-32767: high byte 0x80, one
+    64-byte match per piece) and are deflated like any other."""
+    from topowx_amd import _lib
+    grid, tmin, tmax = golden_case
+    grid = dict(grid)
+    grid["mask"] = np.zeros_like(grid["mask"])
+    ctx = _lib.Context()
+    ctx.set_stations(_lib.TMIN, tmin)
+    ctx.set_stations(_lib.TMAX, tmax)
+    rows, cols = slice(20, 40), slice(30, 50)
+    want = ctx.interp_grid(grid, daily=True, rows=rows, cols=cols)
+    assert np.all(want["daily_tmin"] == _lib.FILL_I2) and np.all(want["daily_tmax"] == _lib.FILL_I2) and _lib.FILL_I2 == -32767
+    got = _stream_one_tile(ctx, grid, rows, cols, 10, 10)
+    ctx.close()
+    _assert_streams(got, want, 10, 10, lambda n: range(n))
+    n = tmin.days.size * 100
+    assert all(len(b) < 0.52 * 2 * n for b in got["tmin"])              # the high plane is next to nothing
+
+
+def test_the_full_day_axis_through_the_stream():
+    """The production day axis (1948-01-01 .. 2016-12-31, 25 203 days; construction of test_gpu_fullsize.py's
+    test_full_day_axis_1948_2016 with fewer stations: the kriging is not under test) on a 20 x 20 tile: chunks of 10 x 10 give
+    154 segments (the Adler scan of k_deflate_scan takes two passes), chunks of 10 x 20 give 308 (both scans do) -- what every
+    production chunk (50 x 50: 3 846 segments) goes through.  Every stream inflated by zlib; the first and the last chunk of
+    both variables byte for byte against the restatement."""
+    from oracle import deflate_oracle as dorc
+    days, grid, ctx = _synthetic((1948, 1, 1), (2016, 12, 31), 300, 64, 64)
+    assert days.size == 25203
+    rows, cols = slice(22, 42), slice(8, 28)
+    want = ctx.interp_grid(grid, daily=True, rows=rows, cols=cols)
+    assert np.all(want["status"] == 0)
+    for (cy, cx), nseg in (((10, 10), 154), ((10, 20), 308)):
+        assert -(-25203 * cy * cx // dorc.SEG) == nseg
+        got = _stream_one_tile(ctx, grid, rows, cols, cy, cx)
+        _assert_streams(got, want, cy, cx, lambda n: (0, n - 1))
+    ctx.close()
 
 
 def test_streamed_deflated_tiles_into_netcdf4(golden_case, tmp_path):

@@ -26,7 +26,7 @@ ctx = _lib.Context()
 ctx.set_stations(_lib.TMIN, tmin)
 ctx.set_stations(_lib.TMAX, tmax)
 Yg, Xg = grid0["mask"].shape
-res = {"cases": 0, "failed": [], "chunks": 0, "bytes_over_int16": [], "odd_chunk_width": 0, "single_variable": 0, "stored_only_tiles": 0}
+res = {"cases": 0, "failed": [], "chunks": 0, "bytes_over_int16": [], "odd_chunk_width": 0, "single_variable": 0}
 t0 = time.time()
 for seed in range(seed0, seed0 + ncases):
     rng = np.random.default_rng(1000 + seed)
