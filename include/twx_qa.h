@@ -7,7 +7,8 @@
  *   - every function returns 0 = ok or -1 = call-level failure (bad arguments,
  *     HIP errors); the message goes to errbuf (errlen bytes, NUL-terminated).
  *   - per-item failures are not call failures: they are reported in status[]
- *     with the TWX_CELL_* numbers of include/twx.h.
+ *     with the TWX_CELL_* numbers of include/twx.h where one applies (the
+ *     spatial check adds two of its own, TWXQA_SP_FEW_DAYS / _FEW_VALID).
  *   - all buffers are host memory owned by the caller; a call is synchronous.
  */
 #ifndef TWX_QA_H
@@ -52,6 +53,67 @@ int twxqa_outlier_wls(int device, int64_t nstn, const double *lon, const double 
                       const double *lst13, const double *norm13, int64_t npts, const double *pt, int32_t k,
                       const int32_t *idx, const double *wgt, const int32_t *knn_status, double *err,
                       int32_t *status, float *kernel_ms, char *errbuf, int errlen);
+
+/* ---- step08's spatial regression check (_qa_spatial_regress, twx/qa/qa_temp.py:688-738, 858-1015) ---- */
+#define TWXQA_NGH_RADIUS_KM 75.0        /* NGH_RADIUS, qa_temp.py:66 */
+#define TWXQA_MIN_DAYS_MTH_WINDOW 40    /* qa_temp.py:71 */
+#define TWXQA_MIN_NGHS 3                /* qa_temp.py:72 */
+#define TWXQA_MAX_NGHS 7                /* qa_temp.py:73 */
+/* Largest radius neighbourhood a target may have.  A library limit without a reference counterpart: a wavefront keeps
+ * the (weight, slope, intercept, column) of every valid neighbour in LDS, 34 bytes each; 256 of them leave room for 18
+ * waves in the 160 KiB of a compute unit.  A target above it gets TWXQA_SP_NGH_CAP on all of its items, never a
+ * truncated list. */
+#define TWXQA_MAX_RADIUS_NGH 256
+
+/* per-(target, variable, year-month) item status */
+#define TWXQA_SP_OK TWX_CELL_OK                   /* checked (flags or none; r below 0.8 is ok and flags nothing) */
+#define TWXQA_SP_FEW_NGHS TWX_CELL_FEW_STATIONS   /* fewer than 3 stations within 75 km of the target */
+#define TWXQA_SP_DEGENERATE TWX_CELL_NUMERIC      /* see below */
+#define TWXQA_SP_NGH_CAP TWX_CELL_CAND_OVERFLOW   /* more than TWXQA_MAX_RADIUS_NGH stations within 75 km */
+#define TWXQA_SP_FEW_DAYS 16                      /* fewer than 40 finite target days in the window */
+#define TWXQA_SP_FEW_VALID 17                     /* fewer than 3 neighbours with a model for this window */
+
+/*
+ * The number of (year, month) items of a day axis: the calendar months from that of ymd[0] to that of
+ * ymd[ndays - 1]; -1 on bad arguments.  (A month of the first or last year outside that span holds no day of the
+ * series.  Its window may still reach into the series -- one that ends on Feb 20 lies inside March's window of
+ * Feb 14 to Apr 15 -- but flags go to a month's own days only, so such a month flags nothing in the reference either.)
+ */
+int twxqa_spatial_nmonths(int64_t ndays, const int32_t *ymd);
+
+/*
+ * For every target station, variable (0 = tmin, 1 = tmax) and (year, month): the window is the month plus 15 days on
+ * either side; every station within 75 km (haversine, util_geo.py:24-40; the target left out by index; ascending
+ * table order) whose finite days overlap the target's finite window days on >= 40 days, with more than one distinct
+ * value on either side, gets an index-of-agreement weight (perf_metrics.py:59-62) and the model of
+ * linregress(neighbour, target); each finite window day is estimated from the (up to) 7 heaviest neighbours that have
+ * a finite value on that day of the series or the one before / after it (the one nearest the observation; the first
+ * of previous, own, next on a tie), a day with fewer than 3 has no estimate; if Pearson's r of estimates against
+ * observations over the window is >= 0.8, a day of the month is flagged where |obs - est| >= 8.0 and that residual
+ * lies >= 4.0 population standard deviations from the mean window residual.
+ * Arithmetic is fp64 on the float32 observations widened exactly (NaN = missing).
+ *
+ * Deviation from the reference: an item with fewer than two estimated window days, a zero standard deviation of
+ * the window residuals or a non-finite r is TWXQA_SP_DEGENERATE and flags nothing.  The reference raises there
+ * (pearsonr on one point; a division by zero under step08's np.seterr), which drops ALL of that station's QA, or
+ * its result depends on the scipy version (r of a constant series).
+ *
+ * lon, lat [nstn]            finite
+ * tmin, tmax [nstn][ndays]   station-major observations
+ * ymd [ndays]                consecutive calendar days, YYYYMMDD
+ * target_idx [ntarget]       0 <= index < nstn
+ * flag_tmin, flag_tmax [ntarget][ndays]   out: 1 = flagged, 0 = not
+ * est (optional) [ntarget][2][ndays]      out: the estimate of each day within its own month's item, NaN if none
+ * item_r, item_nvalid, item_status (each optional) [ntarget][2][nmonths]   out: r (NaN if not computed), the number
+ *                            of valid neighbours, TWXQA_SP_*
+ * kernel_ms (optional) [2]   device time of the radius kernel (both passes) and of the item kernel
+ * Call-level failures: non-consecutive days, an index out of range, a non-finite longitude / latitude.
+ */
+int twxqa_spatial_regress(int device, int64_t nstn, int64_t ndays, const double *lon, const double *lat,
+                          const float *tmin, const float *tmax, const int32_t *ymd, int64_t ntarget,
+                          const int32_t *target_idx, uint8_t *flag_tmin, uint8_t *flag_tmax, double *est,
+                          double *item_r, int32_t *item_nvalid, int32_t *item_status, float *kernel_ms,
+                          char *errbuf, int errlen);
 
 #ifdef __cplusplus
 }

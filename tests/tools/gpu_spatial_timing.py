@@ -1,0 +1,93 @@
+#!/usr/bin/env python3
+"""Time step08's spatial regression check (``topowx_amd.qa.qa_spatial_regress``) on two synthetic pools
+(tests/spatial_cases.py): 2 000 stations x 10 years with every station a target, and a 12 000-station pool x 69 years
+(1948-2016) with 2 000 targets.  Per case one JSON line: items, the device time of the two kernels (HIP events inside
+the call), the seconds of the first and of a second, warm call (upload of the observations, both kernels, download
+of the flags), what is left of the warm call beside the kernels (``host_and_copies_s``) and how much of that the
+station-major copies of the two observation matrices take (``of_which_transpose_s``, the same operation timed apart).
+``measured_on`` is the device name the runtime reports.
+
+``--ref-s-per-station-year`` is the executed reference's rate (tests/golden/make_golden_spatial.py prints it: one CPU
+core of the build machine, not an MI355X figure); it is only carried into the line, next to the station-years of the
+targets, so that the two can be read together.
+
+    python tests/tools/gpu_spatial_timing.py [--case small|large|both] [--out profiles/qa_spatial_timing.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import numpy as np  # noqa: E402
+
+import spatial_cases  # noqa: E402
+from topowx_amd.qa import QA_SPATIAL_REGRESS, StationObsPool, qa_spatial_regress  # noqa: E402
+
+CASES = {"small": dict(n=2000, years=10, ntarget=None), "large": dict(n=12000, years=69, ntarget=2000)}
+
+
+def device_name(device):
+    """What the runtime calls the device the figures come from."""
+    import torch
+    p = torch.cuda.get_device_properties(device)
+    return "%s (%s)" % (p.name, getattr(p, "gcnArchName", "?"))
+
+
+def run_case(name, device, ref_rate):
+    c = CASES[name]
+    t0 = time.perf_counter()
+    if name == "small":
+        ids, lon, lat, tmin, tmax, days, _ = spatial_cases.big_case(c["n"], c["years"])
+    else:
+        ids, lon, lat, tmin, tmax, days, _ = spatial_cases.big_case(c["n"], c["years"], seed=12, year0=1948)
+    pool = StationObsPool(ids, lon, lat, tmin, tmax, days)
+    targets = None if c["ntarget"] is None else ids[np.linspace(0, ids.size - 1, c["ntarget"]).astype(int)]
+    t1 = time.perf_counter()
+    qa_spatial_regress(pool, targets, device=device)                       # first call: module load, first launches
+    t2 = time.perf_counter()
+    tm = {}
+    f_tmin, f_tmax, det = qa_spatial_regress(pool, targets, device=device, details=True, timing=tm)
+    t3 = time.perf_counter()
+    ta = time.perf_counter()                   # the station-major copies every call makes, timed apart (same operation)
+    np.ascontiguousarray(pool.tmin.T), np.ascontiguousarray(pool.tmax.T)
+    transpose_s = time.perf_counter() - ta
+    nt = ids.size if targets is None else len(targets)
+    kern_s = (tm["radius_kernel_ms"] + tm["regress_kernel_ms"]) / 1e3
+    st, cnt = np.unique(det["status"], return_counts=True)
+    rec = dict(tool="gpu_spatial_timing", case=name, measured_on=device_name(device),
+               measured_how="HIP events inside the call (kernel ms), time.perf_counter around the call (seconds)",
+               pool_stations=int(ids.size), targets=int(nt), days=int(days.size), items=int(det["status"].size),
+               status_counts={str(int(a)): int(b) for a, b in zip(st, cnt)},
+               flags_tmin=int((f_tmin == QA_SPATIAL_REGRESS).sum()), flags_tmax=int((f_tmax == QA_SPATIAL_REGRESS).sum()),
+               setup_s=round(t1 - t0, 2), first_call_s=round(t2 - t1, 3), warm_call_with_details_s=round(t3 - t2, 3),
+               radius_kernel_ms=round(tm["radius_kernel_ms"], 3), regress_kernel_ms=round(tm["regress_kernel_ms"], 3),
+               host_and_copies_s=round(t3 - t2 - kern_s, 3), of_which_transpose_s=round(transpose_s, 3),
+               target_station_years=int(nt * c["years"]),
+               reference_s_per_station_year=ref_rate,
+               reference_note="executed reference slice, one CPU core of the build machine (make_golden_spatial.py); "
+                              "not run on the MI355X host and not at this size")
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--case", choices=("small", "large", "both"), default="both")
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--ref-s-per-station-year", type=float, default=None)
+    ap.add_argument("--out", help="also write the records to this JSON file")
+    a = ap.parse_args(argv)
+    recs = [run_case(n, a.device, a.ref_s_per_station_year) for n in (("small", "large") if a.case == "both" else (a.case,))]
+    if a.out:
+        with open(a.out, "w") as fh:
+            json.dump(recs, fh, indent=1)
+            fh.write("\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -14,7 +14,10 @@ NTARGET = 13              # TWXQA_NTARGET: 12 monthly normals + the annual one
 PT_STRIDE = 29            # TWXQA_PT_STRIDE: lon, lat, elev, lst[13], norm[13]
 MAX_K = 159               # TWXQA_MAX_K
 STATUS_OK, STATUS_FEW_STATIONS, STATUS_SINGULAR = 0, 1, 4     # TWX_CELL_* numbers (include/twx.h)
-EXPORTS = ("twxqa_outlier_wls",)
+EXPORTS = ("twxqa_outlier_wls", "twxqa_spatial_nmonths", "twxqa_spatial_regress")
+# the spatial regression check (TWXQA_SP_* / TWXQA_* of include/twx_qa.h)
+MAX_RADIUS_NGH = 256      # TWXQA_MAX_RADIUS_NGH
+SP_OK, SP_FEW_NGHS, SP_DEGENERATE, SP_NGH_CAP, SP_FEW_DAYS, SP_FEW_VALID = 0, 1, 4, 7, 16, 17
 
 _LIB = None
 
@@ -34,6 +37,11 @@ def load():
         L.twxqa_outlier_wls.restype = C.c_int
         L.twxqa_outlier_wls.argtypes = [C.c_int, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_int32] + \
             [C.c_void_p] * 6 + [C.c_char_p, C.c_int]
+        L.twxqa_spatial_nmonths.restype = C.c_int
+        L.twxqa_spatial_nmonths.argtypes = [C.c_int64, C.c_void_p]
+        L.twxqa_spatial_regress.restype = C.c_int
+        L.twxqa_spatial_regress.argtypes = [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64] + \
+            [C.c_void_p] * 8 + [C.c_char_p, C.c_int]
         _LIB = L
     return _LIB
 
@@ -75,3 +83,47 @@ def outlier_wls(lon, lat, elev, lst13, norm13, pt, idx, wgt, knn_status, device=
     if timing is not None:
         timing["kernel_ms"] = float(ms.value)
     return err, status
+
+
+def spatial_nmonths(ymd):
+    """``twxqa_spatial_nmonths``: the number of (year, month) items of a day axis."""
+    ymd = _c(ymd, np.int32)
+    n = load().twxqa_spatial_nmonths(ymd.size, ymd.ctypes.data)
+    if n < 1:
+        raise ValueError("ymd must hold at least one day, in ascending order")
+    return int(n)
+
+
+def spatial_regress(lon, lat, tmin, tmax, ymd, target_idx, device=0, details=False, timing=None):
+    """``twxqa_spatial_regress``: step08's spatial regression check (qa_temp.py:688-738, 858-1015).
+
+    lon, lat [nstn]; tmin, tmax [nstn, ndays] float32, station-major, NaN = missing; ymd [ndays] consecutive days;
+    target_idx [ntarget].  Returns (flag_tmin, flag_tmax), each uint8 [ntarget, ndays] (1 = flagged); with ``details``
+    also a dict of est [ntarget, 2, ndays] and r / nvalid / status [ntarget, 2, nmonths].  ``timing`` (a dict) receives
+    ``radius_kernel_ms`` and ``regress_kernel_ms``."""
+    L = load()
+    lon, lat = _c(lon, np.float64), _c(lat, np.float64)
+    tmin, tmax = _c(tmin, np.float32), _c(tmax, np.float32)
+    ymd, target_idx = _c(ymd, np.int32), _c(target_idx, np.int32)
+    nstn, ndays, nt = lon.size, ymd.size, target_idx.size
+    if lon.ndim != 1 or lat.shape != lon.shape or tmin.shape != (nstn, ndays) or tmax.shape != (nstn, ndays):
+        raise ValueError("lon / lat must be [nstn] and tmin / tmax [nstn, ndays]")
+    if target_idx.ndim != 1:
+        raise ValueError("target_idx must be [ntarget]")
+    buf = C.create_string_buffer(512)
+    fmin, fmax = np.zeros((nt, ndays), np.uint8), np.zeros((nt, ndays), np.uint8)
+    det, ptr = {}, [None, None, None, None]
+    if details:
+        nm = spatial_nmonths(ymd) if ndays else 0
+        det = dict(est=np.empty((nt, 2, ndays)), r=np.empty((nt, 2, nm)), nvalid=np.empty((nt, 2, nm), np.int32),
+                   status=np.empty((nt, 2, nm), np.int32))
+        ptr = [det[k].ctypes.data for k in ("est", "r", "nvalid", "status")]
+    ms = (C.c_float * 2)(0.0, 0.0)
+    rc = L.twxqa_spatial_regress(int(device), nstn, ndays, lon.ctypes.data, lat.ctypes.data, tmin.ctypes.data,
+                                 tmax.ctypes.data, ymd.ctypes.data, nt, target_idx.ctypes.data, fmin.ctypes.data,
+                                 fmax.ctypes.data, ptr[0], ptr[1], ptr[2], ptr[3], C.addressof(ms), buf, 512)
+    if rc != 0:
+        raise QaError("twxqa_spatial_regress failed: %s" % buf.value.decode(errors="replace"))
+    if timing is not None:
+        timing["radius_kernel_ms"], timing["regress_kernel_ms"] = float(ms[0]), float(ms[1])
+    return (fmin, fmax, det) if details else (fmin, fmax)

@@ -1,0 +1,123 @@
+"""step08's spatial regression check of the daily Tmin / Tmax observations (``_qa_spatial_regress``,
+twx/qa/qa_temp.py:688-738, 858-1015) on the GPU: the flag and threshold constants of the reference, a small in-memory
+pool of raw observations, and ``qa_spatial_regress`` -- one batched call of libtwxqa's ``twxqa_spatial_regress`` over
+all target stations.  There is no CPU fallback: without the library the call raises.
+
+Out of scope here (see ``topowx_amd.step08``): the corroboration check, the non-spatial checks, and writing flags into
+a database.
+"""
+import numpy as np
+
+from .. import _qalib, ncio
+from ..dates import YMD
+
+__all__ = ["StationObsPool", "qa_spatial_regress", "ITEM_STATUS", "QA_OK", "QA_MISSING", "QA_SPATIAL_REGRESS", "NGH_RADIUS",
+           "NGH_CORR", "NGH_RESID_CUTOFF", "NGH_RESID_STD_CUTOFF", "MIN_DAYS_MTH_WINDOW", "MIN_NGHS", "MAX_NGHS",
+           "TWX_TO_GHCN_FLAGS_MAP"]
+
+# flag numbers (qa_temp.py:41-59) -- the ones a spatial-only run can produce or map
+QA_OK = 1
+QA_MISSING = 2
+QA_NAUGHT = 3
+DUP = 25
+QA_DUP_YEAR = 4
+QA_DUP_MONTH = 5
+QA_DUP_YEAR_MONTH = 6
+QA_DUP_WITHIN_MONTH = 7
+QA_IMPOSS_VALUE = 8
+QA_STREAK = 9
+QA_GAP = 10
+QA_INTERNAL_INCONSIST = 11
+QA_LAGRANGE_INCONSIST = 12
+QA_SPIKE_DIP = 13
+QA_CLIM_OUTLIER = 15
+QA_SPATIAL_REGRESS = 16
+QA_SPATIAL_CORROB = 17
+QA_MEGA_INCONSIST = 18    # (the reference assigns 14, then 18: 18 is what its module holds)
+
+# thresholds of the spatial checks (qa_temp.py:65-73)
+NGH_RADIUS = 75.0
+NGH_CORR = 0.8
+NGH_RESID_CUTOFF = 8.0
+NGH_RESID_STD_CUTOFF = 4.0
+MIN_DAYS_MTH_WINDOW = 40
+MIN_NGHS = 3
+MAX_NGHS = 7
+
+TWX_TO_GHCN_FLAGS_MAP = {QA_OK: "", QA_MISSING: "", DUP: "D", QA_DUP_YEAR: "D", QA_DUP_MONTH: "D", QA_DUP_YEAR_MONTH: "D",
+                         QA_DUP_WITHIN_MONTH: "D", QA_GAP: "G", QA_INTERNAL_INCONSIST: "I", QA_STREAK: "K",
+                         QA_MEGA_INCONSIST: "M", QA_NAUGHT: "N", QA_CLIM_OUTLIER: "O", QA_LAGRANGE_INCONSIST: "R",
+                         QA_SPATIAL_REGRESS: "S", QA_SPATIAL_CORROB: "S", QA_SPIKE_DIP: "T", QA_IMPOSS_VALUE: "X"}
+
+# per-item status of the check (TWXQA_SP_* of include/twx_qa.h)
+ITEM_STATUS = {_qalib.SP_OK: "ok", _qalib.SP_FEW_DAYS: "too few window days", _qalib.SP_FEW_NGHS: "too few neighbours",
+               _qalib.SP_FEW_VALID: "too few valid neighbours", _qalib.SP_DEGENERATE: "degenerate",
+               _qalib.SP_NGH_CAP: "more neighbours than TWXQA_MAX_RADIUS_NGH"}
+
+
+class StationObsPool(object):
+    """Raw daily observations of a set of stations, in memory: ``ids``, ``lon``, ``lat`` [n], ``tmin`` / ``tmax``
+    [ndays, n] float32 with NaN for missing (the reference's ``(time, station_id)`` layout) and ``days``
+    (``topowx_amd.dates.get_days_metadata``)."""
+
+    def __init__(self, ids, lon, lat, tmin, tmax, days):
+        self.ids = np.asarray(ids).astype(str)
+        self.lon, self.lat = np.asarray(lon, np.float64), np.asarray(lat, np.float64)
+        self.tmin, self.tmax = np.asarray(tmin, np.float32), np.asarray(tmax, np.float32)
+        self.days = days
+        n, nd = self.ids.size, days.size
+        if self.lon.shape != (n,) or self.lat.shape != (n,) or self.tmin.shape != (nd, n) or self.tmax.shape != (nd, n):
+            raise ValueError("lon / lat must be [n] and tmin / tmax [ndays, n]")
+        self.idxs = {s: i for i, s in enumerate(self.ids)}
+        if len(self.idxs) != n:
+            raise ValueError("station ids must be unique")
+
+    @classmethod
+    def from_netcdf(cls, path):
+        """The numeric part of the reference's all-stations database (create_db_all_stations.py:233-316): ``tmin`` and
+        ``tmax`` on ``(time, station_id)``, ``longitude``, ``latitude``, the ids and the daily time axis;
+        ``missing_value`` / ``_FillValue`` entries read as NaN.  The quality-flag character variables are not read."""
+        ds = ncio.open_dataset(path, "r")
+        try:
+            days = ncio.days_of(ds)
+            ids = ncio._read_ids(ds.variables["station_id"])
+            col = {}
+            for name in ("longitude", "latitude", "tmin", "tmax"):
+                v = ds.variables[name]
+                col[name] = ncio._masked_to_nan(v, v[:])
+        finally:
+            ds.close()
+        return cls(ids, col["longitude"], col["latitude"], col["tmin"], col["tmax"], days)
+
+    def qa_spatial_regress(self, targets=None, device=0, details=False):
+        return qa_spatial_regress(self, targets, device, details)
+
+
+def qa_spatial_regress(pool, targets=None, device=0, details=False, timing=None):
+    """The spatial regression check of ``targets`` (station ids; default: every station of the pool) against the pool,
+    all targets in one call.  Returns ``(flags_tmin, flags_tmax)``, each uint8 ``[ndays, ntarget]`` in the reference's
+    numbering: ``QA_OK`` (1), ``QA_MISSING`` (2, the observation is NaN) or ``QA_SPATIAL_REGRESS`` (16).  With
+    ``details=True`` a third value: a dict of ``est`` [ntarget, 2, ndays] (variable 0 = tmin, 1 = tmax; the estimate of
+    each day within its own month's item, NaN if none), ``r``, ``nvalid`` and ``status`` [ntarget, 2, nmonths]
+    (``ITEM_STATUS``) and ``nmonths``.  ``timing`` (a dict) receives the device time of the two kernels."""
+    if targets is None:
+        tidx = np.arange(pool.ids.size, dtype=np.int32)
+    else:
+        try:
+            tidx = np.array([pool.idxs[str(s)] for s in np.atleast_1d(np.asarray(targets))], np.int32)
+        except KeyError as e:
+            raise KeyError("target station %s is not in the pool" % e)
+    # station-major: a wavefront reads a window as one contiguous run
+    tmin_s, tmax_s = np.ascontiguousarray(pool.tmin.T), np.ascontiguousarray(pool.tmax.T)
+    res = _qalib.spatial_regress(pool.lon, pool.lat, tmin_s, tmax_s, pool.days[YMD], tidx, device=device, details=details,
+                                 timing=timing)
+    out = []
+    for flagged, obs in ((res[0], tmin_s), (res[1], tmax_s)):
+        f = np.where(np.isnan(obs[tidx]), QA_MISSING, QA_OK).astype(np.uint8)
+        f[flagged != 0] = QA_SPATIAL_REGRESS           # (only finite days are ever flagged)
+        out.append(np.ascontiguousarray(f.T))
+    if details:
+        det = dict(res[2])
+        det["nmonths"] = det["r"].shape[2]
+        out.append(det)
+    return tuple(out)
