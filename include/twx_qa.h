@@ -115,6 +115,69 @@ int twxqa_spatial_regress(int device, int64_t nstn, int64_t ndays, const double 
                           double *item_r, int32_t *item_nvalid, int32_t *item_status, float *kernel_ms,
                           char *errbuf, int errlen);
 
+/* ---- the rest of step08's spatial stage (run_qa_spatial_only, qa_temp.py:218-258): day-of-year normals, the
+ * corroboration check (_qa_spatial_corrob, :740-813, 1017-1082) and _qa_mega_inconsist (:815-840) ---- */
+#define TWXQA_ANOMALY_CUTOFF 10.0       /* ANOMALY_CUTOFF, qa_temp.py:70 */
+#define TWXQA_MIN_NORM_VALUES 100       /* MIN_NORM_VALUES, qa_temp.py:84 */
+#define TWXQA_NORM_ROWS 731             /* the 365-row table (dates of 2003), then the 366-row table (dates of 2004) */
+/* Most values a row of the normals may draw on: 15 calendar dates per year the series touches, so 136 years.  A
+ * library limit without a reference counterpart: a workgroup of 4 waves sorts a row's values in LDS, 4 bytes each plus
+ * 2 KiB of reduction scratch; at 2048 values that is 10 KiB, and the 8 workgroups that fill the 32 wave slots of a
+ * compute unit take 80 KiB of its 160 KiB.  4096 values (18 KiB, 144 KiB for 8 workgroups) would leave a compute
+ * unit no LDS to share with any other kernel; 8192 would halve the waves in flight.  A series that touches more
+ * years fails the call with a message, never a truncated window. */
+#define TWXQA_MAX_NORM_VALUES 2048
+
+/*
+ * The two day-of-year tables of each series (_get_norms_md_masks / _build_mean_norms / _biweight_mean,
+ * qa_temp.py:1111-1130, 1171-1184, 1215-1228).  Row x of the 365-row table takes every finite day of the series whose
+ * (month, day) is one of the 15 dates from 7 days before to 7 days after day x of 2003 (windows wrap the year end;
+ * Feb 29 is in none of them); the 366-row table likewise with the dates of 2004.  Fewer than 100 values: NaN.  Else
+ * M = median (the mean of the two middle values of an even count), MAD = median |X - M|; MAD == 0: the plain mean;
+ * else u = (X - M) / (7.5 MAD), |u| >= 1 set to 1, row = M + sum (X - M)(1 - u^2)^2 / sum (1 - u^2)^2.  Both medians
+ * are exact.  fp64 on float32 values widened exactly; the sums run over the sorted values.
+ *
+ * series [nseries][ndays]   float32, NaN (or any non-finite value) = missing
+ * ymd [ndays]               consecutive calendar days, YYYYMMDD
+ * norms [nseries][731]      out: rows 0..364 the 365-row table, rows 365..730 the 366-row table
+ * kernel_ms (optional) [1]  device time of the kernel
+ * Call-level failures: non-consecutive days; a series that touches more than TWXQA_MAX_NORM_VALUES / 15 years.
+ */
+int twxqa_doy_norms(int device, int64_t nseries, int64_t ndays, const float *series, const int32_t *ymd,
+                    double *norms, float *kernel_ms, char *errbuf, int errlen);
+
+/*
+ * run_qa_spatial_only for all targets in one call: the regression check (twxqa_spatial_regress, above) -> its flagged
+ * days removed from the target -> normals -> the corroboration check -> its flagged days removed -> the
+ * mega-inconsistency check.
+ *
+ * Corroboration: the neighbours are the stations within 75 km, the target left out by index, in ascending distance
+ * (equal distances in table order); fewer than 3: nothing is flagged.  The normals of a neighbour come from the pool's
+ * observations as they are, those of the target from its series without the regression check's days.  For each
+ * variable and day x except the first and last of the series: anom = |obs[x] - target normal of x's day of year, table
+ * by x's own year|; NaN: no flag.  The day is tested if at least 3 neighbours have a finite observation on each of
+ * x - 1, x, x + 1; per such day the first 7 neighbours with a finite |obs - own normal| (row and table from that
+ * day's own date) give up to 21 anomalies, and x is flagged if every one differs from anom by >= 10.0 -- also if
+ * there is none (no neighbour has a normal: the reference's empty-list case, kept).
+ * Mega-inconsistency, per calendar month over all years on the series after both removals: finite Tmin above the
+ * month's highest Tmax and finite Tmax below the month's lowest Tmin; a month empty on either side is skipped.
+ *
+ * Inputs as twxqa_spatial_regress.
+ * flag_tmin, flag_tmax [ntarget][ndays]  out: the reference's numbers: 1 ok, 2 missing (NaN), 16 regression,
+ *                            17 corroboration, 18 mega-inconsistency; a later check writes only where the flag is 1
+ * norms (optional) [ntarget][2][731]     out: the target tables (variable 0 = tmin), 365 rows then 366 rows
+ * status (optional) [ntarget]            out: TWXQA_SP_OK, TWXQA_SP_FEW_NGHS (fewer than 3 neighbours: no spatial
+ *                            flags) or TWXQA_SP_NGH_CAP (more than TWXQA_MAX_RADIUS_NGH: no spatial flags either);
+ *                            the mega-inconsistency check runs for every target
+ * kernel_ms (optional) [6]   device time: regression radius passes, regression items, distance-ordered radius lists,
+ *                            normals, corroboration, mega-inconsistency + final flags
+ * Call-level failures: those of twxqa_spatial_regress and of twxqa_doy_norms.
+ */
+int twxqa_spatial_only(int device, int64_t nstn, int64_t ndays, const double *lon, const double *lat,
+                       const float *tmin, const float *tmax, const int32_t *ymd, int64_t ntarget,
+                       const int32_t *target_idx, uint8_t *flag_tmin, uint8_t *flag_tmax, double *norms,
+                       int32_t *status, float *kernel_ms, char *errbuf, int errlen);
+
 #ifdef __cplusplus
 }
 #endif

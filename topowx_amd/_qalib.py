@@ -14,10 +14,16 @@ NTARGET = 13              # TWXQA_NTARGET: 12 monthly normals + the annual one
 PT_STRIDE = 29            # TWXQA_PT_STRIDE: lon, lat, elev, lst[13], norm[13]
 MAX_K = 159               # TWXQA_MAX_K
 STATUS_OK, STATUS_FEW_STATIONS, STATUS_SINGULAR = 0, 1, 4     # TWX_CELL_* numbers (include/twx.h)
-EXPORTS = ("twxqa_outlier_wls", "twxqa_spatial_nmonths", "twxqa_spatial_regress")
+EXPORTS = ("twxqa_outlier_wls", "twxqa_spatial_nmonths", "twxqa_spatial_regress", "twxqa_doy_norms", "twxqa_spatial_only")
 # the spatial regression check (TWXQA_SP_* / TWXQA_* of include/twx_qa.h)
 MAX_RADIUS_NGH = 256      # TWXQA_MAX_RADIUS_NGH
 SP_OK, SP_FEW_NGHS, SP_DEGENERATE, SP_NGH_CAP, SP_FEW_DAYS, SP_FEW_VALID = 0, 1, 4, 7, 16, 17
+# the normals and the corroboration check
+ANOMALY_CUTOFF = 10.0     # TWXQA_ANOMALY_CUTOFF
+MIN_NORM_VALUES = 100     # TWXQA_MIN_NORM_VALUES
+NORM_ROWS = 731           # TWXQA_NORM_ROWS: the 365-row table, then the 366-row table
+MAX_NORM_VALUES = 2048    # TWXQA_MAX_NORM_VALUES
+SPATIAL_ONLY_KERNELS = ("regress_radius", "regress_items", "radius_dist", "doy_norms", "corrob", "mega_final")
 
 _LIB = None
 
@@ -42,6 +48,11 @@ def load():
         L.twxqa_spatial_regress.restype = C.c_int
         L.twxqa_spatial_regress.argtypes = [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64] + \
             [C.c_void_p] * 8 + [C.c_char_p, C.c_int]
+        L.twxqa_doy_norms.restype = C.c_int
+        L.twxqa_doy_norms.argtypes = [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 4 + [C.c_char_p, C.c_int]
+        L.twxqa_spatial_only.restype = C.c_int
+        L.twxqa_spatial_only.argtypes = [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64] + \
+            [C.c_void_p] * 6 + [C.c_char_p, C.c_int]
         _LIB = L
     return _LIB
 
@@ -127,3 +138,53 @@ def spatial_regress(lon, lat, tmin, tmax, ymd, target_idx, device=0, details=Fal
     if timing is not None:
         timing["radius_kernel_ms"], timing["regress_kernel_ms"] = float(ms[0]), float(ms[1])
     return (fmin, fmax, det) if details else (fmin, fmax)
+
+
+def doy_norms(series, ymd, device=0, timing=None):
+    """``twxqa_doy_norms``: the two day-of-year tables of biweight means of each series (qa_temp.py:1111-1130, 1171-1184,
+    1215-1228).  series [nseries, ndays] float32 (NaN = missing), ymd [ndays] consecutive days.  Returns norms
+    [nseries, 731]: rows 0..364 the 365-row table, rows 365..730 the 366-row table.  ``timing`` receives ``kernel_ms``."""
+    L = load()
+    series, ymd = _c(series, np.float32), _c(ymd, np.int32)
+    if series.ndim != 2 or ymd.ndim != 1 or series.shape[1] != ymd.size:
+        raise ValueError("series must be [nseries, ndays] and ymd [ndays]")
+    out = np.empty((series.shape[0], NORM_ROWS))
+    ms = C.c_float(0.0)
+    buf = C.create_string_buffer(512)
+    rc = L.twxqa_doy_norms(int(device), series.shape[0], ymd.size, series.ctypes.data, ymd.ctypes.data, out.ctypes.data,
+                           C.addressof(ms), buf, 512)
+    if rc != 0:
+        raise QaError("twxqa_doy_norms failed: %s" % buf.value.decode(errors="replace"))
+    if timing is not None:
+        timing["kernel_ms"] = float(ms.value)
+    return out
+
+
+def spatial_only(lon, lat, tmin, tmax, ymd, target_idx, device=0, timing=None):
+    """``twxqa_spatial_only``: regression check -> normals -> corroboration check -> mega-inconsistency check
+    (``run_qa_spatial_only``, qa_temp.py:218-258), inputs as ``spatial_regress``.  Returns (flag_tmin, flag_tmax), each
+    uint8 [ntarget, ndays] in the reference's numbering (1, 2, 16, 17, 18), norms [ntarget, 2, 731] (the target tables)
+    and status [ntarget] (SP_OK / SP_FEW_NGHS / SP_NGH_CAP).  ``timing`` receives ``<kernel>_kernel_ms`` for the names in
+    ``SPATIAL_ONLY_KERNELS``."""
+    L = load()
+    lon, lat = _c(lon, np.float64), _c(lat, np.float64)
+    tmin, tmax = _c(tmin, np.float32), _c(tmax, np.float32)
+    ymd, target_idx = _c(ymd, np.int32), _c(target_idx, np.int32)
+    nstn, ndays, nt = lon.size, ymd.size, target_idx.size
+    if lon.ndim != 1 or lat.shape != lon.shape or tmin.shape != (nstn, ndays) or tmax.shape != (nstn, ndays):
+        raise ValueError("lon / lat must be [nstn] and tmin / tmax [nstn, ndays]")
+    if target_idx.ndim != 1:
+        raise ValueError("target_idx must be [ntarget]")
+    buf = C.create_string_buffer(512)
+    fmin, fmax = np.zeros((nt, ndays), np.uint8), np.zeros((nt, ndays), np.uint8)
+    norms, status = np.empty((nt, 2, NORM_ROWS)), np.empty(nt, np.int32)
+    ms = (C.c_float * 6)()
+    rc = L.twxqa_spatial_only(int(device), nstn, ndays, lon.ctypes.data, lat.ctypes.data, tmin.ctypes.data,
+                              tmax.ctypes.data, ymd.ctypes.data, nt, target_idx.ctypes.data, fmin.ctypes.data,
+                              fmax.ctypes.data, norms.ctypes.data, status.ctypes.data, C.addressof(ms), buf, 512)
+    if rc != 0:
+        raise QaError("twxqa_spatial_only failed: %s" % buf.value.decode(errors="replace"))
+    if timing is not None:
+        for k, name in enumerate(SPATIAL_ONLY_KERNELS):
+            timing[name + "_kernel_ms"] = float(ms[k])
+    return fmin, fmax, norms, status

@@ -201,6 +201,10 @@ class _Classic(object):
         self.variables[varname] = var
         if fill_value is not None and fill_value is not False:
             fv = np.array(fill_value).astype(dt)[()]
+            if dt.kind == "S" and fv == b"":                # the empty character (the reference's qflag_* fill): NUL bytes;
+                if v.shape:                                 # a classic header cannot hold an empty attribute value
+                    v[:] = np.zeros(v.shape, "S1")
+                return var
             v._FillValue = fv
             if v.shape:
                 v[:] = fv                                   # the classic format has no implicit fill on this writer

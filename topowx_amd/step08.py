@@ -1,18 +1,35 @@
-"""The spatial regression check of ``scripts/step08_mpi_qa_temp.py --spatial`` as a report.
+"""The spatial quality checks of ``scripts/step08_mpi_qa_stn_obs.py --spatial``: a report by default, the whole stage
+with ``--spatial``, and the ``qflag_*`` update with ``--spatial --write``.
 
 Every station of an all-stations database (or the ``--targets`` subset) is checked against the stations within 75 km
-(``topowx_amd.qa.qa_spatial_regress``: one batched GPU call instead of the reference's MPI farm over stations).
+in one batched GPU call instead of the reference's MPI farm over stations.
 
-Nothing is written into the database.  The reference's ``run_qa_spatial_only`` (qa_temp.py:218-240) goes on from this
-check to the corroboration check -- which sees the observations this check removed -- and to ``_qa_mega_inconsist``;
-only the three together decide the ``qflag_*`` that step08 writes.  The corroboration check is not built yet, so the
-flags of this check alone go into a report:
+Default: the spatial regression check alone (``topowx_amd.qa.qa_spatial_regress``), as a report; nothing is written into
+the database.
 
     python -m topowx_amd.step08 --db all.nc --out report.npz [--targets ids.txt] [--device N]
 
 prints one JSON line (stations, items, flags per variable, seconds, kernel milliseconds) and writes ``report.npz``:
 ``ids`` [ntarget], ``ymd`` [ndays], ``flags_tmin`` / ``flags_tmax`` [ndays, ntarget] (1 ok, 2 missing, 16 flagged) and
-the per-item ``status`` [ntarget, 2, nmonths].  Exits with 1 if the database cannot be opened or a target is unknown.
+the per-item ``status`` [ntarget, 2, nmonths].
+
+``--spatial``: the reference's ``run_qa_spatial_only`` (qa_temp.py:218-258; ``topowx_amd.qa.run_qa_spatial_only``): the
+regression check, the corroboration check on what it left, the mega-inconsistency check on what both left.  If the
+database has ``qflag_tmin`` / ``qflag_tmax`` the observations that already carry a flag are set to NaN first, as the
+reference's ``load_all_stn_obs`` does.  The report holds ``flags_tmin`` / ``flags_tmax`` in the reference's numbering
+(1 ok, 2 missing, 16 regression, 17 corroboration, 18 mega-inconsistency) and the per-target ``status`` [ntarget]; the
+JSON line counts each flag per variable.  The database is left alone.
+
+``--spatial --write`` then updates ``qflag_tmin`` / ``qflag_tmax`` as the reference's ``create_update_iter`` /
+``set_prev_flags`` / ``update_flags`` do (step08_mpi_qa_stn_obs.py:58-95, 160-213): the rows are the days on which either
+variable carries a flag other than 1 or 2; both variables are written on every such row, as the characters of
+``TWX_TO_GHCN_FLAGS_MAP``; a previous non-empty flag is kept wherever the new flag is 1 or 2.  A database without the
+``qflag_*`` variables gives exit 1 and a message.
+
+Out of scope: the refresh of the observation counts after the write (the reference's ``add_obs_cnt``), and the
+non-spatial checks.
+
+Exits with 1 if the database cannot be opened, a target is unknown, or ``--write`` has nothing to write into.
 """
 import argparse
 import json
@@ -21,10 +38,89 @@ import time
 
 import numpy as np
 
+from . import ncio
 from .dates import YMD
-from .qa import QA_SPATIAL_REGRESS, StationObsPool, qa_spatial_regress
+from .qa import (QA_MEGA_INCONSIST, QA_MISSING, QA_OK, QA_SPATIAL_CORROB, QA_SPATIAL_REGRESS, TWX_TO_GHCN_FLAGS_MAP,
+                 StationObsPool, qa_spatial_regress, run_qa_spatial_only)
+from .qa.qa_temp import read_qflags
 
-__all__ = ["main"]
+__all__ = ["main", "merge_qflags", "write_qflags"]
+
+QFLAG_VARS = ("qflag_tmin", "qflag_tmax")
+
+
+def merge_qflags(flags_tmin, flags_tmax, prev_tmin, prev_tmax):
+    """``create_update_iter`` + ``set_prev_flags`` (step08_mpi_qa_stn_obs.py:160-213) on whole arrays.  flags_* : the new
+    flag numbers, prev_* : the characters the database holds (``"S1"``, ``b""`` = none), all of one shape.  Returns
+    ``(rows, chars_tmin, chars_tmax)``: the boolean mask of the entries to write (either variable has a flag other than
+    1 / 2) and the characters to write there for each variable -- the new flag's character, or the previous one where
+    the new flag is 1 / 2 and a previous one exists.  (A previous character outside ``GHCN_TO_TWX_FLAGS_MAP`` is kept
+    as it is; the reference raises a KeyError there.)"""
+    flags = [np.asarray(flags_tmin), np.asarray(flags_tmax)]
+    prev = [np.asarray(prev_tmin, "S1"), np.asarray(prev_tmax, "S1")]
+    if not (flags[0].shape == flags[1].shape == prev[0].shape == prev[1].shape):
+        raise ValueError("flags and previous flags must have one shape")
+    plain = [(f == QA_OK) | (f == QA_MISSING) for f in flags]
+    rows = ~plain[0] | ~plain[1]
+    lut = np.zeros(256, "S1")
+    for num, ch in TWX_TO_GHCN_FLAGS_MAP.items():
+        lut[num] = ch.encode()
+    chars = []
+    for f, p, pl in zip(flags, prev, plain):
+        known = np.isin(f, list(TWX_TO_GHCN_FLAGS_MAP))
+        if not known.all():
+            raise ValueError("flag number %d has no character" % int(f[~known].ravel()[0]))
+        c = lut[f.astype(np.int64)]
+        keep = pl & (p != b"")
+        c[keep] = p[keep]
+        chars.append(c)
+    return rows, chars[0], chars[1]
+
+
+def write_qflags(path, cols, flags_tmin, flags_tmax):
+    """Apply ``merge_qflags`` to the database at ``path``: ``cols`` [ntarget] are the station columns of the flag arrays
+    [ndays, ntarget].  Only the rows ``merge_qflags`` names are changed.  Returns the number of (day, station) rows
+    written; raises ``KeyError`` if the database has no ``qflag_*`` variables."""
+    ds = ncio.open_dataset(path, "a")
+    try:
+        for name in QFLAG_VARS:
+            if name not in ds.variables:
+                raise KeyError("%s has no variable %s to write into" % (path, name))
+        v0, v1 = (ds.variables[name] for name in QFLAG_VARS)
+        prev0, prev1 = read_qflags(v0), read_qflags(v1)
+        n = 0
+        for k, j in enumerate(cols):
+            rows, c0, c1 = merge_qflags(flags_tmin[:, k], flags_tmax[:, k], prev0[:, j], prev1[:, j])
+            if not rows.any():
+                continue
+            for v, prev, c in ((v0, prev0, c0), (v1, prev1, c1)):
+                col = prev[:, j].copy()
+                col[rows] = c[rows]
+                v[:, int(j)] = col
+            n += int(rows.sum())
+    finally:
+        ds.close()
+    return n
+
+
+def _spatial(a, pool, targets, ids):
+    tm = {}
+    t0 = time.perf_counter()
+    f_tmin, f_tmax, det = run_qa_spatial_only(pool, targets, device=a.device, details=True, timing=tm)
+    sec = time.perf_counter() - t0
+    np.savez_compressed(a.out, ids=ids, ymd=np.asarray(pool.days[YMD], np.int32), flags_tmin=f_tmin, flags_tmax=f_tmax,
+                        status=det["status"])
+    line = {"stations": int(ids.size), "pool": int(pool.ids.size), "days": int(pool.days.size)}
+    for name, f in (("flags_tmin", f_tmin), ("flags_tmax", f_tmax)):
+        line[name] = {str(k): int((f == k).sum()) for k in (QA_OK, QA_MISSING, QA_SPATIAL_REGRESS, QA_SPATIAL_CORROB,
+                                                             QA_MEGA_INCONSIST)}
+    line["seconds"] = round(sec, 3)
+    for k in sorted(tm):
+        line[k] = round(tm[k], 3)
+    if a.write:
+        line["rows_written"] = write_qflags(a.db, [pool.idxs[s] for s in ids], f_tmin, f_tmax)
+    print(json.dumps(line), flush=True)
+    return 0
 
 
 def main(argv=None):
@@ -35,9 +131,23 @@ def main(argv=None):
     ap.add_argument("--out", required=True, help="report to write (.npz)")
     ap.add_argument("--targets", help="text file of station ids to check, one per line (default: every station)")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--spatial", action="store_true",
+                    help="run the whole spatial stage (regression, corroboration, mega-inconsistency) and report its flags")
+    ap.add_argument("--write", action="store_true", help="with --spatial: update qflag_tmin / qflag_tmax in the database")
     a = ap.parse_args(argv)
+    if a.write and not a.spatial:
+        ap.error("--write needs --spatial")
     try:
-        pool = StationObsPool.from_netcdf(a.db)
+        qflags = False
+        if a.spatial:
+            ds = ncio.open_dataset(a.db, "r")
+            try:
+                qflags = all(name in ds.variables for name in QFLAG_VARS)
+            finally:
+                ds.close()
+            if a.write and not qflags:
+                raise ValueError("no qflag_tmin / qflag_tmax variables to write into")
+        pool = StationObsPool.from_netcdf(a.db, qflags=True) if qflags else StationObsPool.from_netcdf(a.db)
         targets = None
         if a.targets:
             with open(a.targets) as fh:
@@ -48,11 +158,13 @@ def main(argv=None):
     except (IOError, OSError, ValueError, KeyError) as e:
         print("step08: cannot open %s: %s" % (a.db, e), file=sys.stderr)
         return 1
+    ids = pool.ids if targets is None else np.array(targets, dtype=str)
+    if a.spatial:
+        return _spatial(a, pool, targets, ids)
     tm = {}
     t0 = time.perf_counter()
     f_tmin, f_tmax, det = qa_spatial_regress(pool, targets, device=a.device, details=True, timing=tm)
     sec = time.perf_counter() - t0
-    ids = pool.ids if targets is None else np.array(targets, dtype=str)
     np.savez_compressed(a.out, ids=ids, ymd=np.asarray(pool.days[YMD], np.int32), flags_tmin=f_tmin, flags_tmax=f_tmax,
                         status=det["status"])
     print(json.dumps({"stations": int(ids.size), "pool": int(pool.ids.size), "items": int(det["status"].size),
