@@ -178,6 +178,56 @@ int twxqa_spatial_only(int device, int64_t nstn, int64_t ndays, const double *lo
                        const int32_t *target_idx, uint8_t *flag_tmin, uint8_t *flag_tmax, double *norms,
                        int32_t *status, float *kernel_ms, char *errbuf, int errlen);
 
+/* ---- step08's first run: the non-spatial checks (run_qa_non_spatial, qa_temp.py:172-216) ---- */
+/* Most values the gap check may sort for one calendar month: 31 per year the series touches, so 132 years.  A library
+ * limit without a reference counterpart: a workgroup of 4 waves sorts the month's values in LDS, 4 bytes each; at 4096
+ * values that is 16 KiB, and the 8 workgroups that fill the 32 wave slots of a compute unit take 128 KiB of its
+ * 160 KiB.  8192 values (32 KiB) would leave room for 5 workgroups.  The day-of-year rows of the outlier check are
+ * bounded by TWXQA_MAX_NORM_VALUES (136 years), so this cap is the one a long axis meets first.  A series that touches
+ * more years fails the call with a message, never a truncated month. */
+#define TWXQA_MAX_GAP_VALUES 4096
+#define TWXQA_NS_NKERNELS 8             /* kernel groups timed by the entry below */
+
+/*
+ * run_qa_non_spatial for nstn stations in one call; every station is checked on its own.  The checks run in the
+ * reference's order, each on the series without the observations every earlier check flagged; a check writes its number
+ * only where the flag is still 1; all decisions of one check are taken on the same snapshot.  In execution order:
+ *    2 missing: NaN.   3 naught: both variables round to -17.8 at one decimal (rintf(v * 10) / 10 in float32), or both
+ *   are 0.0.   4 duplicate year: per variable, two years of the axis with a value each whose first min(len, len) days
+ *   on the axis are all ==, by position.   6 duplicate months of one year, by position over the shorter; the month
+ *   NUMBER equal to (distinct months on the axis) - 1 is never the first of a pair (the reference's loop, kept: on a
+ *   12-month axis November and December are never compared).   5 the same calendar month of two years, by position.
+ *    7 a (year, month) with >= 10 days of Tmin == Tmax: the whole month, both variables.   8 below -89.4 or above 57.7
+ *   (float32).   9 a run of >= 20 equal values among the non-missing ones, ended by a different value (a run that
+ *   reaches the end of the series is not flagged: kept).   10 gap: per calendar month over all years, the sorted values,
+ *   numpy's float32 median; walking up from the median the first step >= 10.0 (float32 subtraction) gives a bound and
+ *   every value of the month >= it is flagged, likewise downwards; a step across the median of an even count is never
+ *   looked at (kept).   15 outlier: |(v - mean) / std| >= 6.0 against the day-of-year row of the day's own year (365- or
+ *   366-row table, windows and minimum count of the normals above); a row holds the biweight mean and the biweight
+ *   standard deviation sqrt(n sum (X - M)^2 (1 - u^2)^4) / |sum (1 - u^2)(1 - 5 u^2)|, or the plain mean and std(ddof = 1)
+ *   when MAD == 0; fp64 on the values widened exactly, both medians exact.   11 Tmin > Tmax: both.   13 spike / dip:
+ *   |cur - prev| >= 25 and |cur - next| >= 25 (float32) on adjacent days of the axis.   12 lagged range: day x with the
+ *   window x - 1 .. x + 1 clipped to the axis, a value of each variable somewhere in it: Tmax[x] >= warmest Tmin of the
+ *   window + 40 flags Tmax[x] and the whole window of Tmin; Tmin[x] <= coldest Tmax - 40 flags Tmin[x] and the whole
+ *   window of Tmax; compared in fp64 on the widened values.   18 mega-inconsistency as in the spatial stage above.
+ *
+ * Deviation from the reference: a row of >= 100 identical values has standard deviation 0; here it flags nothing (0 / 0);
+ * the reference divides by zero, which under step08's np.seterr drops all of that station's QA.
+ *
+ * tmin, tmax [nstn][ndays]   station-major float32, NaN = missing; not modified
+ * ymd [ndays]                consecutive calendar days, YYYYMMDD; need not start or end at a year boundary
+ * flag_tmin, flag_tmax [nstn][ndays]   out: the reference's numbers 1 .. 13, 15, 18
+ * norms (optional) [nstn][2][731][2]   out: mean and standard deviation of each row as the outlier check used them
+ *                            (variable 0 = tmin; the 365-row table, then the 366-row table; NaN: fewer than 100 values)
+ * kernel_ms (optional) [TWXQA_NS_NKERNELS]   device time: missing + naught, duplicates + impossible values, streaks,
+ *                            gaps, day-of-year rows, outliers + Tmin > Tmax, spike + lagged range, mega-inconsistency
+ * Call-level failures: non-consecutive days; a series that touches more than TWXQA_MAX_GAP_VALUES / 31 years (or more
+ * than TWXQA_MAX_NORM_VALUES / 15): the message names the macro.
+ */
+int twxqa_non_spatial(int device, int64_t nstn, int64_t ndays, const float *tmin, const float *tmax,
+                      const int32_t *ymd, uint8_t *flag_tmin, uint8_t *flag_tmax, double *norms, float *kernel_ms,
+                      char *errbuf, int errlen);
+
 #ifdef __cplusplus
 }
 #endif

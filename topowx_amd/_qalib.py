@@ -14,7 +14,8 @@ NTARGET = 13              # TWXQA_NTARGET: 12 monthly normals + the annual one
 PT_STRIDE = 29            # TWXQA_PT_STRIDE: lon, lat, elev, lst[13], norm[13]
 MAX_K = 159               # TWXQA_MAX_K
 STATUS_OK, STATUS_FEW_STATIONS, STATUS_SINGULAR = 0, 1, 4     # TWX_CELL_* numbers (include/twx.h)
-EXPORTS = ("twxqa_outlier_wls", "twxqa_spatial_nmonths", "twxqa_spatial_regress", "twxqa_doy_norms", "twxqa_spatial_only")
+EXPORTS = ("twxqa_outlier_wls", "twxqa_spatial_nmonths", "twxqa_spatial_regress", "twxqa_doy_norms", "twxqa_spatial_only",
+           "twxqa_non_spatial")
 # the spatial regression check (TWXQA_SP_* / TWXQA_* of include/twx_qa.h)
 MAX_RADIUS_NGH = 256      # TWXQA_MAX_RADIUS_NGH
 SP_OK, SP_FEW_NGHS, SP_DEGENERATE, SP_NGH_CAP, SP_FEW_DAYS, SP_FEW_VALID = 0, 1, 4, 7, 16, 17
@@ -24,6 +25,9 @@ MIN_NORM_VALUES = 100     # TWXQA_MIN_NORM_VALUES
 NORM_ROWS = 731           # TWXQA_NORM_ROWS: the 365-row table, then the 366-row table
 MAX_NORM_VALUES = 2048    # TWXQA_MAX_NORM_VALUES
 SPATIAL_ONLY_KERNELS = ("regress_radius", "regress_items", "radius_dist", "doy_norms", "corrob", "mega_final")
+# the non-spatial checks
+MAX_GAP_VALUES = 4096     # TWXQA_MAX_GAP_VALUES: 31 values per year of the series
+NON_SPATIAL_KERNELS = ("init", "dups", "streak", "gap", "norms", "clim", "spike_lagrange", "mega")     # TWXQA_NS_NKERNELS
 
 _LIB = None
 
@@ -53,6 +57,8 @@ def load():
         L.twxqa_spatial_only.restype = C.c_int
         L.twxqa_spatial_only.argtypes = [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64] + \
             [C.c_void_p] * 6 + [C.c_char_p, C.c_int]
+        L.twxqa_non_spatial.restype = C.c_int
+        L.twxqa_non_spatial.argtypes = [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 7 + [C.c_char_p, C.c_int]
         _LIB = L
     return _LIB
 
@@ -188,3 +194,29 @@ def spatial_only(lon, lat, tmin, tmax, ymd, target_idx, device=0, timing=None):
         for k, name in enumerate(SPATIAL_ONLY_KERNELS):
             timing[name + "_kernel_ms"] = float(ms[k])
     return fmin, fmax, norms, status
+
+
+def non_spatial(tmin, tmax, ymd, device=0, details=False, timing=None):
+    """``twxqa_non_spatial``: ``run_qa_non_spatial`` (qa_temp.py:172-216) of every station on its own.  tmin, tmax
+    [nstn, ndays] float32, station-major, NaN = missing; ymd [ndays] consecutive days.  Returns (flag_tmin, flag_tmax),
+    each uint8 [nstn, ndays] in the reference's numbering (1 .. 13, 15, 18); with ``details`` also norms
+    [nstn, 2, 731, 2]: mean and standard deviation of the day-of-year rows as the outlier check used them.  ``timing``
+    receives ``<kernel>_kernel_ms`` for the names in ``NON_SPATIAL_KERNELS``."""
+    L = load()
+    tmin, tmax, ymd = _c(tmin, np.float32), _c(tmax, np.float32), _c(ymd, np.int32)
+    if tmin.ndim != 2 or tmax.shape != tmin.shape or ymd.ndim != 1 or tmin.shape[1] != ymd.size:
+        raise ValueError("tmin / tmax must be [nstn, ndays] and ymd [ndays]")
+    nstn, ndays = tmin.shape
+    buf = C.create_string_buffer(512)
+    fmin, fmax = np.zeros((nstn, ndays), np.uint8), np.zeros((nstn, ndays), np.uint8)
+    norms = np.empty((nstn, 2, NORM_ROWS, 2)) if details else None
+    ms = (C.c_float * len(NON_SPATIAL_KERNELS))()
+    rc = L.twxqa_non_spatial(int(device), nstn, ndays, tmin.ctypes.data, tmax.ctypes.data, ymd.ctypes.data,
+                             fmin.ctypes.data, fmax.ctypes.data, norms.ctypes.data if details else None, C.addressof(ms),
+                             buf, 512)
+    if rc != 0:
+        raise QaError("twxqa_non_spatial failed: %s" % buf.value.decode(errors="replace"))
+    if timing is not None:
+        for k, name in enumerate(NON_SPATIAL_KERNELS):
+            timing[name + "_kernel_ms"] = float(ms[k])
+    return (fmin, fmax, norms) if details else (fmin, fmax)

@@ -1,18 +1,22 @@
-"""step08's spatial checks of the daily Tmin / Tmax observations on the GPU: the flag and threshold constants of the
+"""step08's checks of the daily Tmin / Tmax observations on the GPU: the flag and threshold constants of the
 reference, a small in-memory pool of raw observations, ``qa_spatial_regress`` (``_qa_spatial_regress``,
 twx/qa/qa_temp.py:688-738, 858-1015: one batched call of libtwxqa's ``twxqa_spatial_regress`` over all target stations),
 ``run_qa_spatial_only`` (qa_temp.py:218-258: the regression check, the corroboration check and the mega-inconsistency
-check, ``twxqa_spatial_only``) and ``doy_norms`` (the day-of-year normals the corroboration check compares against).
-There is no CPU fallback: without the library the calls raise.
+check, ``twxqa_spatial_only``), ``doy_norms`` (the day-of-year normals the corroboration check compares against) and
+``run_qa_non_spatial`` (qa_temp.py:172-216: the fourteen checks of step08's first run, every station on its own,
+``twxqa_non_spatial``).  There is no CPU fallback: without the library the calls raise.
 
-Out of scope here: the non-spatial checks.  Writing flags into a database is ``topowx_amd.step08``.
+Out of scope here: ``run_qa_all`` (step08 never calls it).  Writing flags into a database is ``topowx_amd.step08``.
 """
 import numpy as np
 
 from .. import _qalib, ncio
 from ..dates import YMD
 
-__all__ = ["StationObsPool", "qa_spatial_regress", "run_qa_spatial_only", "doy_norms", "ITEM_STATUS", "QA_SPATIAL_CORROB",
+__all__ = ["StationObsPool", "qa_spatial_regress", "run_qa_spatial_only", "run_qa_non_spatial", "doy_norms", "ITEM_STATUS",
+           "QA_NAUGHT", "QA_DUP_YEAR", "QA_DUP_MONTH", "QA_DUP_YEAR_MONTH", "QA_DUP_WITHIN_MONTH", "QA_IMPOSS_VALUE",
+           "QA_STREAK", "QA_GAP", "QA_INTERNAL_INCONSIST", "QA_LAGRANGE_INCONSIST", "QA_SPIKE_DIP", "QA_CLIM_OUTLIER",
+           "NON_SPATIAL_FLAGS", "QA_SPATIAL_CORROB",
            "QA_MEGA_INCONSIST", "ANOMALY_CUTOFF", "MIN_NORM_VALUES", "GHCN_TO_TWX_FLAGS_MAP", "QA_OK", "QA_MISSING", "QA_SPATIAL_REGRESS", "NGH_RADIUS",
            "NGH_CORR", "NGH_RESID_CUTOFF", "NGH_RESID_STD_CUTOFF", "MIN_DAYS_MTH_WINDOW", "MIN_NGHS", "MAX_NGHS",
            "TWX_TO_GHCN_FLAGS_MAP"]
@@ -36,6 +40,11 @@ QA_CLIM_OUTLIER = 15
 QA_SPATIAL_REGRESS = 16
 QA_SPATIAL_CORROB = 17
 QA_MEGA_INCONSIST = 18    # (the reference assigns 14, then 18: 18 is what its module holds)
+
+# the numbers a non-spatial run can produce, in the order its checks run (qa_temp.py:202-214, 288-291)
+NON_SPATIAL_FLAGS = (QA_MISSING, QA_NAUGHT, QA_DUP_YEAR, QA_DUP_YEAR_MONTH, QA_DUP_MONTH, QA_DUP_WITHIN_MONTH, QA_IMPOSS_VALUE,
+                     QA_STREAK, QA_GAP, QA_CLIM_OUTLIER, QA_INTERNAL_INCONSIST, QA_SPIKE_DIP, QA_LAGRANGE_INCONSIST,
+                     QA_MEGA_INCONSIST)
 
 # thresholds of the spatial checks (qa_temp.py:65-73)
 NGH_RADIUS = 75.0
@@ -114,6 +123,12 @@ class StationObsPool(object):
     def run_qa_spatial_only(self, targets=None, device=0, details=False, timing=None):
         return run_qa_spatial_only(self, targets, device, details, timing)
 
+    def run_qa_non_spatial(self, targets=None, device=0, details=False, timing=None):
+        """``run_qa_non_spatial`` of the columns of ``targets`` (station ids; default: every station): ``(flags_tmin,
+        flags_tmax)`` [ndays, ntarget], with ``details=True`` also the dict of ``norms`` [ntarget, 2, 731, 2]."""
+        cols = _target_rows(self, targets)
+        return run_qa_non_spatial(self.tmin[:, cols], self.tmax[:, cols], self.days, device, details, timing)
+
 
 def read_qflags(var):
     """A quality-flag variable as ``"S1"`` [ndays, n]: ``b""`` where no flag is set (a NUL or blank character, a
@@ -148,6 +163,29 @@ def doy_norms(series, days, device=0):
     out = _qalib.doy_norms(np.ascontiguousarray(np.atleast_2d(a.T if not one else a)), days[YMD], device=device)
     n365, n366 = np.ascontiguousarray(out[:, :365].T), np.ascontiguousarray(out[:, 365:].T)
     return (n365[:, 0], n366[:, 0]) if one else (n365, n366)
+
+
+def run_qa_non_spatial(tmin, tmax, days, device=0, details=False, timing=None):
+    """``run_qa_non_spatial`` (qa_temp.py:172-216) on the GPU: ``tmin`` / ``tmax`` [ndays] (the reference's signature) or
+    [ndays, n], NaN = missing, ``days`` from ``get_days_metadata``; every column is a station checked on its own, all
+    in one call.  The checks in order: missing, naught, duplicate years / months of a year / calendar months / Tmin ==
+    Tmax months, impossible values, streaks, gaps, climatological outliers, Tmin > Tmax, spikes, lagged range,
+    mega-inconsistency; each sees the series without what the earlier ones flagged.  Returns ``(flags_tmin,
+    flags_tmax)`` as uint8 of the inputs' shape in the reference's numbering (``NON_SPATIAL_FLAGS`` and ``QA_OK``).  With
+    ``details=True`` a third value: a dict of ``norms`` [n, 2, 731, 2] ([2, 731, 2] for a 1-d series): mean and
+    standard deviation of the day-of-year rows (variable 0 = tmin, the 365-row table then the 366-row table) as the
+    outlier check used them.  ``timing`` (a dict) receives the device time of each kernel group.  The inputs are not
+    modified."""
+    a, b = np.asarray(tmin, np.float32), np.asarray(tmax, np.float32)
+    if a.shape != b.shape or a.ndim not in (1, 2) or a.shape[0] != days.size:
+        raise ValueError("tmin / tmax must be [ndays] or [ndays, n], with the days of ``days``")
+    one = a.ndim == 1
+    a2, b2 = (np.ascontiguousarray(np.atleast_2d(x) if one else x.T) for x in (a, b))
+    res = _qalib.non_spatial(a2, b2, days[YMD], device=device, details=details, timing=timing)
+    out = [res[0][0].copy(), res[1][0].copy()] if one else [np.ascontiguousarray(res[0].T), np.ascontiguousarray(res[1].T)]
+    if details:
+        out.append({"norms": res[2][0] if one else res[2]})
+    return tuple(out)
 
 
 def run_qa_spatial_only(pool, targets=None, device=0, details=False, timing=None):

@@ -1,5 +1,5 @@
-"""The spatial quality checks of ``scripts/step08_mpi_qa_stn_obs.py --spatial``: a report by default, the whole stage
-with ``--spatial``, and the ``qflag_*`` update with ``--spatial --write``.
+"""The quality checks of ``scripts/step08_mpi_qa_stn_obs.py``: its first run with ``--nonspatial``, its second with
+``--spatial``, the ``qflag_*`` update of either with ``--write``, and a report of the regression check alone by default.
 
 Every station of an all-stations database (or the ``--targets`` subset) is checked against the stations within 75 km
 in one batched GPU call instead of the reference's MPI farm over stations.
@@ -26,8 +26,18 @@ variable carries a flag other than 1 or 2; both variables are written on every s
 ``TWX_TO_GHCN_FLAGS_MAP``; a previous non-empty flag is kept wherever the new flag is 1 or 2.  A database without the
 ``qflag_*`` variables gives exit 1 and a message.
 
-Out of scope: the refresh of the observation counts after the write (the reference's ``add_obs_cnt``), and the
-non-spatial checks.
+``--nonspatial``: the reference's ``run_qa_non_spatial`` (qa_temp.py:172-216; ``topowx_amd.qa.run_qa_non_spatial``),
+the run that comes first: missing, naught, the duplicate checks, impossible values, streaks, gaps, climatological
+outliers, Tmin > Tmax, spikes, lagged range and mega-inconsistency of every station on its own.  Observations that
+already carry a flag are set to NaN first, as above.  The report holds ``flags_tmin`` / ``flags_tmax`` (1 .. 13, 15, 18);
+the JSON line counts every flag number per variable.  ``--nonspatial --write`` updates the ``qflag_*`` variables by the
+same rules as ``--spatial --write``; a later ``--spatial`` run then reads those observations as NaN.
+
+    python -m topowx_amd.step08 --db all.nc --out report.npz --nonspatial [--write] [--targets ids.txt]
+    python -m topowx_amd.step08 --db all.nc --out report.npz --spatial [--write] [--targets ids.txt]
+
+Out of scope: the refresh of the observation counts after the write (the reference's ``add_obs_cnt``), the reference's
+filter of stations by data provider (use ``--targets``), and ``run_qa_all``, which step08 never calls.
 
 Exits with 1 if the database cannot be opened, a target is unknown, or ``--write`` has nothing to write into.
 """
@@ -40,8 +50,8 @@ import numpy as np
 
 from . import ncio
 from .dates import YMD
-from .qa import (QA_MEGA_INCONSIST, QA_MISSING, QA_OK, QA_SPATIAL_CORROB, QA_SPATIAL_REGRESS, TWX_TO_GHCN_FLAGS_MAP,
-                 StationObsPool, qa_spatial_regress, run_qa_spatial_only)
+from .qa import (NON_SPATIAL_FLAGS, QA_MEGA_INCONSIST, QA_MISSING, QA_OK, QA_SPATIAL_CORROB, QA_SPATIAL_REGRESS,
+                 TWX_TO_GHCN_FLAGS_MAP, StationObsPool, qa_spatial_regress, run_qa_non_spatial, run_qa_spatial_only)
 from .qa.qa_temp import read_qflags
 
 __all__ = ["main", "merge_qflags", "write_qflags"]
@@ -123,23 +133,48 @@ def _spatial(a, pool, targets, ids):
     return 0
 
 
+def _nonspatial(a, pool, targets, ids):
+    tm = {}
+    cols = [pool.idxs[s] for s in ids]
+    t0 = time.perf_counter()
+    f_tmin, f_tmax = run_qa_non_spatial(pool.tmin[:, cols], pool.tmax[:, cols], pool.days, device=a.device, timing=tm)
+    sec = time.perf_counter() - t0
+    np.savez_compressed(a.out, ids=ids, ymd=np.asarray(pool.days[YMD], np.int32), flags_tmin=f_tmin, flags_tmax=f_tmax)
+    line = {"stations": int(ids.size), "pool": int(pool.ids.size), "days": int(pool.days.size)}
+    for name, f in (("flags_tmin", f_tmin), ("flags_tmax", f_tmax)):
+        line[name] = {str(k): int((f == k).sum()) for k in (QA_OK,) + NON_SPATIAL_FLAGS}
+    line["seconds"] = round(sec, 3)
+    for k in sorted(tm):
+        line[k] = round(tm[k], 3)
+    if a.write:
+        line["rows_written"] = write_qflags(a.db, cols, f_tmin, f_tmax)
+    print(json.dumps(line), flush=True)
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m topowx_amd.step08",
-                                 description="step08's spatial regression check of daily Tmin / Tmax: a report of the "
-                                             "flags, nothing is written into the database")
+                                 description="step08's quality checks of daily Tmin / Tmax: by default a report of the "
+                                             "spatial regression check's flags; --nonspatial and --spatial run the "
+                                             "reference's two runs, --write puts their flags into the database")
     ap.add_argument("--db", required=True, help="all-stations database (netCDF): tmin / tmax on (time, station_id)")
     ap.add_argument("--out", required=True, help="report to write (.npz)")
     ap.add_argument("--targets", help="text file of station ids to check, one per line (default: every station)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--spatial", action="store_true",
                     help="run the whole spatial stage (regression, corroboration, mega-inconsistency) and report its flags")
-    ap.add_argument("--write", action="store_true", help="with --spatial: update qflag_tmin / qflag_tmax in the database")
+    ap.add_argument("--nonspatial", action="store_true",
+                    help="run the non-spatial checks of step08's first run and report their flags")
+    ap.add_argument("--write", action="store_true",
+                    help="with --spatial or --nonspatial: update qflag_tmin / qflag_tmax in the database")
     a = ap.parse_args(argv)
-    if a.write and not a.spatial:
-        ap.error("--write needs --spatial")
+    if a.spatial and a.nonspatial:
+        ap.error("--spatial and --nonspatial exclude each other")
+    if a.write and not (a.spatial or a.nonspatial):
+        ap.error("--write needs --spatial or --nonspatial")
     try:
         qflags = False
-        if a.spatial:
+        if a.spatial or a.nonspatial:
             ds = ncio.open_dataset(a.db, "r")
             try:
                 qflags = all(name in ds.variables for name in QFLAG_VARS)
@@ -161,6 +196,8 @@ def main(argv=None):
     ids = pool.ids if targets is None else np.array(targets, dtype=str)
     if a.spatial:
         return _spatial(a, pool, targets, ids)
+    if a.nonspatial:
+        return _nonspatial(a, pool, targets, ids)
     tm = {}
     t0 = time.perf_counter()
     f_tmin, f_tmax, det = qa_spatial_regress(pool, targets, device=a.device, details=True, timing=tm)
