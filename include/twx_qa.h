@@ -228,6 +228,91 @@ int twxqa_non_spatial(int device, int64_t nstn, int64_t ndays, const float *tmin
                       const int32_t *ymd, uint8_t *flag_tmin, uint8_t *flag_tmax, double *norms, float *kernel_ms,
                       char *errbuf, int errlen);
 
+/* ---- the neighbour matrices of the infill family (step14 / step15 / step16): _InfillMatrix.__init__, the widening
+ * loop of _InfillMatrix.infill and _shrink_matrix (twx/infill/infill_normals.py:52-237, 239-299, 324-343, 391-420) ---- */
+#define TWXIF_RING_KM 37.5              /* MAX_DISTANCE / 2: the width of every ring after the first (75 km) */
+#define TWXIF_MIN_POR_OVERLAP (2.0 / 3.0)   /* MIN_POR_OVERLAP */
+#define TWXIF_BESTNGH_MIN_IOA 0.7       /* infill_normals.py:184 */
+#define TWXIF_MAX_COLS_NORM_IMPUTE 31   /* MAX_COLS_NORM_IMPUTE: the target's column and at most 30 stations */
+#define TWXIF_MAX_GROUPS 12             /* day groups of one call (step14: the calendar months) */
+#define TWXIF_MAX_MIN_NNGHS 16          /* largest min_daily_nnghs (the reference's default is 3) */
+#define TWXIF_NKERNELS 4                /* kernel groups timed by the entry below */
+#define TWXIF_NTIMES 6                  /* entries of kernel_ms: the kernel groups, then two host-clock figures */
+/* The ring of a target and the ranked list of an item hold at most TWXQA_MAX_RADIUS_NGH (256) stations.  A library limit
+ * without a reference counterpart: the item kernel keeps the ranked list (28 bytes per station), the ring with its pair
+ * results (28 bytes) and the sorted rows (4 bytes) in LDS, plus 1 KiB of reduction scratch: 16 KiB per workgroup of 4
+ * waves at 256, and the 8 workgroups that fill the 32 wave slots of a compute unit take 128 KiB of its 160 KiB; 512
+ * would take 31 KiB and leave room for 5 workgroups.  An item above it gets TWXIF_NGH_CAP and an empty list, never a
+ * truncated one. */
+
+/* per-(target, group) item status */
+#define TWXIF_OK TWX_CELL_OK                      /* every day of the item has min_daily_nnghs neighbour observations */
+#define TWXIF_NUMERIC TWX_CELL_NUMERIC            /* a pair the reference would rank has a d1 denominator of 0 (it raises
+                                                     under step14's np.seterr); the list is empty */
+#define TWXIF_NGH_CAP TWX_CELL_CAND_OVERFLOW      /* a ring or the ranked list above TWXQA_MAX_RADIUS_NGH; the list is empty */
+#define TWXIF_NO_TARGET_OBS 18                    /* the target has no finite day in the item (nthres_target_por == 0); the
+                                                     reference takes the mean of an empty slice and loses the station */
+#define TWXIF_UNSATISFIED 19                      /* no eligible station is left beyond max_dist and some day still has
+                                                     fewer observations (the reference loops forever, :124-126); the ranked
+                                                     list as far as it got, keep all 0, nnghs as the loop left it */
+
+/*
+ * For every target and day group g (an item; its days are those with group[day] == g):
+ *   1. ring 1 is the eligible stations (the target left out by index) with haversine distance (util_geo.py:24-40, fp64)
+ *      in [0, 75] km; an empty ring's outer radius grows by 37.5 km until it holds a station, and the grown radius is the
+ *      item's max_dist.  Stations are taken in ascending distance, equal distances in table order.
+ *   2. a ring station with nlap (its finite days of the item) >= nthres_all and nlap_stn (days finite in both series) >=
+ *      nthres_target_por is ranked with ioa = d1(o = target, p = neighbour) over the overlap (perf_metrics.py:59-62).  In
+ *      ring 1 only, a station that misses nthres_all but reaches nthres_target_por is the best-neighbour candidate if its
+ *      ioa is strictly above every earlier candidate's (and 0); the last candidate is ranked only if no ranked station of
+ *      the ring has a larger ioa and its ioa is >= 0.7.
+ *   3. the ranked stations are ordered by ioa descending, over all rings taken so far (equal ioa: the larger distance
+ *      first, then table order; the reference's order is undefined there).
+ *   4. nnghs starts at min_daily_nnghs.  While fewer than nnghs stations are ranked, the next ring (max_dist,
+ *      max_dist + 37.5] is taken (grown likewise); else while some day of the item has fewer than min_daily_nnghs finite
+ *      values among the first nnghs ranked stations, nnghs grows by one.  nnghs is never reset.
+ *   5. of the first nnghs ranked stations the first min_daily_nnghs are kept, a later one only if it has a finite value
+ *      on a day with fewer than min_daily_nnghs finite values among the stations kept before it (_shrink_matrix).
+ * fp64 on the float32 observations widened exactly; every sum runs in a fixed order: two calls give the same bytes.
+ * Not done here: the reanalysis columns, the cut to TWXIF_MAX_COLS_NORM_IMPUTE columns (the caller's, on keep), em.norm.
+ *
+ * lon, lat [nstn]            finite
+ * obs [nstn][ndays]          station-major float32 of one variable, NaN (any non-finite value) = missing
+ * ymd [ndays]                consecutive calendar days, YYYYMMDD
+ * eligible [nstn]            the reference's stns_mask: 0 = never a neighbour
+ * target_idx [ntarget]       0 <= index < nstn
+ * group [ndays]              -1 (day not used) or 0 .. ngroups - 1, ngroups <= TWXIF_MAX_GROUPS
+ * nthres_all [ngroups], nthres_target_por [ntarget][ngroups]
+ *                            np.round(2 / 3 * days of the item) and np.round(2 / 3 * finite target days of the item), the
+ *                            caller's (infill_normals.py:110-115); nthres_target_por == 0 marks a target without a finite
+ *                            day (round(2 / 3 n) >= 1 for n >= 1)
+ * status, nnghs [ntarget][ngroups], max_dist [ntarget][ngroups]       out; for an item that did not end TWXIF_OK nnghs is
+ *                            what the loop had reached and max_dist the last ring taken (NaN: none)
+ * csr_off [ntarget * ngroups + 1]   out: the ranked list of item i is csr_off[i] .. csr_off[i + 1]
+ * ngh_idx, ngh_ioa, ngh_dist, ngh_nlap, ngh_nlap_stn, keep [csr_cap]   out: pool row, ioa, distance, nlap, nlap_stn, and 1
+ *                            where the station is among the first nnghs and survived the shrink (status TWXIF_OK only);
+ *                            ntarget * ngroups * TWXQA_MAX_RADIUS_NGH entries always suffice, fewer fail the call if the
+ *                            lists need more
+ * nrounds (optional)         out: the rings the host ran (the largest number any item took, + 1 if some item ended
+ *                            unsatisfied)
+ * kernel_ms (optional) [TWXIF_NTIMES]   device time over all rounds: rings, pairs, items, the CSR gather; then host-clock
+ *                            milliseconds of the allocations and copies to the device before the first round, and of
+ *                            the copies back after the last (the gather kernel left out)
+ * Failure order within a ring: the stations are scanned in ascending distance and the first that fails decides the item:
+ * a zero d1 denominator at a station that would be ranked or weighed as a candidate (TWXIF_NUMERIC), or a station that
+ * would be entry TWXQA_MAX_RADIUS_NGH + 1 of the list (TWXIF_NGH_CAP); at one station the denominator is looked at first.
+ * A ring above the cap is TWXIF_NGH_CAP before any of its stations is looked at.
+ * Call-level failures: non-consecutive days, an index out of range, a group value outside -1 .. ngroups - 1, a non-finite
+ * longitude / latitude.
+ */
+int twxif_infill_matrix(int device, int64_t nstn, int64_t ndays, const double *lon, const double *lat, const float *obs,
+                        const int32_t *ymd, const uint8_t *eligible, int64_t ntarget, const int32_t *target_idx,
+                        int32_t ngroups, const int8_t *group, const int32_t *nthres_all,
+                        const int32_t *nthres_target_por, int32_t min_daily_nnghs, int32_t *status, int32_t *nnghs,
+                        double *max_dist, int64_t *csr_off, int64_t csr_cap, int32_t *ngh_idx, double *ngh_ioa,
+                        double *ngh_dist, int32_t *ngh_nlap, int32_t *ngh_nlap_stn, uint8_t *keep, int32_t *nrounds,
+                        float *kernel_ms, char *errbuf, int errlen);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,302 @@
+"""GPU: the infill neighbour matrices (``twxif_infill_matrix``; ``topowx_amd.infill``) against the executed-reference
+golden, against the numpy restatement on random pools and on the smallest shapes that can still go wrong, twice for
+determinism, and through the facade and the command line.
+
+Integers, ranked rows, ``keep``, status and ``max_dist`` are compared exactly; ioa to 1e-10: a d1 sum has at most 25 203
+terms, so re-ordering moves it by at most about n 2^-53 = 3e-12 relative; 1e-10 leaves a factor 30, and the decision
+margins asserted by the golden maker (and below which a random item is left out) are 10 times that.  Distances to the
+tolerance of the other radius tests."""
+import datetime as dt
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from topowx_amd import h5nc
+from topowx_amd.dates import MONTH, get_days_metadata
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import restate_infillmat as RI  # noqa: E402
+from spatial_cases import TOL  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+IOA_TOL = 1e-10
+MAX_KNIFE = 1e-3
+CAP = 256
+
+
+def make_pool(lon, lat, tmin, first=dt.date(2001, 1, 1)):
+    from topowx_amd.qa import StationObsPool
+    tmin = np.asarray(tmin, np.float32)
+    days = get_days_metadata(first, first + dt.timedelta(days=tmin.shape[0] - 1))
+    ids = np.array(["S%04d" % i for i in range(tmin.shape[1])])
+    return StationObsPool(ids, lon, lat, tmin, tmin + 10, days)
+
+
+def compare(got, want, skip=None):
+    """``got``: an InfillMatrices; ``want``: the restatement's dict; ``skip`` [nt, G]: items left out."""
+    nt, G = want["status"].shape
+    skip = np.zeros((nt, G), bool) if skip is None else skip
+    use = ~skip
+    assert got.status.shape == (nt, G)
+    assert np.array_equal(got.nthres_all, want["nthres_all"]) and np.array_equal(got.nthres_target_por, want["nthres_target_por"])
+    for k in ("status", "nnghs"):
+        bad = np.argwhere((getattr(got, k) != want[k]) & use)
+        assert bad.size == 0, (k, bad[:5].tolist(), getattr(got, k)[tuple(bad[0])], want[k][tuple(bad[0])])
+    assert np.array_equal(got.max_dist[use], want["max_dist"][use], equal_nan=True)
+    worst = 0.0
+    for i in np.nonzero(use.ravel())[0]:
+        a, b = slice(int(got.off[i]), int(got.off[i + 1])), slice(int(want["off"][i]), int(want["off"][i + 1]))
+        for k in ("idx", "keep", "nlap", "nlap_stn"):
+            assert np.array_equal(getattr(got, k)[a], want[k][b]), (k, divmod(int(i), G), getattr(got, k)[a], want[k][b])
+        if b.stop > b.start:
+            worst = max(worst, float(np.abs(got.ioa[a] - want["ioa"][b]).max()))
+            assert np.abs(got.dist[a] - want["dist"][b]).max() <= TOL
+    print("max |ioa - expected| %.3g over %d items" % (worst, int(use.sum())))
+    assert worst <= IOA_TOL
+
+
+@pytest.fixture(scope="module")
+def gold():
+    return np.load(os.path.join(ROOT, "tests", "golden", "golden_infillmat_v1.npz"))
+
+
+@pytest.fixture(scope="module")
+def case(gold):
+    import make_golden_infillmat as mk
+    ids, lon, lat, tmin, days = mk.case_inputs()
+    assert mk.input_hash(ids, lon, lat, tmin, days) == str(gold["input_hash"]), "synthetic generator drifted: regenerate the golden"
+    from topowx_amd.qa import StationObsPool
+    return StationObsPool(ids, lon, lat, tmin, tmin + 10, days)
+
+
+@pytest.fixture(scope="module")
+def built(case):
+    from topowx_amd.infill import build_infill_matrices
+    tm = {}
+    m = build_infill_matrices(case, "tmin", timing=tm)
+    return m, tm
+
+
+def test_golden(gold, case, built):
+    import make_golden_infillmat as mk
+    m, tm = built
+    assert (m.status == 0).all() and m.ngroups == 12 and m.rounds == int(gold["nrings"].max())
+    assert sorted(tm) == ["compact_kernel_ms", "download_ms", "item_kernel_ms", "library_s", "pair_kernel_ms", "ring_kernel_ms",
+                          "rounds", "thresholds_s", "transpose_s", "upload_ms"]
+    assert np.array_equal(m.nnghs, gold["nnghs"]) and np.array_equal(m.max_dist, gold["max_dist"])
+    assert np.array_equal(m.off, gold["off"]) and np.array_equal(m.idx, gold["idx"]) and np.array_equal(m.keep, gold["keep"])
+    print("max |ioa - golden| %.3g, max |dist - golden| %.3g" % (np.abs(m.ioa - gold["ioa"]).max(),
+                                                                  np.abs(m.dist - gold["dist"]).max()))
+    assert np.abs(m.ioa - gold["ioa"]).max() <= IOA_TOL and np.abs(m.dist - gold["dist"]).max() <= TOL
+    for t in range(48):
+        for g in range(12):
+            a = m.matrix(t, g)
+            assert a.dtype == np.float64 and a.shape[1] == 1 + gold["matrix_ncols"][t, g]
+            assert np.array_equal(a[:, 0], case.tmin[case.days[MONTH] == g + 1, t].astype(np.float64), equal_nan=True)
+            assert np.array_equal(mk.matrix_hash(a[:, 1:]), gold["matrix_hash"][t, g]), (t, g)
+    for t, g in gold["full_items"]:
+        assert np.array_equal(m.matrix(case.ids[t], g)[:, 1:], gold["full_%d_%d" % (t, g)].astype(np.float64), equal_nan=True)
+
+
+def test_two_calls_give_the_same_bytes(case, built):
+    from topowx_amd.infill import build_infill_matrices
+    again = build_infill_matrices(case, "tmin")
+    for k in ("status", "nnghs", "max_dist", "off", "idx", "ioa", "dist", "nlap", "nlap_stn", "keep"):
+        assert getattr(again, k).tobytes() == getattr(built[0], k).tobytes(), k
+
+
+def random_pool(seed, n, first, last, box=(3.0, 2.0)):
+    rs = np.random.RandomState(seed)
+    days = get_days_metadata(first, last)
+    nd = days.size
+    lon, lat = -110.0 + box[0] * rs.rand(n), 44.0 + box[1] * rs.rand(n)
+    lon[-3:] += 6.0                                                # a few far away: wide rings
+    t = np.arange(nd)
+    reg, e = np.zeros(nd), rs.randn(nd) * 3.0
+    for i in range(1, nd):
+        reg[i] = 0.7 * reg[i - 1] + e[i]
+    tmin = -12.0 * np.cos(2 * np.pi * (t - 15) / 365.25)[:, None] + reg[:, None] + rs.randn(n)[None, :] * 2 + \
+        rs.randn(nd, n) * (0.5 + 2.0 * rs.rand(n))[None, :]
+    tmin = np.round(tmin, 1)
+    tmin[rs.rand(nd, n) < 0.08] = np.nan
+    for s in range(0, n, 3):                                       # long gaps and short records
+        a = int(rs.randint(0, nd))
+        tmin[a:a + int(rs.randint(nd // 10, nd // 2)), s] = np.nan
+    for s in range(1, n, 7):
+        tmin[:nd // 2 + int(rs.randint(-20, 20)), s] = np.nan
+    from topowx_amd.qa import StationObsPool
+    ids = np.array(["R%05d" % i for i in range(n)])
+    return StationObsPool(ids, lon, lat, tmin.astype(np.float32), (tmin + 10).astype(np.float32), days), rs
+
+
+RANDOM = {"300x8y": (11, 300, dt.date(1996, 1, 1), dt.date(2003, 12, 31), None, 40),
+          "mid_year_axis": (12, 80, dt.date(2001, 3, 15), dt.date(2004, 10, 2), None, 30),
+          "one_group": (13, 80, dt.date(2001, 1, 1), dt.date(2003, 12, 31), "all", 30)}
+
+
+@pytest.mark.parametrize("name", sorted(RANDOM))
+def test_restatement_on_random_pools(name):
+    from topowx_amd.infill import build_infill_matrices
+    seed, n, first, last, groups, ntarget = RANDOM[name]
+    pool, rs = random_pool(seed, n, first, last)
+    mask = rs.rand(n) < 0.9
+    targets = np.sort(rs.choice(n, ntarget, replace=False))
+    grp = np.zeros(pool.days.size, np.int8) if groups == "all" else (pool.days[MONTH] - 1).astype(np.int8)
+    want = RI.run(pool.lon, pool.lat, pool.tmin, mask, targets, grp)
+    skip = RI.knife(want)
+    print("%s: %d of %d items left out as knife-edge; statuses %s; rings up to %d" % (
+        name, int(skip.sum()), skip.size, np.unique(want["status"]).tolist(), int(want["nrings"].max())))
+    assert skip.sum() <= MAX_KNIFE * skip.size
+    assert (want["status"] == 0).sum() > 0.9 * skip.size and want["nnghs"].max() > 3 and want["nrings"].max() > 1
+    got = build_infill_matrices(pool, "tmin", pool.ids[targets], mask, groups)
+    compare(got, want, skip)
+    t = 0
+    for g in range(want["status"].shape[1]):
+        if not skip[t, g]:
+            assert np.array_equal(got.matrix(t, g), RI.matrix(pool.tmin, grp, want, targets, t, g), equal_nan=True)
+
+
+def line(n, nd=40, step=0.1, seed=3, lon0=-110.0):
+    """n stations on a parallel, ``step`` degrees apart (about 7.9 km at 45 N), a common signal plus noise, no gaps."""
+    rs = np.random.RandomState(seed)
+    sig = rs.randn(nd) * 5
+    return lon0 + step * np.arange(n), np.full(n, 45.0), np.round(sig[:, None] + rs.randn(nd, n), 1)
+
+
+def small_cases():
+    out = {}
+    lon, lat, t = line(6)
+    g0 = np.zeros(40, np.int8)
+    out["three_eligible"] = (lon, lat, t, np.array([1, 1, 1, 1, 0, 0], bool), [0], g0, [RI.OK])
+    out["two_eligible_unsatisfied"] = (lon, lat, t, np.array([1, 1, 1, 0, 0, 0], bool), [0], g0, [RI.UNSATISFIED])
+    out["nobody_eligible"] = (lon, lat, t, np.zeros(6, bool), [0, 3], g0, [RI.UNSATISFIED] * 2)
+    g = np.full(40, -1, np.int8)
+    g[17], g[18:] = 0, 1
+    out["item_of_one_day"] = (lon, lat, t, np.ones(6, bool), [0, 5], g, [RI.OK] * 4)
+    lon, lat, t = line(12, nd=333, seed=5)                          # 333 days: not a multiple of 64 or of 256
+    t[np.random.RandomState(6).rand(333, 12) < 0.3] = np.nan
+    out["days_not_a_multiple_of_64"] = (lon, lat, t, np.ones(12, bool), [0, 4, 11], np.zeros(333, np.int8), [RI.OK] * 3)
+    for n in (64, 65):                                               # a ring of exactly 64 / 65 stations
+        lon, lat, t = line(n + 1, step=0.005, seed=n)
+        t[np.random.RandomState(n).rand(40, n + 1) < 0.2] = np.nan
+        t[:, 0] = np.round(t[:, 0])                                  # the target, finite on most days
+        out["ring_of_%d" % n] = (lon, lat, t, np.ones(n + 1, bool), [0], g0, None)
+    lon, lat, t = line(7)
+    lon[0] -= 3.0                                                    # about 236 km from the next: rings 1 .. 4 are empty
+    out["first_ring_empty"] = (lon, lat, t, np.ones(7, bool), [0, 1], g0, [RI.OK] * 2)
+    lon, lat, t = line(7)
+    out["nearest_ineligible"] = (lon, lat, t, np.array([1, 0, 1, 1, 1, 1, 1], bool), [0], g0, [RI.OK])
+    lon, lat, t = line(6)
+    t[20:, 0] = np.nan
+    out["all_nan_target_month"] = (lon, lat, t, np.ones(6, bool), [0, 1], np.repeat([0, 1], 20).astype(np.int8),
+                                   [RI.OK, RI.NO_TARGET_OBS, RI.OK, RI.OK])
+    lon, lat, t = line(6)
+    t[:, 0] = t[:, 1] = 4.0
+    out["denominator_zero"] = (lon, lat, t, np.ones(6, bool), [0, 2], g0, [RI.NUMERIC, RI.OK])
+    for extra, status in ((56, RI.OK), (57, RI.NGH_CAP)):            # 200 near, 56 / 57 at 95 km: a list of 256 / 257
+        n = 1 + 200 + extra
+        lon, lat, t = line(n, step=0.0005, seed=extra)
+        lon[201:] += 1.1
+        t[0, 1:201] = np.nan                                         # the near ones all miss the first day
+        out["list_of_%d" % (200 + extra)] = (lon, lat, t, np.ones(n, bool), [0], g0, [status])
+    # a zero denominator and entry 257 of the list in one ring (200 near, 58 at 95 km; the 57th of those is entry 257):
+    # the first failing station in distance order decides, and at one station the denominator is looked at first
+    for const, status in ((258, RI.NGH_CAP), (201, RI.NUMERIC), (257, RI.NUMERIC)):
+        lon, lat, t = line(259, step=0.0005, seed=58)
+        lon[201:] += 1.1
+        t[0, 1:201] = np.nan
+        t[:, 0] = t[:, const] = 4.0
+        out["cap_and_zero_denominator_at_%d" % const] = (lon, lat, t, np.ones(259, bool), [0], g0, [status])
+    lon, lat, t = line(258, step=0.0005, seed=8)
+    out["ring_of_257"] = (lon, lat, t, np.ones(258, bool), [0], g0, [RI.NGH_CAP])
+    lon, lat, t = line(257, step=0.0005, seed=9)
+    out["ring_of_256"] = (lon, lat, t, np.ones(257, bool), [0], g0, [RI.OK])
+    return out
+
+
+SMALL = small_cases()
+
+
+@pytest.mark.parametrize("name", sorted(SMALL))
+def test_smallest_shapes(name):
+    from topowx_amd.infill import build_infill_matrices
+    lon, lat, t, mask, targets, grp, statuses = SMALL[name]
+    pool = make_pool(lon, lat, t)
+    want = RI.run(lon, lat, np.asarray(t, np.float32), mask, targets, grp)
+    # (one-day items have ioa 0 throughout and the two constant stations the same ioa: there the tie rule decides)
+    assert not RI.knife(want).any() or name in ("item_of_one_day", "denominator_zero") or name.startswith("cap_and_")
+    if statuses is not None:
+        assert want["status"].ravel().tolist() == statuses
+    if name.startswith("ring_of_6"):
+        assert want["nrings"][0, 0] == 1 and (want["off"][1] <= int(name[-2:]))
+    if name == "first_ring_empty":
+        assert want["max_dist"][0, 0] == 262.5 and want["nrings"][0, 0] == 1
+    if name == "list_of_256":
+        assert want["off"][1] == CAP and want["nrings"][0, 0] == 2 and want["nnghs"][0, 0] > 200
+    got = build_infill_matrices(pool, "tmin", pool.ids[targets], mask, grp)
+    compare(got, want)
+    for t_ in range(len(targets)):
+        for g in range(want["status"].shape[1]):
+            assert np.array_equal(got.matrix(t_, g), RI.matrix(pool.tmin, grp, want, np.asarray(targets), t_, g), equal_nan=True)
+
+
+def test_facade(case, built):
+    from topowx_amd.infill import InfillMatrix
+    m = built[0]
+    mask = np.ones(48, bool)
+    for t, g in ((30, 6), (44, 1)):
+        f = InfillMatrix(case.ids[t], case, mask, "tmin", day_mask=case.days[MONTH] == g + 1)
+        r = m.ranked(t, g)
+        assert f.status == 0 and f.nnghs == m.nnghs[t, g] and f.max_dist == m.max_dist[t, g]
+        assert np.array_equal(f.ngh_ioa, np.concatenate([[1.0], r["ioa"]])) and np.array_equal(f.ngh_dists[1:], r["dist"])
+        assert f.ngh_dists[0] == 0 and f.ngh_ids.tolist() == case.ids[r["idx"]].tolist()
+        assert f.imp_tair_mat.shape == (int((case.days[MONTH] == g + 1).sum()), 1 + r["idx"].size)
+        assert np.array_equal(f.valid_imp_mask, np.isfinite(f.imp_tair_mat))
+        assert np.array_equal(f.nnghs_per_day, np.isfinite(f.imp_tair_mat[:, 1:]).sum(axis=1))
+        assert np.array_equal(f.trim_matrix(), m.matrix(t, g), equal_nan=True)
+        assert (np.isfinite(f.imp_tair_mat[:, 1:1 + f.nnghs]).sum(axis=1) >= 3).all()
+    whole = InfillMatrix(case.ids[0], case, None, "tmax")              # day_mask=None: one group of every day
+    assert whole.status == 0 and whole.imp_tair_mat.shape[0] == case.days.size and whole.nnghs >= 3
+
+
+FORMATS = [pytest.param("NETCDF4", marks=pytest.mark.skipif(not h5nc.available(), reason="libhdf5 not loadable")),
+           "NETCDF3_64BIT"]
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_step14_command_line(tmp_path, capsys, fmt):
+    import corrob_cases
+    from topowx_amd import step14
+    from topowx_amd.infill import build_infill_matrices
+    pool, rs = random_pool(21, 30, dt.date(2001, 1, 1), dt.date(2002, 12, 31), box=(1.0, 0.7))
+    prev = (("qflag_tmin", 40, 1, b"G"), ("qflag_tmin", 41, 1, b"D"))
+    db = corrob_cases.write_db(str(tmp_path / "all.nc"), pool.ids, pool.lon, pool.lat, pool.tmin, pool.tmax, pool.days, fmt,
+                               prev=prev)
+    targets, ngh = pool.ids[[0, 1, 7, 29]], pool.ids[2:]
+    (tmp_path / "t.txt").write_text("\n".join(targets) + "\n")
+    (tmp_path / "n.txt").write_text("\n".join(ngh) + "\n")
+    out = str(tmp_path / "m.npz")
+    assert step14.main(["--db", db, "--var", "tmin", "--out", out, "--targets", str(tmp_path / "t.txt"), "--neighbours",
+                        str(tmp_path / "n.txt")]) == 0
+    rep = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert rep["stations"] == 4 and rep["pool"] == 30 and rep["eligible"] == 28 and rep["items"] == 48 and rep["rounds"] >= 1
+    assert "pair_kernel_ms" in rep and sum(rep["status"].values()) == 48
+    pool.tmin[40:42, 1] = np.nan                                     # the flagged observations are read as NaN
+    mask = np.zeros(30, bool)
+    mask[2:] = True
+    want = build_infill_matrices(pool, "tmin", targets, mask)
+    got = np.load(out)
+    for k in step14.COLUMNS:
+        assert np.array_equal(got[k], getattr(want, k), equal_nan=True), k
+    assert got["ids"].tolist() == targets.tolist() and got["pool_ids"].tolist() == pool.ids.tolist()
+    assert np.array_equal(got["group"], pool.days[MONTH] - 1)
+    assert step14.main(["--db", str(tmp_path / "missing.nc"), "--var", "tmin", "--out", out]) == 1
+    (tmp_path / "bad.txt").write_text("NOBODY\n")
+    assert step14.main(["--db", db, "--var", "tmin", "--out", out, "--targets", str(tmp_path / "bad.txt")]) == 1
+    assert "NOBODY" in capsys.readouterr().err

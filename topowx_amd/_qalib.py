@@ -220,3 +220,72 @@ def non_spatial(tmin, tmax, ymd, device=0, details=False, timing=None):
         for k, name in enumerate(NON_SPATIAL_KERNELS):
             timing[name + "_kernel_ms"] = float(ms[k])
     return (fmin, fmax, norms) if details else (fmin, fmax)
+
+
+# ---- the neighbour matrices of the infill family (twxif_infill_matrix; TWXIF_* of include/twx_qa.h) ----
+IF_EXPORTS = ("twxif_infill_matrix",)
+IF_OK, IF_NUMERIC, IF_NGH_CAP, IF_NO_TARGET_OBS, IF_UNSATISFIED = 0, 4, 7, 18, 19
+IF_MAX_GROUPS = 12        # TWXIF_MAX_GROUPS
+IF_MAX_MIN_NNGHS = 16     # TWXIF_MAX_MIN_NNGHS
+IF_MAX_COLS_NORM_IMPUTE = 31    # TWXIF_MAX_COLS_NORM_IMPUTE
+INFILL_MATRIX_KERNELS = ("ring", "pair", "item", "compact")     # TWXIF_NKERNELS
+INFILL_MATRIX_HOST_TIMES = ("upload", "download")               # the rest of TWXIF_NTIMES: host-clock milliseconds
+
+
+def infill_matrix(lon, lat, obs, ymd, eligible, target_idx, group, nthres_all, nthres_target_por, min_daily_nnghs=3,
+                  device=0, timing=None):
+    """``twxif_infill_matrix``: the ranked, widened and shrunk neighbour lists of ``_InfillMatrix``
+    (infill_normals.py:52-237, 324-343, 391-420) of every (target, day group) item.
+
+    lon, lat [nstn]; obs [nstn, ndays] float32, station-major, NaN = missing; ymd [ndays] consecutive days; eligible
+    [nstn] bool; target_idx [ntarget]; group [ndays] int8, -1 or 0 .. G - 1; nthres_all [G], nthres_target_por
+    [ntarget, G].  Returns a dict of status, nnghs, max_dist [ntarget, G], off [ntarget * G + 1] and the CSR columns idx,
+    ioa, dist, nlap, nlap_stn, keep, and ``rounds``.  ``timing`` receives ``<kernel>_kernel_ms`` for the names in
+    ``INFILL_MATRIX_KERNELS``, the host-clock ``upload_ms`` / ``download_ms`` and ``rounds``."""
+    L = load()
+    if not hasattr(L.twxif_infill_matrix, "_twx_ready"):
+        L.twxif_infill_matrix.restype = C.c_int
+        L.twxif_infill_matrix.argtypes = [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_int32] + \
+            [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 8 + [C.c_char_p, C.c_int]
+        L.twxif_infill_matrix._twx_ready = True
+    lon, lat, obs = _c(lon, np.float64), _c(lat, np.float64), _c(obs, np.float32)
+    ymd, target_idx = _c(ymd, np.int32), _c(target_idx, np.int32)
+    eligible, group = _c(eligible, np.uint8), _c(group, np.int8)
+    nthres_all, nthres_target_por = _c(nthres_all, np.int32), _c(nthres_target_por, np.int32)
+    nstn, ndays, nt = lon.size, ymd.size, target_idx.size
+    if lon.ndim != 1 or lat.shape != lon.shape or obs.shape != (nstn, ndays) or eligible.shape != (nstn,):
+        raise ValueError("lon / lat / eligible must be [nstn] and obs [nstn, ndays]")
+    if target_idx.ndim != 1 or group.shape != (ndays,) or nthres_all.ndim != 1:
+        raise ValueError("target_idx must be [ntarget], group [ndays] and nthres_all [ngroups]")
+    ng = nthres_all.size
+    if nthres_target_por.shape != (nt, ng):
+        raise ValueError("nthres_target_por must be [ntarget, ngroups]")
+    ni = nt * ng
+    cap = ni * MAX_RADIUS_NGH                      # always enough; the pages of an empty array are not touched
+    out = dict(status=np.empty((nt, ng), np.int32), nnghs=np.empty((nt, ng), np.int32), max_dist=np.empty((nt, ng)),
+               off=np.zeros(ni + 1, np.int64))
+    col = dict(idx=np.empty(cap, np.int32), ioa=np.empty(cap), dist=np.empty(cap), nlap=np.empty(cap, np.int32),
+               nlap_stn=np.empty(cap, np.int32), keep=np.empty(cap, np.uint8))
+    rounds = C.c_int32(0)
+    ms = (C.c_float * (len(INFILL_MATRIX_KERNELS) + len(INFILL_MATRIX_HOST_TIMES)))()
+    buf = C.create_string_buffer(512)
+    rc = L.twxif_infill_matrix(int(device), nstn, ndays, lon.ctypes.data, lat.ctypes.data, obs.ctypes.data, ymd.ctypes.data,
+                               eligible.ctypes.data, nt, target_idx.ctypes.data, ng, group.ctypes.data,
+                               nthres_all.ctypes.data, nthres_target_por.ctypes.data, int(min_daily_nnghs),
+                               out["status"].ctypes.data, out["nnghs"].ctypes.data, out["max_dist"].ctypes.data,
+                               out["off"].ctypes.data, cap, col["idx"].ctypes.data, col["ioa"].ctypes.data,
+                               col["dist"].ctypes.data, col["nlap"].ctypes.data, col["nlap_stn"].ctypes.data,
+                               col["keep"].ctypes.data, C.addressof(rounds), C.addressof(ms), buf, 512)
+    if rc != 0:
+        raise QaError("twxif_infill_matrix failed: %s" % buf.value.decode(errors="replace"))
+    total = int(out["off"][-1])
+    for k, a in col.items():
+        out[k] = a[:total].copy()
+    out["rounds"] = int(rounds.value)
+    if timing is not None:
+        for k, name in enumerate(INFILL_MATRIX_KERNELS):
+            timing[name + "_kernel_ms"] = float(ms[k])
+        for k, name in enumerate(INFILL_MATRIX_HOST_TIMES):          # allocations + copies in, copies out
+            timing[name + "_ms"] = float(ms[len(INFILL_MATRIX_KERNELS) + k])
+        timing["rounds"] = out["rounds"]
+    return out

@@ -1,0 +1,102 @@
+"""The first stage of ``scripts/step14_mpi_infill_stn_normals.py``: the infill neighbour matrices of every target
+station and calendar month (``topowx_amd.infill.build_infill_matrices``), all in one batched GPU call instead of the
+reference's MPI farm over stations.  A report: nothing is written into the database.
+
+    python -m topowx_amd.step14 --db all.nc --var tmin --out matrices.npz [--targets ids.txt] [--neighbours ids.txt]
+                                [--device N]
+
+``--targets``: the stations to build matrices for (default: every station); ``--neighbours``: the stations that may serve
+as neighbours, the reference's ``stns_mask`` (default: every station; a target is never its own neighbour).  Both are
+text files of station ids, one per line; they stand in for the reference's ``build_por_mask``.  If the database has
+``qflag_tmin`` / ``qflag_tmax`` the observations that carry a flag are set to NaN first, as the reference's
+``load_all_stn_obs_var(set_flagged_nan=True)`` does.
+
+Prints one JSON line (stations, items, items per status, rounds, seconds, kernel milliseconds) and writes
+``matrices.npz``: ``ids`` [ntarget], ``pool_ids`` [n], ``ymd`` [ndays], ``group`` [ndays] (month - 1), ``status``, ``nnghs``,
+``max_dist``, ``nthres_target_por`` [ntarget, 12], ``nthres_all`` [12], and the ranked lists as CSR columns over ``off``
+[ntarget * 12 + 1] (item = target * 12 + month - 1): ``idx`` (row of ``pool_ids``), ``ioa``, ``dist``, ``nlap``, ``nlap_stn``,
+``keep``.  The observation matrix of an item is the target's column and the columns ``idx[keep == 1][:30]`` of the
+database on the item's days (``InfillMatrices.matrix``).
+
+Out of scope: the estimate of mean and variance from the matrix (``infill_mu_sigma`` / ``em.norm``), the reanalysis
+columns and their PCA, ``build_por_mask``.
+
+Exits with 1 if the database cannot be opened or a station id is unknown.
+"""
+import argparse
+import json
+import sys
+import time
+
+import numpy as np
+
+from . import ncio
+from .dates import YMD
+from .infill import ITEM_STATUS, build_infill_matrices
+from .qa import StationObsPool
+
+__all__ = ["main"]
+
+QFLAG_VARS = ("qflag_tmin", "qflag_tmax")
+COLUMNS = ("status", "nnghs", "max_dist", "nthres_all", "nthres_target_por", "off", "idx", "ioa", "dist", "nlap", "nlap_stn",
+           "keep")
+
+
+class _UnknownIds(Exception):
+    pass
+
+
+def _read_ids(path, pool, what):
+    with open(path) as fh:
+        ids = [ln.strip() for ln in fh if ln.strip()]
+    missing = [s for s in ids if s not in pool.idxs]
+    if missing:
+        raise _UnknownIds("%s: %d %s ids are not in the database (first: %s)" % (path, len(missing), what, missing[0]))
+    return ids
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m topowx_amd.step14", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--db", required=True, help="all-stations database (netCDF): tmin / tmax on (time, station_id)")
+    ap.add_argument("--var", required=True, choices=("tmin", "tmax"))
+    ap.add_argument("--out", required=True, help="report to write (.npz)")
+    ap.add_argument("--targets", help="text file of target station ids, one per line (default: every station)")
+    ap.add_argument("--neighbours", help="text file of the station ids that may be neighbours (default: every station)")
+    ap.add_argument("--device", type=int, default=0)
+    a = ap.parse_args(argv)
+    try:
+        ds = ncio.open_dataset(a.db, "r")
+        try:
+            qflags = all(name in ds.variables for name in QFLAG_VARS)
+        finally:
+            ds.close()
+        pool = StationObsPool.from_netcdf(a.db, qflags=qflags)
+        targets = _read_ids(a.targets, pool, "target") if a.targets else None
+        mask = None
+        if a.neighbours:
+            mask = np.zeros(pool.ids.size, bool)
+            mask[[pool.idxs[s] for s in _read_ids(a.neighbours, pool, "neighbour")]] = True
+    except _UnknownIds as e:
+        print("step14: %s" % e, file=sys.stderr)
+        return 1
+    except (IOError, OSError, ValueError, KeyError) as e:
+        print("step14: cannot open %s: %s" % (getattr(e, "filename", None) or a.db, e), file=sys.stderr)
+        return 1
+    tm = {}
+    t0 = time.perf_counter()
+    m = build_infill_matrices(pool, a.var, targets, mask, device=a.device, timing=tm)
+    sec = time.perf_counter() - t0
+    np.savez_compressed(a.out, ids=m.target_ids, pool_ids=pool.ids, ymd=np.asarray(pool.days[YMD], np.int32), group=m.group,
+                        **{k: getattr(m, k) for k in COLUMNS})
+    line = {"var": a.var, "stations": int(m.target_ids.size), "pool": int(pool.ids.size), "days": int(pool.days.size),
+            "eligible": int(pool.ids.size if mask is None else mask.sum()), "items": int(m.status.size),
+            "status": {ITEM_STATUS[k]: int((m.status == k).sum()) for k in sorted(ITEM_STATUS) if (m.status == k).any()},
+            "ranked": int(m.idx.size), "kept": int(m.keep.sum()), "seconds": round(sec, 3)}
+    for k in sorted(tm):
+        line[k] = round(tm[k], 3) if isinstance(tm[k], float) else tm[k]
+    print(json.dumps(line), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
