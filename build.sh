@@ -26,7 +26,7 @@ python3 tests/tools/isa_resources.py "$LOG" > topowx_amd/libtwxhip.resources.txt
 if ! hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared -std=c++17 -Iinclude \
     -Rpass-analysis=kernel-resource-usage "$@" -o topowx_amd/libtwxqa.so topowx_amd/qa/twx_outlier.hip \
     topowx_amd/qa/twx_spatial.hip topowx_amd/qa/twx_corrob.hip topowx_amd/qa/twx_nonspatial.hip \
-    topowx_amd/qa/twx_infillmat.hip 2> "$LOG"; then
+    topowx_amd/qa/twx_infillmat.hip topowx_amd/qa/twx_emnorm.hip 2> "$LOG"; then
     show_diagnostics "$LOG"
     rm -f "$LOG"
     exit 1

@@ -313,6 +313,86 @@ int twxif_infill_matrix(int device, int64_t nstn, int64_t ndays, const double *l
                         double *ngh_dist, int32_t *ngh_nlap, int32_t *ngh_nlap_stn, uint8_t *keep, int32_t *nrounds,
                         float *kernel_ms, char *errbuf, int errlen);
 
+/* ---- the mean / variance estimator of step14: infill_mu_sigma of twx/infill/rpy/norm_infill.R (prelim.norm, em.norm,
+ * getparam.norm; the reference keeps mu[1] and sigma[1, 1]), restated from Schafer (1997, section 5.3) and norm's
+ * documented defaults.  Neither R nor norm can be run against it: the divisor of prelim.norm's column scaling and whether
+ * the stopping rule is absolute or relative are not fixed by the reference tree; both move the iteration at which EM
+ * stops, not the fixed point it approaches (DESIGN.md section 17 gives the size of that). ---- */
+#define TWXEM_MAX_COLS TWXIF_MAX_COLS_NORM_IMPUTE   /* columns of an item: the target, its stations, its extra columns */
+#define TWXEM_MAX_ROWS 8192             /* rows (days) of an item: k_em_prep sorts the rows of an item in LDS, 8 bytes each;
+                                           the longest axis the other caps admit has 31 days x 136 years = 4216 */
+#define TWXEM_RUN_ROWS 128              /* a stretch of equal missingness patterns is cut into runs of at most this */
+#define TWXEM_DEFAULT_CRITERION 1e-4            /* em.norm's default criterion */
+#define TWXEM_DEFAULT_MAXITS 1000               /* em.norm's default maxits */
+#define TWXEM_ITERS_PER_LAUNCH 16       /* default: iterations of one launch of k_em_iter */
+#define TWXEM_WORKSPACE_BYTES (256ll << 20)   /* default budget of the per-batch device workspace */
+#define TWXEM_NKERNELS 2                /* kernel groups timed: k_em_prep, k_em_iter */
+#define TWXEM_NTIMES 4                  /* entries of kernel_ms: the kernel groups, then two host-clock figures */
+/* LDS per workgroup.  k_em_prep (256 threads): the sort keys 8 B x TWXEM_MAX_ROWS = 64 KiB + cnt / xbar / sdv 3 x 32 x 8 B
+ * = 64.8 KiB: two workgroups fit a compute unit's 160 KiB.  k_em_iter (256 threads, 4 wavefronts): theta 32 x 32 x 8 B =
+ * 8 KiB + one swept copy W per wavefront 4 x 8 KiB (reused for the partial T) + one completed row per wavefront
+ * 4 x 256 B + xbar / sdv / reduction 0.6 KiB = 41.6 KiB: three workgroups fit.  Both are below 80 KiB.
+ * Workspace per item of a batch: the row permutation and the run starts (8 bytes per row), theta (8 KiB), xbar / sdv
+ * (512 B); the matrix is gathered again from obs in every iteration, no standardised copy is kept. */
+
+/* per-item status */
+#define TWXEM_OK TWX_CELL_OK                      /* converged: delta <= criterion */
+#define TWXEM_NUMERIC TWX_CELL_NUMERIC            /* a sweep pivot <= 0 or not finite (R would return NaN / Inf); NaN results */
+#define TWXEM_MAXITS 20                   /* maxits iterations without convergence: the last iterate is returned,
+                                                     as em.norm does silently */
+#define TWXEM_NO_MATRIX 21                        /* item_matrix_status was not TWXIF_OK: nothing computed, NaN */
+#define TWXEM_EMPTY_COLUMN 22                     /* a column without a finite value on the item's days; NaN */
+#define TWXEM_ROW_CAP 23                          /* more rows than TWXEM_MAX_ROWS; NaN, never an estimate from fewer rows */
+
+/*
+ * For every item (a target, a day group, its station columns, optionally one set of extra columns), X [n, P]: column 0
+ * the target's observations on the days of the group, then the stations of its CSR list in order, then the columns of
+ * its extra set; a non-finite value is missing.
+ *   1. per column over its finite values: cnt, xbar = sum / cnt, sdv = sqrt((sum x^2 - (sum x)^2 / cnt) / cnt), 0 -> 1;
+ *      z = (x - xbar) / sdv.
+ *   2. theta, symmetric (P + 1) x (P + 1): theta[0][0] = -1, theta[0][j] = mu_j = 0, theta[j][k] = sigma_jk = I.
+ *   3. an iteration: the rows grouped by their 32-bit mask of finite columns (equal masks keep day order), T = 0; per
+ *      pattern with observed set O and missing set M: W = a fresh copy of theta swept on every k in O in ascending k
+ *      (pivot d = W[k][k], r = 1 / d, c = W[:, k]: W -= (c c') r, W[:, k] = W[k, :] = c r, W[k][k] = -r); per row zhat = z on
+ *      O and W[0][m] + sum over o in O (ascending) of W[o][m] z_o on m in M; T[0][j] += zhat_j, T[j][k] += zhat_j zhat_k, and
+ *      W[j][k] for j, k in M (added once per run as rows x W[j][k]).  A row with nothing observed is a pattern like any
+ *      other.  mu = T[0][.] / n, sigma = T / n - mu mu'; delta = the largest absolute change of an element of theta.
+ *   4. stop at delta <= criterion or after maxits iterations.
+ *   5. mean = mu_0 sdv_0 + xbar_0, variance = sigma_00 sdv_0^2.
+ * iters counts completed iterations.  Every sum has a fixed order and no float atomics are used: two calls give the same
+ * bytes, whatever iters_per_launch and workspace_bytes.
+ *
+ * obs [nstn][ndays]          station-major float32 of one variable, NaN (any non-finite value) = missing
+ * group [ndays]              -1 (day not used) or 0 .. ngroups - 1
+ * item_target, item_group [nitem]   the target's row of obs and the day group
+ * item_matrix_status (optional) [nitem]   the item's status from twxif_infill_matrix; not TWXIF_OK: TWXEM_NO_MATRIX
+ * col_off [nitem + 1], col_idx   CSR of each item's station columns (rows of obs), in order
+ * set_group, set_ncol [nset], set_vals   extra-column sets: set s holds set_ncol[s] float64 columns over the days of group
+ *                            set_group[s] in day order, column after column, the sets one after the other
+ * item_set [nitem]           the item's set (of the item's own group) or -1; sets are shared between items; may be NULL
+ *                            when nset == 0
+ * criterion, maxits          > 0
+ * iters_per_launch, workspace_bytes   <= 0: TWXEM_ITERS_PER_LAUNCH, TWXEM_WORKSPACE_BYTES.  A launch of k_em_iter runs at
+ *                            most iters_per_launch iterations of the unfinished items of a batch; a batch is a run of
+ *                            consecutive items whose workspace fits the budget (at least one item)
+ * mean, variance, iters, delta, status [nitem]   out; delta is the last iteration's; NaN unless TWXEM_OK or
+ *                            TWXEM_MAXITS
+ * mu [nitem][31], sigma [nitem][31][31] (optional, both or neither)   out: all of mu and sigma on the original scale, NaN
+ *                            beyond the item's columns
+ * counts (optional) [2]      out: launches of k_em_iter, batches
+ * kernel_ms (optional) [TWXEM_NTIMES]   device time of k_em_prep and of k_em_iter over all launches; then host-clock
+ *                            milliseconds of the allocations and copies in, and of the copies back
+ * Call-level failures (the message names the macro): an item with more than TWXEM_MAX_COLS columns in all; a target,
+ * column, group or set index out of range; a set of another group than the item's; criterion or maxits not positive.
+ */
+int twxem_mean_variance(int device, int64_t nstn, int64_t ndays, const float *obs, int32_t ngroups, const int8_t *group,
+                        int64_t nitem, const int32_t *item_target, const int32_t *item_group,
+                        const int32_t *item_matrix_status, const int64_t *col_off, const int32_t *col_idx, int64_t nset,
+                        const int32_t *set_group, const int32_t *set_ncol, const double *set_vals, const int32_t *item_set,
+                        double criterion, int32_t maxits, int32_t iters_per_launch, int64_t workspace_bytes, double *mean,
+                        double *variance, int32_t *iters, double *delta, int32_t *status, double *mu, double *sigma,
+                        int32_t *counts, float *kernel_ms, char *errbuf, int errlen);
+
 #ifdef __cplusplus
 }
 #endif

@@ -289,3 +289,89 @@ def infill_matrix(lon, lat, obs, ymd, eligible, target_idx, group, nthres_all, n
             timing[name + "_ms"] = float(ms[len(INFILL_MATRIX_KERNELS) + k])
         timing["rounds"] = out["rounds"]
     return out
+
+
+# ---- the mean / variance estimator of step14 (twxem_mean_variance; TWXEM_* of include/twx_qa.h) ----
+EM_EXPORTS = ("twxem_mean_variance",)
+EM_OK, EM_NUMERIC, EM_MAXITS, EM_NO_MATRIX, EM_EMPTY_COLUMN, EM_ROW_CAP = 0, 4, 20, 21, 22, 23
+EM_MAX_COLS = 31          # TWXEM_MAX_COLS
+EM_MAX_ROWS = 8192        # TWXEM_MAX_ROWS
+EM_KERNELS = ("em_prep", "em_iter")                     # TWXEM_NKERNELS
+EM_HOST_TIMES = ("em_upload", "em_download")            # the rest of TWXEM_NTIMES: host-clock milliseconds
+
+
+def em_mean_variance(obs, group, item_target, item_group, col_off, col_idx, sets=(), item_set=None, matrix_status=None,
+                     criterion=1e-4, maxits=1000, iters_per_launch=0, workspace_bytes=0, full=False, device=0, timing=None):
+    """``twxem_mean_variance``: the EM estimate of mean and variance of every item's target column (norm's ``em.norm`` as
+    include/twx_qa.h restates it).
+
+    obs [nstn, ndays] float32, station-major, NaN = missing; group [ndays] int8, -1 or 0 .. G - 1; item_target, item_group
+    [nitem]; col_off [nitem + 1] / col_idx: the CSR of each item's station columns (rows of obs) in order; ``sets``: a
+    sequence of (group, values [ndays of the group, ncol] float64), ``item_set`` [nitem] the set of each item or -1;
+    ``matrix_status`` [nitem]: the items' ``twxif_infill_matrix`` status (not 0: EM_NO_MATRIX).  ``iters_per_launch`` and
+    ``workspace_bytes`` of 0 take the library's defaults.  Returns a dict of mean, variance, iters, delta, status [nitem],
+    ``rounds`` and ``batches``, and with ``full`` mu [nitem, 31] and sigma [nitem, 31, 31].  ``timing`` receives
+    ``em_prep_kernel_ms`` / ``em_iter_kernel_ms``, the host-clock ``em_upload_ms`` / ``em_download_ms``, ``em_rounds`` and
+    ``em_batches``."""
+    L = load()
+    if not hasattr(L.twxem_mean_variance, "_twx_ready"):
+        L.twxem_mean_variance.restype = C.c_int
+        L.twxem_mean_variance.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64] + \
+            [C.c_void_p] * 5 + [C.c_int64] + [C.c_void_p] * 4 + [C.c_double, C.c_int32, C.c_int32, C.c_int64] + \
+            [C.c_void_p] * 9 + [C.c_char_p, C.c_int]
+        L.twxem_mean_variance._twx_ready = True
+    obs, group = _c(obs, np.float32), _c(group, np.int8)
+    item_target, item_group = _c(item_target, np.int32), _c(item_group, np.int32)
+    col_off, col_idx = _c(col_off, np.int64), _c(col_idx, np.int32)
+    if obs.ndim != 2 or group.shape != (obs.shape[1],):
+        raise ValueError("obs must be [nstn, ndays] and group [ndays]")
+    ni = item_target.size
+    if item_target.ndim != 1 or item_group.shape != (ni,) or col_off.shape != (ni + 1,) or col_idx.ndim != 1 or \
+            (ni and (col_off[0] != 0 or col_off[-1] != col_idx.size)):
+        raise ValueError("item_target / item_group must be [nitem] and col_off [nitem + 1] the CSR offsets of col_idx")
+    ng = int(group.max()) + 1 if group.size and group.max() >= 0 else 1
+    ng = max(ng, int(item_group.max()) + 1 if ni else 1)
+    nrows = np.bincount(group[group >= 0].astype(np.int64), minlength=ng)
+    sets = list(sets)
+    set_group, set_ncol = np.zeros(len(sets), np.int32), np.zeros(len(sets), np.int32)
+    vals = []
+    for s, (g, v) in enumerate(sets):
+        v = np.asarray(v, np.float64)
+        if v.ndim != 2 or not 0 <= int(g) < ng or v.shape[0] != nrows[int(g)]:
+            raise ValueError("extra-column set %d must be [days of its group, ncol]" % s)
+        set_group[s], set_ncol[s] = int(g), v.shape[1]
+        vals.append(np.ascontiguousarray(v.T).ravel())              # column after column
+    set_vals = np.concatenate(vals) if vals else np.zeros(0)
+    item_set = np.full(ni, -1, np.int32) if item_set is None else _c(item_set, np.int32)
+    if item_set.shape != (ni,):
+        raise ValueError("item_set must be [nitem]")
+    if matrix_status is not None:
+        matrix_status = _c(matrix_status, np.int32)
+        if matrix_status.shape != (ni,):
+            raise ValueError("matrix_status must be [nitem]")
+    out = dict(mean=np.empty(ni), variance=np.empty(ni), iters=np.empty(ni, np.int32), delta=np.empty(ni),
+               status=np.empty(ni, np.int32))
+    if full:
+        out["mu"], out["sigma"] = np.empty((ni, EM_MAX_COLS)), np.empty((ni, EM_MAX_COLS, EM_MAX_COLS))
+    counts = (C.c_int32 * 2)()
+    ms = (C.c_float * (len(EM_KERNELS) + len(EM_HOST_TIMES)))()
+    buf = C.create_string_buffer(512)
+    rc = L.twxem_mean_variance(int(device), obs.shape[0], obs.shape[1], obs.ctypes.data, ng, group.ctypes.data, ni,
+                               item_target.ctypes.data, item_group.ctypes.data,
+                               matrix_status.ctypes.data if matrix_status is not None else None, col_off.ctypes.data,
+                               col_idx.ctypes.data, len(sets), set_group.ctypes.data, set_ncol.ctypes.data,
+                               set_vals.ctypes.data, item_set.ctypes.data, float(criterion), int(maxits),
+                               int(iters_per_launch), int(workspace_bytes), out["mean"].ctypes.data,
+                               out["variance"].ctypes.data, out["iters"].ctypes.data, out["delta"].ctypes.data,
+                               out["status"].ctypes.data, out["mu"].ctypes.data if full else None,
+                               out["sigma"].ctypes.data if full else None, C.addressof(counts), C.addressof(ms), buf, 512)
+    if rc != 0:
+        raise QaError("twxem_mean_variance failed: %s" % buf.value.decode(errors="replace"))
+    out["rounds"], out["batches"] = int(counts[0]), int(counts[1])
+    if timing is not None:
+        for k, name in enumerate(EM_KERNELS):
+            timing[name + "_kernel_ms"] = float(ms[k])
+        for k, name in enumerate(EM_HOST_TIMES):
+            timing[name + "_ms"] = float(ms[len(EM_KERNELS) + k])
+        timing["em_rounds"], timing["em_batches"] = out["rounds"], out["batches"]
+    return out

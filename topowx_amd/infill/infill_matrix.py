@@ -8,8 +8,9 @@ call raises.
 the observation matrix of an item on the host (target first, then the kept stations in rank order, at most
 ``MAX_COLS_NORM_IMPUTE`` columns).  ``InfillMatrix`` is a facade with the reference's attribute names for one target.
 
-Out of scope (the follow-ups that sit on top of the matrix): ``infill_mu_sigma`` / ``em.norm``, the reanalysis
-neighbour matrix and its PCA, ``build_por_mask``, ``tair_mask`` and ``InfillMatrixPPCA``.
+The estimate of mean and variance from the matrices (``infill_mu_sigma`` / ``em.norm``, the PCA of the reanalysis columns)
+is ``topowx_amd.infill.infill_normals``.  Out of scope: the reanalysis reader, ``build_por_mask``, ``tair_mask`` and
+``InfillMatrixPPCA``.
 """
 import time
 
@@ -70,10 +71,13 @@ class InfillMatrices(object):
     """The result of ``build_infill_matrices``.  Per item [ntarget, G]: ``status`` (``ITEM_STATUS``), ``nnghs``,
     ``max_dist``, ``nthres_all`` [G], ``nthres_target_por``; the ranked lists as CSR columns over ``off`` [ntarget * G + 1]
     (item = target * G + group): ``idx`` (pool column), ``ioa``, ``dist``, ``nlap``, ``nlap_stn`` and ``keep`` (1: among the
-    first ``nnghs`` and not dropped by the shrink).  ``rounds`` is the number of rings the call ran."""
+    first ``nnghs`` and not dropped by the shrink).  ``rounds`` is the number of rings the call ran.
+    ``obs_station_major``: the transposed copy of the observations the call made, kept for ``estimate_mean_variance``."""
 
-    def __init__(self, pool, var, target_ids, target_cols, group, ngroups, res, nthres_all, nthres_por, min_daily_nnghs):
+    def __init__(self, pool, var, target_ids, target_cols, group, ngroups, res, nthres_all, nthres_por, min_daily_nnghs,
+                 obs_station_major=None):
         self.pool, self.var = pool, var
+        self.obs_station_major = obs_station_major                  # [n, ndays] float32: kept for the estimator's call
         self.target_ids, self.target_cols = target_ids, target_cols
         self.group, self.ngroups = group, ngroups
         self.min_daily_nnghs = min_daily_nnghs
@@ -96,6 +100,12 @@ class InfillMatrices(object):
 
     def day_idx(self, group):
         return np.nonzero(self.group == int(group))[0]
+
+    def nrows(self, group):
+        """The number of days of a group (the rows of its items' matrices)."""
+        if getattr(self, "_nrows", None) is None:
+            self._nrows = np.bincount(self.group[self.group >= 0].astype(np.int64), minlength=self.ngroups)
+        return int(self._nrows[int(group)])
 
     def columns(self, target, group, max_cols=MAX_COLS_NORM_IMPUTE):
         """The pool columns of the stations that reach the estimator: the first ``max_cols - 1`` kept ones, in rank
@@ -154,7 +164,8 @@ def build_infill_matrices(pool, var, targets=None, stns_mask=None, day_groups=No
                                int(min_daily_nnghs), device=device, timing=timing)
     if timing is not None:
         timing.update(transpose_s=t1 - t0, thresholds_s=t2 - t1, library_s=time.perf_counter() - t2)
-    return InfillMatrices(pool, var, pool.ids[tcols], tcols, group, ng, res, nthres_all, nthres_por, int(min_daily_nnghs))
+    return InfillMatrices(pool, var, pool.ids[tcols], tcols, group, ng, res, nthres_all, nthres_por, int(min_daily_nnghs),
+                          obs)
 
 
 class InfillMatrix(object):

@@ -1,9 +1,10 @@
-"""The first stage of ``scripts/step14_mpi_infill_stn_normals.py``: the infill neighbour matrices of every target
-station and calendar month (``topowx_amd.infill.build_infill_matrices``), all in one batched GPU call instead of the
-reference's MPI farm over stations.  A report: nothing is written into the database.
+"""``scripts/step14_mpi_infill_stn_normals.py``: the infill neighbour matrices of every target station and calendar
+month (``topowx_amd.infill.build_infill_matrices``) and, with ``--estimate``, the mean and variance of every item from
+them (``topowx_amd.infill.estimate_mean_variance``), each in one batched GPU call instead of the reference's MPI farm
+over stations.  A report: nothing is written into the database.
 
     python -m topowx_amd.step14 --db all.nc --var tmin --out matrices.npz [--targets ids.txt] [--neighbours ids.txt]
-                                [--device N]
+                                [--device N] [--estimate]
 
 ``--targets``: the stations to build matrices for (default: every station); ``--neighbours``: the stations that may serve
 as neighbours, the reference's ``stns_mask`` (default: every station; a target is never its own neighbour).  Both are
@@ -18,8 +19,13 @@ Prints one JSON line (stations, items, items per status, rounds, seconds, kernel
 ``keep``.  The observation matrix of an item is the target's column and the columns ``idx[keep == 1][:30]`` of the
 database on the item's days (``InfillMatrices.matrix``).
 
-Out of scope: the estimate of mean and variance from the matrix (``infill_mu_sigma`` / ``em.norm``), the reanalysis
-columns and their PCA, ``build_por_mask``.
+``--estimate`` adds ``mean``, ``variance``, ``em_iters``, ``em_status`` [ntarget, 12] (``topowx_amd.infill.EM_STATUS``) to the
+report, and the items per estimator status (``em_status``), the launches and the kernel milliseconds to the JSON line.
+The values are estimated from station columns ONLY: they carry no reanalysis columns, because the reanalysis reader is
+not ported, so they are not what the reference would write as ``mean_tminMM`` / ``vari_tminMM`` and there is no ``--write``.
+Without the flag the output is what it was before the flag existed.
+
+Out of scope: the reanalysis reader (``NNRNghData``), ``build_por_mask``, writing the estimates into the database.
 
 Exits with 1 if the database cannot be opened or a station id is unknown.
 """
@@ -32,7 +38,7 @@ import numpy as np
 
 from . import ncio
 from .dates import YMD
-from .infill import ITEM_STATUS, build_infill_matrices
+from .infill import EM_STATUS, ITEM_STATUS, build_infill_matrices, estimate_mean_variance
 from .qa import StationObsPool
 
 __all__ = ["main"]
@@ -63,6 +69,8 @@ def main(argv=None):
     ap.add_argument("--targets", help="text file of target station ids, one per line (default: every station)")
     ap.add_argument("--neighbours", help="text file of the station ids that may be neighbours (default: every station)")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--estimate", action="store_true",
+                    help="also estimate the mean and variance of every item (station columns only, no reanalysis columns)")
     a = ap.parse_args(argv)
     try:
         ds = ncio.open_dataset(a.db, "r")
@@ -85,13 +93,19 @@ def main(argv=None):
     tm = {}
     t0 = time.perf_counter()
     m = build_infill_matrices(pool, a.var, targets, mask, device=a.device, timing=tm)
+    extra = {}
+    if a.estimate:
+        e = estimate_mean_variance(m, device=a.device, timing=tm)
+        extra = dict(mean=e.mean, variance=e.variance, em_iters=e.iters, em_status=e.status)
     sec = time.perf_counter() - t0
     np.savez_compressed(a.out, ids=m.target_ids, pool_ids=pool.ids, ymd=np.asarray(pool.days[YMD], np.int32), group=m.group,
-                        **{k: getattr(m, k) for k in COLUMNS})
+                        **dict({k: getattr(m, k) for k in COLUMNS}, **extra))
     line = {"var": a.var, "stations": int(m.target_ids.size), "pool": int(pool.ids.size), "days": int(pool.days.size),
             "eligible": int(pool.ids.size if mask is None else mask.sum()), "items": int(m.status.size),
             "status": {ITEM_STATUS[k]: int((m.status == k).sum()) for k in sorted(ITEM_STATUS) if (m.status == k).any()},
             "ranked": int(m.idx.size), "kept": int(m.keep.sum()), "seconds": round(sec, 3)}
+    if a.estimate:
+        line["em_status"] = {EM_STATUS[k]: int((e.status == k).sum()) for k in sorted(EM_STATUS) if (e.status == k).any()}
     for k in sorted(tm):
         line[k] = round(tm[k], 3) if isinstance(tm[k], float) else tm[k]
     print(json.dumps(line), flush=True)
