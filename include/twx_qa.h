@@ -393,6 +393,87 @@ int twxem_mean_variance(int device, int64_t nstn, int64_t ndays, const float *ob
                         double *variance, int32_t *iters, double *delta, int32_t *status, double *mu, double *sigma,
                         int32_t *counts, float *kernel_ms, char *errbuf, int errlen);
 
+/* ---- the estimator of step16: pca(method = 'ppca') of pcaMethods as twx/infill/rpy/pca_infill.R calls it, restated: EM
+ * for probabilistic PCA with missing values (Tipping and Bishop 1999; Verbeek's ppca_mv, which pcaMethods follows).  Neither
+ * R nor pcaMethods can be run against it.  Deviation: the start C0 is an ARGUMENT (R's rnorm stream under set.seed(4324)
+ * cannot be reproduced); the facade passes np.random.RandomState(4324).standard_normal(D * d), column-major.  C0 moves
+ * the iteration at which EM stops, not the fixed point (DESIGN.md section 18 gives the size of that). ---- */
+#define TWXPP_MAX_COLS 64               /* columns of an item: one lane of a wavefront per column */
+#define TWXPP_MAX_PCS 32                /* components of a fit */
+#define TWXPP_MAX_ROWS 8192             /* rows (days) of an item; the longest axis the other caps admit has 4216 */
+#define TWXPP_DEFAULT_THRESHOLD 1e-5            /* pca_infill.R: THRESHOLD */
+#define TWXPP_DEFAULT_MAXITS 1000               /* pcaMethods' maxIterations */
+#define TWXPP_ITERS_PER_LAUNCH 32       /* default: iterations of one launch of k_pp_iter */
+#define TWXPP_WORKSPACE_BYTES (256ll << 20)   /* default budget of the per-batch device workspace */
+#define TWXPP_NKERNELS 2                /* kernel groups timed: k_pp_prep, k_pp_iter */
+#define TWXPP_NTIMES 4                  /* entries of kernel_ms: the kernel groups, then two host-clock figures */
+/* The caps are library limits without a reference counterpart.  LDS per workgroup of k_pp_iter (256 threads, 4
+ * wavefronts): C and Ye'X (which becomes the new C) 2 x 64 x 33 x 8 B = 33 KiB (row stride 33: lane j walks row j), S, Sx,
+ * CtC and the inverse scratch 4 x 32 x 32 x 8 B = 32 KiB, per wavefront one row of Ye and three d-vectors 4 x 1.25 KiB,
+ * reduction scratch 1.1 KiB: 71.3 KiB, two workgroups fit a compute unit's 160 KiB.  k_pp_prep: 32 KiB.  Workspace per
+ * item of a batch: X twice (2 x N x d x 8 B), C (16.5 KiB), M and three scalars; the matrix is gathered again from obs in
+ * every pass, no filled copy is kept. */
+
+/* per-item status */
+#define TWXPP_OK TWX_CELL_OK                      /* stopped at rel < threshold with count > 5 */
+#define TWXPP_NUMERIC TWX_CELL_NUMERIC            /* a pivot of an inverse <= 0 or not finite, ss <= 0 or not finite, or a
+                                                     column of C without norm in the orthonormalisation; NaN results */
+#define TWXPP_MAXITS 20                           /* count passed maxits: the last iterate is returned (pcaMethods warns) */
+#define TWXPP_NO_MATRIX 21                        /* item_matrix_status was not TWXIF_OK: nothing computed, NaN */
+#define TWXPP_EMPTY_COLUMN 22                     /* a column without a finite standardised value; NaN */
+#define TWXPP_ROW_CAP 23                          /* more rows than TWXPP_MAX_ROWS; NaN, never a fit from fewer rows */
+#define TWXPP_COL_CAP 24                          /* more columns than TWXPP_MAX_COLS; NaN */
+#define TWXPP_PCS_CAP 25                          /* more components than TWXPP_MAX_PCS; NaN */
+
+/*
+ * For every item: Y [N, D], column 0 the target's observations on the days of the group, then the stations of its CSR
+ * list, then the columns of its extra set, each (value - norm_j) / std_j; a non-finite result is missing.  d = item_npcs.
+ *   set-up    hidden = the missing positions, missing their count.  M_j = the mean of column j over its observed values;
+ *             Ye = Y - M with the hidden positions 0; C = C0 [D, d]; CtC = C'C; X = (Ye C) CtC^-1;
+ *             ss = sum over the observed positions of (X C' - Ye)^2 / (N D - missing); count = 1, old = infinity.
+ *   iterate   Sx = (I + CtC / ss)^-1, ss_old = ss; Ye[hidden] = (X C')[hidden]; X = ((Ye C) Sx) / ss; S = X'X;
+ *             C = (Ye'X) (S + N Sx)^-1; CtC = C'C;
+ *             ss = (sum (C X' - Ye')^2 + N sum(CtC o Sx) + missing ss_old) / (N D);
+ *             objective = N (D log ss + tr Sx - log det Sx) + tr S - missing log ss_old;
+ *             rel = |1 - objective / old|, old = objective, count += 1;
+ *             stop when rel < threshold and count > 5 (TWXPP_OK), else when count > maxits (TWXPP_MAXITS, the last iterate).
+ *   after     Q = the columns of C orthonormalised in order (modified Gram-Schmidt, every column against the earlier ones
+ *             twice); T = Ye Q with Ye holding its last fill; cov = (T'T - s s' / N) / (N - 1), s the column sums of T;
+ *             V = the eigenvectors of cov, eigenvalues descending (cyclic Jacobi); C = Q V; X = Ye C.
+ *   out       R2cum[i] = 1 - sum_obs (Ye - X[:, :i] C[:, :i]')^2 / sum_obs Ye^2, i = 1 .. d;
+ *             fit = (X C[0, :]' + M_0) std_0 + norm_0: the reference keeps only column 0 of fitted().
+ * An inverse is Gauss-Jordan without pivoting, the pivot row divided by the pivot; log det Sx is minus the sum of the logs
+ * of the pivots of I + CtC / ss.  iters = count - 1.  Every sum has a fixed order and no float atomics are used: two calls
+ * give the same bytes, whatever iters_per_launch and workspace_bytes.
+ *
+ * obs, group, item_target, item_group, item_matrix_status, col_off, col_idx, nset .. item_set   as twxem_mean_variance
+ *                            takes them (a set may hold any number of columns)
+ * item_npcs [nitem]          d of the item
+ * norms, stds                per item its D values, the items one after the other (an item without a matrix has 1 column)
+ * c0                         per item D x d values, column after column, the items one after the other; an item whose
+ *                            item_matrix_status is not TWXIF_OK has none
+ * threshold, maxits          > 0
+ * iters_per_launch, workspace_bytes   <= 0: TWXPP_ITERS_PER_LAUNCH, TWXPP_WORKSPACE_BYTES
+ * fit                        out: per item its N values in day order, the items one after the other; NaN unless TWXPP_OK
+ *                            or TWXPP_MAXITS
+ * r2cum [nitem][32], iters, rel, status [nitem]   out; rel is the last iteration's
+ * c_out [nitem][64][32], m_out [nitem][64] (optional, each)   out: the rotated C and M, NaN beyond the item's D and d
+ * counts (optional) [2]      out: launches of k_pp_iter, batches
+ * kernel_ms (optional) [TWXPP_NTIMES]   device time of k_pp_prep and of k_pp_iter over all launches; then host-clock
+ *                            milliseconds of the allocations and copies in, and of the copies back
+ * An item above a cap gets TWXPP_ROW_CAP / TWXPP_COL_CAP / TWXPP_PCS_CAP (looked at in this order) and NaN.
+ * Call-level failures: an item with a matrix and d < 1, d > D or N <= d; a target, column, group or set index out of range;
+ * a set of another group than the item's; threshold or maxits not positive.
+ */
+int twxpp_ppca_fit(int device, int64_t nstn, int64_t ndays, const float *obs, int32_t ngroups, const int8_t *group,
+                   int64_t nitem, const int32_t *item_target, const int32_t *item_group,
+                   const int32_t *item_matrix_status, const int32_t *item_npcs, const int64_t *col_off,
+                   const int32_t *col_idx, int64_t nset, const int32_t *set_group, const int32_t *set_ncol,
+                   const double *set_vals, const int32_t *item_set, const double *norms, const double *stds,
+                   const double *c0, double threshold, int32_t maxits, int32_t iters_per_launch, int64_t workspace_bytes,
+                   double *fit, double *r2cum, int32_t *iters, double *rel, int32_t *status, double *c_out, double *m_out,
+                   int32_t *counts, float *kernel_ms, char *errbuf, int errlen);
+
 #ifdef __cplusplus
 }
 #endif

@@ -375,3 +375,125 @@ def em_mean_variance(obs, group, item_target, item_group, col_off, col_idx, sets
             timing[name + "_ms"] = float(ms[len(EM_KERNELS) + k])
         timing["em_rounds"], timing["em_batches"] = out["rounds"], out["batches"]
     return out
+
+
+# ---- the estimator of step16 (twxpp_ppca_fit; TWXPP_* of include/twx_qa.h) ----
+PP_EXPORTS = ("twxpp_ppca_fit",)
+PP_OK, PP_NUMERIC, PP_MAXITS, PP_NO_MATRIX, PP_EMPTY_COLUMN, PP_ROW_CAP, PP_COL_CAP, PP_PCS_CAP = 0, 4, 20, 21, 22, 23, 24, 25
+PP_MAX_COLS = 64          # TWXPP_MAX_COLS
+PP_MAX_PCS = 32           # TWXPP_MAX_PCS
+PP_MAX_ROWS = 8192        # TWXPP_MAX_ROWS
+PP_SEED = 4324            # pca_infill.R: SEED
+PP_KERNELS = ("pp_prep", "pp_iter")                     # TWXPP_NKERNELS
+PP_HOST_TIMES = ("pp_upload", "pp_download")            # the rest of TWXPP_NTIMES: host-clock milliseconds
+
+
+def ppca_default_c0(ncols, npcs, seed=PP_SEED):
+    """The start of a fit, flat and column-major [D, d]: ``np.random.RandomState(seed).standard_normal(D * d)`` (R's
+    ``rnorm`` stream under ``set.seed(4324)`` cannot be reproduced; this generator is frozen across numpy versions)."""
+    return np.random.RandomState(seed).standard_normal(int(ncols) * int(npcs))
+
+
+def ppca_pack(obs, group, item_target, item_group, item_npcs, col_off, col_idx, norms, stds, c0=None, sets=(),
+              item_set=None, matrix_status=None):
+    """The arrays ``twxpp_ppca_fit`` takes, checked: a dict.  See ``ppca_fit``."""
+    obs, group = _c(obs, np.float32), _c(group, np.int8)
+    item_target, item_group, item_npcs = _c(item_target, np.int32), _c(item_group, np.int32), _c(item_npcs, np.int32)
+    col_off, col_idx = _c(col_off, np.int64), _c(col_idx, np.int32)
+    if obs.ndim != 2 or group.shape != (obs.shape[1],):
+        raise ValueError("obs must be [nstn, ndays] and group [ndays]")
+    ni = item_target.size
+    if item_target.ndim != 1 or ni < 1 or item_group.shape != (ni,) or item_npcs.shape != (ni,) or \
+            col_off.shape != (ni + 1,) or col_idx.ndim != 1 or col_off[0] != 0 or col_off[-1] != col_idx.size:
+        raise ValueError("item_target / item_group / item_npcs must be [nitem >= 1] and col_off [nitem + 1] the CSR "
+                         "offsets of col_idx")
+    ng = int(group.max()) + 1 if group.size and group.max() >= 0 else 1
+    ng = max(ng, int(item_group.max()) + 1)
+    if item_group.min() < 0:
+        raise ValueError("item_group must be >= 0")
+    nrows = np.bincount(group[group >= 0].astype(np.int64), minlength=ng)
+    sets = list(sets)
+    set_group, set_ncol = np.zeros(len(sets), np.int32), np.zeros(len(sets), np.int32)
+    vals = []
+    for s, (g, v) in enumerate(sets):
+        v = np.asarray(v, np.float64)
+        if v.ndim != 2 or not 0 <= int(g) < ng or v.shape[0] != nrows[int(g)]:
+            raise ValueError("extra-column set %d must be [days of its group, ncol]" % s)
+        set_group[s], set_ncol[s] = int(g), v.shape[1]
+        vals.append(np.ascontiguousarray(v.T).ravel())              # column after column
+    set_vals = np.concatenate(vals) if vals else np.zeros(0)
+    item_set = np.full(ni, -1, np.int32) if item_set is None else _c(item_set, np.int32)
+    if item_set.shape != (ni,) or (ni and (item_set.min() < -1 or item_set.max() >= len(sets))):
+        raise ValueError("item_set must be [nitem] of -1 or a set index")
+    if matrix_status is None:
+        matrix_status = np.zeros(ni, np.int32)
+    matrix_status = _c(matrix_status, np.int32)
+    if matrix_status.shape != (ni,):
+        raise ValueError("matrix_status must be [nitem]")
+    ncols = (1 + np.diff(col_off) + np.where(item_set >= 0, set_ncol[np.maximum(item_set, 0)] if len(sets) else 0, 0)
+             ).astype(np.int64)
+    norms, stds = _c(norms, np.float64), _c(stds, np.float64)
+    if norms.shape != (int(ncols.sum()),) or stds.shape != norms.shape:
+        raise ValueError("norms / stds must hold the columns of every item, the items one after the other")
+    nc0 = np.where(matrix_status == IF_OK, ncols * item_npcs, 0)
+    if c0 is None:
+        c0 = np.concatenate([ppca_default_c0(ncols[i], item_npcs[i]) if nc0[i] else np.zeros(0) for i in range(ni)])
+    c0 = _c(c0, np.float64)
+    if c0.shape != (int(nc0.sum()),):
+        raise ValueError("c0 must hold D * d values per item with a matrix, column-major, the items one after the other")
+    fit_off = np.concatenate([[0], np.cumsum(nrows[item_group])]).astype(np.int64)
+    return dict(obs=obs, group=group, ng=ng, item_target=item_target, item_group=item_group, matrix_status=matrix_status,
+                item_npcs=item_npcs, col_off=col_off, col_idx=col_idx, set_group=set_group, set_ncol=set_ncol,
+                set_vals=set_vals, item_set=item_set, norms=norms, stds=stds, c0=c0, fit_off=fit_off, ncols=ncols)
+
+
+def ppca_fit(obs, group, item_target, item_group, item_npcs, col_off, col_idx, norms, stds, c0=None, sets=(),
+             item_set=None, matrix_status=None, threshold=1e-5, maxits=1000, iters_per_launch=0, workspace_bytes=0,
+             full=False, device=0, timing=None):
+    """``twxpp_ppca_fit``: one PPCA fit (pcaMethods' ``ppca`` as include/twx_qa.h restates it) per item.
+
+    obs [nstn, ndays] float32, station-major, NaN = missing; group [ndays] int8, -1 or 0 .. G - 1; item_target,
+    item_group, item_npcs [nitem]; col_off [nitem + 1] / col_idx: the CSR of each item's station columns; ``sets`` /
+    ``item_set`` / ``matrix_status`` as ``em_mean_variance`` takes them; norms / stds: the D values of every item, flat;
+    ``c0``: the starts, flat, D * d values per item column-major (default ``ppca_default_c0``).  Returns a dict of ``fit``
+    (flat) with ``fit_off`` [nitem + 1], r2cum [nitem, 32], iters, rel, status [nitem], ``rounds``, ``batches``, and with
+    ``full`` C [nitem, 64, 32] and M [nitem, 64].  ``timing`` receives ``pp_prep_kernel_ms`` / ``pp_iter_kernel_ms``, the
+    host-clock ``pp_upload_ms`` / ``pp_download_ms`` (accumulated over calls when present), ``pp_rounds``, ``pp_batches``."""
+    L = load()
+    if not hasattr(L.twxpp_ppca_fit, "_twx_ready"):
+        L.twxpp_ppca_fit.restype = C.c_int
+        L.twxpp_ppca_fit.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64] + \
+            [C.c_void_p] * 6 + [C.c_int64] + [C.c_void_p] * 7 + [C.c_double, C.c_int32, C.c_int32, C.c_int64] + \
+            [C.c_void_p] * 9 + [C.c_char_p, C.c_int]
+        L.twxpp_ppca_fit._twx_ready = True
+    p = ppca_pack(obs, group, item_target, item_group, item_npcs, col_off, col_idx, norms, stds, c0, sets, item_set,
+                  matrix_status)
+    ni = p["item_target"].size
+    out = dict(fit=np.empty(int(p["fit_off"][-1])), fit_off=p["fit_off"], r2cum=np.empty((ni, PP_MAX_PCS)),
+               iters=np.empty(ni, np.int32), rel=np.empty(ni), status=np.empty(ni, np.int32))
+    if full:
+        out["C"], out["M"] = np.empty((ni, PP_MAX_COLS, PP_MAX_PCS)), np.empty((ni, PP_MAX_COLS))
+    counts = (C.c_int32 * 2)()
+    ms = (C.c_float * (len(PP_KERNELS) + len(PP_HOST_TIMES)))()
+    buf = C.create_string_buffer(512)
+    rc = L.twxpp_ppca_fit(int(device), p["obs"].shape[0], p["obs"].shape[1], p["obs"].ctypes.data, p["ng"],
+                          p["group"].ctypes.data, ni, p["item_target"].ctypes.data, p["item_group"].ctypes.data,
+                          p["matrix_status"].ctypes.data, p["item_npcs"].ctypes.data, p["col_off"].ctypes.data,
+                          p["col_idx"].ctypes.data, p["set_group"].size, p["set_group"].ctypes.data,
+                          p["set_ncol"].ctypes.data, p["set_vals"].ctypes.data, p["item_set"].ctypes.data,
+                          p["norms"].ctypes.data, p["stds"].ctypes.data, p["c0"].ctypes.data, float(threshold), int(maxits),
+                          int(iters_per_launch), int(workspace_bytes), out["fit"].ctypes.data, out["r2cum"].ctypes.data,
+                          out["iters"].ctypes.data, out["rel"].ctypes.data, out["status"].ctypes.data,
+                          out["C"].ctypes.data if full else None, out["M"].ctypes.data if full else None,
+                          C.addressof(counts), C.addressof(ms), buf, 512)
+    if rc != 0:
+        raise QaError("twxpp_ppca_fit failed: %s" % buf.value.decode(errors="replace"))
+    out["rounds"], out["batches"] = int(counts[0]), int(counts[1])
+    if timing is not None:
+        for k, name in enumerate(PP_KERNELS + PP_HOST_TIMES):
+            key = name + ("_kernel_ms" if k < len(PP_KERNELS) else "_ms")
+            timing[key] = timing.get(key, 0.0) + float(ms[k])
+        timing["pp_rounds"] = timing.get("pp_rounds", 0) + out["rounds"]
+        timing["pp_batches"] = timing.get("pp_batches", 0) + out["batches"]
+        timing["pp_calls"] = timing.get("pp_calls", 0) + 1
+    return out

@@ -1,0 +1,112 @@
+"""``scripts/step16_mpi_infill_stn_daily.py``: the daily infill of every target station and calendar month
+(``topowx_amd.infill.infill_daily``): neighbour matrices, then the PPCA with its search for the number of components, in
+batched GPU calls instead of the reference's MPI farm over stations.  A report: nothing is written into the database.
+
+    python -m topowx_amd.step16 --db all.nc --var tmin --normals step14_report.npz --out infilled.npz [--targets ids.txt]
+                                [--device N]
+
+``--normals``: the report of ``python -m topowx_amd.step14 --estimate`` run for EVERY station of the database (``ids``,
+``mean``, ``variance`` [n, 12]); a station without a finite mean and variance in a month is no neighbour that month, as
+the reference's ``stns_mask`` has it.  ``--targets``: a text file of station ids, one per line (default: every station).
+If the database has ``qflag_tmin`` / ``qflag_tmax`` the flagged observations are set to NaN first.
+
+Prints one JSON line (stations, items, items per status, fits, calls, seconds, kernel milliseconds) and writes
+``infilled.npz``: ``ids`` [ntarget], ``ymd`` [ndays], ``fnl_tair``, ``mask_infill``, ``infill_tair`` [ntarget, ndays], ``mae``,
+``bias`` [ntarget], and per item [ntarget, 12] ``status`` (``topowx_amd.infill.PP_STATUS``), ``matrix_status``, ``npcs``,
+``nfits``, ``iters``, ``r2_not_reached``, ``ncols``, ``item_mae``, ``item_r2``, ``item_impossible``.
+
+The values come from station columns ONLY (the reanalysis reader is not ported) and from a restated estimator whose start
+is not R's: they are not what the reference would write, and there is no ``--write``.
+
+Out of scope: the retry ladder of ``chk_perf``, the variance change-point check, ``tair_mask``, the reanalysis reader, the
+writer of the infilled database.
+
+Exits with 1 if a file cannot be opened, a station id is unknown or the normals do not cover the database's stations.
+"""
+import argparse
+import json
+import sys
+import time
+import zipfile
+
+import numpy as np
+
+from . import ncio
+from .dates import YMD
+from .infill import PP_STATUS, infill_daily
+from .qa import StationObsPool
+from .step14 import QFLAG_VARS, _read_ids, _UnknownIds
+
+__all__ = ["main"]
+
+ITEM_COLUMNS = ("status", "matrix_status", "npcs", "nfits", "iters", "r2_not_reached", "ncols", "item_mae", "item_r2",
+                "item_impossible")
+
+
+class _BadNormals(Exception):
+    pass
+
+
+def _normals(path, pool):
+    """(mean, vari) [n, 12] in the pool's station order from a step14 report."""
+    try:
+        with np.load(path) as z:
+            if not all(k in z.files for k in ("ids", "mean", "variance")):
+                raise _BadNormals("%s has no ids / mean / variance: write it with step14 --estimate" % path)
+            ids, mean, vari = [str(s) for s in z["ids"]], np.asarray(z["mean"], np.float64), np.asarray(z["variance"], np.float64)
+    except (IOError, OSError, ValueError, KeyError, zipfile.BadZipFile) as e:
+        raise _BadNormals("cannot read the normals %s: %s" % (path, e))
+    if mean.shape != (len(ids), 12) or vari.shape != mean.shape:
+        raise _BadNormals("%s: mean / variance must be [%d, 12] over its ids" % (path, len(ids)))
+    pos = {s: i for i, s in enumerate(ids)}
+    missing = [s for s in pool.ids if str(s) not in pos]
+    if missing:
+        raise _UnknownIds("%s: %d stations of the database have no normals (first: %s)" % (path, len(missing), missing[0]))
+    order = [pos[str(s)] for s in pool.ids]
+    return mean[order], vari[order]
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m topowx_amd.step16", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--db", required=True, help="all-stations database (netCDF): tmin / tmax on (time, station_id)")
+    ap.add_argument("--var", required=True, choices=("tmin", "tmax"))
+    ap.add_argument("--normals", required=True, help="report of step14 --estimate over every station (.npz)")
+    ap.add_argument("--out", required=True, help="report to write (.npz)")
+    ap.add_argument("--targets", help="text file of target station ids, one per line (default: every station)")
+    ap.add_argument("--device", type=int, default=0)
+    a = ap.parse_args(argv)
+    try:
+        ds = ncio.open_dataset(a.db, "r")
+        try:
+            qflags = all(name in ds.variables for name in QFLAG_VARS)
+        finally:
+            ds.close()
+        pool = StationObsPool.from_netcdf(a.db, qflags=qflags)
+        targets = _read_ids(a.targets, pool, "target") if a.targets else list(pool.ids)
+        mean, vari = _normals(a.normals, pool)
+    except (_UnknownIds, _BadNormals) as e:
+        print("step16: %s" % e, file=sys.stderr)
+        return 1
+    except (IOError, OSError, ValueError, KeyError) as e:
+        print("step16: cannot open %s: %s" % (getattr(e, "filename", None) or a.db, e), file=sys.stderr)
+        return 1
+    tm = {}
+    t0 = time.perf_counter()
+    r = infill_daily(pool, a.var, targets, mean, vari, device=a.device, timing=tm)
+    sec = time.perf_counter() - t0
+    np.savez_compressed(a.out, ids=r.target_ids, ymd=np.asarray(pool.days[YMD], np.int32), fnl_tair=r.fnl_tair,
+                        mask_infill=r.mask_infill, infill_tair=r.infill_tair, mae=r.mae, bias=r.bias,
+                        **{k: getattr(r, k) for k in ITEM_COLUMNS})
+    line = {"var": a.var, "stations": int(r.target_ids.size), "pool": int(pool.ids.size), "days": int(pool.days.size),
+            "items": int((r.status >= 0).sum()),
+            "status": {PP_STATUS[k]: int((r.status == k).sum()) for k in sorted(PP_STATUS) if (r.status == k).any()},
+            "fits": int(r.nfits.sum()), "calls": int(r.calls), "r2_not_reached": int(r.r2_not_reached.sum()),
+            "seconds": round(sec, 3)}
+    for k in sorted(tm):
+        line[k] = round(tm[k], 3) if isinstance(tm[k], float) else tm[k]
+    print(json.dumps(line), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
