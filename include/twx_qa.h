@@ -474,6 +474,75 @@ int twxpp_ppca_fit(int device, int64_t nstn, int64_t ndays, const float *obs, in
                    double *fit, double *r2cum, int32_t *iters, double *rel, int32_t *status, double *c_out, double *m_out,
                    int32_t *counts, float *kernel_ms, char *errbuf, int errlen);
 
+/* ---- the check of step16's fits: _is_nonoptimal_infill (twx/infill/infill_daily.py:563-595) with hasVarChgPt
+ * (twx/infill/rpy/pca_infill.R:306-310: cpt.var(vals, penalty = "Asymptotic", pen.value = sig) of R's changepoint with the
+ * package defaults: at most one change, normal likelihood, mean unknown), restated: neither R nor the package's text can be
+ * read or run against it.  Deviations: the range tau = 2 .. N - 2 is the package's of the reference's time as recalled
+ * (later versions differ at the ends); the decision is cpt_stat >= pen; a NaN penalty (N too small for the asymptotic
+ * formula, where R stops with an error) means "no change point"; a fit with a non-finite value gets the status
+ * TWXCK_NOT_FITTED where R would raise. ---- */
+#define TWXCK_MAX_ROWS 8192             /* rows of an item: the cap of TWXPP_MAX_ROWS */
+#define TWXCK_DEFAULT_MAE_MAX 2.0               /* infill_daily.py:578 */
+#define TWXCK_DEFAULT_R2_MIN 0.7
+#define TWXCK_DEFAULT_IMPOSSIBLE_HIGH 57.7      /* infill_daily.py:584 */
+#define TWXCK_DEFAULT_IMPOSSIBLE_LOW (-89.4)
+#define TWXCK_VAR_FLOOR 1e-10           /* what a segment variance <= 0 is replaced by */
+#define TWXCK_WORKSPACE_BYTES (256ll << 20)   /* default budget of the per-batch device copies of fit and obs */
+#define TWXCK_NTIMES 3                  /* entries of kernel_ms: k_ck_check, then two host-clock figures */
+
+/* bits of reasons */
+#define TWXCK_LOW_PERF 1                /* mae > mae_max or r2 < r2_min (a NaN compares false, as in the reference) */
+#define TWXCK_IMPOSSIBLE 2              /* nimpossible > 0 */
+#define TWXCK_VAR_CHGPT 4               /* a variance change point */
+#define TWXCK_UNFITTED 8                /* nothing to judge: status TWXCK_NOT_FITTED or TWXCK_ROW_CAP */
+
+/* per-item status */
+#define TWXCK_OK TWX_CELL_OK                      /* checked */
+#define TWXCK_NOT_FITTED 26                       /* a non-finite value in fit: nothing computed; mae, r2, cpt_stat NaN, the
+                                                     counts and cpt_tau 0, reasons = TWXCK_UNFITTED */
+#define TWXCK_FEW_ROWS 27                         /* N < 4 (the package refuses such data): no change point, cpt_stat NaN,
+                                                     cpt_tau 0; the other diagnostics are computed */
+#define TWXCK_ROW_CAP 28                          /* N > TWXCK_MAX_ROWS: as TWXCK_NOT_FITTED, fit and obs are not read */
+
+/*
+ * For every item: fit [N] (degrees C) and obs [N] (NaN, any non-finite value, = missing) on the same days, N = off[i + 1] -
+ * off[i]; V = the rows with a finite obs.
+ *   performance   nobs = |V|; mae = sum_V |fit - obs| / nobs; xbar = sum_V obs / nobs, ybar = sum_V fit / nobs;
+ *                 ssxm = sum_V (obs - xbar)^2, ssym = sum_V (fit - ybar)^2, ssxym = sum_V (obs - xbar)(fit - ybar) (the means
+ *                 first, then the centred sums: two passes); r = ssxym / sqrt(ssxm ssym) clipped to [-1, 1], r = 0 when ssxm
+ *                 or ssym is 0 (scipy.stats.linregress of the reference's time); r2 = r r.  nobs = 0: mae = r2 = NaN.
+ *   impossible    nimpossible = the count of fit > impossible_high plus the count of fit < impossible_low, over all N rows.
+ *   change point  mu = sum fit / N; y2[t] = sum over i <= t of (fit_i - mu)^2, t = 1 .. N; null = N log(y2[N] / N); for
+ *                 tau = 2 .. N - 2: s1 = y2[tau] / tau, sn = (y2[N] - y2[tau]) / (N - tau), each replaced by TWXCK_VAR_FLOOR
+ *                 if <= 0, tmp(tau) = tau log s1 + (N - tau) log sn.  cpt_tau = the FIRST tau of the smallest tmp (a NaN
+ *                 tmp is never the smallest; all NaN: cpt_tau = 0, cpt_stat = NaN); cpt_stat = null - tmp(cpt_tau).  There
+ *                 is a change point iff pen is not NaN and cpt_stat >= pen.  A constant series has null = -infinity and
+ *                 every tmp equal: cpt_tau = 2, cpt_stat = -infinity, no change point.
+ *   reasons       the TWXCK_* bits above.
+ * The kernel (one workgroup of 256 per item, thread k owns the rows k c .. k c + c - 1, c = ceil(N / 256)) sums every
+ * thread's rows in row order, the 64 lanes of a wavefront in a butterfly, the four wavefronts in order; y2[tau] is the
+ * exclusive scan of the 256 chunk sums (shuffle-up inside a wavefront, the wavefront totals added in order) plus the
+ * thread's own partial sum, y2[N] the scan's total.  That order is fixed and there are no float atomics: two calls give the
+ * same bytes, whatever workspace_bytes.  The arg-min compares (tmp, tau) lexicographically.
+ *
+ * off [nitem + 1]            non-decreasing from 0: item i owns fit / obs [off[i], off[i + 1])
+ * fit, obs                   float64, the items one after the other
+ * pen [nitem]                the penalty of each item (the binding's cpt_penalty(N, sig)); NaN: no change point
+ * mae_max, r2_min, impossible_high, impossible_low   finite; the reference's are the TWXCK_DEFAULT_* above
+ * workspace_bytes            <= 0: TWXCK_WORKSPACE_BYTES.  A batch is a run of consecutive items whose fit and obs (16 B a
+ *                            row) fit the budget (at least one item)
+ * nobs, mae, r2, nimpossible, cpt_stat, cpt_tau, reasons, status [nitem]   out
+ * counts (optional) [2]      out: launches of k_ck_check, batches (equal)
+ * kernel_ms (optional) [TWXCK_NTIMES]   device time of k_ck_check over all launches; then host-clock milliseconds of the
+ *                            allocations and copies in, and of the copies back
+ * Call-level failures: nitem < 1, a null buffer, off not non-decreasing from 0, a non-finite scalar.
+ */
+int twxck_infill_check(int device, int64_t nitem, const int64_t *off, const double *fit, const double *obs,
+                       const double *pen, double mae_max, double r2_min, double impossible_high, double impossible_low,
+                       int64_t workspace_bytes, int32_t *nobs, double *mae, double *r2, int32_t *nimpossible,
+                       double *cpt_stat, int32_t *cpt_tau, int32_t *reasons, int32_t *status, int32_t *counts,
+                       float *kernel_ms, char *errbuf, int errlen);
+
 #ifdef __cplusplus
 }
 #endif

@@ -497,3 +497,80 @@ def ppca_fit(obs, group, item_target, item_group, item_npcs, col_off, col_idx, n
         timing["pp_batches"] = timing.get("pp_batches", 0) + out["batches"]
         timing["pp_calls"] = timing.get("pp_calls", 0) + 1
     return out
+
+
+# ---- the check of step16's fits (twxck_infill_check; TWXCK_* of include/twx_qa.h) ----
+CK_EXPORTS = ("twxck_infill_check",)
+CK_OK, CK_NOT_FITTED, CK_FEW_ROWS, CK_ROW_CAP = 0, 26, 27, 28
+CK_LOW_PERF, CK_IMPOSSIBLE, CK_VAR_CHGPT, CK_UNFITTED = 1, 2, 4, 8      # bits of reasons
+CK_MAX_ROWS = 8192        # TWXCK_MAX_ROWS
+CK_MAE_MAX, CK_R2_MIN = 2.0, 0.7                          # infill_daily.py:578
+CK_IMPOSSIBLE_HIGH, CK_IMPOSSIBLE_LOW = 57.7, -89.4       # infill_daily.py:584
+CK_SIG = 1e-10            # pca_infill.R: hasVarChgPt's default sig
+CK_KERNELS = ("ck_check",)
+CK_HOST_TIMES = ("ck_upload", "ck_download")              # the rest of TWXCK_NTIMES: host-clock milliseconds
+
+
+def cpt_penalty(n, sig=CK_SIG):
+    """The "Asymptotic" penalty of ``cpt.var`` for a series of ``n`` values at the level ``sig`` (changepoint's formula for
+    a change in variance, restated): NaN where a logarithm or root has a negative argument (n < 63 at sig = 1e-10), which
+    the check reads as "no change point" and where R stops with an error."""
+    import math
+    try:
+        ll = math.log(math.log(n))
+        a = math.sqrt(2.0 * ll)
+        b = 2.0 * ll + math.log(ll) / 2.0 - math.log(math.gamma(0.5))
+        return (-(math.log(math.log((1.0 - sig + math.exp(-2.0 * math.exp(b))) ** -0.5)) / a) + b / a) ** 2
+    except (ValueError, ZeroDivisionError, OverflowError):
+        return float("nan")
+
+
+def infill_check(off, fit, obs, pen=None, sig=CK_SIG, mae_max=CK_MAE_MAX, r2_min=CK_R2_MIN,
+                 impossible_high=CK_IMPOSSIBLE_HIGH, impossible_low=CK_IMPOSSIBLE_LOW, workspace_bytes=0, device=0,
+                 timing=None):
+    """``twxck_infill_check``: ``_is_nonoptimal_infill`` with ``hasVarChgPt`` (as include/twx_qa.h restates them) of every
+    item.
+
+    off [nitem + 1] non-decreasing from 0; fit, obs [off[-1]] float64, the items one after the other, obs NaN = missing;
+    ``pen`` [nitem] or a scalar: the change-point penalty (default ``cpt_penalty(N, sig)`` per item; NaN: no change point).
+    Returns a dict of nobs, mae, r2, nimpossible, cpt_stat, cpt_tau, reasons (``CK_*`` bits), status and pen [nitem], and
+    ``batches``.  ``timing`` receives ``ck_check_kernel_ms``, the host-clock ``ck_upload_ms`` / ``ck_download_ms``
+    (accumulated over calls when present), ``ck_batches`` and ``ck_calls``."""
+    L = load()
+    if not hasattr(L.twxck_infill_check, "_twx_ready"):
+        L.twxck_infill_check.restype = C.c_int
+        L.twxck_infill_check.argtypes = [C.c_int, C.c_int64] + [C.c_void_p] * 4 + [C.c_double] * 4 + [C.c_int64] + \
+            [C.c_void_p] * 10 + [C.c_char_p, C.c_int]
+        L.twxck_infill_check._twx_ready = True
+    off, fit, obs = _c(off, np.int64), _c(fit, np.float64), _c(obs, np.float64)
+    if off.ndim != 1 or off.size < 2 or fit.ndim != 1 or obs.shape != fit.shape:
+        raise ValueError("off must be [nitem + 1 >= 2] and fit / obs flat arrays of one length")
+    ni = off.size - 1
+    if (np.diff(off) >= 0).all() and off[0] == 0 and off[-1] != fit.size:
+        raise ValueError("off[-1] must be the length of fit / obs")
+    if pen is None:
+        cache = {}
+        pen = np.array([cache.setdefault(int(n), cpt_penalty(int(n), sig)) for n in np.diff(off)], np.float64)
+    pen = _c(np.broadcast_to(np.asarray(pen, np.float64), (ni,)), np.float64)
+    out = dict(nobs=np.empty(ni, np.int32), mae=np.empty(ni), r2=np.empty(ni), nimpossible=np.empty(ni, np.int32),
+               cpt_stat=np.empty(ni), cpt_tau=np.empty(ni, np.int32), reasons=np.empty(ni, np.int32),
+               status=np.empty(ni, np.int32))
+    counts = (C.c_int32 * 2)()
+    ms = (C.c_float * (len(CK_KERNELS) + len(CK_HOST_TIMES)))()
+    buf = C.create_string_buffer(512)
+    rc = L.twxck_infill_check(int(device), ni, off.ctypes.data, fit.ctypes.data, obs.ctypes.data, pen.ctypes.data,
+                              float(mae_max), float(r2_min), float(impossible_high), float(impossible_low),
+                              int(workspace_bytes), out["nobs"].ctypes.data, out["mae"].ctypes.data, out["r2"].ctypes.data,
+                              out["nimpossible"].ctypes.data, out["cpt_stat"].ctypes.data, out["cpt_tau"].ctypes.data,
+                              out["reasons"].ctypes.data, out["status"].ctypes.data, C.addressof(counts), C.addressof(ms),
+                              buf, 512)
+    if rc != 0:
+        raise QaError("twxck_infill_check failed: %s" % buf.value.decode(errors="replace"))
+    out["pen"], out["batches"] = pen, int(counts[1])
+    if timing is not None:
+        for k, name in enumerate(CK_KERNELS + CK_HOST_TIMES):
+            key = name + ("_kernel_ms" if k < len(CK_KERNELS) else "_ms")
+            timing[key] = timing.get(key, 0.0) + float(ms[k])
+        timing["ck_batches"] = timing.get("ck_batches", 0) + out["batches"]
+        timing["ck_calls"] = timing.get("ck_calls", 0) + 1
+    return out

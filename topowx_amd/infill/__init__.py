@@ -2,9 +2,11 @@
 matrices every infill worker starts from (``infill_matrix``; libtwxqa.so's ``twxif_infill_matrix``, kernel source
 ``topowx_amd/qa/twx_infillmat.hip``) and step14's estimate of mean and variance from them (``infill_normals``;
 ``twxem_mean_variance``, ``topowx_amd/qa/twx_emnorm.hip``), and step16's daily infill: the batched PPCA of the matrices
-with its component search (``infill_daily``; ``twxpp_ppca_fit``, ``topowx_amd/qa/twx_ppca.hip``).
+with its component search (``infill_daily``; ``twxpp_ppca_fit``, ``topowx_amd/qa/twx_ppca.hip``) and, with ``chk_perf``, the
+reference's check of every fit and its retry ladder (``RetryLadder``; ``twxck_infill_check``,
+``topowx_amd/qa/twx_infillchk.hip``).
 """
-from .infill_daily import (PP_STATUS, InfillDaily, PcSearch, add_npcs, assemble_daily_columns, daily_items, first_npcs,
+from .infill_daily import (PP_STATUS, InfillDaily, PcSearch, RetryLadder, add_npcs, assemble_daily_columns, daily_items, first_npcs,
                            infill_daily, infill_daily_obs, item_matrix)
 from .infill_matrix import (ITEM_STATUS, MAX_COLS_NORM_IMPUTE, MAX_DISTANCE, MIN_DAILY_NGHBRS, MIN_POR_OVERLAP, InfillMatrices,
                             InfillMatrix, build_infill_matrices, item_thresholds)
@@ -15,4 +17,4 @@ __all__ = ["build_infill_matrices", "InfillMatrices", "InfillMatrix", "item_thre
            "MIN_POR_OVERLAP", "MIN_DAILY_NGHBRS", "MAX_COLS_NORM_IMPUTE", "assemble_columns", "nnr_components",
            "estimate_mean_variance", "infill_mean_variance", "InfillEstimates", "EM_STATUS", "NNGH_NNR", "infill_daily",
            "infill_daily_obs", "InfillDaily", "PcSearch", "assemble_daily_columns", "daily_items", "item_matrix", "first_npcs",
-           "add_npcs", "PP_STATUS"]
+           "add_npcs", "PP_STATUS", "RetryLadder"]

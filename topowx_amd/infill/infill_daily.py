@@ -8,9 +8,15 @@ Deviations (none of them is built).  Neither R nor ``pcaMethods`` can be run: th
 ``RandomState(4324)``, not from R's ``rnorm`` stream, which moves the iteration EM stops at.  The
 warning branch of ``run_ppca`` parses a ``pcaMethods`` warning text and is replaced by a stated rule: a request is never
 above ``min(D - 1, TWXPP_MAX_PCS)``; the bound is tried once and accepted, flagged ``r2_not_reached`` if it misses
-``max_r2cum``.  The retry ladder of ``chk_perf``, ``hasVarChgPt`` / ``changepoint``, ``tair_mask`` (step15), the reanalysis
-reader ``NNRNghData`` (``nnr=None``: station columns only; any object with ``get_nngh_matrix`` may be passed) and the writer
-of the infilled database are out of scope.
+``max_r2cum``.  ``tair_mask`` (step15), the reanalysis reader ``NNRNghData`` (``nnr=None``: station columns only; any object
+with ``get_nngh_matrix`` may be passed) and the writer of the infilled database are out of scope.
+
+``chk_perf=True`` adds the reference's judgement of every fit (``_is_nonoptimal_infill``, :563-595) and its retry ladder
+(:438-518): libtwxqa's ``twxck_infill_check`` judges all items of a stage in ONE call, and ``RetryLadder`` decides per item
+which attempt runs next and which is kept.  ``hasVarChgPt`` (R's ``changepoint``) is restated as include/twx_qa.h states it,
+not executed.  Two rules of ours: an attempt whose inputs equal an earlier one's is not fitted again
+and takes that attempt's result; an attempt that is not fitted is non-optimal and is never kept while a fitted one exists
+(the reference would raise).
 """
 import hashlib
 import time
@@ -23,9 +29,13 @@ from .infill_matrix import MIN_DAILY_NGHBRS, build_infill_matrices
 from .infill_normals import NNGH_NNR, nnr_components
 
 __all__ = ["infill_daily", "infill_daily_obs", "InfillDaily", "PcSearch", "assemble_daily_columns", "daily_items",
-           "item_matrix", "first_npcs", "add_npcs", "PP_STATUS", "MAX_NNR_VAR", "IMPOSSIBLE_HIGH", "IMPOSSIBLE_LOW"]
+           "item_matrix", "first_npcs", "add_npcs", "PP_STATUS", "MAX_NNR_VAR", "IMPOSSIBLE_HIGH", "IMPOSSIBLE_LOW",
+           "RetryLadder", "MIN_NNR_VAR", "RETRY_THRESHOLDS", "NATTEMPTS"]
 
 MAX_NNR_VAR = 0.99                 # infill_daily.py:44
+MIN_NNR_VAR = 0.90                 # infill_daily.py:45: the reanalysis variance of the ladder's first retry
+RETRY_THRESHOLDS = (1e-6, 1e-7)    # infill_daily.py:471: the PPCA thresholds of the second and third retry
+NATTEMPTS = 4
 IMPOSSIBLE_HIGH, IMPOSSIBLE_LOW = 57.7, -89.4      # infill_daily.py:584
 
 PP_STATUS = {_qalib.PP_OK: "ok", _qalib.PP_NUMERIC: "a pivot or ss is <= 0 or not finite",
@@ -100,6 +110,60 @@ class PcSearch(object):
             self.request = min(k + add_npcs(r2, self.max_r2cum), self.bound)
 
 
+class RetryLadder(object):
+    """The ``chk_perf`` block of ``InfillMatrixPPCA.infill`` (infill_daily.py:438-518) for ONE item as a state machine.
+    ``inputs``: what identifies the inputs of the attempts 0 .. 3 (anything comparable; None: the attempt does not exist,
+    which only attempt 1 may: ``MIN_NNR_VAR < max_nnr_var`` fails).  ``request`` is the attempt to run next (None:
+    finished) and ``duplicate`` the earlier attempt with equal inputs, whose result the caller feeds again instead of
+    fitting (None: fit).  ``feed(reasons, mae, fitted=True)`` hands in the check of that attempt (``reasons``: the bit mask of
+    ``twxck_infill_check``; 0 = optimal).  After the end: ``kept`` (the attempt whose series is the result), ``attempts``
+    (those that ran, in order), ``nonoptimal`` (the kept attempt is) and ``retry_fixed`` (a retry was optimal).
+
+    Attempt 0 optimal: done.  Otherwise attempt 1, if it exists; while the latest attempt is non-optimal, attempts 2 and 3.
+    The first optimal attempt is kept.  If none is: among the attempts whose reasons are exactly {low performance}, or among
+    all of them if there is none, the one of least MAE, the first on ties (``np.argmin``); an attempt that was not fitted
+    is left out of that choice while a fitted one exists."""
+
+    def __init__(self, inputs):
+        self.inputs = list(inputs)
+        if len(self.inputs) != NATTEMPTS or any(self.inputs[a] is None for a in (0, 2, 3)):
+            raise ValueError("inputs must describe the attempts 0 .. 3; only attempt 1 may be None")
+        self.request, self.kept, self.nonoptimal, self.retry_fixed = 0, -1, False, False
+        self.attempts, self.reasons, self.mae, self.fitted = [], [], [], []
+
+    @property
+    def duplicate(self):
+        if self.request is None:
+            return None
+        for a in self.attempts:
+            if self.inputs[a] == self.inputs[self.request]:
+                return a
+        return None
+
+    def feed(self, reasons, mae, fitted=True):
+        a = self.request
+        if a is None:
+            raise ValueError("the ladder has ended")
+        self.attempts.append(a)
+        self.reasons.append(int(reasons))
+        self.mae.append(float(mae))
+        self.fitted.append(bool(fitted))
+        if fitted and int(reasons) == 0:
+            self.kept, self.request, self.retry_fixed = a, None, a > 0
+        elif a == 0:
+            self.request = 1 if self.inputs[1] is not None else 2
+        elif a < NATTEMPTS - 1:
+            self.request = a + 1 if a > 1 else 2
+        else:
+            self.request = None
+        if self.request is None and self.kept < 0:
+            self.nonoptimal = True
+            idx = [k for k in range(len(self.attempts)) if self.fitted[k]] or list(range(len(self.attempts)))
+            pure = [k for k in idx if self.reasons[k] == _qalib.CK_LOW_PERF]
+            idx = pure or idx
+            self.kept = self.attempts[idx[int(np.argmin([self.mae[k] for k in idx]))]]
+
+
 def assemble_daily_columns(matrices, target, group, mean_g, vari_g, nnr_scores=None):
     """The matrix ``infill`` hands ``ppca_tair`` for an item (infill_daily.py:373-419): ``(cols, extra, norms, stds)`` with
     ``cols`` the pool columns of the station part after the target (every kept station in rank order: no 31-column cut),
@@ -141,8 +205,8 @@ def daily_items(pool, tair_var, target_ids, mean, vari, nnr=None, utc_offset=Non
                 nnghs_nnr=NNGH_NNR, max_nnr_var=MAX_NNR_VAR, device=0, timing=None):
     """The items of ``infill_daily``, item = target * 12 + month - 1: a list of dicts of ``t`` (row of ``target_ids``),
     ``col`` (the target's pool column), ``g``, ``matrix_status``, ``max_dist``, ``cols``, ``extra``, ``norms``, ``stds``,
-    ``ncomp`` and ``key`` (None or what identifies the item's extra columns); and the station-major observations of the
-    call.  One ``build_infill_matrices`` call per group of months with equal eligibility masks."""
+    ``ncomp``, ``key`` (None or what identifies the item's extra columns) and ``nnr`` (None or the target's reanalysis
+    matrix over every day, shared between its items); and the station-major observations of the call.  One ``build_infill_matrices`` call per group of months with equal eligibility masks."""
     mean, vari = np.asarray(mean, np.float64), np.asarray(vari, np.float64)
     n = pool.ids.size
     if mean.shape != (n, 12) or vari.shape != (n, 12):
@@ -170,7 +234,7 @@ def daily_items(pool, tair_var, target_ids, mean, vari, nnr=None, utc_offset=Non
                 it = dict(t=t, col=int(m.target_cols[t]), g=g, matrix_status=int(m.status[t, g]),
                           max_dist=float(m.max_dist[t, g]), cols=np.zeros(0, np.int64), extra=np.zeros((m.nrows(g), 0)),
                           norms=np.array([mean[m.target_cols[t], g]]),
-                          stds=np.sqrt(np.array([vari[m.target_cols[t], g]])), ncomp=0, key=None)
+                          stds=np.sqrt(np.array([vari[m.target_cols[t], g]])), ncomp=0, key=None, nnr=None)
                 if it["matrix_status"] == _qalib.IF_OK:
                     sc = None
                     if key is not None:
@@ -180,6 +244,7 @@ def daily_items(pool, tair_var, target_ids, mean, vari, nnr=None, utc_offset=Non
                     it["cols"], it["extra"], it["norms"], it["stds"] = assemble_daily_columns(m, t, g, mean[:, g], vari[:, g], sc)
                     it["ncomp"] = it["extra"].shape[1]
                     it["key"] = (key, g) if it["ncomp"] else None
+                    it["nnr"] = a if key is not None else None
                 items[(t, g)] = it
     if obs is None:
         raise ValueError("no day belongs to a calendar month")
@@ -208,7 +273,14 @@ class InfillDaily(object):
     month has no day), ``matrix_status``, ``npcs``, ``nfits``, ``iters`` and ``rel`` of the accepted fit, ``r2_not_reached``,
     ``ncols``, ``ncomp``, and the diagnostics of ``_is_nonoptimal_infill`` that need no R, reported and not acted on:
     ``item_mae``, ``item_r2`` (squared correlation of observed against fit), ``item_impossible`` (fitted values above 57.7 or
-    below -89.4).  ``calls``: library calls (rounds of the search)."""
+    below -89.4).  ``calls``: library calls (rounds of the search).
+
+    With ``chk_perf`` everything above describes the KEPT attempt of the item (``nfits`` and ``calls`` count all attempts),
+    the diagnostics are acted on and ``item_mae`` / ``item_r2`` / ``item_impossible`` are the device's values
+    (``twxck_infill_check``), and per item [ntarget, 12]: ``attempt`` (the kept attempt 0 .. 3; -1: no item or no check),
+    ``nattempts``, ``nonoptimal`` (the kept attempt is), ``retry_fixed`` (a retry was optimal), ``cpt_stat`` / ``cpt_tau`` /
+    ``cpt_pen`` of the kept attempt; per attempt [ntarget, 12, 4]: ``reasons`` (the ``CK_*`` bits of ``_qalib``; -1: the attempt
+    did not run), ``attempt_mae``, ``attempt_r2``.  Without ``chk_perf`` these hold their initial values."""
     PP_STATUS = PP_STATUS
 
     def __init__(self, target_ids, ndays):
@@ -224,6 +296,13 @@ class InfillDaily(object):
         self.rel, self.item_mae, self.item_r2 = (np.full((nt, 12), np.nan) for _ in range(3))
         self.r2_not_reached = np.zeros((nt, 12), bool)
         self.calls = 0
+        self.attempt = np.full((nt, 12), -1, np.int32)
+        self.nattempts = np.zeros((nt, 12), np.int32)
+        self.nonoptimal, self.retry_fixed = np.zeros((nt, 12), bool), np.zeros((nt, 12), bool)
+        self.reasons = np.full((nt, 12, NATTEMPTS), -1, np.int32)
+        self.attempt_mae, self.attempt_r2 = np.full((nt, 12, NATTEMPTS), np.nan), np.full((nt, 12, NATTEMPTS), np.nan)
+        self.cpt_stat, self.cpt_pen = np.full((nt, 12), np.nan), np.full((nt, 12), np.nan)
+        self.cpt_tau = np.zeros((nt, 12), np.int32)
 
 
 def run_search(obs, group, items, npcs=0, frac_obs=0.5, max_r2cum=0.99, threshold=1e-5, maxits=1000, device=0, timing=None,
@@ -267,14 +346,79 @@ def run_search(obs, group, items, npcs=0, frac_obs=0.5, max_r2cum=0.99, threshol
     return search, calls
 
 
+def retry_item(item, nnr_var, day_idx):
+    """The item of the ladder's attempt at ``nnr_var``: the reanalysis scores cut at that variance, the station columns as
+    they are.  ``day_idx``: the day indices of the item's month."""
+    if item["nnr"] is None or item["matrix_status"] != _qalib.IF_OK:
+        return item
+    extra = nnr_components(item["nnr"][day_idx], nnr_var)
+    nst = 1 + len(item["cols"])
+    it = dict(item, extra=extra, ncomp=extra.shape[1], key=(item["key"][0], item["g"], float(nnr_var)) if item["key"] else None)
+    it["norms"] = np.concatenate([item["norms"][:nst], np.mean(extra, axis=0)])
+    it["stds"] = np.concatenate([item["stds"][:nst], np.std(extra, axis=0, ddof=1)])
+    return it
+
+
+def run_ladder(obs, group, items, day_idx, first, max_nnr_var=MAX_NNR_VAR, npcs=0, frac_obs=0.5, max_r2cum=0.99,
+               threshold=1e-5, maxits=1000, cpt_sig=_qalib.CK_SIG, device=0, timing=None, iters_per_launch=0,
+               workspace_bytes=0):
+    """The retry ladder of every item in stages: stage a is one ``run_search`` over the items that take attempt a (``first``:
+    the searches of attempt 0, already run) and ONE ``infill_check`` call for them.  Returns per item its ``RetryLadder``,
+    a dict attempt -> (item, ``PcSearch``, the check's values of the item), and the number of library calls of the search."""
+    has1 = MIN_NNR_VAR < max_nnr_var
+    alt = [retry_item(it, MIN_NNR_VAR, day_idx[it["g"]]) if has1 else None for it in items]
+    thr = (threshold, threshold) + RETRY_THRESHOLDS
+    ladders = [RetryLadder([(it["ncomp"], thr[0]), (alt[i]["ncomp"], thr[1]) if has1 else None, (it["ncomp"], thr[2]),
+                            (it["ncomp"], thr[3])]) for i, it in enumerate(items)]
+    done = [dict() for _ in items]
+    calls, per_attempt = 0, [0] * NATTEMPTS
+    for a in range(NATTEMPTS):
+        stage = [i for i, lad in enumerate(ladders) if lad.request == a]
+        if not stage:
+            continue
+        per_attempt[a] = len(stage)
+        fitl = [i for i in stage if ladders[i].duplicate is None]
+        fitted_here = set(fitl)
+        its = [alt[i] if a == 1 else items[i] for i in fitl]
+        if a == 0:
+            found = dict(zip(fitl, first))
+        elif fitl:
+            srch, n = run_search(obs, group, its, npcs, frac_obs, max_r2cum, thr[a], maxits, device, timing, iters_per_launch,
+                                 workspace_bytes)
+            calls += n
+            found = dict(zip(fitl, srch))
+        if fitl:
+            off = np.concatenate([[0], np.cumsum([found[i].payload[0].size for i in fitl])]).astype(np.int64)
+            ck = _qalib.infill_check(off, np.concatenate([found[i].payload[0] for i in fitl]),
+                                     np.concatenate([obs[items[i]["col"], day_idx[items[i]["g"]]].astype(np.float64)
+                                                     for i in fitl]), None, cpt_sig, device=device, timing=timing)
+            for k, i in enumerate(fitl):
+                done[i][a] = (its[k], found[i], {name: ck[name][k] for name in
+                                                 ("nobs", "mae", "r2", "nimpossible", "cpt_stat", "cpt_tau", "reasons",
+                                                  "status", "pen")})
+        for i in stage:
+            if i not in fitted_here:
+                done[i][a] = done[i][ladders[i].duplicate]
+            it, s, c = done[i][a]
+            ladders[i].feed(int(c["reasons"]), float(c["mae"]), s.status in _FITTED and int(c["status"]) != _qalib.CK_NOT_FITTED
+                            and int(c["status"]) != _qalib.CK_ROW_CAP)
+    if timing is not None:
+        timing["attempt_items"] = per_attempt
+    return ladders, done, calls
+
+
 def infill_daily(pool, tair_var, target_ids, mean, vari, nnr=None, utc_offset=None, min_daily_nnghs=MIN_DAILY_NGHBRS,
                  nnghs_nnr=NNGH_NNR, max_nnr_var=MAX_NNR_VAR, npcs=0, frac_obs_initnpcs=0.5, ppca_varyexplain=0.99,
-                 ppcaConThres=1e-5, maxits=1000, device=0, timing=None, iters_per_launch=0, workspace_bytes=0):
+                 ppcaConThres=1e-5, maxits=1000, device=0, timing=None, iters_per_launch=0, workspace_bytes=0,
+                 chk_perf=False, cpt_sig=_qalib.CK_SIG):
     """Step16 for ``target_ids`` (station ids of ``pool``, a ``StationObsPool`` whose flagged observations are NaN) and
     ``tair_var``, every target and calendar month in batched GPU calls.  ``mean`` / ``vari`` [nstn, 12]: the monthly mean
     and variance of every station of the pool as step14 estimates them (NaN: the station is no neighbour that month).
     ``nnr``: None or an object with the reference's ``get_nngh_matrix``.  The other parameters are ``infill_daily_obs``'s.
-    Returns an ``InfillDaily``.  ``timing`` (a dict) receives kernel milliseconds, launches, calls and host seconds."""
+    ``chk_perf``: judge every fit and refit the non-optimal ones up the reference's ladder (``RetryLadder``; ``cpt_sig``: the
+    level of the variance change-point check); False, the default, stops at every item's first attempt.
+    Returns an ``InfillDaily``.  ``timing`` (a dict) receives kernel milliseconds, launches, calls and host seconds; with
+    ``chk_perf`` also the check's ``ck_*`` figures, ``attempt_items`` (items per attempt), ``nonoptimal`` and ``retry_fixed``."""
     t0 = time.perf_counter()
     items, obs = daily_items(pool, tair_var, target_ids, mean, vari, nnr, utc_offset, min_daily_nnghs, nnghs_nnr,
                              max_nnr_var, device, timing)
@@ -285,9 +429,26 @@ def infill_daily(pool, tair_var, target_ids, mean, vari, nnr=None, utc_offset=No
     t2 = time.perf_counter()
     ids = pool.ids[[pool.idxs[str(s)] for s in np.atleast_1d(np.asarray(target_ids))]]
     out = InfillDaily(ids, pool.days.size)
-    out.calls = calls
     day_idx = [np.nonzero(group == g)[0] for g in range(12)]
-    for it, s in zip(items, search):
+    checks = [None] * len(items)
+    if chk_perf:
+        ladders, done, more = run_ladder(obs, group, items, day_idx, search, max_nnr_var, npcs, frac_obs_initnpcs,
+                                         ppca_varyexplain, ppcaConThres, maxits, cpt_sig, device, timing, iters_per_launch,
+                                         workspace_bytes)
+        calls += more
+        nfits = [sum(s.nfits for s in {id(d[1]): d[1] for d in done[i].values()}.values()) for i in range(len(items))]
+        for i, (it, lad) in enumerate(zip(items, ladders)):
+            t, g = it["t"], it["g"]
+            out.attempt[t, g], out.nattempts[t, g] = lad.kept, len(lad.attempts)
+            out.nonoptimal[t, g], out.retry_fixed[t, g] = lad.nonoptimal, lad.retry_fixed
+            for a in lad.attempts:
+                out.reasons[t, g, a] = done[i][a][2]["reasons"]
+                out.attempt_mae[t, g, a], out.attempt_r2[t, g, a] = done[i][a][2]["mae"], done[i][a][2]["r2"]
+            items[i], search[i], checks[i] = done[i][lad.kept]
+            out.cpt_stat[t, g], out.cpt_tau[t, g], out.cpt_pen[t, g] = (checks[i][k] for k in ("cpt_stat", "cpt_tau", "pen"))
+        t2 = time.perf_counter()
+    out.calls = calls
+    for i, (it, s) in enumerate(zip(items, search)):
         t, g = it["t"], it["g"]
         fit = s.payload[0]
         o = obs[it["col"], day_idx[g]].astype(np.float64)
@@ -305,6 +466,11 @@ def infill_daily(pool, tair_var, target_ids, mean, vari, nnr=None, utc_offset=No
                 out.item_mae[t, g] = np.mean(np.abs(fit[v] - o[v])) if v.any() else np.nan
                 out.item_r2[t, g] = np.corrcoef(o[v], fit[v])[0, 1] ** 2 if v.sum() > 1 else np.nan
             out.item_impossible[t, g] = int(np.sum(fit > IMPOSSIBLE_HIGH) + np.sum(fit < IMPOSSIBLE_LOW))
+            if chk_perf:
+                out.item_mae[t, g], out.item_r2[t, g] = checks[i]["mae"], checks[i]["r2"]
+                out.item_impossible[t, g] = checks[i]["nimpossible"]
+        if chk_perf:
+            out.nfits[t, g] = nfits[i]
     for t in range(len(ids)):                                        # post_infill.update_daily_infill:63-66
         om = ~out.mask_infill[t] & (group >= 0) & np.isfinite(out.infill_tair[t])      # a month without a fit has no part
         with np.errstate(all="ignore"):
@@ -313,7 +479,9 @@ def infill_daily(pool, tair_var, target_ids, mean, vari, nnr=None, utc_offset=No
                 out.mae[t], out.bias[t] = np.mean(np.abs(difs)), np.mean(difs)
     if timing is not None:
         timing.update(assemble_s=t1 - t0, search_s=t2 - t1, writeback_s=time.perf_counter() - t2, pp_items=len(items),
-                      pp_fits=int(sum(s.nfits for s in search)))
+                      pp_fits=int(out.nfits.sum()) if chk_perf else int(sum(s.nfits for s in search)))
+        if chk_perf:
+            timing.update(nonoptimal=int(out.nonoptimal.sum()), retry_fixed=int(out.retry_fixed.sum()))
     return out
 
 
@@ -324,12 +492,14 @@ def infill_daily_obs(stn_id, pool, tair_var, nnr_ds, mean, vari, tair_mask=None,
     mask_infill, infill_tair)`` over the days of the pool.  ``pool`` stands for the reference's ``stn_da``; ``mean`` / ``vari``
     [nstn, 12] for its ``vname_mean`` / ``vname_vari`` (the twelve monthly variables); ``day_masks`` must be the twelve
     calendar-month masks in order, as step16 passes them (``None``, one matrix over every day with one mean and variance, is
-    not implemented).  ``tair_mask`` (step15) and ``chk_perf=True`` (the
-    retry ladder) raise ``NotImplementedError``; ``add_bestngh=False`` is not supported by the matrix builder."""
+    not implemented).  ``tair_mask`` (step15) raises ``NotImplementedError``, and so does ``chk_perf=True`` here: the retry
+    ladder is batched over items, call ``infill_daily(chk_perf=True)`` for it; ``add_bestngh=False`` is not supported by the
+    matrix builder."""
     if tair_mask is not None:
         raise NotImplementedError("tair_mask (cross-validation masking) belongs to step15 and is not implemented")
     if chk_perf:
-        raise NotImplementedError("chk_perf (the retry ladder of InfillMatrixPPCA.infill) is not implemented")
+        raise NotImplementedError("chk_perf (the retry ladder of InfillMatrixPPCA.infill) is not implemented for one "
+                                  "target at a time: call infill_daily(chk_perf=True), which batches it over the items")
     if not add_bestngh:
         raise NotImplementedError("add_bestngh=False is not supported by build_infill_matrices")
     month = np.asarray(pool.days[MONTH], np.int64)

@@ -3,7 +3,7 @@
 batched GPU calls instead of the reference's MPI farm over stations.  A report: nothing is written into the database.
 
     python -m topowx_amd.step16 --db all.nc --var tmin --normals step14_report.npz --out infilled.npz [--targets ids.txt]
-                                [--device N]
+                                [--device N] [--chk-perf [--cpt-sig X]]
 
 ``--normals``: the report of ``python -m topowx_amd.step14 --estimate`` run for EVERY station of the database (``ids``,
 ``mean``, ``variance`` [n, 12]); a station without a finite mean and variance in a month is no neighbour that month, as
@@ -15,11 +15,18 @@ Prints one JSON line (stations, items, items per status, fits, calls, seconds, k
 ``bias`` [ntarget], and per item [ntarget, 12] ``status`` (``topowx_amd.infill.PP_STATUS``), ``matrix_status``, ``npcs``,
 ``nfits``, ``iters``, ``r2_not_reached``, ``ncols``, ``item_mae``, ``item_r2``, ``item_impossible``.
 
+``--chk-perf``: judge every fit as the reference's ``_is_nonoptimal_infill`` does (MAE, r2, impossible values, a variance
+change point at the level ``--cpt-sig``, default 1e-10) and refit the non-optimal ones up its retry ladder
+(``infill_daily(chk_perf=True)``).  The report then also holds ``attempt``, ``nattempts``,
+``nonoptimal``, ``retry_fixed``, ``cpt_stat``, ``cpt_tau``, ``cpt_pen`` [ntarget, 12] and ``reasons``, ``attempt_mae``,
+``attempt_r2`` [ntarget, 12, 4], and the JSON line ``attempt_items`` (items per attempt), ``nonoptimal``, ``retry_fixed`` and
+the check's ``ck_check_kernel_ms``.  Without the flag the report and the JSON line are what they were.
+
 The values come from station columns ONLY (the reanalysis reader is not ported) and from a restated estimator whose start
 is not R's: they are not what the reference would write, and there is no ``--write``.
 
-Out of scope: the retry ladder of ``chk_perf``, the variance change-point check, ``tair_mask``, the reanalysis reader, the
-writer of the infilled database.
+Out of scope: ``tair_mask``, the reanalysis reader, the writer of the infilled database.  The variance change-point check
+is restated, not R's ``changepoint`` executed.
 
 Exits with 1 if a file cannot be opened, a station id is unknown or the normals do not cover the database's stations.
 """
@@ -41,6 +48,8 @@ __all__ = ["main"]
 
 ITEM_COLUMNS = ("status", "matrix_status", "npcs", "nfits", "iters", "r2_not_reached", "ncols", "item_mae", "item_r2",
                 "item_impossible")
+CHK_COLUMNS = ("attempt", "nattempts", "nonoptimal", "retry_fixed", "cpt_stat", "cpt_tau", "cpt_pen", "reasons", "attempt_mae",
+               "attempt_r2")
 
 
 class _BadNormals(Exception):
@@ -74,6 +83,8 @@ def main(argv=None):
     ap.add_argument("--out", required=True, help="report to write (.npz)")
     ap.add_argument("--targets", help="text file of target station ids, one per line (default: every station)")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--chk-perf", action="store_true", help="judge every fit and refit the non-optimal ones up the retry ladder")
+    ap.add_argument("--cpt-sig", type=float, default=1e-10, help="level of the variance change-point check (with --chk-perf)")
     a = ap.parse_args(argv)
     try:
         ds = ncio.open_dataset(a.db, "r")
@@ -92,11 +103,14 @@ def main(argv=None):
         return 1
     tm = {}
     t0 = time.perf_counter()
-    r = infill_daily(pool, a.var, targets, mean, vari, device=a.device, timing=tm)
+    if a.chk_perf:
+        r = infill_daily(pool, a.var, targets, mean, vari, device=a.device, timing=tm, chk_perf=True, cpt_sig=a.cpt_sig)
+    else:
+        r = infill_daily(pool, a.var, targets, mean, vari, device=a.device, timing=tm)
     sec = time.perf_counter() - t0
     np.savez_compressed(a.out, ids=r.target_ids, ymd=np.asarray(pool.days[YMD], np.int32), fnl_tair=r.fnl_tair,
                         mask_infill=r.mask_infill, infill_tair=r.infill_tair, mae=r.mae, bias=r.bias,
-                        **{k: getattr(r, k) for k in ITEM_COLUMNS})
+                        **{k: getattr(r, k) for k in ITEM_COLUMNS + (CHK_COLUMNS if a.chk_perf else ())})
     line = {"var": a.var, "stations": int(r.target_ids.size), "pool": int(pool.ids.size), "days": int(pool.days.size),
             "items": int((r.status >= 0).sum()),
             "status": {PP_STATUS[k]: int((r.status == k).sum()) for k in sorted(PP_STATUS) if (r.status == k).any()},
