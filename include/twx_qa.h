@@ -543,6 +543,69 @@ int twxck_infill_check(int device, int64_t nitem, const int64_t *off, const doub
                        double *cpt_stat, int32_t *cpt_tau, int32_t *reasons, int32_t *status, int32_t *counts,
                        float *kernel_ms, char *errbuf, int errlen);
 
+/* ---- step15, the cross-validation of the infill (twx/infill/xval_infill.py, scripts/step15_mpi_xval_infill.py): which
+ * observations of a station are hidden from its own infill, the neighbour matrices of a target that must not see its own
+ * full record, and the comparison of the infilled series with the hidden observations.  The chain between them is
+ * twxem_mean_variance, twxpp_ppca_fit and twxck_infill_check as they are: the masked series of a cross-validation station
+ * travels as a row APPENDED to the pool (same longitude / latitude, never eligible), the target is that row, and the
+ * station's own row is the one excluded from its neighbours, so every other target still sees the full record. ---- */
+#define TWXXV_NGROUPS 12                /* day groups of twxxv_score (the calendar months) */
+#define TWXXV_NSCORES 13                /* entries per series of n / bias / mae: the groups, then the whole series */
+
+/*
+ * XvalInfill.__init__ (:73-86) in closed form.  For target row t = obs[target_idx[t]]: day d is HELD iff its value is
+ * finite and, when nkeep > 0, at least nkeep finite days of the row lie after d (the reference keeps
+ * np.nonzero(fin)[0][-nkeep:]).  nkeep == 0 holds nothing ([-0:] is the whole list: the reference's quirk, kept); a row
+ * with at most nkeep finite days holds nothing.  Any non-finite value is missing.  nkeep is the caller's
+ * int(np.round(ntrain_yrs * 365.25)), rounded half to even.
+ *
+ * obs [nstn][ndays]          station-major float32; only the targets' rows are copied to the device
+ * target_idx [ntarget]       0 <= index < nstn
+ * held [ntarget][ndays]      out: 1 = held
+ * train_obs [ntarget][ndays] out: the row with the held days NaN (0x7fc00000), every other value bit for bit
+ * nheld, nfinite [ntarget]   out: held days, finite days of the row
+ * kernel_ms (optional) [1]   device time of k_xv_holdout
+ * Call-level failures: nstn, ndays or ntarget < 1, nkeep < 0, a null buffer, an index out of range.
+ */
+int twxxv_holdout(int device, int64_t nstn, int64_t ndays, const float *obs, int64_t ntarget, const int32_t *target_idx,
+                  int32_t nkeep, uint8_t *held, float *train_obs, int32_t *nheld, int32_t *nfinite, float *kernel_ms,
+                  char *errbuf, int errlen);
+
+/*
+ * twxif_infill_matrix (same driver, same kernels, same outputs) with exclude_idx [ntarget]: a row of the pool that is never
+ * a neighbour of that target, or -1.  With every entry -1 the outputs are twxif_infill_matrix's byte for byte; with row x
+ * excluded they are those of a call in which eligible[x] is 0 for that target alone.
+ * Call-level failures: twxif_infill_matrix's, and an exclude_idx outside -1 .. nstn - 1.
+ */
+int twxxv_infill_matrix(int device, int64_t nstn, int64_t ndays, const double *lon, const double *lat, const float *obs,
+                        const int32_t *ymd, const uint8_t *eligible, int64_t ntarget, const int32_t *target_idx,
+                        const int32_t *exclude_idx, int32_t ngroups, const int8_t *group, const int32_t *nthres_all,
+                        const int32_t *nthres_target_por, int32_t min_daily_nnghs, int32_t *status, int32_t *nnghs,
+                        double *max_dist, int64_t *csr_off, int64_t csr_cap, int32_t *ngh_idx, double *ngh_ioa,
+                        double *ngh_dist, int32_t *ngh_nlap, int32_t *ngh_nlap_stn, uint8_t *keep, int32_t *nrounds,
+                        float *kernel_ms, char *errbuf, int errlen);
+
+/*
+ * run_xval:153-154 and the writer's np.ma arithmetic (step15:127-134).  A day of series s is SCORED iff held[s][d] != 0
+ * and infill[s][d] is finite.  Over the scored days of the series, and over those of each group g (group[d] == g):
+ *   n, bias = sum(infill - obs) / n, mae = sum |infill - obs| / n     (n == 0: NaN)
+ * fp64 on the float32 observations widened exactly.  One workgroup of 256 per series, one pass: thread i adds its days i,
+ * i + 256, ... in ascending order to thirteen accumulators of its own, and for each of them the 256 partial sums meet in
+ * a halving tree; no float atomics: two calls give the same bytes.
+ *
+ * infill [nseries][ndays]    float64, NaN = not fitted
+ * obs [nseries][ndays]       float32; finite wherever held is set (what twxxv_holdout gives)
+ * held [nseries][ndays]      0 / not 0
+ * group [ndays]              -1 (in no group) or 0 .. TWXXV_NGROUPS - 1; shared by the series
+ * n, bias, mae [nseries][TWXXV_NSCORES]   out: entries 0 .. 11 the groups, entry 12 the whole series
+ * obs_out, infill_out [nseries][ndays]    out, float32: the value on the scored days, NaN elsewhere (what step15 stores)
+ * kernel_ms (optional) [1]   device time of k_xv_score
+ * Call-level failures: nseries or ndays < 1, a null buffer, a group value outside -1 .. 11.
+ */
+int twxxv_score(int device, int64_t nseries, int64_t ndays, const double *infill, const float *obs, const uint8_t *held,
+                const int8_t *group, int32_t *n, double *bias, double *mae, float *obs_out, float *infill_out,
+                float *kernel_ms, char *errbuf, int errlen);
+
 #ifdef __cplusplus
 }
 #endif

@@ -233,7 +233,7 @@ INFILL_MATRIX_HOST_TIMES = ("upload", "download")               # the rest of TW
 
 
 def infill_matrix(lon, lat, obs, ymd, eligible, target_idx, group, nthres_all, nthres_target_por, min_daily_nnghs=3,
-                  device=0, timing=None):
+                  device=0, timing=None, exclude_idx=None):
     """``twxif_infill_matrix``: the ranked, widened and shrunk neighbour lists of ``_InfillMatrix``
     (infill_normals.py:52-237, 324-343, 391-420) of every (target, day group) item.
 
@@ -241,8 +241,19 @@ def infill_matrix(lon, lat, obs, ymd, eligible, target_idx, group, nthres_all, n
     [nstn] bool; target_idx [ntarget]; group [ndays] int8, -1 or 0 .. G - 1; nthres_all [G], nthres_target_por
     [ntarget, G].  Returns a dict of status, nnghs, max_dist [ntarget, G], off [ntarget * G + 1] and the CSR columns idx,
     ioa, dist, nlap, nlap_stn, keep, and ``rounds``.  ``timing`` receives ``<kernel>_kernel_ms`` for the names in
-    ``INFILL_MATRIX_KERNELS``, the host-clock ``upload_ms`` / ``download_ms`` and ``rounds``."""
+    ``INFILL_MATRIX_KERNELS``, the host-clock ``upload_ms`` / ``download_ms`` and ``rounds``.
+
+    ``exclude_idx`` [ntarget] (-1 or a pool row that is never a neighbour of that target) picks ``twxxv_infill_matrix``, the
+    same driver and kernels with that one comparison more (step15)."""
     L = load()
+    if exclude_idx is not None:
+        if not hasattr(L.twxxv_infill_matrix, "_twx_ready"):
+            L.twxxv_infill_matrix.restype = C.c_int
+            L.twxxv_infill_matrix.argtypes = [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + \
+                [C.c_int64, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 4 + \
+                [C.c_int64] + [C.c_void_p] * 8 + [C.c_char_p, C.c_int]
+            L.twxxv_infill_matrix._twx_ready = True
+        exclude_idx = _c(exclude_idx, np.int32)
     if not hasattr(L.twxif_infill_matrix, "_twx_ready"):
         L.twxif_infill_matrix.restype = C.c_int
         L.twxif_infill_matrix.argtypes = [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_int32] + \
@@ -260,6 +271,8 @@ def infill_matrix(lon, lat, obs, ymd, eligible, target_idx, group, nthres_all, n
     ng = nthres_all.size
     if nthres_target_por.shape != (nt, ng):
         raise ValueError("nthres_target_por must be [ntarget, ngroups]")
+    if exclude_idx is not None and exclude_idx.shape != (nt,):
+        raise ValueError("exclude_idx must be [ntarget]")
     ni = nt * ng
     cap = ni * MAX_RADIUS_NGH                      # always enough; the pages of an empty array are not touched
     out = dict(status=np.empty((nt, ng), np.int32), nnghs=np.empty((nt, ng), np.int32), max_dist=np.empty((nt, ng)),
@@ -269,15 +282,18 @@ def infill_matrix(lon, lat, obs, ymd, eligible, target_idx, group, nthres_all, n
     rounds = C.c_int32(0)
     ms = (C.c_float * (len(INFILL_MATRIX_KERNELS) + len(INFILL_MATRIX_HOST_TIMES)))()
     buf = C.create_string_buffer(512)
-    rc = L.twxif_infill_matrix(int(device), nstn, ndays, lon.ctypes.data, lat.ctypes.data, obs.ctypes.data, ymd.ctypes.data,
-                               eligible.ctypes.data, nt, target_idx.ctypes.data, ng, group.ctypes.data,
-                               nthres_all.ctypes.data, nthres_target_por.ctypes.data, int(min_daily_nnghs),
-                               out["status"].ctypes.data, out["nnghs"].ctypes.data, out["max_dist"].ctypes.data,
-                               out["off"].ctypes.data, cap, col["idx"].ctypes.data, col["ioa"].ctypes.data,
-                               col["dist"].ctypes.data, col["nlap"].ctypes.data, col["nlap_stn"].ctypes.data,
-                               col["keep"].ctypes.data, C.addressof(rounds), C.addressof(ms), buf, 512)
+    head = (int(device), nstn, ndays, lon.ctypes.data, lat.ctypes.data, obs.ctypes.data, ymd.ctypes.data,
+            eligible.ctypes.data, nt, target_idx.ctypes.data)
+    tail = (ng, group.ctypes.data, nthres_all.ctypes.data, nthres_target_por.ctypes.data, int(min_daily_nnghs),
+            out["status"].ctypes.data, out["nnghs"].ctypes.data, out["max_dist"].ctypes.data, out["off"].ctypes.data, cap,
+            col["idx"].ctypes.data, col["ioa"].ctypes.data, col["dist"].ctypes.data, col["nlap"].ctypes.data,
+            col["nlap_stn"].ctypes.data, col["keep"].ctypes.data, C.addressof(rounds), C.addressof(ms), buf, 512)
+    if exclude_idx is None:
+        name, rc = "twxif_infill_matrix", L.twxif_infill_matrix(*(head + tail))
+    else:
+        name, rc = "twxxv_infill_matrix", L.twxxv_infill_matrix(*(head + (exclude_idx.ctypes.data,) + tail))
     if rc != 0:
-        raise QaError("twxif_infill_matrix failed: %s" % buf.value.decode(errors="replace"))
+        raise QaError("%s failed: %s" % (name, buf.value.decode(errors="replace")))
     total = int(out["off"][-1])
     for k, a in col.items():
         out[k] = a[:total].copy()
@@ -574,3 +590,77 @@ def infill_check(off, fit, obs, pen=None, sig=CK_SIG, mae_max=CK_MAE_MAX, r2_min
         timing["ck_batches"] = timing.get("ck_batches", 0) + out["batches"]
         timing["ck_calls"] = timing.get("ck_calls", 0) + 1
     return out
+
+
+# ---- step15, the cross-validation of the infill (twxxv_*; TWXXV_* of include/twx_qa.h) ----
+XV_EXPORTS = ("twxxv_holdout", "twxxv_infill_matrix", "twxxv_score")
+XV_NGROUPS = 12           # TWXXV_NGROUPS
+XV_NSCORES = 13           # TWXXV_NSCORES: the groups, then the whole series
+
+
+def xval_nkeep(ntrain_yrs):
+    """The observations kept for training (xval_infill.py:73): ``int(np.round(ntrain_yrs * 365.25))``, half to even."""
+    return int(np.round(ntrain_yrs * 365.25))
+
+
+def holdout(obs, target_idx, nkeep, device=0, timing=None):
+    """``twxxv_holdout``: the held-out observations of ``XvalInfill.__init__`` (xval_infill.py:73-86) for the rows
+    ``target_idx`` of obs [nstn, ndays] float32 (station-major).  A finite day is held iff ``nkeep > 0`` and at least
+    ``nkeep`` finite days of the row lie after it.  Returns a dict of ``held`` [ntarget, ndays] bool, ``train_obs``
+    [ntarget, ndays] float32 (held days NaN, the rest bit for bit), ``nheld`` and ``nfinite`` [ntarget]."""
+    L = load()
+    if not hasattr(L.twxxv_holdout, "_twx_ready"):
+        L.twxxv_holdout.restype = C.c_int
+        L.twxxv_holdout.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32] + \
+            [C.c_void_p] * 5 + [C.c_char_p, C.c_int]
+        L.twxxv_holdout._twx_ready = True
+    obs, target_idx = _c(obs, np.float32), _c(target_idx, np.int32)
+    if obs.ndim != 2 or target_idx.ndim != 1:
+        raise ValueError("obs must be [nstn, ndays] and target_idx [ntarget]")
+    if not isinstance(nkeep, (int, np.integer)):
+        raise ValueError("nkeep must be an integer (xval_nkeep(ntrain_yrs))")
+    nstn, ndays = obs.shape
+    nt = target_idx.size
+    held, train = np.zeros((nt, ndays), np.uint8), np.empty((nt, ndays), np.float32)
+    nheld, nfin = np.zeros(nt, np.int32), np.zeros(nt, np.int32)
+    ms = C.c_float(0.0)
+    buf = C.create_string_buffer(512)
+    rc = L.twxxv_holdout(int(device), nstn, ndays, obs.ctypes.data, nt, target_idx.ctypes.data, int(nkeep),
+                         held.ctypes.data, train.ctypes.data, nheld.ctypes.data, nfin.ctypes.data, C.addressof(ms), buf, 512)
+    if rc != 0:
+        raise QaError("twxxv_holdout failed: %s" % buf.value.decode(errors="replace"))
+    if timing is not None:
+        timing["xv_holdout_kernel_ms"] = float(ms.value)
+    return dict(held=held.view(np.bool_), train_obs=train, nheld=nheld, nfinite=nfin)
+
+
+def xval_score(infill, obs, held, group, device=0, timing=None):
+    """``twxxv_score``: bias and MAE of the infilled series against the held-out observations (run_xval:153-154 and the
+    writer's arithmetic, step15:127-134).  infill [ns, ndays] float64; obs [ns, ndays] float32; held [ns, ndays] bool; group
+    [ndays] int8, -1 or 0 .. 11.  Returns a dict of ``n``, ``bias``, ``mae`` [ns] over the whole series, ``group_n``,
+    ``group_bias``, ``group_mae`` [ns, 12], and ``obs_out`` / ``infill_out`` [ns, ndays] float32 (NaN off the scored days)."""
+    L = load()
+    if not hasattr(L.twxxv_score, "_twx_ready"):
+        L.twxxv_score.restype = C.c_int
+        L.twxxv_score.argtypes = [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 10 + [C.c_char_p, C.c_int]
+        L.twxxv_score._twx_ready = True
+    infill, obs = _c(infill, np.float64), _c(obs, np.float32)
+    held, group = _c(np.asarray(held) != 0, np.uint8), _c(group, np.int8)
+    if infill.ndim != 2 or obs.shape != infill.shape or held.shape != infill.shape or group.shape != infill.shape[1:]:
+        raise ValueError("infill / obs / held must be [nseries, ndays] and group [ndays]")
+    ns, ndays = infill.shape
+    n = np.zeros((ns, XV_NSCORES), np.int32)
+    bias, mae = np.empty((ns, XV_NSCORES)), np.empty((ns, XV_NSCORES))
+    oo, io = np.empty((ns, ndays), np.float32), np.empty((ns, ndays), np.float32)
+    ms = C.c_float(0.0)
+    buf = C.create_string_buffer(512)
+    rc = L.twxxv_score(int(device), ns, ndays, infill.ctypes.data, obs.ctypes.data, held.ctypes.data, group.ctypes.data,
+                       n.ctypes.data, bias.ctypes.data, mae.ctypes.data, oo.ctypes.data, io.ctypes.data, C.addressof(ms),
+                       buf, 512)
+    if rc != 0:
+        raise QaError("twxxv_score failed: %s" % buf.value.decode(errors="replace"))
+    if timing is not None:
+        timing["xv_score_kernel_ms"] = float(ms.value)
+    return dict(n=n[:, XV_NGROUPS].copy(), bias=bias[:, XV_NGROUPS].copy(), mae=mae[:, XV_NGROUPS].copy(),
+                group_n=n[:, :XV_NGROUPS].copy(), group_bias=bias[:, :XV_NGROUPS].copy(),
+                group_mae=mae[:, :XV_NGROUPS].copy(), obs_out=oo, infill_out=io)

@@ -4,7 +4,8 @@ matrices every infill worker starts from (``infill_matrix``; libtwxqa.so's ``twx
 ``twxem_mean_variance``, ``topowx_amd/qa/twx_emnorm.hip``), and step16's daily infill: the batched PPCA of the matrices
 with its component search (``infill_daily``; ``twxpp_ppca_fit``, ``topowx_amd/qa/twx_ppca.hip``) and, with ``chk_perf``, the
 reference's check of every fit and its retry ladder (``RetryLadder``; ``twxck_infill_check``,
-``topowx_amd/qa/twx_infillchk.hip``).
+``topowx_amd/qa/twx_infillchk.hip``); and step15's cross-validation of that chain (``xval_infill``: ``XvalInfill``;
+``twxxv_holdout`` / ``twxxv_infill_matrix`` / ``twxxv_score``, ``topowx_amd/qa/twx_xvalinfill.hip``).
 """
 from .infill_daily import (PP_STATUS, InfillDaily, PcSearch, RetryLadder, add_npcs, assemble_daily_columns, daily_items, first_npcs,
                            infill_daily, infill_daily_obs, item_matrix)
@@ -12,9 +13,10 @@ from .infill_matrix import (ITEM_STATUS, MAX_COLS_NORM_IMPUTE, MAX_DISTANCE, MIN
                             InfillMatrix, build_infill_matrices, item_thresholds)
 from .infill_normals import (EM_STATUS, NNGH_NNR, InfillEstimates, assemble_columns, estimate_mean_variance,
                              infill_mean_variance, nnr_components)
+from .xval_infill import XvalInfill, XvalInfillParams, XvalInfillResult
 
 __all__ = ["build_infill_matrices", "InfillMatrices", "InfillMatrix", "item_thresholds", "ITEM_STATUS", "MAX_DISTANCE",
            "MIN_POR_OVERLAP", "MIN_DAILY_NGHBRS", "MAX_COLS_NORM_IMPUTE", "assemble_columns", "nnr_components",
            "estimate_mean_variance", "infill_mean_variance", "InfillEstimates", "EM_STATUS", "NNGH_NNR", "infill_daily",
            "infill_daily_obs", "InfillDaily", "PcSearch", "assemble_daily_columns", "daily_items", "item_matrix", "first_npcs",
-           "add_npcs", "PP_STATUS", "RetryLadder"]
+           "add_npcs", "PP_STATUS", "RetryLadder", "XvalInfill", "XvalInfillParams", "XvalInfillResult"]

@@ -8,8 +8,9 @@ Deviations (none of them is built).  Neither R nor ``pcaMethods`` can be run: th
 ``RandomState(4324)``, not from R's ``rnorm`` stream, which moves the iteration EM stops at.  The
 warning branch of ``run_ppca`` parses a ``pcaMethods`` warning text and is replaced by a stated rule: a request is never
 above ``min(D - 1, TWXPP_MAX_PCS)``; the bound is tried once and accepted, flagged ``r2_not_reached`` if it misses
-``max_r2cum``.  ``tair_mask`` (step15), the reanalysis reader ``NNRNghData`` (``nnr=None``: station columns only; any object
-with ``get_nngh_matrix`` may be passed) and the writer of the infilled database are out of scope.
+``max_r2cum``.  ``tair_mask`` is not an argument here (step15 is ``topowx_amd.infill.XvalInfill``); the reanalysis reader
+``NNRNghData`` (``nnr=None``: station columns only; any object with ``get_nngh_matrix`` may be passed) and the writer of the
+infilled database are out of scope.
 
 ``chk_perf=True`` adds the reference's judgement of every fit (``_is_nonoptimal_infill``, :563-595) and its retry ladder
 (:438-518): libtwxqa's ``twxck_infill_check`` judges all items of a stage in ONE call, and ``RetryLadder`` decides per item
@@ -187,10 +188,13 @@ def assemble_daily_columns(matrices, target, group, mean_g, vari_g, nnr_scores=N
     return kept, extra, norms, stds
 
 
-def month_mask_groups(mean, vari):
+def month_mask_groups(mean, vari, never_neighbour=None):
     """The calendar months grouped by equal eligibility masks (the reference's ``stns_mask``: finite mean and variance of
-    the month): a list of (mask [nstn] bool, months)."""
+    the month): a list of (mask [nstn] bool, months).  ``never_neighbour`` [nstn] bool: rows that are eligible in no month
+    (step15's appended rows: their estimates must not split the months into more groups)."""
     elig = np.isfinite(mean) & np.isfinite(vari)
+    if never_neighbour is not None:
+        elig[np.asarray(never_neighbour, bool)] = False
     out, seen = [], {}
     for g in range(12):
         key = elig[:, g].tobytes()
@@ -202,22 +206,25 @@ def month_mask_groups(mean, vari):
 
 
 def daily_items(pool, tair_var, target_ids, mean, vari, nnr=None, utc_offset=None, min_daily_nnghs=MIN_DAILY_NGHBRS,
-                nnghs_nnr=NNGH_NNR, max_nnr_var=MAX_NNR_VAR, device=0, timing=None):
+                nnghs_nnr=NNGH_NNR, max_nnr_var=MAX_NNR_VAR, device=0, timing=None, exclude_cols=None,
+                never_neighbour=None):
     """The items of ``infill_daily``, item = target * 12 + month - 1: a list of dicts of ``t`` (row of ``target_ids``),
     ``col`` (the target's pool column), ``g``, ``matrix_status``, ``max_dist``, ``cols``, ``extra``, ``norms``, ``stds``,
     ``ncomp``, ``key`` (None or what identifies the item's extra columns) and ``nnr`` (None or the target's reanalysis
-    matrix over every day, shared between its items); and the station-major observations of the call.  One ``build_infill_matrices`` call per group of months with equal eligibility masks."""
+    matrix over every day, shared between its items); and the station-major observations of the call.  One ``build_infill_matrices`` call per group of months with equal eligibility masks.
+    ``exclude_cols`` / ``never_neighbour``: as ``build_infill_matrices`` takes them (step15)."""
     mean, vari = np.asarray(mean, np.float64), np.asarray(vari, np.float64)
     n = pool.ids.size
     if mean.shape != (n, 12) or vari.shape != (n, 12):
         raise ValueError("mean / vari must be [nstn, 12] over the stations of the pool")
     month = np.asarray(pool.days[MONTH], np.int64) - 1
     items, obs = {}, None
-    for mask, months in month_mask_groups(mean, vari):
+    for mask, months in month_mask_groups(mean, vari, never_neighbour):
         grp = np.where(np.isin(month, months), month, -1).astype(np.int8)
         if not (grp >= 0).any():
             continue
-        m = build_infill_matrices(pool, tair_var, target_ids, mask, grp, min_daily_nnghs, device, timing=timing)
+        m = build_infill_matrices(pool, tair_var, target_ids, mask, grp, min_daily_nnghs, device, timing=timing,
+                                  exclude_cols=exclude_cols)
         obs = m.obs_station_major
         scores = {}
         for t in range(len(m.target_ids)):
@@ -410,18 +417,19 @@ def run_ladder(obs, group, items, day_idx, first, max_nnr_var=MAX_NNR_VAR, npcs=
 def infill_daily(pool, tair_var, target_ids, mean, vari, nnr=None, utc_offset=None, min_daily_nnghs=MIN_DAILY_NGHBRS,
                  nnghs_nnr=NNGH_NNR, max_nnr_var=MAX_NNR_VAR, npcs=0, frac_obs_initnpcs=0.5, ppca_varyexplain=0.99,
                  ppcaConThres=1e-5, maxits=1000, device=0, timing=None, iters_per_launch=0, workspace_bytes=0,
-                 chk_perf=False, cpt_sig=_qalib.CK_SIG):
+                 chk_perf=False, cpt_sig=_qalib.CK_SIG, exclude_cols=None, never_neighbour=None):
     """Step16 for ``target_ids`` (station ids of ``pool``, a ``StationObsPool`` whose flagged observations are NaN) and
     ``tair_var``, every target and calendar month in batched GPU calls.  ``mean`` / ``vari`` [nstn, 12]: the monthly mean
     and variance of every station of the pool as step14 estimates them (NaN: the station is no neighbour that month).
     ``nnr``: None or an object with the reference's ``get_nngh_matrix``.  The other parameters are ``infill_daily_obs``'s.
     ``chk_perf``: judge every fit and refit the non-optimal ones up the reference's ladder (``RetryLadder``; ``cpt_sig``: the
     level of the variance change-point check); False, the default, stops at every item's first attempt.
+    ``exclude_cols`` [ntarget] / ``never_neighbour`` [nstn]: as ``build_infill_matrices`` takes them (step15's ``XvalInfill``).
     Returns an ``InfillDaily``.  ``timing`` (a dict) receives kernel milliseconds, launches, calls and host seconds; with
     ``chk_perf`` also the check's ``ck_*`` figures, ``attempt_items`` (items per attempt), ``nonoptimal`` and ``retry_fixed``."""
     t0 = time.perf_counter()
     items, obs = daily_items(pool, tair_var, target_ids, mean, vari, nnr, utc_offset, min_daily_nnghs, nnghs_nnr,
-                             max_nnr_var, device, timing)
+                             max_nnr_var, device, timing, exclude_cols, never_neighbour)
     t1 = time.perf_counter()
     group = (np.asarray(pool.days[MONTH], np.int64) - 1).astype(np.int8)
     search, calls = run_search(obs, group, items, npcs, frac_obs_initnpcs, ppca_varyexplain, ppcaConThres, maxits, device,
@@ -492,7 +500,7 @@ def infill_daily_obs(stn_id, pool, tair_var, nnr_ds, mean, vari, tair_mask=None,
     mask_infill, infill_tair)`` over the days of the pool.  ``pool`` stands for the reference's ``stn_da``; ``mean`` / ``vari``
     [nstn, 12] for its ``vname_mean`` / ``vname_vari`` (the twelve monthly variables); ``day_masks`` must be the twelve
     calendar-month masks in order, as step16 passes them (``None``, one matrix over every day with one mean and variance, is
-    not implemented).  ``tair_mask`` (step15) raises ``NotImplementedError``, and so does ``chk_perf=True`` here: the retry
+    not implemented).  ``tair_mask`` raises ``NotImplementedError`` (step15 is ``topowx_amd.infill.XvalInfill``), and so does ``chk_perf=True`` here: the retry
     ladder is batched over items, call ``infill_daily(chk_perf=True)`` for it; ``add_bestngh=False`` is not supported by the
     matrix builder."""
     if tair_mask is not None:

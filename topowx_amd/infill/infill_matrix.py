@@ -9,8 +9,9 @@ the observation matrix of an item on the host (target first, then the kept stati
 ``MAX_COLS_NORM_IMPUTE`` columns).  ``InfillMatrix`` is a facade with the reference's attribute names for one target.
 
 The estimate of mean and variance from the matrices (``infill_mu_sigma`` / ``em.norm``, the PCA of the reanalysis columns)
-is ``topowx_amd.infill.infill_normals``.  Out of scope: the reanalysis reader, ``build_por_mask``, ``tair_mask`` and
-``InfillMatrixPPCA``.
+is ``topowx_amd.infill.infill_normals``.  Out of scope: the reanalysis reader, ``build_por_mask`` and
+``InfillMatrixPPCA``; the reference's ``tair_mask`` is ``topowx_amd.infill.XvalInfill`` (step15), which hands the masked
+series in as rows appended to the pool (``exclude_cols`` / ``never_neighbour`` below).
 """
 import time
 
@@ -126,14 +127,17 @@ class InfillMatrices(object):
 
 
 def build_infill_matrices(pool, var, targets=None, stns_mask=None, day_groups=None, min_daily_nnghs=MIN_DAILY_NGHBRS,
-                          device=0, timing=None):
+                          device=0, timing=None, exclude_cols=None, never_neighbour=None):
     """The infill neighbour matrices of ``targets`` (station ids; default: every station of ``pool``, a
     ``topowx_amd.qa.StationObsPool`` whose flagged observations are NaN) for ``var`` (``"tmin"`` / ``"tmax"``), all
     targets and day groups in one GPU call.  ``stns_mask`` [n] bool: the stations that may be neighbours (default: all;
     the target itself never is).  ``day_groups``: None = the twelve calendar months (step14's ``mth_masks``), ``"all"`` =
     one group of every day (the reference's ``day_masks=None``), or an integer array [ndays] of -1 (day not used) or
     0 .. G - 1, G <= 12.  Returns an ``InfillMatrices``.  ``timing`` (a dict) receives the device time of each kernel group
-    the number of rounds and the host seconds of the transposed copy, the thresholds and the library call."""
+    the number of rounds and the host seconds of the transposed copy, the thresholds and the library call.
+    Step15 (``XvalInfill``): ``exclude_cols`` [ntarget], -1 or the pool column that is never a neighbour of that target, and
+    ``never_neighbour`` [n] bool, stations that are no target's neighbour whatever ``stns_mask`` says; both default to
+    nothing."""
     if var not in ("tmin", "tmax"):
         raise ValueError("var must be 'tmin' or 'tmax'")
     n = pool.ids.size
@@ -152,6 +156,17 @@ def build_infill_matrices(pool, var, targets=None, stns_mask=None, day_groups=No
         mask = np.asarray(stns_mask)
         if mask.shape != (n,) or mask.dtype != np.bool_:
             raise ValueError("stns_mask must be a boolean array over the %d stations of the pool" % n)
+    if never_neighbour is not None:
+        never = np.asarray(never_neighbour)
+        if never.shape != (n,) or never.dtype != np.bool_:
+            raise ValueError("never_neighbour must be a boolean array over the %d stations of the pool" % n)
+        mask = mask & ~never
+    if exclude_cols is not None:
+        exclude_cols = np.asarray(exclude_cols)
+        if exclude_cols.shape != tcols.shape or exclude_cols.dtype.kind not in "iu" or \
+                (exclude_cols.size and (exclude_cols.min() < -1 or exclude_cols.max() >= n)):
+            raise ValueError("exclude_cols must be an integer array over the targets, -1 or a pool column")
+        exclude_cols = exclude_cols.astype(np.int32)
     if not isinstance(min_daily_nnghs, (int, np.integer)) or not 1 <= min_daily_nnghs <= _qalib.IF_MAX_MIN_NNGHS:
         raise ValueError("min_daily_nnghs must be an integer in 1 .. %d" % _qalib.IF_MAX_MIN_NNGHS)
     group, ng = _groups(pool.days, day_groups)
@@ -161,7 +176,7 @@ def build_infill_matrices(pool, var, targets=None, stns_mask=None, day_groups=No
     nthres_all, nthres_por = item_thresholds(obs[tcols], group, ng)
     t2 = time.perf_counter()
     res = _qalib.infill_matrix(pool.lon, pool.lat, obs, pool.days[YMD], mask, tcols, group, nthres_all, nthres_por,
-                               int(min_daily_nnghs), device=device, timing=timing)
+                               int(min_daily_nnghs), device=device, timing=timing, exclude_idx=exclude_cols)
     if timing is not None:
         timing.update(transpose_s=t1 - t0, thresholds_s=t2 - t1, library_s=time.perf_counter() - t2)
     return InfillMatrices(pool, var, pool.ids[tcols], tcols, group, ng, res, nthres_all, nthres_por, int(min_daily_nnghs),

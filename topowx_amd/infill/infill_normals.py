@@ -8,7 +8,7 @@ There is no CPU fallback: without the library the call raises.
 Deviations.  Neither R nor ``norm`` can be run against the restatement: the iteration at which EM stops is not pinned
 (DESIGN.md section 17).  The reanalysis reader ``NNRNghData`` is not ported: ``nnr=None`` gives an estimate from station
 columns only; any object with the reference's ``get_nngh_matrix(lon, lat, var, utc_offset=, nngh=)`` can be passed.
-``tair_mask`` (cross-validation, step15) is not implemented.
+``tair_mask`` is not an argument here: step15's cross-validation is ``topowx_amd.infill.XvalInfill``.
 """
 import hashlib
 import time
@@ -151,7 +151,7 @@ def infill_mean_variance(stn_id, pool, stn_mask, tair_var, nnr_ds=None, tair_mas
     """``infill_mean_variance`` (infill_normals.py:452-517) of one target, routed through the batched calls: ``(mean,
     variance)`` as two floats for ``day_masks=None`` (every day), else as two arrays over the boolean masks [ndays] of
     ``day_masks``.  ``pool``: a ``StationObsPool`` in place of the reference's ``stn_da``.  ``tair_mask`` is step15's
-    cross-validation masking and raises ``NotImplementedError``."""
+    cross-validation masking and raises ``NotImplementedError``: use ``topowx_amd.infill.XvalInfill``."""
     if tair_mask is not None:
         raise NotImplementedError("tair_mask (cross-validation masking) belongs to step15 and is not implemented")
     if day_masks is None:

@@ -11,7 +11,9 @@
 //
 // k_if_ring: one wavefront per active target.  Pass A: the nearest eligible station beyond the inner radius (none: the
 // target is exhausted), from it the outer radius by the reference's own additions of 37.5.  Pass B: the stations of the
-// ring into LDS, rank-sorted by distance (equal distances in table order).  LDS 12 bytes per ring station.
+// ring into LDS, rank-sorted by distance (equal distances in table order).  LDS 12 bytes per ring station.  Both passes
+// leave out the target itself and the one row of exclude_idx (twxxv_infill_matrix, step15: the full record of the
+// station whose masked series is the target; -1 for twxif_infill_matrix).
 //
 // k_if_pair: one wavefront per (active target, ring station), all groups.  The host sorts the used days by group once
 // (perm / goff), so a group is a run of that list and nothing is indexed by a run-time group number.  Per group, pass 1
@@ -85,7 +87,8 @@ __device__ __forceinline__ int wave_sum_i(int v)
 
 __global__ __launch_bounds__(64) void k_if_ring(int64_t nstn, const double *__restrict__ lon,
                                                 const double *__restrict__ lat, const uint8_t *__restrict__ elig,
-                                                const int32_t *__restrict__ target_idx, const int32_t *__restrict__ act_t,
+                                                const int32_t *__restrict__ target_idx,
+                                                const int32_t *__restrict__ exclude_idx, const int32_t *__restrict__ act_t,
                                                 int first, double *__restrict__ cur_max, int32_t *__restrict__ ring_n,
                                                 int32_t *__restrict__ ring_idx, double *__restrict__ ring_dist)
 {
@@ -93,7 +96,7 @@ __global__ __launch_bounds__(64) void k_if_ring(int64_t nstn, const double *__re
     __shared__ int32_t lj[IF_CAP];
     const int lane = threadIdx.x;
     const int64_t t = act_t[blockIdx.x];
-    const int32_t self = target_idx[t];
+    const int32_t self = target_idx[t], excl = exclude_idx[t];   // excl: -1 (no row has it) or the row twxxv_ leaves out
     const double lat1rad = lat[self] * IF_RADIAN, lon1rad = lon[self] * IF_RADIAN;
     const double cos1 = cos(lat1rad);
     const double rin = first ? -1.0 : cur_max[t];                // the reference's dists > min_dist, min_dist = -1
@@ -101,7 +104,7 @@ __global__ __launch_bounds__(64) void k_if_ring(int64_t nstn, const double *__re
     double dmin = __builtin_inf();
     for (int64_t j0 = 0; j0 < nstn; j0 += 64) {                  // uniform
         const int64_t j = j0 + lane;
-        if (j < nstn && j != self && elig[j]) {
+        if (j < nstn && j != self && j != excl && elig[j]) {
             const double d = if_dist(lat1rad, lon1rad, cos1, lat[j], lon[j]);
             if (d > rin && d < dmin) dmin = d;
         }
@@ -120,7 +123,7 @@ __global__ __launch_bounds__(64) void k_if_ring(int64_t nstn, const double *__re
         const int64_t j = j0 + lane;
         bool in = false;
         double d = 0.0;
-        if (j < nstn && j != self && elig[j]) {
+        if (j < nstn && j != self && j != excl && elig[j]) {
             d = if_dist(lat1rad, lon1rad, cos1, lat[j], lon[j]);
             in = d > rin && d <= rout;
         }
@@ -434,16 +437,15 @@ int64_t if_first_gap(int64_t ndays, const int32_t *ymd)
     } while (0)
 #define IFALLOC(ptr, type, count) IFCHK(bufs.get((void **)&(ptr), (size_t)(count) * sizeof(type)))
 
-extern "C" int twxif_infill_matrix(int device, int64_t nstn, int64_t ndays, const double *lon, const double *lat,
-                                   const float *obs, const int32_t *ymd, const uint8_t *eligible, int64_t ntarget,
-                                   const int32_t *target_idx, int32_t ngroups, const int8_t *group,
-                                   const int32_t *nthres_all, const int32_t *nthres_target_por, int32_t min_daily_nnghs,
-                                   int32_t *status, int32_t *nnghs, double *max_dist, int64_t *csr_off, int64_t csr_cap,
-                                   int32_t *ngh_idx, double *ngh_ioa, double *ngh_dist, int32_t *ngh_nlap,
-                                   int32_t *ngh_nlap_stn, uint8_t *keep, int32_t *nrounds, float *kernel_ms, char *errbuf,
-                                   int errlen)
+// the driver of twxif_infill_matrix and twxxv_infill_matrix; exclude_idx: nullptr (no exclusion) or [ntarget]
+static int if_matrix(const char *fn, int device, int64_t nstn, int64_t ndays, const double *lon, const double *lat,
+                     const float *obs, const int32_t *ymd, const uint8_t *eligible, int64_t ntarget,
+                     const int32_t *target_idx, const int32_t *exclude_idx, int32_t ngroups, const int8_t *group,
+                     const int32_t *nthres_all, const int32_t *nthres_target_por, int32_t min_daily_nnghs,
+                     int32_t *status, int32_t *nnghs, double *max_dist, int64_t *csr_off, int64_t csr_cap,
+                     int32_t *ngh_idx, double *ngh_ioa, double *ngh_dist, int32_t *ngh_nlap, int32_t *ngh_nlap_stn,
+                     uint8_t *keep, int32_t *nrounds, float *kernel_ms, char *errbuf, int errlen)
 {
-    const char *fn = "twxif_infill_matrix";
     char msg[256];
     if (errbuf && errlen > 0) errbuf[0] = 0;
     if (nstn < 1 || ndays < 1 || ntarget < 1 || nstn > INT32_MAX || ndays > INT32_MAX || ngroups < 1 ||
@@ -473,6 +475,11 @@ extern "C" int twxif_infill_matrix(int device, int64_t nstn, int64_t ndays, cons
     for (int64_t t = 0; t < ntarget; ++t)
         if (target_idx[t] < 0 || target_idx[t] >= nstn) {
             snprintf(msg, sizeof msg, "%s: target index %d outside [0, %lld)", fn, (int)target_idx[t], (long long)nstn);
+            return if_fail(errbuf, errlen, msg);
+        }
+    for (int64_t t = 0; exclude_idx && t < ntarget; ++t)
+        if (exclude_idx[t] < -1 || exclude_idx[t] >= nstn) {
+            snprintf(msg, sizeof msg, "%s: exclude index %d outside -1 .. %lld", fn, (int)exclude_idx[t], (long long)nstn - 1);
             return if_fail(errbuf, errlen, msg);
         }
     // the used days sorted by group, in day order within a group
@@ -507,12 +514,12 @@ extern "C" int twxif_infill_matrix(int device, int64_t nstn, int64_t ndays, cons
     double *d_lon, *d_lat, *d_curmax, *d_rdist, *d_pioa, *d_maxdist, *d_lioa, *d_ldist;
     float *d_obs;
     uint8_t *d_elig, *d_done, *d_lkeep, *d_daycnt;
-    int32_t *d_tidx, *d_actt, *d_acti, *d_perm, *d_goff, *d_thrall, *d_thrpor, *d_ringn, *d_ridx, *d_pnlap, *d_pnst,
+    int32_t *d_tidx, *d_excl, *d_actt, *d_acti, *d_perm, *d_goff, *d_thrall, *d_thrpor, *d_ringn, *d_ridx, *d_pnlap, *d_pnst,
         *d_status, *d_nnghs, *d_n, *d_lidx, *d_lnlap, *d_lnst;
     const size_t NS = (size_t)nstn, ND = (size_t)ndays, NT = (size_t)ntarget, NI = (size_t)ni, G = (size_t)ngroups;
     IFALLOC(d_lon, double, NS); IFALLOC(d_lat, double, NS); IFALLOC(d_elig, uint8_t, NS);
     IFALLOC(d_obs, float, NS * ND);
-    IFALLOC(d_tidx, int32_t, NT); IFALLOC(d_actt, int32_t, NT); IFALLOC(d_acti, int32_t, NI);
+    IFALLOC(d_tidx, int32_t, NT); IFALLOC(d_excl, int32_t, NT); IFALLOC(d_actt, int32_t, NT); IFALLOC(d_acti, int32_t, NI);
     IFALLOC(d_perm, int32_t, perm.size()); IFALLOC(d_goff, int32_t, G + 1);
     IFALLOC(d_thrall, int32_t, G); IFALLOC(d_thrpor, int32_t, NI);
     IFALLOC(d_curmax, double, NT); IFALLOC(d_ringn, int32_t, NT);
@@ -529,6 +536,8 @@ extern "C" int twxif_infill_matrix(int device, int64_t nstn, int64_t ndays, cons
     IFCHK(hipMemcpy(d_elig, eligible, NS, hipMemcpyHostToDevice));
     IFCHK(hipMemcpy(d_obs, obs, NS * ND * 4, hipMemcpyHostToDevice));
     IFCHK(hipMemcpy(d_tidx, target_idx, NT * 4, hipMemcpyHostToDevice));
+    if (exclude_idx) IFCHK(hipMemcpy(d_excl, exclude_idx, NT * 4, hipMemcpyHostToDevice));
+    else IFCHK(hipMemset(d_excl, 0xff, NT * 4));                 // -1: no station has that row
     if (!perm.empty()) IFCHK(hipMemcpy(d_perm, perm.data(), perm.size() * 4, hipMemcpyHostToDevice));
     IFCHK(hipMemcpy(d_goff, goff.data(), (G + 1) * 4, hipMemcpyHostToDevice));
     IFCHK(hipMemcpy(d_thrall, nthres_all, G * 4, hipMemcpyHostToDevice));
@@ -570,7 +579,7 @@ extern "C" int twxif_infill_matrix(int device, int64_t nstn, int64_t ndays, cons
         if (kernel_ms) IFCHK(tm.start());
         hipLaunchKernelGGL(k_if_ring, dim3((unsigned)act_t.size()), dim3(64), 0, nullptr, nstn, (const double *)d_lon,
                            (const double *)d_lat, (const uint8_t *)d_elig, (const int32_t *)d_tidx,
-                           (const int32_t *)d_actt, first, d_curmax, d_ringn, d_ridx, d_rdist);
+                           (const int32_t *)d_excl, (const int32_t *)d_actt, first, d_curmax, d_ringn, d_ridx, d_rdist);
         IFCHK(hipGetLastError());
         if (kernel_ms) IFCHK(tm.stop(&ms[0]));
         // the pair grid is sized by the round's largest ring (about 26 stations on a real pool, not the cap of 256)
@@ -647,4 +656,38 @@ extern "C" int twxif_infill_matrix(int device, int64_t nstn, int64_t ndays, cons
     ms[5] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_down).count() - compact_ms;
     if (kernel_ms) memcpy(kernel_ms, ms, sizeof ms);
     return 0;
+}
+
+extern "C" int twxif_infill_matrix(int device, int64_t nstn, int64_t ndays, const double *lon, const double *lat,
+                                   const float *obs, const int32_t *ymd, const uint8_t *eligible, int64_t ntarget,
+                                   const int32_t *target_idx, int32_t ngroups, const int8_t *group,
+                                   const int32_t *nthres_all, const int32_t *nthres_target_por, int32_t min_daily_nnghs,
+                                   int32_t *status, int32_t *nnghs, double *max_dist, int64_t *csr_off, int64_t csr_cap,
+                                   int32_t *ngh_idx, double *ngh_ioa, double *ngh_dist, int32_t *ngh_nlap,
+                                   int32_t *ngh_nlap_stn, uint8_t *keep, int32_t *nrounds, float *kernel_ms, char *errbuf,
+                                   int errlen)
+{
+    return if_matrix("twxif_infill_matrix", device, nstn, ndays, lon, lat, obs, ymd, eligible, ntarget, target_idx, nullptr,
+                     ngroups, group, nthres_all, nthres_target_por, min_daily_nnghs, status, nnghs, max_dist, csr_off,
+                     csr_cap, ngh_idx, ngh_ioa, ngh_dist, ngh_nlap, ngh_nlap_stn, keep, nrounds, kernel_ms, errbuf, errlen);
+}
+
+// step15: twxif_infill_matrix with one pool row per target that is never its neighbour (include/twx_qa.h)
+extern "C" int twxxv_infill_matrix(int device, int64_t nstn, int64_t ndays, const double *lon, const double *lat,
+                                   const float *obs, const int32_t *ymd, const uint8_t *eligible, int64_t ntarget,
+                                   const int32_t *target_idx, const int32_t *exclude_idx, int32_t ngroups,
+                                   const int8_t *group, const int32_t *nthres_all, const int32_t *nthres_target_por,
+                                   int32_t min_daily_nnghs, int32_t *status, int32_t *nnghs, double *max_dist,
+                                   int64_t *csr_off, int64_t csr_cap, int32_t *ngh_idx, double *ngh_ioa, double *ngh_dist,
+                                   int32_t *ngh_nlap, int32_t *ngh_nlap_stn, uint8_t *keep, int32_t *nrounds,
+                                   float *kernel_ms, char *errbuf, int errlen)
+{
+    const char *fn = "twxxv_infill_matrix";
+    if (!exclude_idx) {
+        if (errbuf && errlen > 0) snprintf(errbuf, (size_t)errlen, "%s: null buffer", fn);
+        return -1;
+    }
+    return if_matrix(fn, device, nstn, ndays, lon, lat, obs, ymd, eligible, ntarget, target_idx, exclude_idx, ngroups,
+                     group, nthres_all, nthres_target_por, min_daily_nnghs, status, nnghs, max_dist, csr_off, csr_cap,
+                     ngh_idx, ngh_ioa, ngh_dist, ngh_nlap, ngh_nlap_stn, keep, nrounds, kernel_ms, errbuf, errlen);
 }

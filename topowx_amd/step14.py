@@ -37,6 +37,7 @@ import time
 import numpy as np
 
 from . import ncio
+from ._cli import UnknownIds as _UnknownIds, read_ids as _read_ids
 from .dates import YMD
 from .infill import EM_STATUS, ITEM_STATUS, build_infill_matrices, estimate_mean_variance
 from .qa import StationObsPool
@@ -46,19 +47,6 @@ __all__ = ["main"]
 QFLAG_VARS = ("qflag_tmin", "qflag_tmax")
 COLUMNS = ("status", "nnghs", "max_dist", "nthres_all", "nthres_target_por", "off", "idx", "ioa", "dist", "nlap", "nlap_stn",
            "keep")
-
-
-class _UnknownIds(Exception):
-    pass
-
-
-def _read_ids(path, pool, what):
-    with open(path) as fh:
-        ids = [ln.strip() for ln in fh if ln.strip()]
-    missing = [s for s in ids if s not in pool.idxs]
-    if missing:
-        raise _UnknownIds("%s: %d %s ids are not in the database (first: %s)" % (path, len(missing), what, missing[0]))
-    return ids
 
 
 def main(argv=None):

@@ -25,8 +25,8 @@ the check's ``ck_check_kernel_ms``.  Without the flag the report and the JSON li
 The values come from station columns ONLY (the reanalysis reader is not ported) and from a restated estimator whose start
 is not R's: they are not what the reference would write, and there is no ``--write``.
 
-Out of scope: ``tair_mask``, the reanalysis reader, the writer of the infilled database.  The variance change-point check
-is restated, not R's ``changepoint`` executed.
+Out of scope: the reanalysis reader, ``tair_mask`` (step15's cross-validation is ``python -m topowx_amd.step15``) and the
+writer of the infilled database.  The variance change-point check is restated, not R's ``changepoint`` executed.
 
 Exits with 1 if a file cannot be opened, a station id is unknown or the normals do not cover the database's stations.
 """
@@ -34,15 +34,15 @@ import argparse
 import json
 import sys
 import time
-import zipfile
 
 import numpy as np
 
 from . import ncio
+from ._cli import BadNormals as _BadNormals, UnknownIds as _UnknownIds, normals as _normals, read_ids as _read_ids
 from .dates import YMD
 from .infill import PP_STATUS, infill_daily
 from .qa import StationObsPool
-from .step14 import QFLAG_VARS, _read_ids, _UnknownIds
+from .step14 import QFLAG_VARS
 
 __all__ = ["main"]
 
@@ -50,29 +50,6 @@ ITEM_COLUMNS = ("status", "matrix_status", "npcs", "nfits", "iters", "r2_not_rea
                 "item_impossible")
 CHK_COLUMNS = ("attempt", "nattempts", "nonoptimal", "retry_fixed", "cpt_stat", "cpt_tau", "cpt_pen", "reasons", "attempt_mae",
                "attempt_r2")
-
-
-class _BadNormals(Exception):
-    pass
-
-
-def _normals(path, pool):
-    """(mean, vari) [n, 12] in the pool's station order from a step14 report."""
-    try:
-        with np.load(path) as z:
-            if not all(k in z.files for k in ("ids", "mean", "variance")):
-                raise _BadNormals("%s has no ids / mean / variance: write it with step14 --estimate" % path)
-            ids, mean, vari = [str(s) for s in z["ids"]], np.asarray(z["mean"], np.float64), np.asarray(z["variance"], np.float64)
-    except (IOError, OSError, ValueError, KeyError, zipfile.BadZipFile) as e:
-        raise _BadNormals("cannot read the normals %s: %s" % (path, e))
-    if mean.shape != (len(ids), 12) or vari.shape != mean.shape:
-        raise _BadNormals("%s: mean / variance must be [%d, 12] over its ids" % (path, len(ids)))
-    pos = {s: i for i, s in enumerate(ids)}
-    missing = [s for s in pool.ids if str(s) not in pos]
-    if missing:
-        raise _UnknownIds("%s: %d stations of the database have no normals (first: %s)" % (path, len(missing), missing[0]))
-    order = [pos[str(s)] for s in pool.ids]
-    return mean[order], vari[order]
 
 
 def main(argv=None):
