@@ -606,6 +606,95 @@ int twxxv_score(int device, int64_t nseries, int64_t ndays, const double *infill
                 const int8_t *group, int32_t *n, double *bias, double *mae, float *obs_out, float *infill_out,
                 float *kernel_ms, char *errbuf, int errlen);
 
+/* ---- step17 and step18, from the infilled database to the serially-complete one: the choice between "observations +
+ * infill" and "all model" per station with the scrub of what is still missing (create_serially_complete_db,
+ * twx/infill/post_infill.py:106-149), the 1981-2010 monthly normals (add_monthly_normals :354-402 with
+ * TairAggregate.daily_to_mthly / daily_to_mthly_norms, twx/utils/util_tair.py:67-158), and the check of a suspect station's
+ * WHOLE series (has_bad_infill, scripts/step17_find_bad_infill_stns.py:40-68).  The change-point test is the restated one of
+ * the twxck_infill_check block above, same caveat. ---- */
+#define TWXSC_MAX_DAYS 1048576          /* days of a series (2^20); the reference's axis has 25 203 */
+#define TWXSC_MAX_GROUPS 1536           /* (year, month) groups of the normals: 128 years; one double of LDS each */
+#define TWXSC_DEFAULT_RUN_THRESHOLD 1826        /* USE_ALL_INFILL_THRESHOLD = np.round(365.25 * 5.0), post_infill.py:39 */
+#define TWXSC_DEFAULT_MAX_MISS 9                /* util_tair.py:67,109 */
+#define TWXSC_WORKSPACE_BYTES (256ll << 20)   /* default budget of the per-batch device copies of the series */
+#define TWXSC_NTIMES 4                  /* entries of kernel_ms, see the entries */
+
+/*
+ * For every series s (station-major rows of ndays days):
+ *   infilled day  flag != 0 (the reference's .astype(np.bool): the int8 fill -127 of a station that failed the infill counts)
+ *   max_run       the longest run of consecutive infilled days (_runs_of_ones_array), 0 if there is none
+ *   all_infill    max_run >= run_threshold
+ *   source row    tair_infilled if all_infill, else tair
+ *   flag_out      all 1 if all_infill, else flag != 0 as 0 / 1
+ *   missing       a source value that is non-finite or compares equal to fill (netCDF4's masking plus the reference's
+ *                 ~np.isfinite scrub); serial holds fill there and the source value bit for bit elsewhere; nmissing counts
+ *                 the missing days
+ *   normals       from serial.  Group g = 12 (year - start_norm_yr) + month - 1 owns the contiguous days group_first[g] ..
+ *                 group_first[g] + group_ndays[g] - 1 (group_ndays[g] = 0: no such day on the axis).  n_miss = its missing
+ *                 days; mean_g = (the sum of its non-missing values IN DAY ORDER) / their count.  The group is masked if it
+ *                 has no day, no non-missing day, or max_miss >= 0 and n_miss > max_miss.  norm[m] = (the sum of the
+ *                 unmasked mean_g, g = m mod 12, IN YEAR ORDER) / their number, which is norm_nmths[m]; none unmasked: NaN
+ *                 and 0.  fp64 on the float32 values widened exactly.
+ * tair_infilled and flag may be null together: the source row is tair as it is, max_run = 0, all_infill = 0, and serial and
+ * flag_out may then be null too (normals only; flag_out, if given, is all 0).  group_first may be null: no normals.
+ * One workgroup of 256 per series.  k_sc_select: thread k reduces its contiguous flags k c .. k c + c - 1, c = ceil(ndays /
+ * 256), to (length, longest prefix run, longest suffix run, longest run), an associative monoid joined in order across the
+ * 64 lanes and the four wavefronts (integers: any tree gives the same answer); then the select-and-write pass.  k_sc_norms
+ * (the batch still on the device): one thread per group adds its days in day order, one thread per month adds its years in
+ * year order.  No float atomics, nothing waits on another workgroup: two calls give the same bytes, whatever workspace_bytes.
+ *
+ * tair [nseries][ndays]      float32: the infilled database's <var>
+ * tair_infilled [nseries][ndays], flag [nseries][ndays]   float32 and int8, or both null
+ * run_threshold              the binding's int(np.round(365.25 * 5.0)) = TWXSC_DEFAULT_RUN_THRESHOLD
+ * fill                       finite; the float32 netCDF fill is 9.96921e36
+ * ngroups, group_first, group_ndays [ngroups]   ngroups a multiple of 12 in 12 .. TWXSC_MAX_GROUPS; the groups with days
+ *                            ascending and disjoint
+ * max_miss                   negative: no threshold (the reference's None)
+ * workspace_bytes            <= 0: TWXSC_WORKSPACE_BYTES.  A batch is a run of consecutive series whose device rows (4 B a
+ *                            day for tair, 5 for tair_infilled and flag, 4 for serial, 1 for flag_out) fit (at least one)
+ * serial [nseries][ndays], flag_out [nseries][ndays]   out, float32 and int8
+ * max_run, nmissing [nseries], all_infill [nseries]    out, int32 and uint8
+ * norm [nseries][12], norm_nmths [nseries][12]         out, float64 and int32 (not written without groups)
+ * counts (optional) [2]      out: kernel launches, batches
+ * kernel_ms (optional) [TWXSC_NTIMES]   device time of k_sc_select and of k_sc_norms over all launches; then host-clock
+ *                            milliseconds of the allocations and copies in, and of the copies back
+ * Call-level failures: nseries or ndays < 1, ndays > TWXSC_MAX_DAYS, exactly one of tair_infilled / flag null, a null buffer,
+ * ngroups not a multiple of 12 in range, a group outside the axis or not after the groups before it, a non-finite fill.
+ */
+int twxsc_serial_complete(int device, int64_t nseries, int64_t ndays, const float *tair, const float *tair_infilled,
+                          const int8_t *flag, int32_t run_threshold, float fill, int32_t ngroups, const int32_t *group_first,
+                          const int32_t *group_ndays, int32_t max_miss, int64_t workspace_bytes, float *serial,
+                          int8_t *flag_out, int32_t *max_run, int32_t *nmissing, uint8_t *all_infill, double *norm,
+                          int32_t *norm_nmths, int32_t *counts, float *kernel_ms, char *errbuf, int errlen);
+
+/*
+ * step17's has_bad_infill of every series (all of N = ndays rows), with the TWXCK_* reason bits and statuses as they are:
+ *   missing       a value that is non-finite or compares equal to fill.  A series with one gets nmissing = their count,
+ *                 status TWXCK_NOT_FITTED, reasons TWXCK_UNFITTED, nimpossible = cpt_tau = 0, cpt_stat NaN (R would raise
+ *                 there, and step17 calls the station bad).
+ *   otherwise     nmissing = 0, and nimpossible, cpt_stat, cpt_tau and the bits TWXCK_IMPOSSIBLE / TWXCK_VAR_CHGPT are the
+ *                 "impossible" and "change point" paragraphs of the twxck_infill_check block with fit := the series widened
+ *                 to float64 and N = ndays, WITHOUT the cap of TWXCK_MAX_ROWS; ndays < 4: TWXCK_FEW_ROWS.
+ * The kernel is k_ck_check's shape and order of summation (thread k owns the rows k c .. k c + c - 1, c = ceil(N / 256), about
+ * 99 at 25 203 days; the chunk is read again from global memory, never held in registers or LDS), so on a series both
+ * entries accept the two give the same bytes.
+ *
+ * series [nseries][ndays]    float32
+ * fill                       finite
+ * pen                        the penalty of every series (the binding's cpt_penalty(ndays, sig)); NaN: no change point
+ * impossible_high, impossible_low   finite; step17's world records are TWXCK_DEFAULT_IMPOSSIBLE_HIGH / _LOW
+ * workspace_bytes            <= 0: TWXSC_WORKSPACE_BYTES; a batch is a run of series whose rows (4 B a day) fit
+ * nimpossible, nmissing, cpt_stat, cpt_tau, reasons, status [nseries]   out
+ * counts (optional) [2]      out: launches of k_sc_series, batches (equal)
+ * kernel_ms (optional) [TWXSC_NTIMES]   device time of k_sc_series; 0; host-clock milliseconds of the allocations and
+ *                            copies in, and of the copies back
+ * Call-level failures: nseries or ndays < 1, ndays > TWXSC_MAX_DAYS, a null buffer, a non-finite fill or bound.
+ */
+int twxsc_series_check(int device, int64_t nseries, int64_t ndays, const float *series, float fill, double pen,
+                       double impossible_high, double impossible_low, int64_t workspace_bytes, int32_t *nimpossible,
+                       int32_t *nmissing, double *cpt_stat, int32_t *cpt_tau, int32_t *reasons, int32_t *status,
+                       int32_t *counts, float *kernel_ms, char *errbuf, int errlen);
+
 #ifdef __cplusplus
 }
 #endif

@@ -664,3 +664,159 @@ def xval_score(infill, obs, held, group, device=0, timing=None):
     return dict(n=n[:, XV_NGROUPS].copy(), bias=bias[:, XV_NGROUPS].copy(), mae=mae[:, XV_NGROUPS].copy(),
                 group_n=n[:, :XV_NGROUPS].copy(), group_bias=bias[:, :XV_NGROUPS].copy(),
                 group_mae=mae[:, :XV_NGROUPS].copy(), obs_out=oo, infill_out=io)
+
+
+# ---- step17 / step18, the serially-complete database (twxsc_*; TWXSC_* of include/twx_qa.h) ----
+SC_EXPORTS = ("twxsc_serial_complete", "twxsc_series_check")
+SC_MAX_DAYS = 1048576     # TWXSC_MAX_DAYS
+SC_MAX_GROUPS = 1536      # TWXSC_MAX_GROUPS
+SC_RUN_THRESHOLD = 1826   # TWXSC_DEFAULT_RUN_THRESHOLD: int(np.round(365.25 * 5.0)), post_infill.py:39
+SC_MAX_MISS = 9           # TWXSC_DEFAULT_MAX_MISS
+SC_FILL_F4 = 9.969209968386869e36       # netCDF4.default_fillvals['f4']
+SC_KERNELS = ("sc_select", "sc_norms")                  # the first entries of TWXSC_NTIMES
+SC_HOST_TIMES = ("sc_upload", "sc_download")            # the rest: host-clock milliseconds
+SC_CHECK_TIMES = ("sc_series_kernel_ms", None, "sc_series_upload_ms", "sc_series_download_ms")
+
+
+def run_threshold(years=5.0):
+    """``USE_ALL_INFILL_THRESHOLD`` (post_infill.py:39): ``int(np.round(365.25 * years))``."""
+    return int(np.round(365.25 * years))
+
+
+def norm_groups(year, month, start_norm_yr, end_norm_yr, day=None):
+    """(group_first, group_ndays) [12 * nyears] of ``twxsc_serial_complete`` for the day axis ``year`` / ``month`` [ndays]:
+    group 12 (y - start_norm_yr) + m - 1 owns the days of month m of year y.  Raises ``ValueError`` for an axis that is not
+    ascending and gap-free (in (year, month); with ``day`` [ndays] day by day), or a period of more than ``SC_MAX_GROUPS``
+    months."""
+    year, month = np.asarray(year, np.int64), np.asarray(month, np.int64)
+    if year.ndim != 1 or month.shape != year.shape or year.size < 1:
+        raise ValueError("year / month must be [ndays >= 1]")
+    start_norm_yr, end_norm_yr = int(start_norm_yr), int(end_norm_yr)
+    if end_norm_yr < start_norm_yr or 12 * (end_norm_yr - start_norm_yr + 1) > SC_MAX_GROUPS:
+        raise ValueError("the normals cover 1 .. %d years" % (SC_MAX_GROUPS // 12))
+    ym = year * 12 + month - 1
+    if month.min() < 1 or month.max() > 12 or ((np.diff(ym) != 0) & (np.diff(ym) != 1)).any():
+        raise ValueError("the day axis must be ascending and gap-free (no skipped month or year)")
+    if day is not None:
+        day = np.asarray(day, np.int64)
+        if day.shape != year.shape or day.min() < 1 or day.max() > 31:
+            raise ValueError("day must be [ndays] of 1 .. 31")
+        d64 = ((year - 1970) * 12 + month - 1).astype("datetime64[M]").astype("datetime64[D]") + (day - 1)
+        if (np.diff(d64).astype(np.int64) != 1).any():
+            raise ValueError("the day axis must be ascending and gap-free (consecutive days)")
+    ng = 12 * (end_norm_yr - start_norm_yr + 1)
+    g = ym - 12 * start_norm_yr
+    first, nd = np.zeros(ng, np.int32), np.zeros(ng, np.int32)
+    inside = np.nonzero((g >= 0) & (g < ng))[0]
+    if inside.size:
+        u, i0, cnt = np.unique(g[inside], return_index=True, return_counts=True)
+        first[u], nd[u] = inside[i0], cnt
+    return first, nd
+
+
+def serial_complete(tair, tair_infilled=None, flag=None, run_threshold=SC_RUN_THRESHOLD, fill=SC_FILL_F4, group_first=None,
+                    group_ndays=None, max_miss=SC_MAX_MISS, workspace_bytes=0, device=0, timing=None):
+    """``twxsc_serial_complete``: ``create_serially_complete_db``'s choice and scrub (post_infill.py:106-149) and the monthly
+    normals of ``add_monthly_normals`` for every series of one call.
+
+    tair [nseries, ndays] float32, station-major; tair_infilled the same and flag [nseries, ndays] int8, or both None
+    ("take tair as it is": no serial / flag_infilled output); group_first / group_ndays [ngroups] (``norm_groups``) or both
+    None (no normals); ``max_miss`` None or negative: no threshold.  Returns a dict of max_run, nmissing [nseries] int32,
+    all_infill [nseries] bool, ``batches``, with flags ``serial`` [nseries, ndays] float32 and ``flag_infilled`` int8, with
+    groups ``norm`` [nseries, 12] float64 and ``norm_nmths`` int32.  ``timing`` receives ``sc_select_kernel_ms`` /
+    ``sc_norms_kernel_ms``, the host-clock ``sc_upload_ms`` / ``sc_download_ms`` (accumulated over calls), ``sc_batches``
+    and ``sc_calls``."""
+    L = load()
+    if not hasattr(L.twxsc_serial_complete, "_twx_ready"):
+        L.twxsc_serial_complete.restype = C.c_int
+        L.twxsc_serial_complete.argtypes = [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 3 + [C.c_int32, C.c_float, C.c_int32] + \
+            [C.c_void_p] * 2 + [C.c_int32, C.c_int64] + [C.c_void_p] * 9 + [C.c_char_p, C.c_int]
+        L.twxsc_serial_complete._twx_ready = True
+    tair = _c(tair, np.float32)
+    if tair.ndim != 2:
+        raise ValueError("tair must be [nseries, ndays]")
+    ns, nd = tair.shape
+    if (tair_infilled is None) != (flag is None):
+        raise ValueError("tair_infilled and flag are given together or not at all")
+    full = flag is not None
+    if full:
+        tair_infilled, flag = _c(tair_infilled, np.float32), _c(flag, np.int8)
+        if tair_infilled.shape != tair.shape or flag.shape != tair.shape:
+            raise ValueError("tair_infilled / flag must be [nseries, ndays] like tair")
+    if (group_first is None) != (group_ndays is None):
+        raise ValueError("group_first and group_ndays are given together or not at all")
+    norms = group_first is not None
+    ng = 0
+    if norms:
+        group_first, group_ndays = _c(group_first, np.int32), _c(group_ndays, np.int32)
+        if group_first.ndim != 1 or group_ndays.shape != group_first.shape:
+            raise ValueError("group_first / group_ndays must be [ngroups]")
+        ng = group_first.size
+    out = dict(max_run=np.zeros(ns, np.int32), nmissing=np.zeros(ns, np.int32), all_infill=np.zeros(ns, np.uint8))
+    if full:
+        out["serial"], out["flag_infilled"] = np.empty((ns, nd), np.float32), np.empty((ns, nd), np.int8)
+    if norms:
+        out["norm"], out["norm_nmths"] = np.empty((ns, 12)), np.empty((ns, 12), np.int32)
+    counts = (C.c_int32 * 2)()
+    ms = (C.c_float * (len(SC_KERNELS) + len(SC_HOST_TIMES)))()
+    buf = C.create_string_buffer(512)
+    rc = L.twxsc_serial_complete(int(device), ns, nd, tair.ctypes.data, tair_infilled.ctypes.data if full else None,
+                                 flag.ctypes.data if full else None, int(run_threshold), float(fill), ng,
+                                 group_first.ctypes.data if norms else None, group_ndays.ctypes.data if norms else None,
+                                 -1 if max_miss is None else int(max_miss), int(workspace_bytes),
+                                 out["serial"].ctypes.data if full else None, out["flag_infilled"].ctypes.data if full else None,
+                                 out["max_run"].ctypes.data, out["nmissing"].ctypes.data, out["all_infill"].ctypes.data,
+                                 out["norm"].ctypes.data if norms else None, out["norm_nmths"].ctypes.data if norms else None,
+                                 C.addressof(counts), C.addressof(ms), buf, 512)
+    if rc != 0:
+        raise QaError("twxsc_serial_complete failed: %s" % buf.value.decode(errors="replace"))
+    out["all_infill"] = out["all_infill"].view(np.bool_)
+    out["batches"] = int(counts[1])
+    if timing is not None:
+        for k, name in enumerate(SC_KERNELS + SC_HOST_TIMES):
+            key = name + ("_kernel_ms" if k < len(SC_KERNELS) else "_ms")
+            timing[key] = timing.get(key, 0.0) + float(ms[k])
+        timing["sc_batches"] = timing.get("sc_batches", 0) + out["batches"]
+        timing["sc_calls"] = timing.get("sc_calls", 0) + 1
+    return out
+
+
+def series_check(series, pen=None, sig=CK_SIG, fill=SC_FILL_F4, impossible_high=CK_IMPOSSIBLE_HIGH,
+                 impossible_low=CK_IMPOSSIBLE_LOW, workspace_bytes=0, device=0, timing=None):
+    """``twxsc_series_check``: step17's ``has_bad_infill`` of every WHOLE series (no cap of ``CK_MAX_ROWS`` rows).
+
+    series [nseries, ndays] float32; ``pen``: the change-point penalty (default ``cpt_penalty(ndays, sig)``; NaN: no change
+    point).  Returns a dict of nimpossible, nmissing, cpt_stat, cpt_tau, reasons (``CK_*`` bits), status [nseries], ``pen``
+    and ``batches``.  ``timing`` receives ``sc_series_kernel_ms``, the host-clock ``sc_series_upload_ms`` /
+    ``sc_series_download_ms`` (accumulated over calls), ``sc_series_batches`` and ``sc_series_calls``."""
+    L = load()
+    if not hasattr(L.twxsc_series_check, "_twx_ready"):
+        L.twxsc_series_check.restype = C.c_int
+        L.twxsc_series_check.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_float] + [C.c_double] * 3 + [C.c_int64] + \
+            [C.c_void_p] * 8 + [C.c_char_p, C.c_int]
+        L.twxsc_series_check._twx_ready = True
+    series = _c(series, np.float32)
+    if series.ndim != 2:
+        raise ValueError("series must be [nseries, ndays]")
+    ns, nd = series.shape
+    pen = cpt_penalty(nd, sig) if pen is None else float(pen)
+    out = dict(nimpossible=np.empty(ns, np.int32), nmissing=np.empty(ns, np.int32), cpt_stat=np.empty(ns),
+               cpt_tau=np.empty(ns, np.int32), reasons=np.empty(ns, np.int32), status=np.empty(ns, np.int32))
+    counts = (C.c_int32 * 2)()
+    ms = (C.c_float * len(SC_CHECK_TIMES))()
+    buf = C.create_string_buffer(512)
+    rc = L.twxsc_series_check(int(device), ns, nd, series.ctypes.data, float(fill), pen, float(impossible_high),
+                              float(impossible_low), int(workspace_bytes), out["nimpossible"].ctypes.data,
+                              out["nmissing"].ctypes.data, out["cpt_stat"].ctypes.data, out["cpt_tau"].ctypes.data,
+                              out["reasons"].ctypes.data, out["status"].ctypes.data, C.addressof(counts), C.addressof(ms),
+                              buf, 512)
+    if rc != 0:
+        raise QaError("twxsc_series_check failed: %s" % buf.value.decode(errors="replace"))
+    out["pen"], out["batches"] = pen, int(counts[1])
+    if timing is not None:
+        for k, key in enumerate(SC_CHECK_TIMES):
+            if key:
+                timing[key] = timing.get(key, 0.0) + float(ms[k])
+        timing["sc_series_batches"] = timing.get("sc_series_batches", 0) + out["batches"]
+        timing["sc_series_calls"] = timing.get("sc_series_calls", 0) + 1
+    return out

@@ -25,8 +25,8 @@ the check's ``ck_check_kernel_ms``.  Without the flag the report and the JSON li
 The values come from station columns ONLY (the reanalysis reader is not ported) and from a restated estimator whose start
 is not R's: they are not what the reference would write, and there is no ``--write``.
 
-Out of scope: the reanalysis reader, ``tair_mask`` (step15's cross-validation is ``python -m topowx_amd.step15``) and the
-writer of the infilled database.  The variance change-point check is restated, not R's ``changepoint`` executed.
+Out of scope: the reanalysis reader and ``tair_mask`` (step15's cross-validation is ``python -m topowx_amd.step15``).  The
+infilled database is written from this report by ``python -m topowx_amd.step17 --report-*``.  The variance change-point check is restated, not R's ``changepoint`` executed.
 
 Exits with 1 if a file cannot be opened, a station id is unknown or the normals do not cover the database's stations.
 """
