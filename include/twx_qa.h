@@ -695,6 +695,75 @@ int twxsc_series_check(int device, int64_t nseries, int64_t ndays, const float *
                        int32_t *nmissing, double *cpt_stat, int32_t *cpt_tau, int32_t *reasons, int32_t *status,
                        int32_t *counts, float *kernel_ms, char *errbuf, int errlen);
 
+/* ---- the reanalysis columns of the infill family (step14 / step15 / step16): pca_svd(A, True, True) of
+ * twx/utils/pca.py:26-76 on the matrix NNRNghData.get_nngh_matrix returns (twx/db/reanalysis.py:372-432), cut as
+ * _InfillMatrix.infill cuts it (twx/infill/infill_normals.py:347-356), for every (column set, day group) item of one call.
+ * The route differs from the reference's: the eigen-decomposition of the Gram matrix of the standardised columns instead of
+ * LAPACK's SVD of the matrix.  The sign of a component is LAPACK's there and fixed by a rule here; the estimate does not
+ * depend on it.  DESIGN.md section 22 gives the measured distance between the two routes. ---- */
+#define TWXNR_MAX_COLS 64               /* columns of a set; the reference's shape is 4 cells x 8 variable / level columns */
+#define TWXNR_MAX_CUTS 4                /* thresholds of one call (the reference uses 0.99, and 0.90 in chk_perf's ladder) */
+#define TWXNR_MAX_SWEEPS 30             /* Jacobi sweeps before TWXNR_NOCONV */
+#define TWXNR_NKERNELS 3                /* kernel groups timed: k_nr_gram, k_nr_eig, k_nr_scores */
+#define TWXNR_NTIMES 5                  /* entries of kernel_ms: the kernel groups, then two host-clock figures */
+/* LDS per workgroup.  k_nr_gram (256 threads): a tile of 64 days x 64 columns at a row stride of 65 doubles = 33 280 B,
+ * mean and sd 2 x 64 x 8 B = 1 024 B, the column verdicts 64 x 4 B = 256 B: 34 560 B, four workgroups fit a compute unit's
+ * 160 KiB.  k_nr_eig (64 threads): the Gram matrix and the rotation accumulator, 2 x P x P x 8 B for the largest P of the
+ * call: 65 536 B at the cap, 16 384 B at P = 32.  k_nr_scores (256 threads): the loadings 64 x 64 x 8 B = 32 768 B, mean and
+ * sd 1 024 B: 33 792 B.  Nothing row-sized lives in LDS: there is no row cap. */
+
+/* per-item status */
+#define TWXNR_OK TWX_CELL_OK                      /* decomposed */
+#define TWXNR_NOCONV 29                           /* the off-diagonal norm is still above eps x trace after
+                                                     TWXNR_MAX_SWEEPS sweeps: the last iterate is returned, no scores */
+#define TWXNR_NONFINITE 30                        /* a non-finite value in a column on a day of the group (the reference
+                                                     returns NaN scores); bad_col names the first such column */
+#define TWXNR_CONSTANT 31                         /* a column of zero variance on the days of the group (the reference
+                                                     divides by zero); bad_col names the first such column */
+#define TWXNR_FEW_ROWS 32                         /* fewer than 2 days in the group: nothing computed */
+
+/*
+ * For every set s (P = set_off[s + 1] - set_off[s] columns of cols, in order) and day group g (its days are those with
+ * group[day] == g, n of them, in day order), item = s * ngroups + g:
+ *   1. per column: mean = sum / n, sd = sqrt(sum (x - mean)^2 / (n - 1)) (the mean first, then the centred sum), z = (x -
+ *      mean) / sd.  A non-finite value: TWXNR_NONFINITE; else sd == 0: TWXNR_CONSTANT.
+ *   2. G = Z'Z / (n - 1), every entry one sum over the days in ascending order: symmetric to the bit.
+ *   3. the eigen-decomposition of G by cyclic Jacobi (round-robin pair order, see twx_nnr.hip), until the off-diagonal
+ *      norm is <= eps x trace (eps = 2^-52).  Eigenvalues descending, equal ones by index; a component's loadings are
+ *      signed so that the one of largest magnitude (the first of equal ones) is positive.
+ *   4. var_explain[k] = lambda_k / (lambda_0 + lambda_1 + .. in this order); ncomp[v] = 1 + the first k at which
+ *      var_explain[0] + .. + var_explain[k] (added in order) >= max_var[v]; P if no k does.  With n < P the trailing
+ *      eigenvalues are ~0 (possibly below 0 by rounding) and the cut is unchanged.
+ *   5. the scores of the first max over v of ncomp[v] components: score[r][k] = sum over j (ascending) of z[r][j] x
+ *      loadings[k][j].
+ * fp64 on the float32 values widened exactly; every sum has a fixed order and no float atomics are used: two calls give
+ * the same bytes.
+ *
+ * cols [ncol][ndays]         float32, column-major: a column's days are contiguous.  A column may belong to several sets
+ * set_off [nset + 1], set_col   CSR of the sets' columns (0 <= set_col < ncol), 1 <= P <= TWXNR_MAX_COLS
+ * group [ndays]              -1 (day in no group) or 0 .. ngroups - 1, ngroups <= TWXIF_MAX_GROUPS
+ * max_var [nthr]             in (0, 1), nthr <= TWXNR_MAX_CUTS
+ * status, bad_col, sweeps [nitem], ncomp [nitem][nthr]   out; bad_col = -1 unless the status names a column; ncomp = 0
+ *                            for an item that was not decomposed
+ * mean, sd, var_explain, eigval   out, packed: item (s, g) owns the P entries from ngroups x set_off[s] + g x P
+ * loadings                   out, packed: item (s, g) owns P x P entries from ngroups x (sum of P^2 of the sets before s) +
+ *                            g x P^2, component k the row k P .. k P + P - 1.  The packed entries of an item that was not
+ *                            decomposed are NaN (mean and sd are written before a column is judged)
+ * score_off [nitem + 1], scores   out: the scores of item i are (score_off[i + 1] - score_off[i]) / n columns of n days,
+ *                            column after column; an item whose status is not TWXNR_OK has none.  score_cap entries must
+ *                            suffice: the call fails if they do not (sum over the items of n x P always does)
+ * kernel_ms (optional) [TWXNR_NTIMES]   device time of k_nr_gram, k_nr_eig, k_nr_scores; then host-clock milliseconds of
+ *                            the allocations and copies in, and of the copies back
+ * Call-level failures, all before any device work: ndays, ncol or nset < 1, a null buffer, ngroups outside 1 ..
+ * TWXIF_MAX_GROUPS, nthr outside 1 .. TWXNR_MAX_CUTS, a max_var outside (0, 1), set_off not from 0, a set with no column or
+ * more than TWXNR_MAX_COLS, a set_col out of range, a group value outside -1 .. ngroups - 1.
+ */
+int twxnr_components(int device, int64_t ndays, int64_t ncol, const float *cols, int64_t nset, const int64_t *set_off,
+                     const int32_t *set_col, int32_t ngroups, const int8_t *group, int32_t nthr, const double *max_var,
+                     int32_t *status, int32_t *bad_col, int32_t *ncomp, int32_t *sweeps, double *mean, double *sd,
+                     double *var_explain, double *eigval, double *loadings, int64_t *score_off, int64_t score_cap,
+                     double *scores, float *kernel_ms, char *errbuf, int errlen);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,3 +3,10 @@
 Drop-in for the ``twx.interp`` hot path of jaredwo/topowx.
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    if name == "NNRNghData":                 # the reanalysis reader (topowx_amd.reanalysis), imported at first use
+        from .reanalysis import NNRNghData
+        return NNRNghData
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

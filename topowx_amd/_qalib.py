@@ -820,3 +820,115 @@ def series_check(series, pen=None, sig=CK_SIG, fill=SC_FILL_F4, impossible_high=
         timing["sc_series_batches"] = timing.get("sc_series_batches", 0) + out["batches"]
         timing["sc_series_calls"] = timing.get("sc_series_calls", 0) + 1
     return out
+
+
+# ---- the reanalysis columns of the infill family (twxnr_components; TWXNR_* of include/twx_qa.h) ----
+NR_EXPORTS = ("twxnr_components",)
+NR_OK, NR_NOCONV, NR_NONFINITE, NR_CONSTANT, NR_FEW_ROWS = 0, 29, 30, 31, 32
+NR_MAX_COLS = 64          # TWXNR_MAX_COLS
+NR_MAX_CUTS = 4           # TWXNR_MAX_CUTS
+NR_MAX_SWEEPS = 30        # TWXNR_MAX_SWEEPS
+NR_KERNELS = ("nr_gram", "nr_eig", "nr_scores")         # TWXNR_NKERNELS
+NR_HOST_TIMES = ("nr_upload", "nr_download")            # the rest of TWXNR_NTIMES: host-clock milliseconds
+
+
+class NrComponents(object):
+    """The result of ``nnr_components_batched``, item = set * ngroups + group.  ``status``, ``bad_col``, ``sweeps``
+    [nset, G]; ``ncomp`` [nset, G, nthr]; ``nrows`` [G]; ``ncols`` [nset]; and per item through ``var_explain(s, g)``,
+    ``eigval(s, g)``, ``mean(s, g)``, ``sd(s, g)`` [P], ``loadings(s, g)`` [P, P] (component k is row k) and
+    ``scores(s, g, k=None)`` [n, k] (the first k components, default all that were formed: those of the item's largest
+    cut; an item that was not decomposed has none)."""
+
+    def __init__(self, set_off, nrows, max_var, out):
+        self.set_off, self.nrows, self.max_var = set_off, nrows, tuple(float(v) for v in max_var)
+        self.ncols = np.diff(set_off).astype(np.int64)
+        self.nset, self.ngroups = self.ncols.size, nrows.size
+        self._sq = np.concatenate([[0], np.cumsum(self.ncols ** 2)])
+        self.status, self.bad_col, self.sweeps, self.ncomp = out["status"], out["bad_col"], out["sweeps"], out["ncomp"]
+        self._out = out
+
+    def _p(self, s, g, name):
+        P = int(self.ncols[s])
+        a = self.ngroups * int(self.set_off[s]) + g * P
+        return self._out[name][a:a + P]
+
+    def var_explain(self, s, g):
+        return self._p(s, g, "var_explain")
+
+    def eigval(self, s, g):
+        return self._p(s, g, "eigval")
+
+    def mean(self, s, g):
+        return self._p(s, g, "mean")
+
+    def sd(self, s, g):
+        return self._p(s, g, "sd")
+
+    def loadings(self, s, g):
+        P = int(self.ncols[s])
+        a = self.ngroups * int(self._sq[s]) + g * P * P
+        return self._out["loadings"][a:a + P * P].reshape(P, P)
+
+    def scores(self, s, g, k=None):
+        i, n = s * self.ngroups + g, int(self.nrows[g])
+        a, b = int(self._out["score_off"][i]), int(self._out["score_off"][i + 1])
+        have = (b - a) // n if n else 0
+        if k is None:
+            k = have
+        if k > have:
+            raise ValueError("item (%d, %d) has %d score columns, %d asked for" % (s, g, have, k))
+        return self._out["scores"][a:a + k * n].reshape(k, n).T
+
+
+def nnr_components_batched(cols, set_off, set_col, group, max_var=(0.99,), ngroups=None, device=0, timing=None):
+    """``twxnr_components``: the principal components of every (column set, day group) item in one call.
+
+    cols [ncol, ndays] float32 (a column's days contiguous); set_off [nset + 1] / set_col: the CSR of the sets' columns;
+    group [ndays] int8, -1 or 0 .. G - 1; ``max_var``: the cuts, each in (0, 1).  Returns an ``NrComponents``.  ``timing``
+    receives ``nr_gram_kernel_ms`` / ``nr_eig_kernel_ms`` / ``nr_scores_kernel_ms`` and the host-clock ``nr_upload_ms`` /
+    ``nr_download_ms``."""
+    L = load()
+    if not hasattr(L.twxnr_components, "_twx_ready"):
+        L.twxnr_components.restype = C.c_int
+        L.twxnr_components.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                       C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 11 + [C.c_int64] + \
+            [C.c_void_p] * 2 + [C.c_char_p, C.c_int]
+        L.twxnr_components._twx_ready = True
+    cols, group = _c(cols, np.float32), _c(group, np.int8)
+    set_off, set_col = _c(set_off, np.int64), _c(set_col, np.int32)
+    max_var = _c(np.atleast_1d(np.asarray(max_var, np.float64)), np.float64)
+    if cols.ndim != 2 or group.shape != (cols.shape[1],):
+        raise ValueError("cols must be [ncol, ndays] and group [ndays]")
+    if set_off.ndim != 1 or set_off.size < 2 or set_col.ndim != 1 or max_var.ndim != 1:
+        raise ValueError("set_off must be [nset + 1 >= 2], set_col and max_var flat")
+    nset = set_off.size - 1
+    if ngroups is None:
+        ngroups = int(group.max()) + 1 if group.size and group.max() >= 0 else 1
+    ng, nthr = int(ngroups), max_var.size
+    ok = set_off[0] == 0 and (np.diff(set_off) >= 0).all() and set_off[-1] == set_col.size and 0 < ng <= IF_MAX_GROUPS
+    nrows = np.bincount(group[(group >= 0) & (group < ng)].astype(np.int64), minlength=ng)[:ng] if ok else np.zeros(max(ng, 0), np.int64)
+    ni = nset * max(ng, 0)
+    ncols = np.diff(set_off) if ok else np.zeros(nset, np.int64)
+    ntot, sq = int(ncols.sum()) * max(ng, 0), int((ncols ** 2).sum()) * max(ng, 0)
+    cap = int((np.minimum(ncols, NR_MAX_COLS)[:, None] * nrows[None, :]).sum()) if ok else 0     # always enough; pages of an empty array are not touched
+    out = dict(status=np.empty((nset, max(ng, 0)), np.int32), bad_col=np.empty((nset, max(ng, 0)), np.int32),
+               sweeps=np.empty((nset, max(ng, 0)), np.int32), ncomp=np.empty((nset, max(ng, 0), nthr), np.int32),
+               mean=np.empty(ntot), sd=np.empty(ntot), var_explain=np.empty(ntot), eigval=np.empty(ntot),
+               loadings=np.empty(sq), score_off=np.zeros(ni + 1, np.int64), scores=np.empty(cap))
+    ms = (C.c_float * (len(NR_KERNELS) + len(NR_HOST_TIMES)))()
+    buf = C.create_string_buffer(512)
+    rc = L.twxnr_components(int(device), cols.shape[1], cols.shape[0], cols.ctypes.data, nset, set_off.ctypes.data,
+                            set_col.ctypes.data, ng, group.ctypes.data, nthr, max_var.ctypes.data,
+                            out["status"].ctypes.data, out["bad_col"].ctypes.data, out["ncomp"].ctypes.data,
+                            out["sweeps"].ctypes.data, out["mean"].ctypes.data, out["sd"].ctypes.data,
+                            out["var_explain"].ctypes.data, out["eigval"].ctypes.data, out["loadings"].ctypes.data,
+                            out["score_off"].ctypes.data, cap, out["scores"].ctypes.data, C.addressof(ms), buf, 512)
+    if rc != 0:
+        raise QaError("twxnr_components failed: %s" % buf.value.decode(errors="replace"))
+    out["scores"] = out["scores"][:int(out["score_off"][-1])]
+    if timing is not None:
+        for k, name in enumerate(NR_KERNELS + NR_HOST_TIMES):
+            key = name + ("_kernel_ms" if k < len(NR_KERNELS) else "_ms")
+            timing[key] = timing.get(key, 0.0) + float(ms[k])
+        timing["nr_calls"] = timing.get("nr_calls", 0) + 1
+    return NrComponents(set_off, nrows, max_var, out)

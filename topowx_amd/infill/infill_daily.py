@@ -8,9 +8,10 @@ Deviations (none of them is built).  Neither R nor ``pcaMethods`` can be run: th
 ``RandomState(4324)``, not from R's ``rnorm`` stream, which moves the iteration EM stops at.  The
 warning branch of ``run_ppca`` parses a ``pcaMethods`` warning text and is replaced by a stated rule: a request is never
 above ``min(D - 1, TWXPP_MAX_PCS)``; the bound is tried once and accepted, flagged ``r2_not_reached`` if it misses
-``max_r2cum``.  ``tair_mask`` is not an argument here (step15 is ``topowx_amd.infill.XvalInfill``); the reanalysis reader
-``NNRNghData`` (``nnr=None``: station columns only; any object with ``get_nngh_matrix`` may be passed) and the writer of the
-infilled database are out of scope.
+``max_r2cum``.  ``tair_mask`` is not an argument here (step15 is ``topowx_amd.infill.XvalInfill``).  ``nnr``:
+``topowx_amd.NNRNghData`` gives the reference's model, with the scores of every item and of the ladder's 0.90 attempt
+from ONE ``twxnr_components`` call; an object with only ``get_nngh_matrix`` takes the per-target host route; ``nnr=None``:
+station columns only.
 
 ``chk_perf=True`` adds the reference's judgement of every fit (``_is_nonoptimal_infill``, :563-595) and its retry ladder
 (:438-518): libtwxqa's ``twxck_infill_check`` judges all items of a stage in ONE call, and ``RetryLadder`` decides per item
@@ -210,8 +211,9 @@ def daily_items(pool, tair_var, target_ids, mean, vari, nnr=None, utc_offset=Non
                 never_neighbour=None):
     """The items of ``infill_daily``, item = target * 12 + month - 1: a list of dicts of ``t`` (row of ``target_ids``),
     ``col`` (the target's pool column), ``g``, ``matrix_status``, ``max_dist``, ``cols``, ``extra``, ``norms``, ``stds``,
-    ``ncomp``, ``key`` (None or what identifies the item's extra columns) and ``nnr`` (None or the target's reanalysis
-    matrix over every day, shared between its items); and the station-major observations of the call.  One ``build_infill_matrices`` call per group of months with equal eligibility masks.
+    ``ncomp``, ``key`` (None or what identifies the item's extra columns), ``nnr`` (None or the target's reanalysis
+    matrix over every day, shared between its items: the host route) and ``nnr_batch`` (None or the ``NnrBatch`` of the call and
+    the target's row in it: the batched route); and the station-major observations of the call.  One ``build_infill_matrices`` call per group of months with equal eligibility masks.
     ``exclude_cols`` / ``never_neighbour``: as ``build_infill_matrices`` takes them (step15)."""
     mean, vari = np.asarray(mean, np.float64), np.asarray(vari, np.float64)
     n = pool.ids.size
@@ -219,6 +221,7 @@ def daily_items(pool, tair_var, target_ids, mean, vari, nnr=None, utc_offset=Non
         raise ValueError("mean / vari must be [nstn, 12] over the stations of the pool")
     month = np.asarray(pool.days[MONTH], np.int64) - 1
     items, obs = {}, None
+    batch = None                                                     # ONE reanalysis call for all targets and months
     for mask, months in month_mask_groups(mean, vari, never_neighbour):
         grp = np.where(np.isin(month, months), month, -1).astype(np.int8)
         if not (grp >= 0).any():
@@ -227,9 +230,15 @@ def daily_items(pool, tair_var, target_ids, mean, vari, nnr=None, utc_offset=Non
                                   exclude_cols=exclude_cols)
         obs = m.obs_station_major
         scores = {}
+        if batch is None and nnr is not None and hasattr(nnr, "batched_components"):
+            cuts = (max_nnr_var, MIN_NNR_VAR) if MIN_NNR_VAR < max_nnr_var else (max_nnr_var,)
+            batch = nnr.batched_components(pool.lon[m.target_cols], pool.lat[m.target_cols], tair_var, utc_offset,
+                                           [np.nonzero(month == g)[0] for g in range(12)], cuts, nnghs_nnr, device, timing)
         for t in range(len(m.target_ids)):
             key = a = None
-            if nnr is not None:
+            if batch is not None:
+                key = batch.key(t)
+            elif nnr is not None:
                 c = int(m.target_cols[t])
                 a = np.asarray(nnr.get_nngh_matrix(pool.lon[c], pool.lat[c], tair_var,
                                                    utc_offset=None if utc_offset is None else utc_offset[t],
@@ -241,17 +250,19 @@ def daily_items(pool, tair_var, target_ids, mean, vari, nnr=None, utc_offset=Non
                 it = dict(t=t, col=int(m.target_cols[t]), g=g, matrix_status=int(m.status[t, g]),
                           max_dist=float(m.max_dist[t, g]), cols=np.zeros(0, np.int64), extra=np.zeros((m.nrows(g), 0)),
                           norms=np.array([mean[m.target_cols[t], g]]),
-                          stds=np.sqrt(np.array([vari[m.target_cols[t], g]])), ncomp=0, key=None, nnr=None)
+                          stds=np.sqrt(np.array([vari[m.target_cols[t], g]])), ncomp=0, key=None, nnr=None, nnr_batch=None)
                 if it["matrix_status"] == _qalib.IF_OK:
                     sc = None
                     if key is not None:
                         if (key, g) not in scores:
-                            scores[(key, g)] = nnr_components(a[m.day_idx(g)], max_nnr_var)
+                            scores[(key, g)] = batch.scores(t, g, max_nnr_var) if batch is not None else \
+                                nnr_components(a[m.day_idx(g)], max_nnr_var)
                         sc = scores[(key, g)]
                     it["cols"], it["extra"], it["norms"], it["stds"] = assemble_daily_columns(m, t, g, mean[:, g], vari[:, g], sc)
                     it["ncomp"] = it["extra"].shape[1]
                     it["key"] = (key, g) if it["ncomp"] else None
-                    it["nnr"] = a if key is not None else None
+                    it["nnr"] = a if key is not None and batch is None else None
+                    it["nnr_batch"] = (batch, t) if batch is not None else None
                 items[(t, g)] = it
     if obs is None:
         raise ValueError("no day belongs to a calendar month")
@@ -355,10 +366,15 @@ def run_search(obs, group, items, npcs=0, frac_obs=0.5, max_r2cum=0.99, threshol
 
 def retry_item(item, nnr_var, day_idx):
     """The item of the ladder's attempt at ``nnr_var``: the reanalysis scores cut at that variance, the station columns as
-    they are.  ``day_idx``: the day indices of the item's month."""
-    if item["nnr"] is None or item["matrix_status"] != _qalib.IF_OK:
+    they are.  ``day_idx``: the day indices of the item's month.  An item of the batched route (``nnr_batch``) takes the
+    leading columns of the decomposition it already has; the host route runs ``nnr_components`` again."""
+    if (item["nnr"] is None and item.get("nnr_batch") is None) or item["matrix_status"] != _qalib.IF_OK:
         return item
-    extra = nnr_components(item["nnr"][day_idx], nnr_var)
+    if item.get("nnr_batch") is not None:
+        batch, t = item["nnr_batch"]
+        extra = np.array(batch.scores(t, item["g"], nnr_var), np.float64)
+    else:
+        extra = nnr_components(item["nnr"][day_idx], nnr_var)
     nst = 1 + len(item["cols"])
     it = dict(item, extra=extra, ncomp=extra.shape[1], key=(item["key"][0], item["g"], float(nnr_var)) if item["key"] else None)
     it["norms"] = np.concatenate([item["norms"][:nst], np.mean(extra, axis=0)])
@@ -421,7 +437,7 @@ def infill_daily(pool, tair_var, target_ids, mean, vari, nnr=None, utc_offset=No
     """Step16 for ``target_ids`` (station ids of ``pool``, a ``StationObsPool`` whose flagged observations are NaN) and
     ``tair_var``, every target and calendar month in batched GPU calls.  ``mean`` / ``vari`` [nstn, 12]: the monthly mean
     and variance of every station of the pool as step14 estimates them (NaN: the station is no neighbour that month).
-    ``nnr``: None or an object with the reference's ``get_nngh_matrix``.  The other parameters are ``infill_daily_obs``'s.
+    ``nnr``: None, an ``NNRNghData`` (batched route) or an object with the reference's ``get_nngh_matrix``.  The other parameters are ``infill_daily_obs``'s.
     ``chk_perf``: judge every fit and refit the non-optimal ones up the reference's ladder (``RetryLadder``; ``cpt_sig``: the
     level of the variance change-point check); False, the default, stops at every item's first attempt.
     ``exclude_cols`` [ntarget] / ``never_neighbour`` [nstn]: as ``build_infill_matrices`` takes them (step15's ``XvalInfill``).
@@ -495,14 +511,15 @@ def infill_daily(pool, tair_var, target_ids, mean, vari, nnr=None, utc_offset=No
 
 def infill_daily_obs(stn_id, pool, tair_var, nnr_ds, mean, vari, tair_mask=None, day_masks=None, add_bestngh=True,
                      min_daily_nnghs=MIN_DAILY_NGHBRS, nnghs_nnr=NNGH_NNR, max_nnr_var=MAX_NNR_VAR, chk_perf=False, npcs=0,
-                     frac_obs_initnpcs=0.5, ppca_varyexplain=0.99, ppcaConThres=1e-5, verbose=False, device=0):
+                     frac_obs_initnpcs=0.5, ppca_varyexplain=0.99, ppcaConThres=1e-5, verbose=False, device=0, utc_offset=None):
     """``infill_daily_obs`` (infill_daily.py:526-561) of one target, routed through the batched call: ``(fnl_tair,
     mask_infill, infill_tair)`` over the days of the pool.  ``pool`` stands for the reference's ``stn_da``; ``mean`` / ``vari``
     [nstn, 12] for its ``vname_mean`` / ``vname_vari`` (the twelve monthly variables); ``day_masks`` must be the twelve
     calendar-month masks in order, as step16 passes them (``None``, one matrix over every day with one mean and variance, is
     not implemented).  ``tair_mask`` raises ``NotImplementedError`` (step15 is ``topowx_amd.infill.XvalInfill``), and so does ``chk_perf=True`` here: the retry
     ladder is batched over items, call ``infill_daily(chk_perf=True)`` for it; ``add_bestngh=False`` is not supported by the
-    matrix builder."""
+    matrix builder.  ``utc_offset``: the target's (the reference reads it from the station table), needed with a reanalysis
+    reader."""
     if tair_mask is not None:
         raise NotImplementedError("tair_mask (cross-validation masking) belongs to step15 and is not implemented")
     if chk_perf:
@@ -514,6 +531,6 @@ def infill_daily_obs(stn_id, pool, tair_var, nnr_ds, mean, vari, tair_mask=None,
     masks = [] if day_masks is None else [np.asarray(k) for k in day_masks]
     if len(masks) != 12 or any(k.shape != month.shape or not np.array_equal(k, month == g + 1) for g, k in enumerate(masks)):
         raise NotImplementedError("day_masks other than the twelve calendar months are not implemented")
-    r = infill_daily(pool, tair_var, [stn_id], mean, vari, nnr_ds, None, min_daily_nnghs, nnghs_nnr, max_nnr_var, npcs,
+    r = infill_daily(pool, tair_var, [stn_id], mean, vari, nnr_ds, None if utc_offset is None else [utc_offset], min_daily_nnghs, nnghs_nnr, max_nnr_var, npcs,
                      frac_obs_initnpcs, ppca_varyexplain, ppcaConThres, device=device)
     return r.fnl_tair[0], r.mask_infill[0], r.infill_tair[0]

@@ -9,7 +9,7 @@ the observation matrix of an item on the host (target first, then the kept stati
 ``MAX_COLS_NORM_IMPUTE`` columns).  ``InfillMatrix`` is a facade with the reference's attribute names for one target.
 
 The estimate of mean and variance from the matrices (``infill_mu_sigma`` / ``em.norm``, the PCA of the reanalysis columns)
-is ``topowx_amd.infill.infill_normals``.  Out of scope: the reanalysis reader, ``build_por_mask`` and
+is ``topowx_amd.infill.infill_normals``; the reanalysis reader is ``topowx_amd.NNRNghData``.  Out of scope: ``build_por_mask`` and
 ``InfillMatrixPPCA``; the reference's ``tair_mask`` is ``topowx_amd.infill.XvalInfill`` (step15), which hands the masked
 series in as rows appended to the pool (``exclude_cols`` / ``never_neighbour`` below).
 """

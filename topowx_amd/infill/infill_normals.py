@@ -6,8 +6,10 @@ include/twx_qa.h states it -- runs for every (target, day group) item in ONE cal
 There is no CPU fallback: without the library the call raises.
 
 Deviations.  Neither R nor ``norm`` can be run against the restatement: the iteration at which EM stops is not pinned
-(DESIGN.md section 17).  The reanalysis reader ``NNRNghData`` is not ported: ``nnr=None`` gives an estimate from station
-columns only; any object with the reference's ``get_nngh_matrix(lon, lat, var, utc_offset=, nngh=)`` can be passed.
+(DESIGN.md section 17).  ``nnr``: ``topowx_amd.NNRNghData`` (or any object with its ``batched_components``) gives the
+reference's model, the reanalysis scores of every item from ONE ``twxnr_components`` call; any object with only the
+reference's ``get_nngh_matrix(lon, lat, var, utc_offset=, nngh=)`` takes the per-target host route (``nnr_components``);
+``nnr=None`` gives an estimate from station columns only.
 ``tair_mask`` is not an argument here: step15's cross-validation is ``topowx_amd.infill.XvalInfill``.
 """
 import hashlib
@@ -94,9 +96,11 @@ class InfillEstimates(object):
 def estimate_mean_variance(matrices, nnr=None, utc_offset=None, criterion=1e-4, maxits=1000, device=0, timing=None,
                            nnghs_nnr=NNGH_NNR, max_nnr_var=0.99, iters_per_launch=0, workspace_bytes=0):
     """Mean and variance of every item of ``matrices`` (an ``InfillMatrices``) in one GPU call.  ``nnr``: None (station
-    columns only: a deviation, the reanalysis reader is not ported) or an object with the reference's
-    ``get_nngh_matrix(lon, lat, var, utc_offset=, nngh=)`` returning [ndays, nnghs_nnr]; ``utc_offset`` [ntarget] is handed
-    to it.  Equal returned matrices share one extra-column set on the device.  ``criterion`` / ``maxits`` are ``em.norm``'s.
+    columns only), an ``NNRNghData`` (anything with ``batched_components``: the scores of every item come from one
+    ``twxnr_components`` call on the reader's day axis, which must be the pool's), or an object with only the reference's
+    ``get_nngh_matrix(lon, lat, var, utc_offset=, nngh=)`` returning [ndays, nnghs_nnr] (the host route, one SVD per
+    distinct matrix and month); ``utc_offset`` [ntarget] is handed to it.  Equal matrices share one extra-column set on
+    the device.  ``criterion`` / ``maxits`` are ``em.norm``'s.
     An item whose matrix is not ``ok`` gets status ``no neighbour matrix``.  ``timing`` (a dict) receives the kernel
     milliseconds, launches and batches of the call and ``assemble_s`` / ``em_library_s``."""
     m = matrices
@@ -106,9 +110,15 @@ def estimate_mean_variance(matrices, nnr=None, utc_offset=None, criterion=1e-4, 
     off, cols, sets, set_key, item_set = [0], [], [], {}, np.full(nt * G, -1, np.int32)
     ncols, ncomp = np.zeros((nt, G), np.int32), np.zeros((nt, G), np.int32)
     scores = {}
+    batch = None
+    if nnr is not None and hasattr(nnr, "batched_components"):
+        batch = nnr.batched_components(m.pool.lon[m.target_cols], m.pool.lat[m.target_cols], m.var, utc_offset, day_idx,
+                                       (max_nnr_var,), nnghs_nnr, device, timing)
     for t in range(nt):
         key = None
-        if nnr is not None:
+        if batch is not None:
+            key = batch.key(t)
+        elif nnr is not None:
             c = int(m.target_cols[t])
             a = np.asarray(nnr.get_nngh_matrix(m.pool.lon[c], m.pool.lat[c], m.var,
                                                utc_offset=None if utc_offset is None else utc_offset[t], nngh=nnghs_nnr),
@@ -122,7 +132,8 @@ def estimate_mean_variance(matrices, nnr=None, utc_offset=None, criterion=1e-4, 
             sc = None
             if key is not None:
                 if (key, g) not in scores:
-                    scores[(key, g)] = nnr_components(a[day_idx[g]], max_nnr_var)
+                    scores[(key, g)] = batch.scores(t, g, max_nnr_var) if batch is not None else \
+                        nnr_components(a[day_idx[g]], max_nnr_var)
                 sc = scores[(key, g)]
             c, extra = assemble_columns(m, t, g, sc)
             cols.append(c)
@@ -147,16 +158,18 @@ def estimate_mean_variance(matrices, nnr=None, utc_offset=None, criterion=1e-4, 
 
 
 def infill_mean_variance(stn_id, pool, stn_mask, tair_var, nnr_ds=None, tair_mask=None, day_masks=None,
-                         nnghs=MIN_DAILY_NGHBRS, nnghs_nnr=NNGH_NNR, device=0):
+                         nnghs=MIN_DAILY_NGHBRS, nnghs_nnr=NNGH_NNR, device=0, utc_offset=None):
     """``infill_mean_variance`` (infill_normals.py:452-517) of one target, routed through the batched calls: ``(mean,
     variance)`` as two floats for ``day_masks=None`` (every day), else as two arrays over the boolean masks [ndays] of
-    ``day_masks``.  ``pool``: a ``StationObsPool`` in place of the reference's ``stn_da``.  ``tair_mask`` is step15's
+    ``day_masks``.  ``pool``: a ``StationObsPool`` in place of the reference's ``stn_da``; ``utc_offset``: the target's (the reference reads it from
+    the station table), needed with a reanalysis reader.  ``tair_mask`` is step15's
     cross-validation masking and raises ``NotImplementedError``: use ``topowx_amd.infill.XvalInfill``."""
     if tair_mask is not None:
         raise NotImplementedError("tair_mask (cross-validation masking) belongs to step15 and is not implemented")
+    utc = None if utc_offset is None else [utc_offset]
     if day_masks is None:
         mats = build_infill_matrices(pool, tair_var, [stn_id], stn_mask, "all", nnghs, device)
-        e = estimate_mean_variance(mats, nnr_ds, device=device, nnghs_nnr=nnghs_nnr)
+        e = estimate_mean_variance(mats, nnr_ds, utc, device=device, nnghs_nnr=nnghs_nnr)
         return float(e.mean[0, 0]), float(e.variance[0, 0])
     masks = [np.asarray(k) for k in day_masks]
     for k in masks:
@@ -169,11 +182,11 @@ def infill_mean_variance(stn_id, pool, stn_mask, tair_var, nnr_ds=None, tair_mas
         for x, k in enumerate(masks):
             grp[k] = x
         mats = build_infill_matrices(pool, tair_var, [stn_id], stn_mask, grp, nnghs, device)
-        e = estimate_mean_variance(mats, nnr_ds, device=device, nnghs_nnr=nnghs_nnr)
+        e = estimate_mean_variance(mats, nnr_ds, utc, device=device, nnghs_nnr=nnghs_nnr)
         mean[:], var[:] = e.mean[0], e.variance[0]
     else:
         for x, k in enumerate(masks):
             mats = build_infill_matrices(pool, tair_var, [stn_id], stn_mask, np.where(k, 0, -1).astype(np.int8), nnghs, device)
-            e = estimate_mean_variance(mats, nnr_ds, device=device, nnghs_nnr=nnghs_nnr)
+            e = estimate_mean_variance(mats, nnr_ds, utc, device=device, nnghs_nnr=nnghs_nnr)
             mean[x], var[x] = e.mean[0, 0], e.variance[0, 0]
     return mean, var

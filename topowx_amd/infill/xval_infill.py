@@ -75,10 +75,11 @@ class XvalInfill(object):
     """``XvalInfill`` (xval_infill.py:32-164).  ``pool``: a ``StationObsPool`` whose flagged observations are NaN, in place
     of the reference's ``stnda``; ``mean`` / ``vari`` [n, 12]: the monthly mean and variance of the station table (step14's
     result; NaN: the station is no neighbour).  The neighbour mask of the mean / variance stage is
-    ``isfinite(mean[:, 0])`` (:94).  ``xval_stnids`` is required.  Attributes: ``stn_ids``, ``mths``, ``stn_xval_masks``
+    ``isfinite(mean[:, 0])`` (:94).  ``xval_stnids`` is required.  ``utc_offset`` [n] (the station variable step13 writes; None: none
+    is handed on) goes to the reanalysis reader ``infill_params.nnr_ds`` with each station's own value.  Attributes: ``stn_ids``, ``mths``, ``stn_xval_masks``
     ([nx, ndays] bool: the held observations, one ``twxxv_holdout`` call made at first use), ``nkeep``."""
 
-    def __init__(self, pool, var_tair, infill_params, mean, vari, xval_stnids=None, ntrain_yrs=5, device=0):
+    def __init__(self, pool, var_tair, infill_params, mean, vari, xval_stnids=None, ntrain_yrs=5, device=0, utc_offset=None):
         if var_tair not in ("tmin", "tmax"):
             raise ValueError("var_tair must be 'tmin' or 'tmax'")
         if xval_stnids is None:
@@ -103,6 +104,9 @@ class XvalInfill(object):
         self.nkeep = _qalib.xval_nkeep(ntrain_yrs)                 # xval_infill.py:73
         self.ngh_stn_mask = np.isfinite(self.mean[:, 0])           # :94
         self._hold = None
+        self.utc_offset = None if utc_offset is None else np.asarray(utc_offset)
+        if self.utc_offset is not None and self.utc_offset.shape != (n,):
+            raise ValueError("utc_offset must be [nstn] over the stations of the pool")
 
     def _holdout(self, timing=None):
         if self._hold is None:
@@ -152,11 +156,12 @@ class XvalInfill(object):
         mats = build_infill_matrices(ext, var, app_ids, np.concatenate([self.ngh_stn_mask, np.zeros(nx, bool)]), None,
                                      p.min_daily_nnghs, self.device, timing=t_mat, exclude_cols=cols, never_neighbour=never)
         t2 = time.perf_counter()
-        est = estimate_mean_variance(mats, p.nnr_ds, device=self.device, timing=t_em, nnghs_nnr=p.nnghs_nnr)
+        utc = None if self.utc_offset is None else self.utc_offset[cols]
+        est = estimate_mean_variance(mats, p.nnr_ds, utc, device=self.device, timing=t_em, nnghs_nnr=p.nnghs_nnr)
         t3 = time.perf_counter()
         mean = np.concatenate([self.mean, est.mean], axis=0)
         vari = np.concatenate([self.vari, est.variance], axis=0)
-        daily = infill_daily(ext, var, app_ids, mean, vari, p.nnr_ds, None, p.min_daily_nnghs, p.nnghs_nnr, p.max_nnr_var,
+        daily = infill_daily(ext, var, app_ids, mean, vari, p.nnr_ds, utc, p.min_daily_nnghs, p.nnghs_nnr, p.max_nnr_var,
                              p.npcs, p.frac_obs_initnpcs, p.ppca_varyexplain, device=self.device, timing=t_day,
                              chk_perf=p.chk_perf, exclude_cols=cols, never_neighbour=never)
         t4 = time.perf_counter()

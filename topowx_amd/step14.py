@@ -4,7 +4,7 @@ them (``topowx_amd.infill.estimate_mean_variance``), each in one batched GPU cal
 over stations.  A report: nothing is written into the database.
 
     python -m topowx_amd.step14 --db all.nc --var tmin --out matrices.npz [--targets ids.txt] [--neighbours ids.txt]
-                                [--device N] [--estimate]
+                                [--device N] [--estimate [--nnr-dir DIR]]
 
 ``--targets``: the stations to build matrices for (default: every station); ``--neighbours``: the stations that may serve
 as neighbours, the reference's ``stns_mask`` (default: every station; a target is never its own neighbour).  Both are
@@ -21,13 +21,18 @@ database on the item's days (``InfillMatrices.matrix``).
 
 ``--estimate`` adds ``mean``, ``variance``, ``em_iters``, ``em_status`` [ntarget, 12] (``topowx_amd.infill.EM_STATUS``) to the
 report, and the items per estimator status (``em_status``), the launches and the kernel milliseconds to the JSON line.
-The values are estimated from station columns ONLY: they carry no reanalysis columns, because the reanalysis reader is
-not ported, so they are not what the reference would write as ``mean_tminMM`` / ``vari_tminMM`` and there is no ``--write``.
-Without the flag the output is what it was before the flag existed.
+Without ``--nnr-dir`` the values are estimated from station columns only and the output is what it was before that flag
+existed.  With ``--nnr-dir DIR`` (the subsets ``nnr_<var>_<time>.nc``, ``topowx_amd.NNRNghData``) every matrix gets the
+reference's reanalysis score columns, all items decomposed in one ``twxnr_components`` call; the station variable
+``utc_offset`` (i2, what step13 writes) is read from the database, and the report gains ``ncols`` / ``ncomp`` [ntarget, 12].
+The estimator is the restated one, so there is still no ``--write``.
 
-Out of scope: the reanalysis reader (``NNRNghData``), ``build_por_mask``, writing the estimates into the database.
+Out of scope: ``build_por_mask``, writing the estimates into the database, step12's subsetting of the raw yearly reanalysis
+files and step13's time-zone lookup.
 
-Exits with 1 if the database cannot be opened or a station id is unknown.
+Exits with 1 if the database cannot be opened, a station id is unknown, or ``--nnr-dir`` is given and the database has no
+``utc_offset`` or the subsets cannot be opened or do not cover the database's days.  ``--nnr-dir`` without ``--estimate`` is a
+usage error.
 """
 import argparse
 import json
@@ -37,7 +42,7 @@ import time
 import numpy as np
 
 from . import ncio
-from ._cli import UnknownIds as _UnknownIds, read_ids as _read_ids
+from ._cli import NNR_DIR_HELP, NnrInputError as _NnrInputError, UnknownIds as _UnknownIds, open_nnr as _open_nnr, read_ids as _read_ids
 from .dates import YMD
 from .infill import EM_STATUS, ITEM_STATUS, build_infill_matrices, estimate_mean_variance
 from .qa import StationObsPool
@@ -58,8 +63,12 @@ def main(argv=None):
     ap.add_argument("--neighbours", help="text file of the station ids that may be neighbours (default: every station)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--estimate", action="store_true",
-                    help="also estimate the mean and variance of every item (station columns only, no reanalysis columns)")
+                    help="also estimate the mean and variance of every item (station columns only unless --nnr-dir is given)")
+    ap.add_argument("--nnr-dir", help=NNR_DIR_HELP + " (with --estimate)")
     a = ap.parse_args(argv)
+    if a.nnr_dir and not a.estimate:
+        ap.error("--nnr-dir needs --estimate: the matrices themselves hold no reanalysis column")
+    nnr = utc = None
     try:
         ds = ncio.open_dataset(a.db, "r")
         try:
@@ -72,7 +81,9 @@ def main(argv=None):
         if a.neighbours:
             mask = np.zeros(pool.ids.size, bool)
             mask[[pool.idxs[s] for s in _read_ids(a.neighbours, pool, "neighbour")]] = True
-    except _UnknownIds as e:
+        if a.nnr_dir:
+            nnr, utc = _open_nnr(a.nnr_dir, a.db, pool)
+    except (_UnknownIds, _NnrInputError) as e:
         print("step14: %s" % e, file=sys.stderr)
         return 1
     except (IOError, OSError, ValueError, KeyError) as e:
@@ -83,8 +94,16 @@ def main(argv=None):
     m = build_infill_matrices(pool, a.var, targets, mask, device=a.device, timing=tm)
     extra = {}
     if a.estimate:
-        e = estimate_mean_variance(m, device=a.device, timing=tm)
+        if nnr is None:
+            e = estimate_mean_variance(m, device=a.device, timing=tm)
+        else:
+            try:
+                e = estimate_mean_variance(m, nnr, utc[m.target_cols], device=a.device, timing=tm)
+            finally:
+                nnr.close()
         extra = dict(mean=e.mean, variance=e.variance, em_iters=e.iters, em_status=e.status)
+        if nnr is not None:
+            extra.update(ncols=e.ncols, ncomp=e.ncomp)
     sec = time.perf_counter() - t0
     np.savez_compressed(a.out, ids=m.target_ids, pool_ids=pool.ids, ymd=np.asarray(pool.days[YMD], np.int32), group=m.group,
                         **dict({k: getattr(m, k) for k in COLUMNS}, **extra))

@@ -6,6 +6,7 @@ parameters of step15:204-211.
 
     python -m topowx_amd.step15 --db all.nc --normals step14_report.npz --xval-stnids ids.txt --out xval_infill.nc
                                 [--report xval.npz] [--ntrain-yrs 5] [--device N] [--format NETCDF4|NETCDF3_64BIT]
+                                [--nnr-dir DIR]
 
 ``--normals``: the monthly mean and variance of EVERY station of the database, which the reference reads from the station
 table: one ``.npz`` with ``ids``, ``mean_tmin``, ``variance_tmin``, ``mean_tmax``, ``variance_tmax`` [n, 12], or a path with
@@ -20,11 +21,15 @@ JSON line (stations, held days, items per status, seconds).  ``--report``: an ``
 ``held_*``, ``n_*``, ``bias_*``, ``mae_*``, ``month_n_*``, ``month_bias_*``, ``month_mae_*``, ``em_status_*``, ``em_mean_*``,
 ``em_variance_*``, ``status_*``, ``matrix_status_*``, ``attempt_*``, ``npcs_*``.
 
-The values come from station columns ONLY (the reanalysis reader is not ported) and from restated estimators (DESIGN.md
-sections 17 to 19): they are not what the reference would write.  ``--ppca-varyexplain`` (default 0.99, step15:209) is
+Without ``--nnr-dir`` the values come from station columns only and the outputs are what they were before that flag
+existed.  With ``--nnr-dir DIR`` (the subsets ``nnr_<var>_<time>.nc``, ``topowx_amd.NNRNghData``) the matrices of both stages
+get the reference's reanalysis score columns; the station variable ``utc_offset`` (i2, what step13 writes) is read from the
+database and the report gains ``ncomp_*``.  The estimators are restated ones (DESIGN.md sections 17 to 19): the values are
+not what the reference would write.  ``--ppca-varyexplain`` (default 0.99, step15:209) is
 there for pools whose noise is not the reference's.
 
-Exits with 1 if a file cannot be opened, a station id is unknown or the normals do not cover the database's stations.
+Exits with 1 if a file cannot be opened, a station id is unknown, the normals do not cover the database's stations, or
+``--nnr-dir`` is given and the database has no ``utc_offset`` or the subsets cannot be opened or do not cover its days.
 """
 import argparse
 import json
@@ -36,7 +41,7 @@ import numpy as np
 
 from . import _qalib, ncio
 from . import stationdb as sdb
-from ._cli import BadNormals, UnknownIds, normals, read_ids
+from ._cli import NNR_DIR_HELP, BadNormals, NnrInputError, UnknownIds, normals, open_nnr, read_ids
 from .dates import YMD
 from .infill import EM_STATUS, PP_STATUS, XvalInfill, XvalInfillParams
 from .qa import StationObsPool
@@ -51,6 +56,7 @@ OUT_VARIABLES = [("obs_tmin", "f4", ncio.FILL_F4, "observed minimum air temperat
                  ("infilled_tmax", "f4", ncio.FILL_F4, "infilled maximum air temperature", "C")]      # step15:25-32
 REPORT = ("held", "n", "bias", "mae", "month_n", "month_bias", "month_mae", "em_status", "em_mean", "em_variance")
 REPORT_DAILY = ("status", "matrix_status", "attempt", "npcs")
+REPORT_DAILY_NNR = ("ncomp",)             # with --nnr-dir
 
 
 def _both_normals(path, pool):
@@ -98,7 +104,9 @@ def main(argv=None):
     ap.add_argument("--ppca-varyexplain", type=float, default=0.99)
     ap.add_argument("--format", choices=ncio.FORMATS, default=None, help="container of --out (default: the build's)")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--nnr-dir", help=NNR_DIR_HELP)
     a = ap.parse_args(argv)
+    nnr = utc = None
     try:
         ds = ncio.open_dataset(a.db, "r")
         try:
@@ -111,19 +119,25 @@ def main(argv=None):
             raise UnknownIds("%s: need at least one station id, each once" % a.xval_stnids)
         normals = _both_normals(a.normals, pool)
         elev = _elevation(a.db, pool.ids.size)
-    except (UnknownIds, BadNormals) as e:
+        if a.nnr_dir:
+            nnr, utc = open_nnr(a.nnr_dir, a.db, pool)
+    except (UnknownIds, BadNormals, NnrInputError) as e:
         print("step15: %s" % e, file=sys.stderr)
         return 1
     except (IOError, OSError, ValueError, KeyError) as e:
         print("step15: cannot open %s: %s" % (getattr(e, "filename", None) or a.db, e), file=sys.stderr)
         return 1
-    params = XvalInfillParams(None, 3, 4, 0.99, True, 0, 0.5, a.ppca_varyexplain, False)      # step15:204-211
+    params = XvalInfillParams(nnr, 3, 4, 0.99, True, 0, 0.5, a.ppca_varyexplain, False)      # step15:204-211
     t0 = time.perf_counter()
     res, tms = {}, {}
-    for v in VARS:
-        tms[v] = {}
-        xv = XvalInfill(pool, v, params, normals[v][0], normals[v][1], ids, a.ntrain_yrs, a.device)
-        res[v] = xv.run_all(tms[v])
+    try:
+        for v in VARS:
+            tms[v] = {}
+            xv = XvalInfill(pool, v, params, normals[v][0], normals[v][1], ids, a.ntrain_yrs, a.device, utc_offset=utc)
+            res[v] = xv.run_all(tms[v])
+    finally:
+        if nnr is not None:
+            nnr.close()
     sec = time.perf_counter() - t0
     cols = np.array([pool.idxs[s] for s in ids])
     stns = np.empty(len(ids), dtype=[(sdb.STN_ID, "U%d" % max(len(s) for s in ids)), (sdb.LON, np.float64),
@@ -145,7 +159,8 @@ def main(argv=None):
             rep = dict(ids=np.array(ids), ymd=np.asarray(pool.days[YMD], np.int32))
             for v in VARS:
                 rep.update({"%s_%s" % (k, v): getattr(res[v], k) for k in REPORT})
-                rep.update({"%s_%s" % (k, v): getattr(res[v].daily, k) for k in REPORT_DAILY})
+                rep.update({"%s_%s" % (k, v): getattr(res[v].daily, k)
+                            for k in REPORT_DAILY + (REPORT_DAILY_NNR if nnr is not None else ())})
             np.savez_compressed(a.report, **rep)
     except (IOError, OSError) as e:
         print("step15: cannot write %s: %s" % (getattr(e, "filename", None) or a.out, e), file=sys.stderr)

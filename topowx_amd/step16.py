@@ -22,13 +22,18 @@ change point at the level ``--cpt-sig``, default 1e-10) and refit the non-optima
 ``attempt_r2`` [ntarget, 12, 4], and the JSON line ``attempt_items`` (items per attempt), ``nonoptimal``, ``retry_fixed`` and
 the check's ``ck_check_kernel_ms``.  Without the flag the report and the JSON line are what they were.
 
-The values come from station columns ONLY (the reanalysis reader is not ported) and from a restated estimator whose start
-is not R's: they are not what the reference would write, and there is no ``--write``.
+Without ``--nnr-dir`` the values come from station columns only and the report is what it was before that flag existed.
+With ``--nnr-dir DIR`` (the subsets ``nnr_<var>_<time>.nc``, ``topowx_amd.NNRNghData``) every matrix gets the reference's
+reanalysis score columns, and the ladder's 0.90 attempt takes the leading columns of the same decomposition; the station
+variable ``utc_offset`` (i2, what step13 writes) is read from the database, and the report gains ``ncomp`` [ntarget, 12].  The
+estimator is a restated one whose start is not R's, so there is no ``--write``.
 
-Out of scope: the reanalysis reader and ``tair_mask`` (step15's cross-validation is ``python -m topowx_amd.step15``).  The
+Out of scope: ``tair_mask`` (step15's cross-validation is ``python -m topowx_amd.step15``), step12's subsetting of the raw
+yearly reanalysis files and step13's time-zone lookup.  The
 infilled database is written from this report by ``python -m topowx_amd.step17 --report-*``.  The variance change-point check is restated, not R's ``changepoint`` executed.
 
-Exits with 1 if a file cannot be opened, a station id is unknown or the normals do not cover the database's stations.
+Exits with 1 if a file cannot be opened, a station id is unknown, the normals do not cover the database's stations, or
+``--nnr-dir`` is given and the database has no ``utc_offset`` or the subsets cannot be opened or do not cover its days.
 """
 import argparse
 import json
@@ -38,7 +43,8 @@ import time
 import numpy as np
 
 from . import ncio
-from ._cli import BadNormals as _BadNormals, UnknownIds as _UnknownIds, normals as _normals, read_ids as _read_ids
+from ._cli import (NNR_DIR_HELP, BadNormals as _BadNormals, NnrInputError as _NnrInputError, UnknownIds as _UnknownIds,
+                   normals as _normals, open_nnr as _open_nnr, read_ids as _read_ids)
 from .dates import YMD
 from .infill import PP_STATUS, infill_daily
 from .qa import StationObsPool
@@ -62,7 +68,9 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--chk-perf", action="store_true", help="judge every fit and refit the non-optimal ones up the retry ladder")
     ap.add_argument("--cpt-sig", type=float, default=1e-10, help="level of the variance change-point check (with --chk-perf)")
+    ap.add_argument("--nnr-dir", help=NNR_DIR_HELP)
     a = ap.parse_args(argv)
+    nnr = utc = None
     try:
         ds = ncio.open_dataset(a.db, "r")
         try:
@@ -72,7 +80,10 @@ def main(argv=None):
         pool = StationObsPool.from_netcdf(a.db, qflags=qflags)
         targets = _read_ids(a.targets, pool, "target") if a.targets else list(pool.ids)
         mean, vari = _normals(a.normals, pool)
-    except (_UnknownIds, _BadNormals) as e:
+        if a.nnr_dir:
+            nnr, utc = _open_nnr(a.nnr_dir, a.db, pool)
+            utc = utc[[pool.idxs[str(s)] for s in targets]]
+    except (_UnknownIds, _BadNormals, _NnrInputError) as e:
         print("step16: %s" % e, file=sys.stderr)
         return 1
     except (IOError, OSError, ValueError, KeyError) as e:
@@ -80,14 +91,21 @@ def main(argv=None):
         return 1
     tm = {}
     t0 = time.perf_counter()
-    if a.chk_perf:
+    if nnr is not None:
+        try:
+            r = infill_daily(pool, a.var, targets, mean, vari, nnr, utc, device=a.device, timing=tm, chk_perf=a.chk_perf,
+                             cpt_sig=a.cpt_sig)
+        finally:
+            nnr.close()
+    elif a.chk_perf:
         r = infill_daily(pool, a.var, targets, mean, vari, device=a.device, timing=tm, chk_perf=True, cpt_sig=a.cpt_sig)
     else:
         r = infill_daily(pool, a.var, targets, mean, vari, device=a.device, timing=tm)
     sec = time.perf_counter() - t0
     np.savez_compressed(a.out, ids=r.target_ids, ymd=np.asarray(pool.days[YMD], np.int32), fnl_tair=r.fnl_tair,
                         mask_infill=r.mask_infill, infill_tair=r.infill_tair, mae=r.mae, bias=r.bias,
-                        **{k: getattr(r, k) for k in ITEM_COLUMNS + (CHK_COLUMNS if a.chk_perf else ())})
+                        **{k: getattr(r, k) for k in ITEM_COLUMNS + (CHK_COLUMNS if a.chk_perf else ()) +
+                           (("ncomp",) if nnr is not None else ())})
     line = {"var": a.var, "stations": int(r.target_ids.size), "pool": int(pool.ids.size), "days": int(pool.days.size),
             "items": int((r.status >= 0).sum()),
             "status": {PP_STATUS[k]: int((r.status == k).sum()) for k in sorted(PP_STATUS) if (r.status == k).any()},
