@@ -764,6 +764,117 @@ int twxnr_components(int device, int64_t ndays, int64_t ncol, const float *cols,
                      double *var_explain, double *eigval, double *loadings, int64_t *score_off, int64_t score_cap,
                      double *scores, float *kernel_ms, char *errbuf, int errlen);
 
+/* ---- step05 and step09 to step11, from the flagged database to the homogenised one: the observation counts of
+ * add_obs_cnt (twx/db/create_db_all_stations.py:1414-1416), the monthly means of add_monthly_means (:1312-1329 with
+ * TairAggregate.daily_to_mthly, twx/utils/util_tair.py:67-104), the time-of-observation shift of Tmax (_tobs_shift_tmax,
+ * twx/homog/tobs.py:243-264) and the daily homogenisation from PHA's monthly output (HomogDaily.homog_stn,
+ * twx/homog/pha.py:242-290).  PHA itself is an external program and is not part of this library.  A record is station-major,
+ * [nstn][ndays] float32 with NaN for "no value"; year-months are runs of consecutive days mth_first[g] .. mth_first[g] +
+ * mth_ndays[g] - 1 with 1 <= mth_ndays[g] <= 31 and mth_first[g + 1] = mth_first[g] + mth_ndays[g] (a record may start or
+ * end inside a month; days before the first or after the last month belong to none). ---- */
+#define TWXHM_MAX_MONTHS 16384          /* year-months of a record */
+#define TWXHM_MTHS_PER_GROUP 128        /* months one workgroup of k_hm_means stages in LDS: at most 3 968 days */
+#define TWXHM_DEFAULT_MAX_MISS 9        /* add_monthly_means' max_miss */
+#define TWXHM_PHA_MISSING (-9999)       /* PHA's missing monthly value */
+#define TWXHM_NTIMES 4                  /* entries of kernel_ms: two kernel figures, then two host-clock figures */
+/* LDS of k_hm_means (128 threads): 3 968 + 8 floats = 15 904 B (the stretch is read from the 16-byte boundary below its
+ * first day to the one above its last).  The other kernels use a few integers. */
+
+/* per-station status of twxhm_homog_daily */
+#define TWXHM_OK TWX_CELL_OK
+#define TWXHM_NO_ADJ 33                 /* a month needs the adjustment list and the station has none (the reference dies
+                                           on an IndexError there) */
+#define TWXHM_OVERLAP 34                /* a month lies in more than one adjustment interval (the reference raises) */
+
+/*
+ * cnt[s][m - 1] = the number of days d in first_day .. last_day (inclusive day indices) with day_month[d] == m and obs[s][d]
+ * finite.  obs is the raw variable with its fill value as NaN; quality flags are NOT applied (the reference counts ds[elem]).
+ * One workgroup of 256 per station; integer counts, joined by a shuffle tree and through LDS.
+ *
+ * obs [nstn][ndays]          float32
+ * day_month [ndays]          int8, 1 .. 12
+ * workspace_bytes            <= 0: TWXSC_WORKSPACE_BYTES; a batch is a run of stations whose rows (4 B a day) fit, at least one
+ * cnt [nstn][12]             out, int32
+ * counts (optional) [2]      out: kernel launches, batches
+ * kernel_ms (optional) [TWXHM_NTIMES]   device time of k_hm_cnt; 0; host-clock milliseconds of the allocations and copies
+ *                            in, and of the copies back (the same layout in every entry below)
+ * Call-level failures: nstn or ndays < 1, ndays > TWXSC_MAX_DAYS, a null buffer, a window outside the axis or empty, a
+ * day_month outside 1 .. 12.
+ */
+int twxhm_obs_cnt(int device, int64_t nstn, int64_t ndays, const float *obs, const int8_t *day_month, int64_t first_day,
+                  int64_t last_day, int64_t workspace_bytes, int32_t *cnt, int32_t *counts, float *kernel_ms, char *errbuf,
+                  int errlen);
+
+/*
+ * For every station s and month g: mth_miss = the number of non-finite days of the month; mth_mean = (float32)(sum / n),
+ * n the number of finite days and sum the fp64 sum IN DAY ORDER of the month's days with a non-finite day counted as +0.0
+ * and the first day's value (or +0.0) as the start -- numpy's masked sum over the day axis, to the sign of a zero.  NaN if
+ * n = 0, or max_miss >= 0 and mth_miss > max_miss.  obs holds NaN on flagged and on missing days.
+ * k_hm_means: a workgroup of 128 owns TWXHM_MTHS_PER_GROUP consecutive months of one station, loads their days into LDS
+ * with 16-byte loads from the aligned boundary below (the last, partial vector of a batch by scalar loads), then lane g adds
+ * month g's days from LDS in day order.  No atomics: two calls give the same bytes.
+ *
+ * nmth, mth_first, mth_ndays [nmth]   1 <= nmth <= TWXHM_MAX_MONTHS, as the block comment states
+ * max_miss                   negative: no threshold
+ * workspace_bytes            as above
+ * mth_mean [nstn][nmth], mth_miss [nstn][nmth]   out, float32 and int16
+ * Call-level failures: as above, and a month list that is empty, too long, not consecutive or outside the axis.
+ */
+int twxhm_monthly_means(int device, int64_t nstn, int64_t ndays, const float *obs, int32_t nmth, const int32_t *mth_first,
+                        const int32_t *mth_ndays, int32_t max_miss, int64_t workspace_bytes, float *mth_mean,
+                        int16_t *mth_miss, int32_t *counts, float *kernel_ms, char *errbuf, int errlen);
+
+/*
+ * Per station, am[d] = tobs[d] > 0 && tobs[d] < 1100 (a morning observation; NaN is none), ok[d] = !am[d] &&
+ * finite(tmax[d]), S = {d > 0 : am[d] && !ok[d - 1]}, nshift = |S|.
+ *   |S| > 1    out[d] = tmax[d + 1] if d + 1 is in S; else tmax[d] if ok[d]; else NaN (0x7fc00000).  d + 1 in S implies
+ *              !ok[d], so the cases do not collide.
+ *   |S| <= 1   out = tmax, bit for bit.  THE REFERENCE'S QUIRK, KEPT: it tests idx_shift.size > 1, so a station with
+ *              exactly one morning observation to shift keeps it on its day, and keeps its other morning values too.
+ * One workgroup of 256 per station: the count (integers, any tree), then the element-wise pass.
+ *
+ * tmax, tobs [nstn][ndays]   float32, NaN = none
+ * workspace_bytes            as above; 12 B a day
+ * out [nstn][ndays], nshift [nstn]   out, float32 and int32
+ * Call-level failures: nstn or ndays < 1, ndays > TWXSC_MAX_DAYS, a null buffer.
+ */
+int twxhm_tobs_shift(int device, int64_t nstn, int64_t ndays, const float *tmax, const float *tobs, int64_t workspace_bytes,
+                     float *out, int32_t *nshift, int32_t *counts, float *kernel_ms, char *errbuf, int errlen);
+
+/*
+ * HomogDaily.homog_stn for every station.  Per station s and month g, with round2(x) = rint(x * 100) / 100 in fp64 (numpy's
+ * round(x, 2)):
+ *   m = round2((double)mth_mean), masked if mth_mean is NaN;  h = round2((double)pha / 100), masked if pha ==
+ *   TWXHM_PHA_MISSING.
+ *   both present       m != h: delta = h - m, and the month counts in nchanged (the reference's dif_cnt); m == h: untouched.
+ *   h present, m masked, mth_miss < mth_ndays   with the station's adjustments a = adj_off[s] .. adj_off[s + 1] - 1, sorted
+ *                      by adj_ymd_start: none: TWXHM_NO_ADJ; mth_ymd[g] < adj_ymd_start[first]: delta = -adj[first]; else
+ *                      by the number of intervals with adj_ymd_start <= mth_ymd[g] <= adj_ymd_end (inclusive): 0: delta =
+ *                      +0.0, WHICH IS ADDED (-0.0 + 0.0 changes a bit; the reference adds it); 1: delta = -adj of it; more:
+ *                      TWXHM_OVERLAP.  Then delta = round2(delta).
+ *   otherwise          untouched.
+ * delta[s][g] is NaN for an untouched month.  out[s][d] = (float)((double)obs[s][d] + delta[s][g]) on the days of a touched
+ * month, obs[s][d] bit for bit elsewhere.  A station whose status is not TWXHM_OK has its delta and out rows NaN and
+ * nchanged 0; its neighbours are unaffected.
+ * k_hm_delta: one workgroup of 256 per station, a thread per month, the status and the count joined as integers.
+ * k_hm_apply: the batch's rows as one flat array, 16-byte loads and stores of four days a thread (the buffers are aligned,
+ * so every vector is; a row boundary may fall inside one) and a scalar tail of the batch; plain vector stores.
+ *
+ * obs [nstn][ndays]          float32
+ * mth_mean, mth_miss, pha [nstn][nmth]   float32, int16, int32 hundredths
+ * mth_ymd [nmth]             yyyymmdd of a month's first day
+ * adj_off [nstn + 1], adj_ymd_start, adj_ymd_end, adj   CSR of the adjustment list, int64, int32, int32, float64
+ * workspace_bytes            as above; 8 B a day
+ * delta [nstn][nmth], out [nstn][ndays], status [nstn], nchanged [nstn]   out, float64, float32, int32, int32
+ * kernel_ms                  device time of k_hm_delta, of k_hm_apply over all batches, then the host-clock figures
+ * Call-level failures, all before any launch: the above, adj_off not ascending from 0, a station's adj_ymd_start not sorted.
+ */
+int twxhm_homog_daily(int device, int64_t nstn, int64_t ndays, const float *obs, int32_t nmth, const float *mth_mean,
+                      const int16_t *mth_miss, const int32_t *pha, const int32_t *mth_ymd, const int32_t *mth_first,
+                      const int32_t *mth_ndays, const int64_t *adj_off, const int32_t *adj_ymd_start,
+                      const int32_t *adj_ymd_end, const double *adj, int64_t workspace_bytes, double *delta, float *out,
+                      int32_t *status, int32_t *nchanged, int32_t *counts, float *kernel_ms, char *errbuf, int errlen);
+
 #ifdef __cplusplus
 }
 #endif

@@ -932,3 +932,180 @@ def nnr_components_batched(cols, set_off, set_col, group, max_var=(0.99,), ngrou
             timing[key] = timing.get(key, 0.0) + float(ms[k])
         timing["nr_calls"] = timing.get("nr_calls", 0) + 1
     return NrComponents(set_off, nrows, max_var, out)
+
+
+# ---- step05 / step09-11, counts, monthly means, TOB shift, daily homogenisation (twxhm_*; TWXHM_* of include/twx_qa.h) ----
+HM_EXPORTS = ("twxhm_obs_cnt", "twxhm_monthly_means", "twxhm_tobs_shift", "twxhm_homog_daily")
+HM_OK, HM_NO_ADJ, HM_OVERLAP = 0, 33, 34
+HM_MAX_MONTHS = 16384     # TWXHM_MAX_MONTHS
+HM_MAX_MISS = 9           # TWXHM_DEFAULT_MAX_MISS
+HM_PHA_MISSING = -9999    # TWXHM_PHA_MISSING
+HM_KERNELS = ("hm_cnt", "hm_means", "hm_tobs", "hm_delta", "hm_apply")
+_HM_TAIL = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]       # counts, kernel_ms, errbuf, errlen
+
+
+def month_groups(year, month):
+    """(mth_first, mth_ndays, mth_ymd) [nmth] int32 of the ``twxhm_*`` entries for the day axis ``year`` / ``month``
+    [ndays]: one entry per year-month present on the axis, ``mth_ymd`` = yyyymm01.  Raises ``ValueError`` for an axis that
+    skips a month or runs backwards."""
+    year, month = np.asarray(year, np.int64), np.asarray(month, np.int64)
+    if year.ndim != 1 or month.shape != year.shape or year.size < 1:
+        raise ValueError("year / month must be [ndays >= 1]")
+    ym = year * 12 + month - 1
+    if month.min() < 1 or month.max() > 12 or ((np.diff(ym) != 0) & (np.diff(ym) != 1)).any():
+        raise ValueError("the day axis must be ascending and gap-free (no skipped month or year)")
+    u, first, cnt = np.unique(ym, return_index=True, return_counts=True)
+    return first.astype(np.int32), cnt.astype(np.int32), ((u // 12) * 10000 + (u % 12 + 1) * 100 + 1).astype(np.int32)
+
+
+def _hm_rows(name, a, shape=None):
+    a = _c(a, np.float32)
+    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("%s must be [nstn >= 1, ndays >= 1]" % name)
+    if shape is not None and a.shape != shape:
+        raise ValueError("%s must be %s like the record" % (name, list(shape)))
+    return a
+
+
+def _hm_months(ndays, mth_first, mth_ndays):
+    mth_first, mth_ndays = _c(mth_first, np.int32), _c(mth_ndays, np.int32)
+    if mth_first.ndim != 1 or mth_first.size < 1 or mth_ndays.shape != mth_first.shape:
+        raise ValueError("mth_first / mth_ndays must be [nmth >= 1]")
+    if mth_first.size > HM_MAX_MONTHS:
+        raise ValueError("at most %d months" % HM_MAX_MONTHS)
+    f, n = mth_first.astype(np.int64), mth_ndays.astype(np.int64)
+    if (f < 0).any() or (n < 1).any() or (n > 31).any() or (f + n > ndays).any():
+        raise ValueError("a month lies outside the day axis (mth_first) or has not 1 .. 31 days")
+    if (f[1:] != f[:-1] + n[:-1]).any():
+        raise ValueError("the months must be consecutive runs of days")
+    return mth_first, mth_ndays
+
+
+def _hm_call(fn, name, args, timing, kernels):
+    counts = (C.c_int32 * 2)()
+    ms = (C.c_float * 4)()
+    buf = C.create_string_buffer(512)
+    rc = fn(*(list(args) + [C.addressof(counts), C.addressof(ms), buf, 512]))
+    if rc != 0:
+        raise QaError("%s failed: %s" % (name, buf.value.decode(errors="replace")))
+    if timing is not None:
+        for k, kn in enumerate(kernels):
+            key = kn + "_kernel_ms"
+            timing[key] = timing.get(key, 0.0) + float(ms[k])
+        for k, key in ((2, "hm_upload_ms"), (3, "hm_download_ms")):
+            timing[key] = timing.get(key, 0.0) + float(ms[k])
+        timing["hm_batches"] = timing.get("hm_batches", 0) + int(counts[1])
+        timing["hm_calls"] = timing.get("hm_calls", 0) + 1
+    return int(counts[1])
+
+
+def obs_cnt(obs, day_month, first_day, last_day, workspace_bytes=0, device=0, timing=None):
+    """``twxhm_obs_cnt``: [nstn, 12] int32 counts of the finite days of ``obs`` [nstn, ndays] per calendar month
+    (``day_month`` [ndays], 1 .. 12) inside the inclusive day-index window.  Quality flags are not applied."""
+    obs = _hm_rows("obs", obs)
+    ns, nd = obs.shape
+    day_month = _c(day_month, np.int8)
+    if day_month.shape != (nd,):
+        raise ValueError("day_month must be [ndays]")
+    if day_month.min() < 1 or day_month.max() > 12:
+        raise ValueError("day_month must hold 1 .. 12")
+    first_day, last_day = int(first_day), int(last_day)
+    if not 0 <= first_day <= last_day < nd:
+        raise ValueError("need 0 <= first_day <= last_day < ndays")
+    L = load()
+    if not hasattr(L.twxhm_obs_cnt, "_twx_ready"):
+        L.twxhm_obs_cnt.restype = C.c_int
+        L.twxhm_obs_cnt.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int64] * 3 + \
+            [C.c_void_p] + _HM_TAIL
+        L.twxhm_obs_cnt._twx_ready = True
+    cnt = np.empty((ns, 12), np.int32)
+    _hm_call(L.twxhm_obs_cnt, "twxhm_obs_cnt", (int(device), ns, nd, obs.ctypes.data, day_month.ctypes.data, first_day,
+                                                last_day, int(workspace_bytes), cnt.ctypes.data), timing, HM_KERNELS[0:1])
+    return cnt
+
+
+def monthly_means(obs, mth_first, mth_ndays, max_miss=HM_MAX_MISS, workspace_bytes=0, device=0, timing=None):
+    """``twxhm_monthly_means``: (mth_mean [nstn, nmth] float32 with NaN where masked, mth_miss [nstn, nmth] int16) of
+    ``obs`` [nstn, ndays] (NaN on flagged and missing days); ``max_miss`` None or negative: no threshold."""
+    obs = _hm_rows("obs", obs)
+    ns, nd = obs.shape
+    mth_first, mth_ndays = _hm_months(nd, mth_first, mth_ndays)
+    nm = mth_first.size
+    L = load()
+    if not hasattr(L.twxhm_monthly_means, "_twx_ready"):
+        L.twxhm_monthly_means.restype = C.c_int
+        L.twxhm_monthly_means.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_int32, C.c_int64, C.c_void_p, C.c_void_p] + _HM_TAIL
+        L.twxhm_monthly_means._twx_ready = True
+    mean, miss = np.empty((ns, nm), np.float32), np.empty((ns, nm), np.int16)
+    _hm_call(L.twxhm_monthly_means, "twxhm_monthly_means",
+             (int(device), ns, nd, obs.ctypes.data, nm, mth_first.ctypes.data, mth_ndays.ctypes.data,
+              -1 if max_miss is None else int(max_miss), int(workspace_bytes), mean.ctypes.data, miss.ctypes.data),
+             timing, HM_KERNELS[1:2])
+    return mean, miss
+
+
+def tobs_shift(tmax, tobs, workspace_bytes=0, device=0, timing=None):
+    """``twxhm_tobs_shift``: (out [nstn, ndays] float32, nshift [nstn] int32), ``_tobs_shift_tmax`` of every station."""
+    tmax = _hm_rows("tmax", tmax)
+    tobs = _hm_rows("tobs", tobs, tmax.shape)
+    ns, nd = tmax.shape
+    L = load()
+    if not hasattr(L.twxhm_tobs_shift, "_twx_ready"):
+        L.twxhm_tobs_shift.restype = C.c_int
+        L.twxhm_tobs_shift.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                       C.c_void_p] + _HM_TAIL
+        L.twxhm_tobs_shift._twx_ready = True
+    out, nshift = np.empty((ns, nd), np.float32), np.empty(ns, np.int32)
+    _hm_call(L.twxhm_tobs_shift, "twxhm_tobs_shift", (int(device), ns, nd, tmax.ctypes.data, tobs.ctypes.data,
+                                                      int(workspace_bytes), out.ctypes.data, nshift.ctypes.data),
+             timing, HM_KERNELS[2:3])
+    return out, nshift
+
+
+def homog_daily(obs, mth_mean, mth_miss, pha, mth_ymd, mth_first, mth_ndays, adj_off, adj_ymd_start, adj_ymd_end, adj,
+                workspace_bytes=0, device=0, timing=None):
+    """``twxhm_homog_daily``: ``HomogDaily.homog_stn`` of every station.  Returns a dict of ``delta`` [nstn, nmth] float64
+    (NaN: month untouched), ``out`` [nstn, ndays] float32, ``status`` (``HM_*``) and ``nchanged`` [nstn] int32.  The
+    adjustment list is CSR (``adj_off`` [nstn + 1]), each station's entries sorted by ``adj_ymd_start``; an unsorted list,
+    a month outside the day axis or a wrong shape raises ``ValueError`` before any launch."""
+    obs = _hm_rows("obs", obs)
+    ns, nd = obs.shape
+    mth_first, mth_ndays = _hm_months(nd, mth_first, mth_ndays)
+    nm = mth_first.size
+    mth_mean, mth_miss, pha = _c(mth_mean, np.float32), _c(mth_miss, np.int16), _c(pha, np.int32)
+    for name, a in (("mth_mean", mth_mean), ("mth_miss", mth_miss), ("pha", pha)):
+        if a.shape != (ns, nm):
+            raise ValueError("%s must be [nstn, nmth]" % name)
+    mth_ymd = _c(mth_ymd, np.int32)
+    if mth_ymd.shape != (nm,):
+        raise ValueError("mth_ymd must be [nmth]")
+    adj_off = _c(adj_off, np.int64)
+    if adj_off.shape != (ns + 1,) or adj_off[0] != 0 or (np.diff(adj_off) < 0).any():
+        raise ValueError("adj_off must be [nstn + 1], ascending from 0")
+    na = int(adj_off[-1])
+    adj_ymd_start, adj_ymd_end, adj = _c(adj_ymd_start, np.int32), _c(adj_ymd_end, np.int32), _c(adj, np.float64)
+    for name, a in (("adj_ymd_start", adj_ymd_start), ("adj_ymd_end", adj_ymd_end), ("adj", adj)):
+        if a.shape != (na,):
+            raise ValueError("%s must be [adj_off[-1]]" % name)
+    if na > 1:
+        inner = np.ones(na, bool)
+        inner[adj_off[:-1][adj_off[:-1] < na]] = False           # the first entry of a station has no predecessor
+        if (inner[1:] & (np.diff(adj_ymd_start) < 0)).any():
+            raise ValueError("a station's adjustments must be sorted by adj_ymd_start")
+    L = load()
+    if not hasattr(L.twxhm_homog_daily, "_twx_ready"):
+        L.twxhm_homog_daily.restype = C.c_int
+        L.twxhm_homog_daily.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int32] + [C.c_void_p] * 10 + \
+            [C.c_int64] + [C.c_void_p] * 4 + _HM_TAIL
+        L.twxhm_homog_daily._twx_ready = True
+    out = dict(delta=np.empty((ns, nm)), out=np.empty((ns, nd), np.float32), status=np.empty(ns, np.int32),
+               nchanged=np.empty(ns, np.int32))
+    out["batches"] = _hm_call(
+        L.twxhm_homog_daily, "twxhm_homog_daily",
+        (int(device), ns, nd, obs.ctypes.data, nm, mth_mean.ctypes.data, mth_miss.ctypes.data, pha.ctypes.data,
+         mth_ymd.ctypes.data, mth_first.ctypes.data, mth_ndays.ctypes.data, adj_off.ctypes.data,
+         adj_ymd_start.ctypes.data if na else None, adj_ymd_end.ctypes.data if na else None, adj.ctypes.data if na else None,
+         int(workspace_bytes), out["delta"].ctypes.data, out["out"].ctypes.data, out["status"].ctypes.data,
+         out["nchanged"].ctypes.data), timing, HM_KERNELS[3:5])
+    return out
