@@ -875,6 +875,120 @@ int twxhm_homog_daily(int device, int64_t nstn, int64_t ndays, const float *obs,
                       const int32_t *adj_ymd_end, const double *adj, int64_t workspace_bytes, double *delta, float *out,
                       int32_t *status, int32_t *nchanged, int32_t *counts, float *kernel_ms, char *errbuf, int errlen);
 
+/* ---- step19 and the front of step20: raster values at the stations of a serially-complete database
+ * (add_stn_raster_values with _find_nn_data, twx/infill/post_infill.py:248-352 and :443-510), the duplicate stations of
+ * find_dup_stns (:193-246) and the column counts that find_dup_stns and step20's final check
+ * (scripts/step20_add_bad_stn_flag.py:102-112) take from the file.  A raster is [rows][cols], north-up, float32 or float64
+ * (an integer raster is converted by the caller to whichever holds it exactly), with GDAL's geo_t = (left edge, cell width
+ * > 0, 0, top edge, 0, cell height < 0) in the stations' own geographic coordinates: the reference's osr transformation is
+ * an identity that is required here and not performed, and a rotated raster is refused.  At least 2 x 2:
+ * mpl_toolkits.basemap.interp, which the sampling restates as k_sample does, needs two cell centres on each axis.  The
+ * BAND's no-data value is what read_as_array masks; ndata (a_rast.ndata) is what is written for "no value" and what
+ * _find_nn_data compares with.  The two are separate inputs: step19 reassigns ndata on the mask raster. ---- */
+#define TWXRV_F32 0                     /* dtype of a raster */
+#define TWXRV_F64 1
+#define TWXRV_MAX_EXTENT 134217727      /* rows and columns of a raster: the 8 r + 2 slots of the last ring fit an int32 */
+#define TWXRV_MAX_DUP_STNS 1048576      /* stations of twxrv_dup_classes (all pairs) */
+#define TWXRV_COUNT_I8_SUM 0            /* kind of twxrv_col_count */
+#define TWXRV_COUNT_F32_MISSING 1
+#define TWXRV_NTIMES 3                  /* entries of kernel_ms: the kernel; host-clock milliseconds of the allocations and
+                                           copies in, and of the copies back */
+#define TWXRV_TIE_REL 1e-9              /* the caller decides a ring again on the host when the runner-up lies this close */
+/* LDS: k_rv_dup 4 096 B (the keys of a tile of 256 stations), k_rv_colcount 1 024 B; the others none. */
+
+/* per-station status of twxrv_sample and twxrv_nearest_data */
+#define TWXRV_OK TWX_CELL_OK            /* twxrv_sample: the value of extract_method; twxrv_nearest_data: a data cell found */
+#define TWXRV_NEAREST 35                /* the value of the clipped nearest cell (the checkbounds=False, order=0 call) */
+#define TWXRV_NODATA 36                 /* no value and force_data_value is off: value = ndata */
+#define TWXRV_NEEDS_FORCE 37            /* no value and force_data_value is on: the station goes to twxrv_nearest_data */
+#define TWXRV_NO_DATA_ANYWHERE 38       /* twxrv_nearest_data: no ring up to max(rows, cols) holds a data cell the
+                                           reference's tests admit (the reference loops forever) */
+
+/*
+ * Per station, in the reference's order, with x0, x1 (ylo, yhi) the centres of the first and last columns (rows) as
+ * get_coord_grid_1d gives them, xc = clip((cols - 1) (lon - x0) / (x1 - x0), 0, cols - 1) and yc likewise from the south:
+ *   1. if x0 <= lon <= x1 and ylo <= lat <= yhi (checkbounds=True; outside, interp raises and the value is missing):
+ *      extract_method 1: the bilinear value of the cells (yi, xi), (yi + 1, xi + 1), (yi + 1, xi), (yi, xi + 1), upper
+ *      indices clipped, xi = int(xc), weights from xc - float32(xi) as interp computes them; missing if any of the four
+ *      cells equals the band's no-data value.  extract_method 0: the cell (around(yc), around(xc)), half to even.
+ *   2. if missing and ((is_inbounds(lon, lat), outer edges, and (extract_method 0 or revert_nn)) or force_data_value): the
+ *      cell (around(yc), around(xc)) of the clipped coordinates; status TWXRV_NEAREST if it has a value.
+ *   3. if still missing: TWXRV_NEEDS_FORCE with force_data_value, else TWXRV_NODATA; value = ndata.
+ * row, col: get_row_col(lon, lat, check_bounds=False) = clip(abs(int((lat - geo_t[3]) / geo_t[5])), 0, rows - 1) and the
+ * same of the columns: a station west or north of the raster is mirrored into it by the abs() -- the reference's quirk,
+ * kept, because _find_nn_data starts there.
+ *
+ * data [rows][cols]          float32 (TWXRV_F32) or float64 (TWXRV_F64)
+ * geo_t [6]
+ * has_band_ndata, band_ndata the band's no-data value, if it has one
+ * lon, lat [nstn]            finite
+ * value [nstn], status [nstn], row [nstn], col [nstn]   out: float64, int32 (TWXRV_*), int32, int32
+ * kernel_ms (optional) [TWXRV_NTIMES]
+ * Call-level failures, all before any device work: a raster below 2 x 2 or above TWXRV_MAX_EXTENT, a geo_t that is
+ * non-finite, rotated or not north-up, an unknown dtype or extract_method, nstn < 1, a null buffer, a non-finite coordinate.
+ */
+int twxrv_sample(int device, int64_t rows, int64_t cols, int32_t dtype, const void *data, const double *geo_t,
+                 int32_t has_band_ndata, double band_ndata, double ndata, int64_t nstn, const double *lon, const double *lat,
+                 int32_t extract_method, int32_t revert_nn, int32_t force_data_value, double *value, int32_t *status,
+                 int32_t *row, int32_t *col, float *kernel_ms, char *errbuf, int errlen);
+
+/*
+ * _find_nn_data for every point (row, col): rings r = 1, 2, ... of 8 r + 2 slots in the reference's order -- slots 0 ..
+ * 2 r the top row y - r from column x - r to x + r; 2 r + 1 .. 4 r + 1 the left column x - r from row y - r to y + r;
+ * 4 r + 2 .. 6 r + 1 the bottom row y + r from column x + r down to x - r + 1; 6 r + 2 .. 8 r + 1 the right column x + r
+ * from row y + r down to y - r + 1.  A slot is a candidate if 0 < row < rows and 0 < col < cols (THE REFERENCE'S STRICT
+ * > 0, KEPT: row 0 and column 0 never are) and its cell != ndata.  The search stops at the FIRST ring with a candidate
+ * (kept too: the answer is the nearest cell of that ring, not of the raster).  dist = grt_circle_dist between the centres
+ * (get_coord) of the starting cell and of the candidate in fp64; the winner is the candidate of least (dist, slot): an
+ * exact tie goes to the earlier slot, which the reference's argsort does not define.  runner_up = the least dist of the
+ * ring's candidates in ANOTHER cell than the winner's (+Inf if none): the device's sin / cos / asin are not numpy's, so the
+ * caller decides a point again with numpy's when runner_up - dist <= TWXRV_TIE_REL x runner_up.
+ * k_rv_ring: one wavefront per point.
+ *
+ * row, col [npts]            the start: 0 <= row < rows, 0 <= col < cols
+ * value, dist, runner_up [npts]   out, float64 (kilometres)
+ * ring, winner, status [npts]     out, int32: r, the winner's slot, TWXRV_OK or TWXRV_NO_DATA_ANYWHERE (value = ndata,
+ *                            dist = runner_up = +Inf, ring 0, winner -1)
+ * Call-level failures: as twxrv_sample's of the raster, npts < 1, a null buffer, a start outside the raster.
+ */
+int twxrv_nearest_data(int device, int64_t rows, int64_t cols, int32_t dtype, const void *data, const double *geo_t,
+                       double ndata, int64_t npts, const int32_t *row, const int32_t *col, double *value, double *dist,
+                       int32_t *ring, int32_t *winner, double *runner_up, int32_t *status, float *kernel_ms, char *errbuf,
+                       int errlen);
+
+/*
+ * The location classes of find_dup_stns.  grt_circle_dist(a, b) == 0 exactly when lat_a F == lat_b F and lon_a F == lon_b F
+ * in fp64, F = 0.017453292519943295: the squares and the sum of non-negative terms cannot cancel and the asin of a
+ * non-zero argument is non-zero (coordinates within 1e-150 of each other AND of 0, where the square underflows, excepted).
+ * Raw coordinates one ulp apart can have equal products, so the products are what is compared: one multiplication, no
+ * transcendental, bit-exact under -ffp-contract=off.  cls[i] = the smallest j whose key equals i's, size[i] = the number of
+ * such j.  A NaN coordinate equals nothing: cls[i] = i, size[i] = 1.
+ * k_rv_dup: all pairs, the keys of 256 stations a tile through LDS.
+ *
+ * lon, lat [nstn]            1 <= nstn <= TWXRV_MAX_DUP_STNS
+ * cls [nstn], size [nstn]    out, int32
+ */
+int twxrv_dup_classes(int device, int64_t nstn, const double *lon, const double *lat, int32_t *cls, int32_t *size,
+                      float *kernel_ms, char *errbuf, int errlen);
+
+/*
+ * Column counts of a variable in the file's own layout, [ndays][nstn] with the station fastest (no transpose is taken).
+ *   TWXRV_COUNT_I8_SUM        data int8 (flag_infilled): out[i] = the sum over the days of column cols[i] that do not equal
+ *                             fill (netCDF4 masks them and numpy's sum skips a masked day); a NaN fill: every day counts
+ *   TWXRV_COUNT_F32_MISSING   data float32: out[i] = the number of days of column cols[i] that are non-finite or equal fill
+ * cols may repeat and need not be sorted; null with ncol = nstn: every column in order.  ncol = 0 returns at once.
+ * Integer results: exact in any order, two calls give the same bytes whatever workspace_bytes.
+ *
+ * workspace_bytes            <= 0: TWXSC_WORKSPACE_BYTES; a batch is a run of days whose rows fit, at least one
+ * out [ncol]                 int32
+ * counts (optional) [2]      out: kernel launches, batches
+ * Call-level failures: ndays < 1 or > TWXSC_MAX_DAYS, nstn < 1, an unknown kind, an int8 fill that is neither NaN nor an
+ * integer in -128 .. 127, ncol < 0, no list and ncol != nstn, a null buffer, a column outside 0 .. nstn - 1.
+ */
+int twxrv_col_count(int device, int64_t ndays, int64_t nstn, int32_t kind, const void *data, float fill, int64_t ncol,
+                    const int32_t *cols, int64_t workspace_bytes, int32_t *out, int32_t *counts, float *kernel_ms,
+                    char *errbuf, int errlen);
+
 #ifdef __cplusplus
 }
 #endif

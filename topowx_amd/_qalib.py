@@ -1109,3 +1109,213 @@ def homog_daily(obs, mth_mean, mth_miss, pha, mth_ymd, mth_first, mth_ndays, adj
          int(workspace_bytes), out["delta"].ctypes.data, out["out"].ctypes.data, out["status"].ctypes.data,
          out["nchanged"].ctypes.data), timing, HM_KERNELS[3:5])
     return out
+
+
+# ---- step19 and the front of step20: raster values at stations, duplicate stations, column counts (twxrv_*; TWXRV_* of
+# include/twx_qa.h) ----
+RV_EXPORTS = ("twxrv_sample", "twxrv_nearest_data", "twxrv_dup_classes", "twxrv_col_count")
+RV_OK, RV_NEAREST, RV_NODATA, RV_NEEDS_FORCE, RV_NO_DATA_ANYWHERE = 0, 35, 36, 37, 38
+RV_F32, RV_F64 = 0, 1                 # TWXRV_F32, TWXRV_F64
+RV_MAX_EXTENT = 134217727             # TWXRV_MAX_EXTENT
+RV_MAX_DUP_STNS = 1048576             # TWXRV_MAX_DUP_STNS
+RV_COUNT_I8_SUM, RV_COUNT_F32_MISSING = 0, 1
+RV_NTIMES = 3                         # TWXRV_NTIMES
+RV_TIE_REL = 1e-9                     # TWXRV_TIE_REL
+RV_KERNELS = ("rv_sample", "rv_ring", "rv_dup", "rv_colcount")
+RV_RADIAN = 0.017453292519943295      # RADIAN_CONVERSION_FACTOR (twx/utils/util_geo.py:21)
+RV_EARTH_KM = 6371.009                # AVG_EARTH_RADIUS_KM
+
+
+def _rv_raster(data, geo_t):
+    """The raster as the ``twxrv_*`` entries take it: (array float32 or float64, dtype code, geo_t [6] float64).  An integer
+    raster becomes float32 if every value survives the round trip, float64 otherwise (exact up to 2^53)."""
+    data = np.asarray(data)
+    if data.ndim != 2 or data.shape[0] < 2 or data.shape[1] < 2:
+        raise ValueError("the raster must be [rows >= 2, cols >= 2]")
+    if data.dtype == np.float32 or data.dtype == np.float64:
+        a = np.ascontiguousarray(data)
+    elif data.dtype.kind in "iub":
+        a = np.ascontiguousarray(data, np.float32)
+        if data.dtype.itemsize > 2 and not np.array_equal(a.astype(data.dtype), data):
+            a = np.ascontiguousarray(data, np.float64)
+    else:
+        a = np.ascontiguousarray(data, np.float64)
+    geo_t = _c(geo_t, np.float64)
+    if geo_t.shape != (6,) or not np.isfinite(geo_t).all():
+        raise ValueError("geo_t must be 6 finite numbers")
+    if geo_t[2] != 0.0 or geo_t[4] != 0.0:
+        raise ValueError("a rotated raster is refused (geo_t[2] and geo_t[4] must be 0)")
+    if not (geo_t[1] > 0.0 and geo_t[5] < 0.0):
+        raise ValueError("the raster must be north-up (geo_t[1] > 0, geo_t[5] < 0)")
+    return a, (RV_F32 if a.dtype == np.float32 else RV_F64), geo_t
+
+
+def _rv_call(fn, name, args, timing, kernel, tail=()):
+    ms = (C.c_float * RV_NTIMES)()
+    buf = C.create_string_buffer(512)
+    rc = fn(*(list(args) + list(tail) + [C.addressof(ms), buf, 512]))
+    if rc != 0:
+        raise QaError("%s failed: %s" % (name, buf.value.decode(errors="replace")))
+    if timing is not None:
+        for key, v in ((kernel + "_kernel_ms", ms[0]), ("rv_upload_ms", ms[1]), ("rv_download_ms", ms[2])):
+            timing[key] = timing.get(key, 0.0) + float(v)
+        timing["rv_calls"] = timing.get("rv_calls", 0) + 1
+
+
+def raster_sample(data, geo_t, ndata, lon, lat, band_ndata=None, extract_method=1, revert_nn=False, force_data_value=False,
+                  device=0, timing=None):
+    """``twxrv_sample``: the decision of ``add_stn_raster_values`` (post_infill.py:305-339) up to the ring search, for all
+    stations in one call.  Returns a dict of ``value`` [nstn] float64, ``status`` (``RV_OK`` the value of the method,
+    ``RV_NEAREST`` the clipped nearest cell, ``RV_NODATA`` with ``value = ndata``, ``RV_NEEDS_FORCE``), ``row`` and ``col``
+    [nstn] int32 (``get_row_col(check_bounds=False)``).  ``band_ndata`` None: the band masks nothing."""
+    a, code, geo_t = _rv_raster(data, geo_t)
+    lon, lat = _c(lon, np.float64), _c(lat, np.float64)
+    if lon.ndim != 1 or lon.size < 1 or lat.shape != lon.shape:
+        raise ValueError("lon / lat must be [nstn >= 1]")
+    if not (np.isfinite(lon).all() and np.isfinite(lat).all()):
+        raise ValueError("a station has a non-finite coordinate")
+    if extract_method not in (0, 1):
+        raise ValueError("extract_method must be 0 (nearest) or 1 (bilinear); 3 (cubic spline) is not supported")
+    n = lon.size
+    L = load()
+    if not hasattr(L.twxrv_sample, "_twx_ready"):
+        L.twxrv_sample.restype = C.c_int
+        L.twxrv_sample.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_double,
+                                   C.c_double, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + \
+            [C.c_void_p] * 5 + [C.c_char_p, C.c_int]
+        L.twxrv_sample._twx_ready = True
+    out = dict(value=np.empty(n), status=np.empty(n, np.int32), row=np.empty(n, np.int32), col=np.empty(n, np.int32))
+    _rv_call(L.twxrv_sample, "twxrv_sample",
+             (int(device), a.shape[0], a.shape[1], code, a.ctypes.data, geo_t.ctypes.data, 0 if band_ndata is None else 1,
+              0.0 if band_ndata is None else float(band_ndata), float(ndata), n, lon.ctypes.data, lat.ctypes.data,
+              int(extract_method), 1 if revert_nn else 0, 1 if force_data_value else 0, out["value"].ctypes.data,
+              out["status"].ctypes.data, out["row"].ctypes.data, out["col"].ctypes.data), timing, RV_KERNELS[0])
+    return out
+
+
+def grt_circle_dist(lon1, lat1, lon2, lat2):
+    """``grt_circle_dist`` (twx/utils/util_geo.py:24-40) in numpy, operation for operation."""
+    lat1rad, lat2rad = lat1 * RV_RADIAN, lat2 * RV_RADIAN
+    lon1rad, lon2rad = lon1 * RV_RADIAN, lon2 * RV_RADIAN
+    dlat, dlon = lat1rad - lat2rad, lon1rad - lon2rad
+    ca = 2 * np.arcsin(np.sqrt(np.square(np.sin(dlat / 2)) + np.cos(lat1rad) * np.cos(lat2rad) * np.square(np.sin(dlon / 2))))
+    return RV_EARTH_KM * ca
+
+
+def ring_cells(rows, cols, y, x, r):
+    """The slots of ring ``r`` around (``y``, ``x``) that ``_find_nn_data``'s tests admit, in its order: (slot, row, col)
+    int64 arrays.  Slots are numbered over the whole ring, 0 .. 8 r + 1, as ``twxrv_nearest_data`` numbers them."""
+    lcol, rcol, trow, brow = x - r, x + r, y - r, y + r
+    rr = np.concatenate([np.full(2 * r + 1, trow), np.arange(trow, brow + 1), np.full(2 * r, brow), np.arange(brow, trow, -1)])
+    cc = np.concatenate([np.arange(lcol, rcol + 1), np.full(2 * r + 1, lcol), np.arange(rcol, lcol, -1), np.full(2 * r, rcol)])
+    ok = (rr > 0) & (rr < rows) & (cc > 0) & (cc < cols)
+    return np.nonzero(ok)[0], rr[ok].astype(np.int64), cc[ok].astype(np.int64)
+
+
+def _rv_ring_host(a, geo_t, ndata, y, x, r):
+    """Ring ``r`` decided with numpy's transcendentals: (value, dist, slot) -- the tie guard of ``raster_nearest_data``."""
+    slot, rr, cc = ring_cells(a.shape[0], a.shape[1], y, x, r)
+    keep = a[rr, cc].astype(np.float64) != ndata
+    slot, rr, cc = slot[keep], rr[keep], cc[keep]
+    lons = (geo_t[0] + cc * geo_t[1] + rr * geo_t[2]) + geo_t[1] / 2.0
+    lats = (geo_t[3] + cc * geo_t[4] + rr * geo_t[5]) + geo_t[5] / 2.0
+    pt_lon = (geo_t[0] + x * geo_t[1] + y * geo_t[2]) + geo_t[1] / 2.0
+    pt_lat = (geo_t[3] + x * geo_t[4] + y * geo_t[5]) + geo_t[5] / 2.0
+    d = grt_circle_dist(pt_lon, pt_lat, lons, lats)
+    j = int(np.argsort(d, kind="stable")[0])                      # an exact tie: the earlier slot
+    return float(a[rr[j], cc[j]]), float(d[j]), int(slot[j])
+
+
+def raster_nearest_data(data, geo_t, ndata, row, col, device=0, timing=None):
+    """``twxrv_nearest_data``: ``_find_nn_data`` (post_infill.py:443-510) for every start (``row``, ``col``).  Returns a dict
+    of ``value``, ``dist``, ``runner_up`` [npts] float64, ``ring``, ``winner`` (the slot in the ring), ``status`` [npts] int32
+    (``RV_OK`` / ``RV_NO_DATA_ANYWHERE``) and ``redecided``: the number of points whose winner and runner-up lay within a
+    relative ``RV_TIE_REL`` and were decided again on the host with numpy's sin / cos / arcsin on the same ring."""
+    a, code, geo_t = _rv_raster(data, geo_t)
+    row, col = _c(row, np.int32), _c(col, np.int32)
+    if row.ndim != 1 or row.size < 1 or col.shape != row.shape:
+        raise ValueError("row / col must be [npts >= 1]")
+    if row.min() < 0 or row.max() >= a.shape[0] or col.min() < 0 or col.max() >= a.shape[1]:
+        raise ValueError("a start lies outside the raster")
+    n = row.size
+    L = load()
+    if not hasattr(L.twxrv_nearest_data, "_twx_ready"):
+        L.twxrv_nearest_data.restype = C.c_int
+        L.twxrv_nearest_data.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_double,
+                                         C.c_int64] + [C.c_void_p] * 9 + [C.c_char_p, C.c_int]
+        L.twxrv_nearest_data._twx_ready = True
+    out = dict(value=np.empty(n), dist=np.empty(n), runner_up=np.empty(n), ring=np.empty(n, np.int32),
+               winner=np.empty(n, np.int32), status=np.empty(n, np.int32))
+    _rv_call(L.twxrv_nearest_data, "twxrv_nearest_data",
+             (int(device), a.shape[0], a.shape[1], code, a.ctypes.data, geo_t.ctypes.data, float(ndata), n, row.ctypes.data,
+              col.ctypes.data, out["value"].ctypes.data, out["dist"].ctypes.data, out["ring"].ctypes.data,
+              out["winner"].ctypes.data, out["runner_up"].ctypes.data, out["status"].ctypes.data), timing, RV_KERNELS[1])
+    ok = out["status"] == RV_OK
+    with np.errstate(invalid="ignore"):
+        close = ok & np.isfinite(out["runner_up"]) & (out["runner_up"] - out["dist"] <= RV_TIE_REL * out["runner_up"])
+    for p in np.nonzero(close)[0]:
+        out["value"][p], out["dist"][p], out["winner"][p] = _rv_ring_host(a, geo_t, float(ndata), int(row[p]), int(col[p]),
+                                                                          int(out["ring"][p]))
+    out["redecided"] = int(close.sum())
+    return out
+
+
+def dup_classes(lon, lat, device=0, timing=None):
+    """``twxrv_dup_classes``: (cls, size) [nstn] int32 -- the smallest index at the same location (``grt_circle_dist`` == 0)
+    and the number of stations there.  A NaN coordinate is a class of its own."""
+    lon, lat = _c(lon, np.float64), _c(lat, np.float64)
+    if lon.ndim != 1 or lon.size < 1 or lat.shape != lon.shape:
+        raise ValueError("lon / lat must be [nstn >= 1]")
+    n = lon.size
+    L = load()
+    if not hasattr(L.twxrv_dup_classes, "_twx_ready"):
+        L.twxrv_dup_classes.restype = C.c_int
+        L.twxrv_dup_classes.argtypes = [C.c_int, C.c_int64] + [C.c_void_p] * 5 + [C.c_char_p, C.c_int]
+        L.twxrv_dup_classes._twx_ready = True
+    cls, size = np.empty(n, np.int32), np.empty(n, np.int32)
+    _rv_call(L.twxrv_dup_classes, "twxrv_dup_classes", (int(device), n, lon.ctypes.data, lat.ctypes.data, cls.ctypes.data,
+                                                        size.ctypes.data), timing, RV_KERNELS[2])
+    return cls, size
+
+
+def col_count(data, cols=None, fill=None, workspace_bytes=0, device=0, timing=None):
+    """``twxrv_col_count`` on ``data`` [ndays, nstn] in the file's layout.  int8: the sum of every listed column
+    (``flag_infilled``) without the days that equal ``fill`` (None: every day counts); float32: the number of days of every
+    listed column that are non-finite or equal ``fill`` (None: the f4 fill value).  ``cols`` None: every column; a list may
+    be empty, unsorted and may repeat.  Returns [ncol] int32."""
+    data = np.asarray(data)
+    if data.ndim != 2 or data.shape[0] < 1 or data.shape[1] < 1:
+        raise ValueError("data must be [ndays >= 1, nstn >= 1]")
+    if data.dtype == np.int8:
+        kind, fill = RV_COUNT_I8_SUM, float("nan") if fill is None else float(fill)
+        if fill == fill and not (-128 <= fill <= 127 and fill == int(fill)):
+            raise ValueError("the fill of an int8 variable must be None or an integer in -128 .. 127")
+    elif data.dtype == np.float32:
+        kind, fill = RV_COUNT_F32_MISSING, SC_FILL_F4 if fill is None else float(fill)
+    else:
+        raise ValueError("data must be int8 (a sum) or float32 (a count of missing days)")
+    data = np.ascontiguousarray(data)
+    nd, ns = data.shape
+    if cols is not None:
+        cols = _c(cols, np.int32)
+        if cols.ndim != 1:
+            raise ValueError("cols must be a list of columns")
+        if cols.size and (cols.min() < 0 or cols.max() >= ns):
+            raise ValueError("a column of the list is outside 0 .. nstn - 1")
+        if cols.size == 0:
+            return np.zeros(0, np.int32)
+    ncol = ns if cols is None else cols.size
+    L = load()
+    if not hasattr(L.twxrv_col_count, "_twx_ready"):
+        L.twxrv_col_count.restype = C.c_int
+        L.twxrv_col_count.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_float, C.c_int64, C.c_void_p,
+                                      C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
+        L.twxrv_col_count._twx_ready = True
+    out = np.empty(ncol, np.int32)
+    counts = (C.c_int32 * 2)()
+    _rv_call(L.twxrv_col_count, "twxrv_col_count",
+             (int(device), nd, ns, kind, data.ctypes.data, float(fill), ncol, None if cols is None else cols.ctypes.data,
+              int(workspace_bytes), out.ctypes.data), timing, RV_KERNELS[3], tail=(C.addressof(counts),))
+    if timing is not None:
+        timing["rv_batches"] = timing.get("rv_batches", 0) + int(counts[1])
+    return out

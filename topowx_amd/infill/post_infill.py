@@ -6,9 +6,14 @@ databases the interpolation reads:
   (step17_find_bad_infill_stns.py), the whole series of every suspect station through ONE ``twxsc_series_check`` call per
   variable;
 * ``create_serially_complete_db`` / ``add_monthly_normals``: step18 (post_infill.py:79-156, 354-402), every station through
-  one batched ``twxsc_serial_complete`` call instead of a loop over stations through netCDF.
+  one batched ``twxsc_serial_complete`` call instead of a loop over stations through netCDF;
+* ``add_stn_raster_values``: step19 (post_infill.py:248-352 with ``_find_nn_data``, :443-510), one ``twxrv_sample`` call per
+  raster over all stations and one ``twxrv_nearest_data`` call over those that need a forced value;
+* ``find_dup_stns``: the front of step20 (post_infill.py:193-246), ``twxrv_dup_classes`` and ``twxrv_col_count`` instead of
+  the n x n loop.
 
-The kernels are ``topowx_amd/qa/twx_serial.hip`` (include/twx_qa.h).  There is no CPU fallback.
+The kernels are ``topowx_amd/qa/twx_serial.hip`` and ``topowx_amd/qa/twx_stnrast.hip`` (include/twx_qa.h).  There is no CPU
+fallback.
 """
 import os
 
@@ -16,10 +21,10 @@ import numpy as np
 
 from .. import _qalib, ncio
 from ..dates import DAY, MONTH, YEAR
-from ..stationdb import STN_ID, get_norm_varname
+from ..stationdb import LAT, LON, STN_ID, get_norm_varname
 
 __all__ = ["SERIAL_DB_VARIABLES", "USE_ALL_INFILL_THRESHOLD", "write_infill_db", "get_bad_infill_stnids", "suspect_infill_stnids",
-           "find_bad_infill_stns", "write_bad_stns_csv", "create_serially_complete_db", "add_monthly_normals", "SerialComplete"]
+           "find_bad_infill_stns", "write_bad_stns_csv", "create_serially_complete_db", "add_monthly_normals", "SerialComplete", "add_stn_raster_values", "find_dup_stns"]
 
 FILL_I1 = -127                                   # netCDF4.default_fillvals['i1']
 _LONG = {"tmin": "minimum air temperature", "tmax": "maximum air temperature"}
@@ -257,3 +262,78 @@ def add_monthly_normals(stnda, start_norm_yr=1981, end_norm_yr=2010, device=0, m
     if stnda.ds is not None and getattr(stnda.ds, "mode", "r") != "r":
         stnda.ds.sync()
     return r["norm"], r["norm_nmths"]
+
+
+def add_stn_raster_values(stnda, var_name, long_name, units, a_rast, extract_method=1, revert_nn=False, force_data_value=False,
+                          device=0, timing=None, report=None):
+    """``add_stn_raster_values`` (post_infill.py:248-352): the raster's value at every station as the ``f8`` station
+    variable ``var_name`` with ``fill_value=a_rast.ndata``.  ``a_rast`` is a ``topowx_amd.raster.RasterGrid`` in the
+    stations' own geographic coordinates.  ``extract_method`` 0 (nearest) or 1 (bilinear); ``revert_nn`` and
+    ``force_data_value`` as in the reference, whose ring search (``_find_nn_data``) runs for all forced stations in one
+    ``twxrv_nearest_data`` call.  Returns the ids of the stations left at ``a_rast.ndata``; with ``force_data_value`` such a
+    station raises the reference's exception (also where the reference would search for ever: no data cell in any ring).
+    ``report`` (a dict) receives the counts of bilinear / nearest / forced / no-data stations and ``redecided``, the
+    forced stations whose ring was decided again on the host because winner and runner-up lay within a relative 1e-9."""
+    if a_rast.ndata is None:
+        raise ValueError("the raster has no no-data value (a_rast.ndata): there is nothing to write for 'no value'")
+    lon, lat = np.asarray(stnda.stns[LON], np.float64), np.asarray(stnda.stns[LAT], np.float64)
+    newvar = stnda.add_stn_variable(var_name, long_name, units, "f8", fill_value=a_rast.ndata)
+    counts = dict(stations=int(lon.size), bilinear=0, nearest=0, forced=0, nodata=0, redecided=0)
+    if lon.size:
+        r = _qalib.raster_sample(a_rast.data, a_rast.geo_t, a_rast.ndata, lon, lat, band_ndata=a_rast.band_ndata,
+                                 extract_method=extract_method, revert_nn=revert_nn, force_data_value=force_data_value,
+                                 device=device, timing=timing)
+        rvals, status = r["value"], r["status"]
+        forced = np.nonzero(status == _qalib.RV_NEEDS_FORCE)[0]
+        if forced.size:
+            nn = _qalib.raster_nearest_data(a_rast.data, a_rast.geo_t, a_rast.ndata, r["row"][forced], r["col"][forced],
+                                            device=device, timing=timing)
+            rvals[forced] = nn["value"]                          # ndata where no ring holds a data cell
+            counts["redecided"] = nn["redecided"]
+        by_method = int((status == _qalib.RV_OK).sum())
+        counts.update(bilinear=by_method if extract_method == 1 else 0,
+                      nearest=int((status == _qalib.RV_NEAREST).sum()) + (by_method if extract_method == 0 else 0),
+                      forced=int(forced.size), nodata=int((status == _qalib.RV_NODATA).sum()))
+        newvar[:] = rvals
+        if stnda.ds is not None and getattr(stnda.ds, "mode", "r") != "r":
+            stnda.ds.sync()
+        stnids_ndata = stnda.stn_ids[rvals == a_rast.ndata]
+    else:
+        stnids_ndata = stnda.stn_ids[:0]
+    if report is not None:
+        report.update(counts)
+    if force_data_value and stnids_ndata.size > 0:
+        raise Exception("force_data_value turned on, but station points still had no data values.")
+    return stnids_ndata
+
+
+def find_dup_stns(stnda, device=0, workspace_bytes=0, timing=None):
+    """``find_dup_stns`` (post_infill.py:193-246) of an INFILLED database (its ``flag_infilled`` [ndays, nstn] is read
+    through ``stnda.ds``): of the stations at one location -- ``grt_circle_dist`` == 0, decided by ``twxrv_dup_classes`` --
+    those whose count of infilled days (``twxrv_col_count`` on the file's layout) is not the smallest are returned; stations
+    tied at the minimum are ALL kept, as in the reference.  Classes come in the order of their first member, members sorted
+    by id.  The reference pairs id-sorted ids with sums in database order, which is right only for a table sorted by id:
+    an unsorted table is refused."""
+    ids = np.asarray(stnda.stn_ids)
+    if ids.size > 1 and not np.all(ids[1:] > ids[:-1]):
+        raise ValueError("station table must be sorted by station_id and unique")
+    if ids.size < 2:
+        return np.array([], dtype=ids.dtype)
+    cls, size = _qalib.dup_classes(stnda.stns[LON], stnda.stns[LAT], device=device, timing=timing)
+    firsts = np.nonzero((cls == np.arange(cls.size)) & (size > 1))[0]
+    if firsts.size == 0:
+        return np.array([], dtype=ids.dtype)
+    members = [np.nonzero(cls == f)[0] for f in firsts]          # ascending index = ascending id
+    if stnda.ds is None or "flag_infilled" not in stnda.ds.variables:
+        raise KeyError("find_dup_stns needs the infilled database's flag_infilled variable (open the database from its file)")
+    fvar = stnda.ds.variables["flag_infilled"]
+    fill = fvar.getncattr("_FillValue") if "_FillValue" in fvar.ncattrs() else FILL_I1
+    flag = np.asarray(np.ma.filled(fvar[:], fill)).astype(np.int8)   # a masked day adds nothing to numpy's sum: the kernel skips it
+    sums = _qalib.col_count(flag, np.concatenate(members), fill=int(fill), workspace_bytes=workspace_bytes, device=device,
+                            timing=timing)
+    rm, at = [], 0
+    for m in members:
+        s = sums[at:at + m.size]
+        at += m.size
+        rm.extend(ids[m][s != s.min()])
+    return np.array(rm, dtype=ids.dtype)

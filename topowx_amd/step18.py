@@ -15,7 +15,8 @@ wrote.  An existing output file is not overwritten.  The outputs are what ``pyth
 Prints one JSON line (per variable the stations, days, stations with all infilled values and with missing values, months
 with a normal; seconds, kernel milliseconds).  Exits with 1 if a file cannot be opened or written.
 
-Out of scope: ``find_dup_stns``, the TDI and climate-division checks of step20, ``add_stn_raster_values`` (step19).
+What follows: ``python -m topowx_amd.step19`` (``add_stn_raster_values``) and ``python -m topowx_amd.step20`` with its
+``--infill-*`` arguments (``find_dup_stns``, the TDI and climate-division checks).
 """
 import argparse
 import contextlib
