@@ -989,6 +989,79 @@ int twxrv_col_count(int device, int64_t ndays, int64_t nstn, int32_t kind, const
                     const int32_t *cols, int64_t workspace_bytes, int32_t *out, int32_t *counts, float *kernel_ms,
                     char *errbuf, int errlen);
 
+/* ---- the quality assurance of daily precipitation (twx/qa/qa_prcp.py, Durre et al. 2010): the non-spatial chain
+ * run_qa_non_spatial (:135-176) and the two checks the reference defines but leaves commented out of it, _qa_streak
+ * (:379-407) and _qa_frequent (:409-445); twx_prcpqa.hip.  Out of scope: _qa_spatial_corrob, _qa_yr_clim_outlier,
+ * run_qa_all, run_qa_spatial_only.  These entries have no per-item status: every failure is call-level (a number after
+ * TWXRV_NO_DATA_ANYWHERE = 38 is the next free one). ---- */
+#define TWXPQ_PCTILE_ROWS 366           /* the dates of 2004 (DATES_366) */
+#define TWXPQ_PCTILE_COLS 5             /* the 30th, 50th, 70th, 90th and 95th percentile */
+#define TWXPQ_MIN_PERCENTILE_VALUES 20  /* MIN_PERCENTILE_VALUES: a row with fewer values is NaN */
+/* Values of one row of the percentile table: the values > 0 on 29 month-days over all years, sorted in LDS by one
+ * workgroup.  4096 float32 are 16 KiB: 8 workgroups of 4 waves fill a compute unit's 32 wave slots with 128 KiB of its
+ * 160 KiB.  29 per year: 141 years.  A longer series fails the call, never a truncated window.  (The chain's gap check
+ * sorts 31 slots per year under TWXQA_MAX_GAP_VALUES: 132 years, the cap a chain call meets first.) */
+#define TWXPQ_MAX_WINDOW_VALUES 4096
+#define TWXPQ_NKERNELS 7                /* kernel groups timed by twxpq_non_spatial */
+
+/*
+ * run_qa_non_spatial(prcp, tavg, days) for nstn stations in one call; every station is checked on its own.  The checks run
+ * in the reference's order, each on the series without the observations every earlier one flagged (_update_obs_flags:
+ * flagged days become NaN, a number is written only where the flag is still 1); all decisions of one check are taken on
+ * the same snapshot.  "Wet" below: a finite value > 0 that is still in the series.  In execution order:
+ *    2 missing: NaN.
+ *    4 duplicate year: two years of the axis with >= 3 wet values each whose first min(len, len) days on the axis are all
+ *   ==, by position (one NaN in the overlap: no duplicate).   6 duplicate months of one year, by position over the shorter,
+ *   >= 3 wet values each; the month NUMBER equal to (distinct months on the axis) - 1 is never the first of a pair (the
+ *   reference's loop, kept: on a 12-month axis November and December are never compared; on a March - September axis June
+ *   is never the first).   5 the same calendar month of two years, likewise.
+ *    8 impossible: < 0 or > 182.88f, compared in float32 (float32(182.88) itself is not flagged, its successor is).
+ *    9 streak (only with streak != 0): on the sequence of wet values -- zeros and NaN are skipped and break no run -- every
+ *   maximal run of >= 20 equal values that a different value ends; the last run of the series is never flagged (kept).
+ *   19 frequent value (only with frequent != 0): for every start x of that sequence the window x .. x + 9 (shorter at the
+ *   end) and every value v in it with c occurrences there: flagged when c >= 9 and v >= the 30th percentile of the row of
+ *   each of its days, or c >= 8 against the 50th, c >= 7 against the 70th, c >= 5 against the 90th (the reference's elif
+ *   chain: a tier with a NaN percentile or a smaller v falls through to the next); fp64 comparison; the table is that of
+ *   15 below, built from the series as it stands at this point.
+ *   10 gap: per calendar month over all years the sorted wet values; the first float32 difference of neighbours that is
+ *   >= 30.0f gives the bound (the upper value) and every wet value of the month >= it is flagged.
+ *   15 outlier: the table [366][5] of _build_percentiles: row r holds the five percentiles of all wet values whose
+ *   month-day lies within 14 days of the r-th date of 2004 (29 month-days, wrapping over the year end; 29 February is in
+ *   the windows of rows 45 .. 73 only), NaN below 20 values; numpy's linear interpolation in fp64 on the values widened
+ *   exactly: virtual index (n - 1) q, g its fraction, a + (b - a) g below g = 0.5 and b - (b - a)(1 - g) from 0.5 on.  A wet
+ *   value is flagged when (double)v >= m * p95[row], m = 5 where tavg < 0 (a NaN tavg: 9), row = yday - 1 of the day's OWN
+ *   year (kept: from 1 March of a common year that is the row of the calendar day before).
+ *
+ * Deviation from the reference: numpy subtracts b - a in the series' own precision, so its table on a float32 series can
+ * differ from this one by one float32 rounding of that difference (relative 6e-8 of the result).
+ *
+ * prcp, tavg [nstn][ndays]   station-major float32, NaN = missing (tavg may be all NaN); not modified
+ * ymd [ndays]                consecutive calendar days, YYYYMMDD; need not start or end at a year boundary
+ * streak, frequent           0: the reference's chain; non-zero: with check 9 / check 19
+ * flag [nstn][ndays]         out: 1, 2, 4, 5, 6, 8, 9, 10, 15, 19
+ * pctiles (optional) [nstn][366][5]   out: the table as check 15 used it
+ * kernel_ms (optional) [TWXPQ_NKERNELS]   device time: missing; duplicates + impossible values; streaks; frequent values
+ *                            with their table; gaps; the table; outliers (0 for a check that did not run)
+ * Call-level failures: non-consecutive days; a series that touches more than TWXPQ_MAX_WINDOW_VALUES / 29 years or more
+ * than TWXQA_MAX_GAP_VALUES / 31: the message names the macro; no device work is done.  Integer atomics only count or
+ * take a minimum; no floating-point atomics: two calls give the same bytes.
+ */
+int twxpq_non_spatial(int device, int64_t nstn, int64_t ndays, const float *prcp, const float *tavg, const int32_t *ymd,
+                      int32_t streak, int32_t frequent, uint8_t *flag, double *pctiles, float *kernel_ms, char *errbuf,
+                      int errlen);
+
+/*
+ * _build_percentiles(vals, days, DATES_366) alone: the table above of every series as it is given (NaN = missing).
+ * k_pq_pctiles: one workgroup per (station, row) compacts the window into LDS, sorts it there and reads five pairs of ranks.
+ *
+ * vals [nstn][ndays]         station-major float32
+ * pctiles [nstn][366][5]     out
+ * kernel_ms (optional) [1]   device time of the table
+ * Call-level failures: non-consecutive days; more than TWXPQ_MAX_WINDOW_VALUES / 29 years.
+ */
+int twxpq_percentiles(int device, int64_t nstn, int64_t ndays, const float *vals, const int32_t *ymd, double *pctiles,
+                      float *kernel_ms, char *errbuf, int errlen);
+
 #ifdef __cplusplus
 }
 #endif

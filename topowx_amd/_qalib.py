@@ -1319,3 +1319,70 @@ def col_count(data, cols=None, fill=None, workspace_bytes=0, device=0, timing=No
     if timing is not None:
         timing["rv_batches"] = timing.get("rv_batches", 0) + int(counts[1])
     return out
+
+
+# ---- the precipitation QA: the non-spatial chain and the percentile table (twxpq_*; TWXPQ_* of include/twx_qa.h) ----
+PQ_EXPORTS = ("twxpq_non_spatial", "twxpq_percentiles")
+PQ_PCTILE_ROWS = 366                  # TWXPQ_PCTILE_ROWS: the dates of 2004
+PQ_PCTILE_COLS = 5                    # TWXPQ_PCTILE_COLS: 30th, 50th, 70th, 90th, 95th
+PQ_MIN_PERCENTILE_VALUES = 20         # TWXPQ_MIN_PERCENTILE_VALUES
+PQ_MAX_WINDOW_VALUES = 4096           # TWXPQ_MAX_WINDOW_VALUES: 29 values per year of the series
+PQ_KERNELS = ("pq_init", "pq_dups", "pq_streak", "pq_frequent", "pq_gap", "pq_pctiles", "pq_clim")     # TWXPQ_NKERNELS
+
+
+def _pq_fn(name, argtypes):
+    fn = getattr(load(), name)
+    fn.restype, fn.argtypes = C.c_int, argtypes
+    return fn
+
+
+def _pq_series(name, a, ymd):
+    a = _c(a, np.float32)
+    if a.ndim != 2 or ymd.ndim != 1 or a.shape[1] != ymd.size or a.shape[0] < 1 or ymd.size < 1:
+        raise ValueError("%s must be [nstn >= 1, ndays >= 1] and ymd [ndays]" % name)
+    return a
+
+
+def prcp_non_spatial(prcp, tavg, ymd, streak=False, frequent=False, device=0, details=False, timing=None):
+    """``twxpq_non_spatial``: ``run_qa_non_spatial`` (qa_prcp.py:135-176) of every station on its own, with ``_qa_streak`` /
+    ``_qa_frequent`` in their places if asked for.  prcp, tavg [nstn, ndays] float32, station-major, NaN = missing; ymd
+    [ndays] consecutive days.  Returns flag uint8 [nstn, ndays] (1, 2, 4, 5, 6, 8, 9, 10, 15, 19); with ``details``
+    ``(flag, pctiles [nstn, 366, 5])``, the table as the outlier check used it.  ``timing`` receives
+    ``<kernel>_kernel_ms`` for the names in ``PQ_KERNELS``.  Arguments are checked before anything touches the device."""
+    ymd = _c(ymd, np.int32)
+    prcp, tavg = _pq_series("prcp", prcp, ymd), _pq_series("tavg", tavg, ymd)
+    if tavg.shape != prcp.shape:
+        raise ValueError("prcp and tavg must have one shape")
+    fn = _pq_fn("twxpq_non_spatial", [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 3 + [C.c_int32, C.c_int32] +
+                [C.c_void_p] * 3 + [C.c_char_p, C.c_int])
+    nstn, ndays = prcp.shape
+    buf = C.create_string_buffer(512)
+    flag = np.zeros((nstn, ndays), np.uint8)
+    pct = np.empty((nstn, PQ_PCTILE_ROWS, PQ_PCTILE_COLS)) if details else None
+    ms = (C.c_float * len(PQ_KERNELS))()
+    rc = fn(int(device), nstn, ndays, prcp.ctypes.data, tavg.ctypes.data, ymd.ctypes.data, int(bool(streak)),
+            int(bool(frequent)), flag.ctypes.data, pct.ctypes.data if details else None, C.addressof(ms), buf, 512)
+    if rc != 0:
+        raise QaError("twxpq_non_spatial failed: %s" % buf.value.decode(errors="replace"))
+    if timing is not None:
+        for k, name in enumerate(PQ_KERNELS):
+            timing[name + "_kernel_ms"] = float(ms[k])
+    return (flag, pct) if details else flag
+
+
+def prcp_percentiles(vals, ymd, device=0, timing=None):
+    """``twxpq_percentiles``: ``_build_percentiles(vals, days, DATES_366)`` (qa_prcp.py:790-812) of every row of vals
+    [nstn, ndays] float32 (NaN = missing).  Returns [nstn, 366, 5] float64; a row with fewer than 20 values > 0 is NaN."""
+    ymd = _c(ymd, np.int32)
+    vals = _pq_series("vals", vals, ymd)
+    fn = _pq_fn("twxpq_percentiles", [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 4 + [C.c_char_p, C.c_int])
+    buf = C.create_string_buffer(512)
+    pct = np.empty((vals.shape[0], PQ_PCTILE_ROWS, PQ_PCTILE_COLS))
+    ms = C.c_float(0.0)
+    rc = fn(int(device), vals.shape[0], vals.shape[1], vals.ctypes.data, ymd.ctypes.data, pct.ctypes.data,
+            C.addressof(ms), buf, 512)
+    if rc != 0:
+        raise QaError("twxpq_percentiles failed: %s" % buf.value.decode(errors="replace"))
+    if timing is not None:
+        timing["pq_pctiles_kernel_ms"] = float(ms.value)
+    return pct
