@@ -991,8 +991,8 @@ int twxrv_col_count(int device, int64_t ndays, int64_t nstn, int32_t kind, const
 
 /* ---- the quality assurance of daily precipitation (twx/qa/qa_prcp.py, Durre et al. 2010): the non-spatial chain
  * run_qa_non_spatial (:135-176) and the two checks the reference defines but leaves commented out of it, _qa_streak
- * (:379-407) and _qa_frequent (:409-445); twx_prcpqa.hip.  Out of scope: _qa_spatial_corrob, _qa_yr_clim_outlier,
- * run_qa_all, run_qa_spatial_only.  These entries have no per-item status: every failure is call-level (a number after
+ * (:379-407) and _qa_frequent (:409-445); twx_prcpqa.hip.  The spatial corroboration check that completes run_qa_all and
+ * run_qa_spatial_only is twxpc_spatial_corrob below; out of scope: _qa_yr_clim_outlier.  These entries have no per-item status: every failure is call-level (a number after
  * TWXRV_NO_DATA_ANYWHERE = 38 is the next free one). ---- */
 #define TWXPQ_PCTILE_ROWS 366           /* the dates of 2004 (DATES_366) */
 #define TWXPQ_PCTILE_COLS 5             /* the 30th, 50th, 70th, 90th and 95th percentile */
@@ -1060,6 +1060,63 @@ int twxpq_non_spatial(int device, int64_t nstn, int64_t ndays, const float *prcp
  * Call-level failures: non-consecutive days; more than TWXPQ_MAX_WINDOW_VALUES / 29 years.
  */
 int twxpq_percentiles(int device, int64_t nstn, int64_t ndays, const float *vals, const int32_t *ymd, double *pctiles,
+                      float *kernel_ms, char *errbuf, int errlen);
+
+/* ---- the spatial corroboration check of the precipitation QA, _qa_spatial_corrob / _get_spatial_corrob_flag
+ * (twx/qa/qa_prcp.py:614-664, 683-782; flag 17); twx_prcpcorrob.hip.  With it run_qa_spatial_only (:178-215: missing, then
+ * this check) and run_qa_all (:87-133: the non-spatial chain, then this check) are complete.  Out of scope:
+ * _qa_yr_clim_outlier, which the reference never calls.  Per-target statuses are the TWXQA_SP_* numbers of the temperature
+ * checks. ---- */
+#define TWXPC_NKERNELS 4                /* kernel groups timed by twxpc_spatial_corrob */
+
+/*
+ * _qa_spatial_corrob for ntarget stations of a pool in one call.  A target's series is "flags == 1 ? pool value : NaN" (what
+ * the checks before left); a NEIGHBOUR's observations are the pool's values as they are.  The neighbours are the stations
+ * within TWXQA_NGH_RADIUS_KM (75 km, k_radius_dist's arithmetic), self excluded, in ascending distance, equal distances in
+ * table order; fewer than 3: nothing is flagged.  "pors" counts: a station has 366 rows, row r holds its finite values > 0
+ * whose month-day lies within 14 days of the r-th date of 2004 (the windows of the percentile table above); a row has a
+ * percentile basis when it holds MORE than TWXPQ_MIN_PERCENTILE_VALUES (20) values.  A target's rows come from its series,
+ * a neighbour's from the pool.
+ *
+ * Day x is tested unless it is the first or last day of the axis or its value is NaN:
+ *   1. on each of x - 1, x, x + 1 at least 3 neighbours (of all) have a finite observation, else no flag;
+ *   2. of the first 7 finite observations of each of the three days in distance order (up to 21 values): a value above their
+ *      maximum has abs_dif = value - max, one below their minimum abs_dif = min - value, any other is not flagged;
+ *   3. thres = 26.924 cm unless the target's row yday(x) - 1 (of the day's OWN year: from 1 March of a common year the row
+ *      of the calendar day before) has a basis AND on each of the three days at least 3 of the finite neighbours have a
+ *      basis at that day's own row (31 December and 1 January use different rows).  Then
+ *      pctile = scipy.stats.percentileofscore(target row, value), kind "rank": with left = #(a < v), right = #(a <= v),
+ *      (left + right + (left < right)) * (50.0 / n); pctile_dif = the distance of pctile above the maximum or below the
+ *      minimum of THE OBSERVATIONS IN CM OF ALL FINITE NEIGHBOURS ON THE THREE DAYS (the reference's line 760, kept: not
+ *      capped at 7, not percentiles: a percentile is compared with centimetres; the neighbours' own percentiles are never
+ *      used), 0 inside; thres = 26.924 if pctile_dif == 0, else (-45.72 * ln(pctile_dif) + 269.24) / 10 -- above 26.924
+ *      where pctile_dif < 1;
+ *   4. flagged (17) when abs_dif > thres.
+ * All in fp64 on float32 values widened exactly; ln is the device library's (1 ulp).
+ *
+ * lon, lat [nstn]            degrees
+ * prcp [nstn][ndays]         station-major float32, NaN = missing; not modified
+ * ymd [ndays]                consecutive calendar days, YYYYMMDD
+ * target_idx [ntarget]       rows of the pool
+ * flags [ntarget][ndays]     in / out: 17 is written where the day is flagged and the flag is 1; nothing else changes
+ * status (optional) [ntarget]   TWXQA_SP_OK, TWXQA_SP_FEW_NGHS (fewer than 3 within 75 km) or TWXQA_SP_NGH_CAP (more than
+ *                            TWXQA_MAX_RADIUS_NGH: no flags)
+ * abs_dif, pctile, thres (optional) [ntarget][ndays]   float64, NaN where the day did not reach step 2 / 3 (pctile is NaN
+ *                            where thres is 26.924 for want of a basis)
+ * kernel_ms (optional) [TWXPC_NKERNELS]   device time: neighbour lists; row counts; the walk; rank + threshold + flags
+ * Call-level failures, before any device work: non-consecutive days; more than TWXPQ_MAX_WINDOW_VALUES / 29 years; a
+ * target index outside 0 .. nstn - 1.  Integer atomics only count; no floating-point atomics: two calls give the same
+ * bytes.
+ */
+int twxpc_spatial_corrob(int device, int64_t nstn, int64_t ndays, const double *lon, const double *lat, const float *prcp,
+                         const int32_t *ymd, int64_t ntarget, const int32_t *target_idx, uint8_t *flags, int32_t *status,
+                         double *abs_dif, double *pctile, double *thres, float *kernel_ms, char *errbuf, int errlen);
+
+/*
+ * The sizes of _build_pors' rows alone (:675-681): counts [nstn][366] uint16 of every series as it is given.
+ * kernel_ms (optional) [1].  Call-level failures: non-consecutive days; more than TWXPQ_MAX_WINDOW_VALUES / 29 years.
+ */
+int twxpc_pors_counts(int device, int64_t nstn, int64_t ndays, const float *vals, const int32_t *ymd, uint16_t *counts,
                       float *kernel_ms, char *errbuf, int errlen);
 
 #ifdef __cplusplus

@@ -1,0 +1,306 @@
+"""GPU: the precipitation QA's spatial corroboration check (``twxpc_spatial_corrob`` / ``twxpc_pors_counts`` of libtwxqa,
+``topowx_amd.qa.qa_prcp``: ``qa_spatial_corrob``, ``run_qa_spatial_only``, ``run_qa_all``, ``pors_counts``) against the
+executed-reference golden (tests/golden/make_golden_prcpcorrob.py) and the numpy restatement (tests/restate_prcpcorrob.py),
+a grid of shapes, determinism, and ``python -m topowx_amd.qa.qa_prcp --spatial | --all [--write]`` end to end on both
+containers.
+
+Flags, statuses and row counts are compared exactly; so is ``abs_dif``, the fp64 difference of two float32 values.  Exact
+flags are fair because the margins are asserted first: the golden maker asserted that every ``abs_dif`` lies more than 1e-5
+relative from its ``thres``; on the random pool days whose restatement margin is under 1e-5 may be left out, at most 1e-4 of
+them, and the seed is chosen so that there are none.
+
+The bounds on ``pctile`` and ``thres`` are derived.  With eps = 2^-52 a rounding is eps / 2 relative.
+``pctile = k * (50.0 / n)`` is two fp64 roundings on each side from the same integers: |got - want| <= 2 eps |want| (bit
+equality is what to expect).  ``thres = (-45.72 ln(d) + 269.24) / 10`` with d = |pctile - bound|, bound a float32 widened
+exactly: d carries the two sides' pctile errors, at most 2 eps x 100 absolute, and its own rounding; ln is within 1 ulp of
+the true value on the device (the documented accuracy of the device library's fp64 ``log``) and on the host, and the
+derivative of ln is 1 / d:
+    |d ln| <= 200 eps / d + eps + 2 eps |ln d|
+    |d thres| <= (45.72 |d ln| + eps |45.72 ln d| + eps |269.24 - 45.72 ln d|) / 10 + eps |thres|
+(the last three terms: the product, the sum and the division, a rounding on each side).  d is recovered from the golden's
+own thres, d = exp((269.24 - 10 thres) / 45.72).  Where the golden's thres is 26.924 itself (no basis, or pctile_dif == 0)
+the library's must be the same double."""
+import datetime as dt
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from topowx_amd import _qalib
+from topowx_amd.dates import YMD, get_days_metadata
+from topowx_amd.qa import qa_prcp
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import prcp_cases as PC  # noqa: E402
+import prcpcorrob_cases as CC  # noqa: E402
+import restate_prcpcorrob as RC  # noqa: E402
+from spatial_cases import FORMATS  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+EPS = 2.0 ** -52
+MARGIN, MAX_LEFT_OUT = 1e-5, 1e-4
+
+
+@pytest.fixture(scope="module")
+def gold():
+    return np.load(os.path.join(ROOT, "tests", "golden", "golden_prcpcorrob_v1.npz"))
+
+
+@pytest.fixture(scope="module")
+def case(gold):
+    ids, lon, lat, prcp, tavg, days, plants = CC.case_inputs()
+    assert CC.input_hash(lon, lat, prcp, tavg, days) == str(gold["input_hash"]), "synthetic generator drifted: regenerate the golden"
+    return qa_prcp.PrcpObsPool(ids, lon, lat, prcp, tavg - np.float32(4.0), tavg + np.float32(4.0), days), tavg, plants
+
+
+def _pool(lon, lat, prcp, days, tavg=None):
+    n = prcp.shape[1]
+    t = np.zeros(prcp.shape, np.float32) if tavg is None else tavg
+    return qa_prcp.PrcpObsPool(np.array(["X%04d" % i for i in range(n)]), lon, lat, prcp, t, t, days)
+
+
+def _dense(gold, chain, shape):
+    out = {k: np.full(shape, np.nan) for k in ("abs_dif", "pctile", "thres")}
+    key = gold["reached_" + chain]
+    for k in out:
+        out[k][key[:, 1], key[:, 0]] = gold[k + "_" + chain]
+    return out
+
+
+def thres_bound(want):
+    """The derived absolute bound on |got - want| of thres, per value (see the module docstring)."""
+    d = np.exp((RC.THRES_MM - 10.0 * want) / 45.72)
+    ln = np.abs(np.log(d))
+    dln = 200.0 * EPS / d + EPS + 2.0 * EPS * ln
+    return (45.72 * dln + EPS * 45.72 * ln + EPS * np.abs(RC.THRES_MM - 45.72 * np.log(d))) / 10.0 + EPS * np.abs(want)
+
+
+def _figures_close(got, want, what):
+    """abs_dif exact, pctile and thres within their derived bounds; prints the measured maxima."""
+    for k in ("abs_dif", "pctile", "thres"):
+        assert np.array_equal(np.isnan(got[k]), np.isnan(want[k])), (what, k, "NaN positions")
+    fin = np.isfinite(want["abs_dif"])
+    assert np.array_equal(got["abs_dif"][fin], want["abs_dif"][fin]), what
+    fin = np.isfinite(want["pctile"])
+    g, w = got["pctile"][fin], want["pctile"][fin]
+    dp = np.abs(g - w)
+    rp = float(np.max(dp[w != 0] / w[w != 0])) if (w != 0).any() else 0.0
+    assert (dp <= 2.0 * EPS * np.abs(w)).all(), (what, "pctile", rp)
+    fin = np.isfinite(want["thres"])
+    g, w = got["thres"][fin], want["thres"][fin]
+    base = w == RC.THRES
+    assert np.array_equal(g[base], w[base]), (what, "thres == 26.924")
+    dt_, bound = np.abs(g - w)[~base], thres_bound(w[~base])
+    rt = float(np.max(dt_ / np.abs(w[~base]))) if dt_.size else 0.0
+    print("%s: pctile max relative difference %.3g over %d values (%d not bit-equal); thres %.3g over %d values (%d not "
+          "bit-equal), largest share of its bound %.3g" % (what, rp, int(fin.sum()), int((dp != 0).sum()), rt, dt_.size,
+                                                           int((dt_ != 0).sum()), float(np.max(dt_ / bound)) if dt_.size else 0.0))
+    assert (dt_ <= bound).all(), (what, "thres", rt)
+    return rp, rt
+
+
+# ---- the executed reference ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("chain", ["spatial", "all"])
+def test_golden_through_the_library(gold, case, chain):
+    pool, tavg, P = case
+    assert np.array_equal(pool.tavg < 0, tavg < 0)                  # check 15 looks at the sign of Tavg alone
+    keep = pool.prcp.copy()
+    tm = {}
+    if chain == "spatial":
+        det = qa_prcp.run_qa_spatial_only(pool, details=True, timing=tm)
+    else:
+        det = qa_prcp.run_qa_all(pool, details=True, timing=tm)
+        assert tm["pq_pctiles_kernel_ms"] > 0
+    assert np.array_equal(pool.prcp, keep, equal_nan=True)
+    assert all(tm[k + "_kernel_ms"] > 0 for k in _qalib.PC_KERNELS)
+    want = gold["flags_" + chain]
+    got = det["flags"]
+    assert got.dtype == np.uint8 and got.shape == want.shape
+    print({int(k): int((got == k).sum()) for k in np.unique(got)})
+    bad = np.argwhere(got != want)
+    assert bad.size == 0, bad[:10].tolist()
+    assert np.array_equal(det["status"], np.where(gold["nngh"] < 3, _qalib.SP_FEW_NGHS, _qalib.SP_OK))
+    _figures_close(det, _dense(gold, chain, want.shape), "golden, %s chain" % chain)
+    if chain == "all":                                              # the same through flags handed in
+        assert np.array_equal(qa_prcp.qa_spatial_corrob(pool, flags=gold["flags_chain"]), want)
+    else:
+        for name in ("row20", "row21", "mar1", "dry_wet", "quirk", "eighth", "two_finite", "raw_ngh_kept"):
+            s, d = P[name]
+            assert got[d, s] == want[d, s], name
+
+
+def test_golden_row_counts(gold, case):
+    pool, _, _ = case
+    got = qa_prcp.pors_counts(pool.prcp, pool.days)
+    assert got.dtype == np.uint16 and got.shape == (366, pool.ids.size) and np.array_equal(got, gold["counts_pool"])
+    left = np.where(gold["flags_chain"] == 1, pool.prcp, np.float32(np.nan))
+    assert np.array_equal(qa_prcp.pors_counts(left, pool.days), gold["counts_all"])
+    one = qa_prcp.pors_counts(pool.prcp[:, CC.S_SPARSE], pool.days)
+    assert one.shape == (366,) and np.array_equal(one, gold["counts_pool"][:, CC.S_SPARSE])
+
+
+# ---- a random pool against the restatement -------------------------------------------------------------------------
+@pytest.mark.parametrize("chain", ["spatial", "all"])
+def test_random_pool_equals_the_restatement(chain):
+    ids, lon, lat, p, tv, days = CC.random_inputs()
+    want = CC.restated("random", chain)
+    out = want["margin"] < MARGIN
+    print("%d days of %d left out, smallest margin %.3g" % (int(out.sum()), out.size, want["margin"].min()))
+    assert out.mean() <= MAX_LEFT_OUT
+    pool = _pool(lon, lat, p, days, tv)
+    det = qa_prcp.qa_spatial_corrob(pool, flags=want["flags_in"], details=True)
+    print({int(k): int((det["flags"] == k).sum()) for k in np.unique(det["flags"])})
+    bad = np.argwhere((det["flags"] != want["flags"]) & ~out)
+    assert bad.size == 0, bad[:10].tolist()                      # every flag of every station and day
+    assert np.array_equal(det["status"], want["status"])
+    _figures_close(det, want, "random pool, %s chain" % chain)
+    assert np.array_equal(qa_prcp.pors_counts(p, days), RC.pors_counts(p, days[YMD]))
+
+
+# ---- shapes --------------------------------------------------------------------------------------------------------------
+def _cluster(n, nd, seed, first=dt.date(2001, 1, 1), years=None):
+    rs = np.random.RandomState(seed)
+    days = get_days_metadata(first, first + dt.timedelta(days=nd - 1))
+    lon, lat = -110.0 + 0.3 * rs.rand(n), 45.0 + 0.3 * rs.rand(n)
+    p = np.where(rs.rand(nd, n) < 0.5, np.round(rs.gamma(0.8, 0.9, (nd, n)) + 0.01, 2), 0.0).astype(np.float32)
+    p[rs.rand(nd, n) < 0.03] = np.nan
+    return lon, lat, p, days
+
+
+def _against_restatement(lon, lat, p, days, targets=None, what=""):
+    pool = _pool(lon, lat, p, days)
+    cols = np.arange(p.shape[1]) if targets is None else np.asarray(targets)
+    fl = np.where(np.isnan(p[:, cols]), 2, 1).astype(np.uint8)
+    want = RC.run(lon, lat, p, days[YMD], cols, fl)
+    assert want["margin"].min() > MARGIN, what
+    det = qa_prcp.run_qa_spatial_only(pool, targets=targets, details=True)
+    assert np.array_equal(det["flags"], want["flags"]) and np.array_equal(det["status"], want["status"]), what
+    _figures_close(det, want, what)
+    return det, want
+
+
+@pytest.mark.parametrize("nd", [2, 3, 65, 129])
+def test_short_axes(nd):
+    """2 days: nothing testable; 3 days: only the middle one; 65 and 129: one day past a block of 64 lanes."""
+    lon, lat, p, days = _cluster(6, nd, 100 + nd)
+    p[:, 0] = 45.0                                                  # far above every neighbour on every day
+    p[:, 1:] = np.nan_to_num(p[:, 1:])
+    det, want = _against_restatement(lon, lat, p, days, what="%d days" % nd)
+    assert (det["flags"][:, 0] == 17).tolist() == [False] + [True] * (nd - 2) + [False] * (nd > 1)
+
+
+def test_one_target_and_a_subset_equal_the_columns_of_the_whole(case):
+    pool, _, P = case
+    whole = qa_prcp.run_qa_spatial_only(pool, details=True)
+    one = qa_prcp.run_qa_spatial_only(pool, targets=[CC.S_SPARSE], details=True)
+    assert one["flags"].shape == (pool.days.size, 1) and one["status"].tolist() == [0]
+    sub = [CC.S_SPARSE, 0, 26, 8, 21]
+    part = qa_prcp.run_qa_spatial_only(pool, targets=pool.ids[sub], details=True)
+    for k in ("flags", "abs_dif", "pctile", "thres"):
+        assert part[k].tobytes() == np.ascontiguousarray(whole[k][:, sub]).tobytes(), k
+        assert one[k].tobytes() == np.ascontiguousarray(whole[k][:, [CC.S_SPARSE]]).tobytes(), k
+    assert np.array_equal(part["status"], whole["status"][sub])
+
+
+def test_two_calls_give_identical_bytes(case):
+    pool, _, _ = case
+    a = qa_prcp.run_qa_all(pool, details=True)
+    b = qa_prcp.run_qa_all(pool, details=True)
+    for k in ("flags", "status", "abs_dif", "pctile", "thres"):
+        assert a[k].tobytes() == b[k].tobytes(), k
+    assert qa_prcp.pors_counts(pool.prcp, pool.days).tobytes() == qa_prcp.pors_counts(pool.prcp, pool.days).tobytes()
+
+
+def test_record_of_366_days_from_29_february():
+    lon, lat, p, days = _cluster(9, 366, 29, first=dt.date(2004, 2, 29))
+    assert days[YMD][0] == 20040229 and days[YMD][-1] == 20050228
+    p[np.arange(5, 366, 9), 2] = 33.0
+    det, want = _against_restatement(lon, lat, p, days, what="366 days from 29 February")
+    assert (det["flags"][:, 2] == 17).sum() > 20
+    assert np.array_equal(qa_prcp.pors_counts(p, days), RC.pors_counts(p, days[YMD]))
+
+
+def test_all_nan_target_and_all_dry_pool():
+    lon, lat, p, days = _cluster(8, 800, 7)
+    p[:, 3] = np.nan
+    p[100:700:50, 1] = 30.0
+    det, want = _against_restatement(lon, lat, p, days, what="an all-NaN target")
+    assert (det["flags"][:, 3] == 2).all() and np.isnan(det["abs_dif"][:, 3]).all() and (det["flags"][:, 1] == 17).sum() == 12
+    dry = np.zeros_like(p)
+    det, _ = _against_restatement(lon, lat, dry, days, what="an all-dry pool")
+    assert (det["flags"] == 1).all() and np.isnan(det["abs_dif"]).all()
+    assert (qa_prcp.pors_counts(dry, days) == 0).all()
+
+
+def test_stations_at_one_spot_257_fill_the_neighbour_cap_and_258_report_it():
+    nd = 70
+    days = get_days_metadata(dt.date(2001, 1, 1), dt.date(2001, 1, 1) + dt.timedelta(days=nd - 1))
+    n = _qalib.MAX_RADIUS_NGH + 2                                   # 258 at one spot: 257 neighbours each, one over the cap
+    lon, lat = np.full(n + 1, -110.0), np.full(n + 1, 45.0)
+    lon[-1] = -100.0                                                # one more, far away: 0 neighbours
+    p = np.zeros((nd, n + 1), np.float32)
+    p[10, 0] = 60.0
+    det = qa_prcp.run_qa_spatial_only(_pool(lon, lat, p, days), details=True)
+    assert (det["status"][:n] == _qalib.SP_NGH_CAP).all() and det["status"][n] == _qalib.SP_FEW_NGHS
+    assert (det["flags"] == 1).all() and np.isnan(det["abs_dif"]).all()
+    # 257 at one spot: exactly the cap, equal distances in table order, and the 60 cm are flagged
+    keep = np.r_[np.arange(n - 1), n]
+    det = qa_prcp.run_qa_spatial_only(_pool(lon[keep], lat[keep], p[:, keep], days), details=True)
+    assert (det["status"][:n - 1] == _qalib.SP_OK).all() and det["flags"][10, 0] == 17 and (det["flags"] == 17).sum() == 1
+    assert det["abs_dif"][10, 0] == 60.0 and det["thres"][10, 0] == RC.THRES
+
+
+def test_years_cap_and_non_consecutive_days_fail_the_call():
+    years = _qalib.PQ_MAX_WINDOW_VALUES // 29 + 1
+    days = get_days_metadata(dt.date(1800, 1, 1), dt.date(1800 + years - 1, 12, 31))
+    lon, lat = np.array([-110.0, -110.01, -110.02, -110.03]), np.full(4, 45.0)
+    p = np.zeros((days.size, 4), np.float32)
+    with pytest.raises(_qalib.QaError, match="TWXPQ_MAX_WINDOW_VALUES"):
+        qa_prcp.run_qa_spatial_only(_pool(lon, lat, p, days))
+    with pytest.raises(_qalib.QaError, match="TWXPQ_MAX_WINDOW_VALUES"):
+        qa_prcp.pors_counts(p, days)
+    keep = days.YEAR < 1800 + years - 1                             # one year fewer is inside the cap
+    p[::3] = 0.5
+    p[5000, 0] = 70.0
+    det, _ = _against_restatement(lon, lat, p[keep], days[keep], what="141 years")
+    assert det["flags"][5000, 0] == 17 and (det["flags"] == 17).sum() == 1 and abs(det["pctile"][5000, 0] - 100.0) < 1e-12
+    cnt = qa_prcp.pors_counts(p[keep], days[keep])
+    assert cnt.max() <= _qalib.PQ_MAX_WINDOW_VALUES and np.array_equal(cnt, RC.pors_counts(p[keep], days[keep][YMD]))
+    short = get_days_metadata(dt.date(2001, 1, 1), dt.date(2001, 3, 1))
+    gap = short[np.arange(short.size) != 20]
+    with pytest.raises(_qalib.QaError, match="not consecutive"):
+        qa_prcp.run_qa_spatial_only(_pool(lon, lat, np.zeros((gap.size, 4), np.float32), gap))
+
+
+# ---- the command line -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_command_line_spatial_and_all_write_end_to_end(tmp_path, capsys, gold, case, fmt):
+    pool, tavg, _ = case
+    lut = np.zeros(256, "S1")
+    for num, ch in qa_prcp.PRCP_TWX_TO_GHCN_FLAGS_MAP.items():
+        lut[num] = ch.encode()
+    out = str(tmp_path / "report.npz")
+    for chain in ("spatial", "all"):
+        want = gold["flags_" + chain]
+        db = PC.write_db(str(tmp_path / ("%s_%s.nc" % (chain, fmt))), pool.ids, pool.lon, pool.lat, pool.prcp, pool.tmin,
+                         pool.tmax, pool.days, fmt, qflags=())
+        before = open(db, "rb").read()
+        assert qa_prcp.main(["--db", db, "--out", out, "--" + chain]) == 0
+        rec = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+        assert open(db, "rb").read() == before                    # a report leaves the database alone
+        rep = np.load(out)
+        assert np.array_equal(rep["flags_prcp"], want) and rep["ids"].tolist() == pool.ids.tolist()
+        assert np.array_equal(rep["status"], np.where(gold["nngh"] < 3, 1, 0))
+        assert rec["flags_prcp"]["17"] == int((want == 17).sum()) > 0 and rec["status"] == {"0": 25, "1": 3}
+        assert rec["chain"] == ("spatial_only" if chain == "spatial" else "all") and rec["pc_walk_kernel_ms"] > 0
+        assert qa_prcp.main(["--db", db, "--out", out, "--" + chain, "--write"]) == 0
+        rec = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+        plain = (want == 1) | (want == 2)
+        assert rec["rows_written"] == int((~plain).sum()) > 0
+        back = qa_prcp.load_prcp_pool(db)
+        assert np.array_equal(back.qflag_prcp, lut[want.astype(np.int64)]) and (back.qflag_prcp == b"S").sum() == (want == 17).sum()
+        assert np.array_equal(back.prcp, pool.prcp, equal_nan=True)

@@ -1386,3 +1386,66 @@ def prcp_percentiles(vals, ymd, device=0, timing=None):
     if timing is not None:
         timing["pq_pctiles_kernel_ms"] = float(ms.value)
     return pct
+
+
+# ---- the precipitation QA's spatial corroboration check (twxpc_*; TWXPC_* of include/twx_qa.h) ----
+PC_EXPORTS = ("twxpc_spatial_corrob", "twxpc_pors_counts")
+PC_KERNELS = ("pc_radius", "pc_rowcounts", "pc_walk", "pc_rank")     # TWXPC_NKERNELS
+
+
+def prcp_spatial_corrob(lon, lat, prcp, ymd, target_idx, flags, device=0, details=False, timing=None):
+    """``twxpc_spatial_corrob``: ``_qa_spatial_corrob`` (qa_prcp.py:614-664) of the targets ``target_idx`` (rows of the pool)
+    in one call.  lon, lat [nstn]; prcp [nstn, ndays] float32, station-major, NaN = missing; ymd [ndays] consecutive days;
+    flags [ntarget, ndays] uint8, the working copy: a target's series is the pool value where its flag is 1.  Returns
+    ``(flags, status)``: a copy of the flags with 17 where a day is flagged and the flag was 1, and status [ntarget] int32
+    (``SP_OK``, ``SP_FEW_NGHS``, ``SP_NGH_CAP``); with ``details`` also ``abs_dif``, ``pctile``, ``thres`` [ntarget, ndays]
+    float64, NaN where the day did not reach that step.  ``timing`` receives ``<kernel>_kernel_ms`` for the names in
+    ``PC_KERNELS``.  Arguments are checked before anything touches the device."""
+    ymd = _c(ymd, np.int32)
+    prcp = _pq_series("prcp", prcp, ymd)
+    lon, lat = _c(lon, np.float64), _c(lat, np.float64)
+    nstn, ndays = prcp.shape
+    if lon.shape != (nstn,) or lat.shape != (nstn,):
+        raise ValueError("lon / lat must be [nstn]")
+    tgt = np.asarray(target_idx)
+    if tgt.ndim != 1 or tgt.size < 1 or not np.issubdtype(tgt.dtype, np.integer):
+        raise ValueError("target_idx must be a 1-d integer array with at least one entry")
+    if tgt.min() < 0 or tgt.max() >= nstn:
+        raise ValueError("target_idx outside 0 .. nstn - 1")
+    tgt = _c(tgt, np.int32)
+    fl = np.array(flags, np.uint8, order="C")                    # a copy: the input is not modified
+    if fl.shape != (tgt.size, ndays):
+        raise ValueError("flags must be [ntarget, ndays]")
+    fn = _pq_fn("twxpc_spatial_corrob", [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64] +
+                [C.c_void_p] * 7 + [C.c_char_p, C.c_int])
+    buf = C.create_string_buffer(512)
+    status = np.zeros(tgt.size, np.int32)
+    det = [np.empty((tgt.size, ndays)) for _ in range(3)] if details else [None] * 3
+    ms = (C.c_float * len(PC_KERNELS))()
+    rc = fn(int(device), nstn, ndays, lon.ctypes.data, lat.ctypes.data, prcp.ctypes.data, ymd.ctypes.data, tgt.size,
+            tgt.ctypes.data, fl.ctypes.data, status.ctypes.data, *[d.ctypes.data if details else None for d in det],
+            C.addressof(ms), buf, 512)
+    if rc != 0:
+        raise QaError("twxpc_spatial_corrob failed: %s" % buf.value.decode(errors="replace"))
+    if timing is not None:
+        for k, name in enumerate(PC_KERNELS):
+            timing[name + "_kernel_ms"] = float(ms[k])
+    return (fl, status) + tuple(det) if details else (fl, status)
+
+
+def prcp_pors_counts(vals, ymd, device=0, timing=None):
+    """``twxpc_pors_counts``: the sizes of ``_build_pors``' rows (qa_prcp.py:675-681) of every row of vals [nstn, ndays]
+    float32 (NaN = missing).  Returns [nstn, 366] uint16."""
+    ymd = _c(ymd, np.int32)
+    vals = _pq_series("vals", vals, ymd)
+    fn = _pq_fn("twxpc_pors_counts", [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 4 + [C.c_char_p, C.c_int])
+    buf = C.create_string_buffer(512)
+    cnt = np.empty((vals.shape[0], PQ_PCTILE_ROWS), np.uint16)
+    ms = C.c_float(0.0)
+    rc = fn(int(device), vals.shape[0], vals.shape[1], vals.ctypes.data, ymd.ctypes.data, cnt.ctypes.data,
+            C.addressof(ms), buf, 512)
+    if rc != 0:
+        raise QaError("twxpc_pors_counts failed: %s" % buf.value.decode(errors="replace"))
+    if timing is not None:
+        timing["pc_rowcounts_kernel_ms"] = float(ms.value)
+    return cnt

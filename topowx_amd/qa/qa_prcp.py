@@ -2,20 +2,24 @@
 constants of the reference, ``run_qa_non_spatial`` (qa_prcp.py:135-176: missing, the three duplicate checks, impossible
 values, gaps, climatological outliers; every station on its own, all stations in one call of libtwxqa's
 ``twxpq_non_spatial``), the two checks the reference defines but leaves commented out of its chain (``_qa_streak``,
-``_qa_frequent``; off by default), ``build_percentiles`` (``_build_percentiles``, :790-812, ``twxpq_percentiles``) and
-``load_prcp_pool``.  There is no CPU fallback: without the library the calls raise.
+``_qa_frequent``; off by default), ``build_percentiles`` (``_build_percentiles``, :790-812, ``twxpq_percentiles``),
+``load_prcp_pool``, and the spatial corroboration check ``qa_spatial_corrob`` (``_qa_spatial_corrob``, :614-664, flag 17;
+libtwxqa's ``twxpc_spatial_corrob``, every target in one call) with the two chains that end in it, ``run_qa_spatial_only``
+(:178-215) and ``run_qa_all`` (:87-133).  There is no CPU fallback: without the library the calls raise.
 
-Out of scope here: the spatial corroboration check ``_qa_spatial_corrob`` (flag 17), ``_qa_yr_clim_outlier`` (20),
-``run_qa_all`` and ``run_qa_spatial_only``.
+Out of scope here: ``_qa_yr_clim_outlier`` (20), which the reference defines and never calls.
 
     python -m topowx_amd.qa.qa_prcp --db all.nc --out report.npz [--streak] [--frequent] [--write] [--targets ids.txt]
+                                    [--spatial | --all]
 
 runs the chain on every station of an all-stations database (``prcp`` in cm, ``tmin`` / ``tmax`` for Tavg; observations
 of Tmin / Tmax that carry a quality flag do not enter Tavg), prints one JSON line (stations, days, the count of every
 flag number, seconds, kernel milliseconds) and writes ``report.npz``: ``ids``, ``ymd``, ``flags_prcp`` [ndays, nstn].  It
 is a report by default; ``--write`` puts the flags into ``qflag_prcp`` as the characters of ``TWX_TO_GHCN_FLAGS_MAP``, keeps
 a flag that is already there wherever the new one is 1 or 2, and creates ``qflag_prcp`` if the database lacks it.  Exits
-with 1 if the database cannot be opened or a target is unknown.
+with 1 if the database cannot be opened or a target is unknown.  ``--spatial`` runs ``run_qa_spatial_only`` instead and
+``--all`` ``run_qa_all`` (the two exclude each other): the neighbours of a target are all stations of the database, the
+JSON line also counts the targets of every ``status``, and ``report.npz`` also holds ``status``.
 """
 import argparse
 import json
@@ -29,6 +33,7 @@ from ..dates import YMD
 from .qa_temp import read_qflags
 
 __all__ = ["run_qa_non_spatial", "build_percentiles", "load_prcp_pool", "PrcpObsPool", "PRCP_NON_SPATIAL_FLAGS",
+           "qa_spatial_corrob", "run_qa_spatial_only", "run_qa_all", "pors_counts", "PRCP_SPATIAL_FLAGS",
            "QA_FREQUENT", "QA_YR_CLIM_OUTLIER", "PRCP_MIN_VALUE", "PRCP_MAX_VALUE", "STREAK_LEN", "GAP_THRES",
            "MIN_PERCENTILE_VALUES", "PERCENTILES", "MAX_SPATIAL_COLLAB_THRES", "PRCP_TWX_TO_GHCN_FLAGS_MAP",
            "PRCP_GHCN_TO_TWX_FLAGS_MAP"]
@@ -60,9 +65,12 @@ QA_YR_CLIM_OUTLIER = 20
 PRCP_NON_SPATIAL_FLAGS = (QA_MISSING, QA_DUP_YEAR, QA_DUP_YEAR_MONTH, QA_DUP_MONTH, QA_IMPOSS_VALUE, QA_STREAK, QA_FREQUENT,
                           QA_GAP, QA_CLIM_OUTLIER)
 
+# the numbers the spatial-only chain can produce (qa_prcp.py:210-212); run_qa_all: PRCP_NON_SPATIAL_FLAGS and 17
+PRCP_SPATIAL_FLAGS = (QA_MISSING, QA_SPATIAL_CORROB)
+
 PRCP_MIN_VALUE = 0.0
 PRCP_MAX_VALUE = 182.88               # world record daily precipitation, cm (qa_prcp.py:61)
-MAX_SPATIAL_COLLAB_THRES = 26.924     # qa_prcp.py:64-70: the constants of the spatial check, not used here
+MAX_SPATIAL_COLLAB_THRES = 26.924     # qa_prcp.py:64-70: the constants of the spatial check (the library holds its own)
 MAX_SPATIAL_COLLAB_THRES_MM = MAX_SPATIAL_COLLAB_THRES * 10.0
 NGH_RADIUS = 75.0
 ANOMALY_CUTOFF = 10.0
@@ -176,6 +184,80 @@ def load_prcp_pool(path, qflags=False):
     return PrcpObsPool(ids, col["longitude"], col["latitude"], col["prcp"], col["tmin"], col["tmax"], days, qf)
 
 
+def pors_counts(vals, days, device=0):
+    """The sizes of the rows of ``_build_pors(vals, _get_pctiles_md_masks(days, DATES_366))`` (qa_prcp.py:675-681, 814-832)
+    of each column of ``vals`` [ndays] or [ndays, n] (NaN = missing) on the GPU: row r counts the finite values > 0 whose
+    month-day lies within 14 days of the r-th date of 2004.  The spatial check takes a row as a percentile basis when it
+    holds MORE than ``MIN_PERCENTILE_VALUES`` values.  Returns [366] or [366, n] uint16."""
+    a = np.asarray(vals, np.float32)
+    if a.ndim not in (1, 2) or a.shape[0] != days.size:
+        raise ValueError("vals must be [ndays] or [ndays, n], with the days of ``days``")
+    one = a.ndim == 1
+    out = _qalib.prcp_pors_counts(np.ascontiguousarray(np.atleast_2d(a) if one else a.T), days[YMD], device=device)
+    return out[0].copy() if one else np.ascontiguousarray(out.T)
+
+
+def _target_cols(pool, targets):
+    if targets is None:
+        return np.arange(pool.ids.size, dtype=np.int64)
+    t = np.atleast_1d(np.asarray(targets))
+    if t.ndim != 1 or t.size < 1:
+        raise ValueError("targets must be a non-empty list of station ids or of columns of the pool")
+    if np.issubdtype(t.dtype, np.integer):
+        if t.min() < 0 or t.max() >= pool.ids.size:
+            raise ValueError("a target column lies outside the pool")
+        return t.astype(np.int64)
+    missing = [s for s in t.astype(str) if s not in pool.idxs]
+    if missing:
+        raise ValueError("%d target ids are not in the pool (first: %s)" % (len(missing), missing[0]))
+    return np.array([pool.idxs[s] for s in t.astype(str)], np.int64)
+
+
+def qa_spatial_corrob(pool, targets=None, flags=None, device=0, details=False, timing=None):
+    """``_qa_spatial_corrob`` (qa_prcp.py:614-664, 683-782) of the stations ``targets`` (ids or columns of ``pool``, a
+    ``PrcpObsPool``; default: every station) on the GPU, all in one call.  ``flags`` [ndays, ntarget] are the flags of the
+    checks that ran before: a target's series is its pool value where its flag is 1 (default: the flags of ``_qa_missing``,
+    2 where the value is NaN).  The neighbours of a target are all other stations of the pool within 75 km, with their
+    observations as they are.  Returns the flags with ``QA_SPATIAL_CORROB`` (17) where a day is not corroborated and its
+    flag was 1; the given array is not modified.  With ``details=True`` a dict: ``flags``, ``status`` [ntarget]
+    (``_qalib.SP_OK``, ``SP_FEW_NGHS``: fewer than 3 neighbours, ``SP_NGH_CAP``: more than ``_qalib.MAX_RADIUS_NGH``; no flag
+    in either case), ``abs_dif``, ``pctile`` and ``thres`` [ndays, ntarget] float64, NaN where the check did not get that far
+    on the day.  ``timing`` (a dict) receives the device time of each kernel group."""
+    cols = _target_cols(pool, targets)
+    nd = pool.days.size
+    if flags is None:
+        fl = np.where(np.isnan(pool.prcp[:, cols]), QA_MISSING, QA_OK).astype(np.uint8)
+    else:
+        fl = np.asarray(flags)
+        if fl.shape != (nd, cols.size):
+            raise ValueError("flags must be [ndays, ntarget]")
+    res = _qalib.prcp_spatial_corrob(pool.lon, pool.lat, np.ascontiguousarray(pool.prcp.T), pool.days[YMD], cols,
+                                     np.ascontiguousarray(fl.T), device=device, details=details, timing=timing)
+    out = np.ascontiguousarray(res[0].T)
+    if not details:
+        return out
+    return {"flags": out, "status": res[1], "abs_dif": np.ascontiguousarray(res[2].T),
+            "pctile": np.ascontiguousarray(res[3].T), "thres": np.ascontiguousarray(res[4].T)}
+
+
+def run_qa_spatial_only(pool, targets=None, device=0, details=False, timing=None):
+    """``run_qa_spatial_only`` (qa_prcp.py:178-215) of the stations ``targets`` of ``pool``: ``_qa_missing``, then the
+    spatial corroboration check.  Returns flags [ndays, ntarget] (``QA_OK`` and ``PRCP_SPATIAL_FLAGS``), or the dict of
+    ``qa_spatial_corrob`` with ``details=True``."""
+    return qa_spatial_corrob(pool, targets, None, device=device, details=details, timing=timing)
+
+
+def run_qa_all(pool, targets=None, streak=False, frequent=False, device=0, details=False, timing=None):
+    """``run_qa_all`` (qa_prcp.py:87-133) of the stations ``targets`` of ``pool``: the non-spatial chain
+    (``run_qa_non_spatial``; ``streak`` / ``frequent`` as there), then the spatial corroboration check on what it left.
+    Returns flags [ndays, ntarget] (``QA_OK``, ``PRCP_NON_SPATIAL_FLAGS`` and 17), or the dict of ``qa_spatial_corrob`` with
+    ``details=True``."""
+    cols = _target_cols(pool, targets)
+    fl = run_qa_non_spatial(pool.prcp[:, cols], pool.tavg[:, cols], pool.days, device=device, streak=streak,
+                            frequent=frequent, timing=timing)
+    return qa_spatial_corrob(pool, cols, fl, device=device, details=details, timing=timing)
+
+
 def merge_qflags(flags, prev):
     """The rule of step08's ``merge_qflags`` for one variable: ``(rows, chars)``, the entries to write (a flag other than
     1 / 2) and the character for each entry -- the new flag's, or the previous one where the new flag is 1 / 2."""
@@ -236,6 +318,10 @@ def main(argv=None):
     ap.add_argument("--streak", action="store_true", help="also run the reference's _qa_streak (flag 9)")
     ap.add_argument("--frequent", action="store_true", help="also run the reference's _qa_frequent (flag 19)")
     ap.add_argument("--write", action="store_true", help="update qflag_prcp in the database (created if it is not there)")
+    chain = ap.add_mutually_exclusive_group()
+    chain.add_argument("--spatial", action="store_true", help="run_qa_spatial_only: missing values, then the spatial "
+                       "corroboration check (flag 17) against every station of the database")
+    chain.add_argument("--all", action="store_true", help="run_qa_all: the non-spatial chain, then the spatial corroboration check")
     a = ap.parse_args(argv)
     try:
         ds = ncio.open_dataset(a.db, "r")
@@ -257,13 +343,26 @@ def main(argv=None):
     cols = [pool.idxs[s] for s in ids]
     tm = {}
     t0 = time.perf_counter()
-    flags = run_qa_non_spatial(pool.prcp[:, cols], pool.tavg[:, cols], pool.days, device=a.device, streak=a.streak,
-                               frequent=a.frequent, timing=tm)
+    extra, numbers = {}, (QA_OK,) + PRCP_NON_SPATIAL_FLAGS
+    if a.spatial or a.all:
+        if a.spatial:
+            res = run_qa_spatial_only(pool, cols, device=a.device, details=True, timing=tm)
+            numbers = (QA_OK,) + PRCP_SPATIAL_FLAGS
+        else:
+            res = run_qa_all(pool, cols, streak=a.streak, frequent=a.frequent, device=a.device, details=True, timing=tm)
+            numbers += (QA_SPATIAL_CORROB,)
+        flags, extra = res["flags"], {"status": res["status"]}
+    else:
+        flags = run_qa_non_spatial(pool.prcp[:, cols], pool.tavg[:, cols], pool.days, device=a.device, streak=a.streak,
+                                   frequent=a.frequent, timing=tm)
     sec = time.perf_counter() - t0
-    np.savez_compressed(a.out, ids=ids, ymd=np.asarray(pool.days[YMD], np.int32), flags_prcp=flags)
+    np.savez_compressed(a.out, ids=ids, ymd=np.asarray(pool.days[YMD], np.int32), flags_prcp=flags, **extra)
     line = {"stations": int(ids.size), "pool": int(pool.ids.size), "days": int(pool.days.size),
-            "flags_prcp": {str(k): int((flags == k).sum()) for k in (QA_OK,) + PRCP_NON_SPATIAL_FLAGS},
+            "flags_prcp": {str(k): int((flags == k).sum()) for k in numbers},
             "seconds": round(sec, 3)}
+    if extra:
+        line["chain"] = "spatial_only" if a.spatial else "all"
+        line["status"] = {str(int(k)): int((extra["status"] == k).sum()) for k in np.unique(extra["status"])}
     for k in sorted(tm):
         line[k] = round(tm[k], 3)
     if a.write:
