@@ -1119,6 +1119,65 @@ int twxpc_spatial_corrob(int device, int64_t nstn, int64_t ndays, const double *
 int twxpc_pors_counts(int device, int64_t nstn, int64_t ndays, const float *vals, const int32_t *ymd, uint16_t *counts,
                       float *kernel_ms, char *errbuf, int errlen);
 
+/* ---- the GHCN-Daily ingest of step04: InsertGhcn.parse_stn_obs (twx/db/create_db_all_stations.py:1042-1103) for a batch
+ * of .dly files, and create_tobs_db (twx/homog/tobs.py:121-157) for a batch of by-year CSV files; twx_ghcn.hip.  Both see
+ * one byte buffer of files laid end to end: file_off [nfiles + 1] int64 from 0 to nbytes.  A last line without a newline is
+ * a line; lines never span files.  Out of scope: InsertSnotel / InsertRaws, add_utc_offset, downloading. ---- */
+#define TWXGH_NKERNELS 4                /* kernel groups timed: fill; line index; claim pass; write pass */
+#define TWXGH_MAX_BYTES ((int64_t)2147483584)   /* of one call's buffer: a line's position + 1 is a uint32 */
+#define TWXGH_MAX_CELLS ((int64_t)1 << 31)      /* 3 nrows ndays of a .dly call, nstn nwin of a by-year call */
+#define TWXGH_FB_WORDS 8                /* uint32 words of a fallback entry */
+#define TWXGH_NO_BAD_HEADER 0xffffffffu
+#define TWXGH_DC_LINES 0                /* counts of twxgh_parse_dly: entries of the line index (with the dropped ones) */
+#define TWXGH_DC_VALUES 1               /*   day fields that gave a value (duplicates counted each time) */
+#define TWXGH_DC_FALLBACK 2             /*   fields only Python's float() can decide (may exceed fallback_cap) */
+#define TWXGH_DC_N 3
+#define TWXGH_TC_VALUES 0               /* counts of twxgh_parse_tobs: lines that gave a value in the window */
+#define TWXGH_TC_OUTSIDE 1              /*   selected lines of a known station whose date is no day of the period */
+#define TWXGH_TC_OTHER_WINDOW 2         /*   ... whose date is a day of the period outside the window */
+#define TWXGH_TC_BAD 3                  /*   ... whose date or value int() would not take as [+-]?digits (may exceed bad_cap) */
+#define TWXGH_TC_N 4                    /* counts [TWXGH_TC_N + 1]: the last entry is the line index's size */
+
+/*
+ * parse_stn_obs of nfiles .dly files in one call.  File f writes row file_col[f] (distinct, 0 .. nrows - 1) of
+ * val, qflag [3][nrows][ndays] (TMIN, TMAX, PRCP; float32 pre-set to -9999, uint8 pre-set to 0), ndays the days from
+ * min_ymd to max_ymd.  Per line: int(line[11:15]), int(line[15:17]), line[17:21] one of the three elements (other lines
+ * are skipped whole); per day field, in the reference's order: a valid date, inside the period, the value field
+ * line[21 + 8 (d - 1) : 26 + 8 (d - 1)] clipped to the line's end.  A value is canonical if, stripped of Python's
+ * whitespace, it is [+-]?[0-9]+: -9999 stays, PRCP is v / 100.0, temperatures v / 10.0 in fp64, rounded once to float32;
+ * the flag is byte 27 + 8 (d - 1) if inside the line, whitespace = 0.  An empty value is skipped.  Any other text is listed:
+ * fallback [fallback_cap][TWXGH_FB_WORDS] = file, line position in the file, line length, day field 0 .. 30, element, the
+ * position + 1 in the buffer of the canonical line that won the field's (row, day, element) (0: none), the day's index,
+ * the line's position in the buffer; sorted by position then day.  When several lines give a (day, element) the LAST one
+ * whose field was not skipped wins (value and flag, -9999 included): integer atomicMax of the position, no result depends
+ * on scheduling.  bad_header [nfiles]: the position in the file of the first line whose year or month is not canonical (an
+ * empty line is one), TWXGH_NO_BAD_HEADER if none; such lines write nothing.  counts [TWXGH_DC_N].
+ * kernel_ms (optional) [TWXGH_NKERNELS].  Every argument is checked before anything touches the device.
+ */
+int twxgh_parse_dly(int device, const uint8_t *buf, int64_t nbytes, int64_t nfiles, const int64_t *file_off,
+                    const int32_t *file_col, int64_t nrows, int32_t min_ymd, int32_t max_ymd, int64_t ndays, float *val,
+                    uint8_t *qflag, uint32_t *bad_header, uint32_t *fallback, int64_t fallback_cap, int64_t *counts,
+                    float *kernel_ms, char *errbuf, int errlen);
+
+/*
+ * create_tobs_db on nfiles by-year CSV files (ID(11),YYYYMMDD(8),ELEM(4),value,m,q,s,HHMM), in buffer order.  The filter of
+ * create_tobs_file (tobs.py:61-62) restated: the element field equals element (four characters), the id starts with US / CA
+ * / MX, the last character is a digit, the line does not end in 2400.  ids [nstn][11]: the sorted station ids without
+ * their GHCN_ prefix; an unknown station is skipped.  Day = int(line[12:20]); value = int() of the last five
+ * characters of the line as grep prints it, newline included: the last four of its text.  tobs [nstn][nwin] int16, IN and OUT: the days win0 .. win0 + nwin - 1 of the period; only
+ * the entries a line gives are changed, the last line winning as in twxgh_parse_dly.  One deviation: a date that is no day
+ * of the period is skipped and counted (the reference dies with IndexError).  bad [bad_cap][2]: file and position of the
+ * lines whose date or value is not [+-]?[0-9]+ or does not fit int16, sorted.  counts [TWXGH_TC_N + 1].
+ */
+int twxgh_parse_tobs(int device, const uint8_t *buf, int64_t nbytes, int64_t nfiles, const int64_t *file_off, int64_t nstn,
+                     const uint8_t *ids, const char *element, int32_t min_ymd, int32_t max_ymd, int64_t win0, int64_t nwin,
+                     int16_t *tobs, uint32_t *bad, int64_t bad_cap, int64_t *counts, float *kernel_ms, char *errbuf,
+                     int errlen);
+
+/* Page-locked host memory for the file buffer (NULL on failure), and its release. */
+void *twxgh_host_alloc(int64_t nbytes);
+void twxgh_host_free(void *p);
+
 #ifdef __cplusplus
 }
 #endif

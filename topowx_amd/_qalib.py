@@ -1449,3 +1449,140 @@ def prcp_pors_counts(vals, ymd, device=0, timing=None):
     if timing is not None:
         timing["pc_rowcounts_kernel_ms"] = float(ms.value)
     return cnt
+
+
+# ---- the GHCN-Daily ingest of step04 (twxgh_*; TWXGH_* of include/twx_qa.h) ----
+GH_EXPORTS = ("twxgh_parse_dly", "twxgh_parse_tobs", "twxgh_host_alloc", "twxgh_host_free")
+GH_KERNELS = ("gh_fill", "gh_index", "gh_claim", "gh_write")     # TWXGH_NKERNELS
+GH_MAX_BYTES = 2147483584             # TWXGH_MAX_BYTES
+GH_FB_WORDS = 8                       # TWXGH_FB_WORDS
+GH_NO_BAD_HEADER = 0xffffffff         # TWXGH_NO_BAD_HEADER
+GH_ELEMENTS = ("TMIN", "TMAX", "PRCP")
+GH_MISSING = -9999.0
+
+
+def _gh_buffer(buf, file_off):
+    """(address, nbytes, file_off int64) of a byte buffer and its file offsets, checked."""
+    off = _c(file_off, np.int64)
+    if off.ndim != 1 or off.size < 2 or off[0] != 0 or np.any(np.diff(off) < 0):
+        raise ValueError("file_off must be [nfiles + 1] int64, from 0, not decreasing")
+    mv = memoryview(buf).cast("B")
+    if mv.nbytes < int(off[-1]):
+        raise ValueError("the buffer holds %d bytes, file_off ends at %d" % (mv.nbytes, int(off[-1])))
+    if int(off[-1]) > GH_MAX_BYTES:
+        raise ValueError("a call takes at most TWXGH_MAX_BYTES = %d bytes" % GH_MAX_BYTES)
+    a = np.frombuffer(mv, np.uint8)
+    return a, int(off[-1]), off
+
+
+def _gh_timing(timing, ms):
+    if timing is not None:
+        for k, name in enumerate(GH_KERNELS):
+            timing[name + "_kernel_ms"] = timing.get(name + "_kernel_ms", 0.0) + float(ms[k])
+
+
+def ghcn_parse_dly(buf, file_off, file_col, nrows, min_ymd, max_ymd, ndays, fallback_cap=4096, device=0, timing=None):
+    """``twxgh_parse_dly``: ``InsertGhcn.parse_stn_obs`` (create_db_all_stations.py:1042-1103) of the .dly files laid end to
+    end in ``buf`` (any object with the buffer protocol) at ``file_off`` [nfiles + 1]; file f fills row ``file_col[f]``.
+    Returns ``(val [3, nrows, ndays] float32, qflag [3, nrows, ndays] uint8, bad_header [nfiles] uint32, fallback [n, 8]
+    uint32, counts [3] int64)`` as include/twx_qa.h describes them; the call is repeated once with room for every
+    fallback entry if ``fallback_cap`` was too small.  Arguments are checked before anything touches the device."""
+    a, nbytes, off = _gh_buffer(buf, file_off)
+    col = _c(file_col, np.int32)
+    nfiles = off.size - 1
+    nrows, ndays = int(nrows), int(ndays)
+    if col.shape != (nfiles,) or nrows < 1 or (nfiles and (col.min() < 0 or col.max() >= nrows)) or np.unique(col).size != nfiles:
+        raise ValueError("file_col must be [nfiles] distinct rows in 0 .. nrows - 1")
+    if ndays < 1:
+        raise ValueError("ndays must be the number of days from min_ymd to max_ymd")
+    fn = _pq_fn("twxgh_parse_dly", [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                    C.c_int32, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p,
+                                                                                C.c_char_p, C.c_int])
+    cap = int(fallback_cap)
+    while True:
+        val = np.empty((3, nrows, ndays), np.float32)
+        qf = np.empty((3, nrows, ndays), np.uint8)
+        bad = np.empty(nfiles, np.uint32)
+        fb = np.zeros((max(cap, 1), GH_FB_WORDS), np.uint32)
+        counts = np.zeros(3, np.int64)
+        ms = (C.c_float * len(GH_KERNELS))()
+        buf512 = C.create_string_buffer(512)
+        rc = fn(int(device), a.ctypes.data if nbytes else None, nbytes, nfiles, off.ctypes.data, col.ctypes.data, nrows,
+                int(min_ymd), int(max_ymd), ndays, val.ctypes.data, qf.ctypes.data, bad.ctypes.data, fb.ctypes.data, cap,
+                counts.ctypes.data, C.addressof(ms), buf512, 512)
+        if rc != 0:
+            raise QaError("twxgh_parse_dly failed: %s" % buf512.value.decode(errors="replace"))
+        _gh_timing(timing, ms)
+        if counts[2] <= cap:
+            return val, qf, bad, fb[:int(counts[2])].copy(), counts
+        cap = int(counts[2])
+
+
+def ghcn_parse_tobs(buf, file_off, ids11, element, min_ymd, max_ymd, win0, tobs, bad_cap=4096, device=0, timing=None):
+    """``twxgh_parse_tobs``: ``create_tobs_db`` (tobs.py:121-157) on the by-year CSV files laid end to end in ``buf``.
+    ``ids11``: the sorted station ids without ``GHCN_`` (``"S11"``); ``tobs`` [nstn, nwin] int16, the days ``win0 .. win0 +
+    nwin - 1`` of the period, updated IN PLACE.  Returns ``(bad [n, 2] uint32, counts [5] int64)``: counts are values,
+    dates outside the period, dates outside the window, bad lines, lines."""
+    a, nbytes, off = _gh_buffer(buf, file_off)
+    ids = np.ascontiguousarray(ids11, "S11")
+    if ids.ndim != 1 or ids.size < 1 or np.any(ids[1:] <= ids[:-1]):
+        raise ValueError("ids11 must be a sorted 1-d array of distinct ids")
+    if not (isinstance(tobs, np.ndarray) and tobs.dtype == np.int16 and tobs.flags.c_contiguous and tobs.flags.writeable and
+            tobs.ndim == 2 and tobs.shape[0] == ids.size and tobs.shape[1] >= 1):
+        raise ValueError("tobs must be a C-contiguous writeable int16 array [nstn, nwin]")
+    elem = str(element).encode()
+    if len(elem) != 4:
+        raise ValueError("the element is four characters")
+    table = np.zeros((ids.size, 11), np.uint8)
+    for k, s in enumerate(ids):
+        table[k, :len(s)] = np.frombuffer(s, np.uint8)
+    fn = _pq_fn("twxgh_parse_tobs", [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_char_p,
+                                     C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.c_void_p, C.c_void_p, C.c_char_p, C.c_int])
+    cap = int(bad_cap)
+    keep = tobs.copy()
+    while True:
+        bad = np.zeros((max(cap, 1), 2), np.uint32)
+        counts = np.zeros(5, np.int64)
+        ms = (C.c_float * len(GH_KERNELS))()
+        buf512 = C.create_string_buffer(512)
+        rc = fn(int(device), a.ctypes.data if nbytes else None, nbytes, off.size - 1, off.ctypes.data, ids.size,
+                table.ctypes.data, elem, int(min_ymd), int(max_ymd), int(win0), tobs.shape[1], tobs.ctypes.data,
+                bad.ctypes.data, cap, counts.ctypes.data, C.addressof(ms), buf512, 512)
+        if rc != 0:
+            raise QaError("twxgh_parse_tobs failed: %s" % buf512.value.decode(errors="replace"))
+        _gh_timing(timing, ms)
+        if counts[3] <= cap:
+            return bad[:int(counts[3])].copy(), counts
+        cap = int(counts[3])
+        tobs[:] = keep
+
+
+class PinnedBuffer(object):
+    """``nbytes`` of page-locked host memory (``twxgh_host_alloc``) with the buffer protocol: ``view`` is a writable
+    memoryview, ``close()`` releases it."""
+
+    def __init__(self, nbytes):
+        lib = load()
+        lib.twxgh_host_alloc.restype, lib.twxgh_host_alloc.argtypes = C.c_void_p, [C.c_int64]
+        lib.twxgh_host_free.restype, lib.twxgh_host_free.argtypes = None, [C.c_void_p]
+        self._lib, self.nbytes = lib, int(nbytes)
+        self._p = lib.twxgh_host_alloc(self.nbytes)
+        if not self._p:
+            raise QaError("twxgh_host_alloc(%d) failed" % self.nbytes)
+        self.view = memoryview((C.c_ubyte * self.nbytes).from_address(self._p)).cast("B")
+
+    def close(self):
+        if self._p:
+            try:
+                self.view.release()
+            except BufferError:                                    # still exported somewhere: keep the memory, try again later
+                return
+            self._lib.twxgh_host_free(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -1,0 +1,57 @@
+"""``create_netcdf_db`` / ``insert_data_netcdf_db`` with ``InsertGhcn`` (the reference's step04): the all-stations database
+from GHCN-Daily's ``ghcnd-stations.txt`` and ``.dly`` files, parsed on the GPU (``twxgh_parse_dly``), and with ``--by-year``
+the times of observation of Tmax from the by-year CSV files (``twxgh_parse_tobs``) as ``tobs_tmax``: the file every command
+from step05 on takes as ``--db``.
+
+    python -m topowx_amd.step04 --stations ghcnd-stations.txt --dly-dir DIR --out all.nc --start YMD --end YMD
+                                [--by-year DIR] [--check-obs-exist] [--format NETCDF4|NETCDF3_64BIT] [--device N]
+
+``--start`` / ``--end``: ``yyyymmdd`` or ``yyyy-mm-dd``, inclusive.  US / CA / MX stations outside HI and AK that are not
+SNOTEL or RAWS sites are inserted; a station without a ``.dly`` file is an error unless ``--check-obs-exist`` drops it.
+``--by-year DIR`` holds ``<year>.csv.gz`` (or ``<year>.csv``) for every year of the period.  The station variables are not
+compressed.  Out of scope: SNOTEL / RAWS inserts, ``add_utc_offset``, downloading.
+
+Prints one JSON line (stations, days, bytes, lines, values, fallback fields, seconds, kernel milliseconds).  Exits with 1
+if a file is missing, a date is bad or a line's header is not a number.
+"""
+import argparse
+import json
+import sys
+import time
+
+from . import ghcn, ncio
+
+__all__ = ["main"]
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m topowx_amd.step04", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--stations", required=True, help="ghcnd-stations.txt")
+    ap.add_argument("--dly-dir", required=True, help="directory of the <id>.dly files")
+    ap.add_argument("--out", required=True, help="the all-stations database to write (netCDF)")
+    ap.add_argument("--start", required=True, help="first day of the period, yyyymmdd")
+    ap.add_argument("--end", required=True, help="last day of the period, yyyymmdd")
+    ap.add_argument("--by-year", help="directory of the by-year files <year>.csv.gz: writes tobs_tmax")
+    ap.add_argument("--check-obs-exist", action="store_true", help="drop the stations without a .dly file")
+    ap.add_argument("--format", choices=ncio.FORMATS, help="container (default: NETCDF4 when libhdf5 loads)")
+    ap.add_argument("--device", type=int, default=0)
+    a = ap.parse_args(argv)
+    tm, st = {}, {}
+    t0 = time.perf_counter()
+    try:
+        stns = ghcn.create_all_stations_db(a.out, a.stations, a.dly_dir, a.start, a.end, path_by_year=a.by_year,
+                                           check_obs_exist=a.check_obs_exist, format=a.format, device=a.device, timing=tm,
+                                           stats=st)
+    except (IOError, OSError, ValueError, KeyError) as e:
+        print("step04: %s" % e, file=sys.stderr)
+        return 1
+    line = {"stations": int(stns.size), "days": ghcn._period(a.start, a.end)[3], "seconds": round(time.perf_counter() - t0, 3)}
+    for src in (st, tm):
+        for k in sorted(src):
+            line[k] = round(src[k], 3) if isinstance(src[k], float) else src[k]
+    print(json.dumps(line), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

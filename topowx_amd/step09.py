@@ -11,7 +11,8 @@ existing output file is not overwritten.
 Prints one JSON line (stations kept, per variable the stations with a record, stations whose Tmax moved; seconds, kernel
 milliseconds).  Exits with 1 if a file cannot be opened or written or a variable is missing.
 
-Out of scope: ``create_tobs_file`` / ``create_tobs_db`` (the search of GHCN-D's yearly files that fills ``tobs_tmax``).
+``tobs_tmax`` is what ``python -m topowx_amd.step04 --by-year DIR`` writes (``create_tobs_file`` / ``create_tobs_db``: the
+search of GHCN-D's yearly files).
 """
 import argparse
 import json
