@@ -1178,6 +1178,65 @@ int twxgh_parse_tobs(int device, const uint8_t *buf, int64_t nbytes, int64_t nfi
 void *twxgh_host_alloc(int64_t nbytes);
 void twxgh_host_free(void *p);
 
+/* ---- the North American reanalysis subsets of step12: create_nnr_subset, create_nnr_subset_nolevel and
+ * create_thickness_nnr_subset (twx/db/reanalysis.py:45-305) for every product of one raw variable in one call;
+ * twx_nnrsub.hip.  Out of scope: step13's time-zone lookup, downloading, deflate of the subsets. ---- */
+#define TWXNS_NKERNELS 3                /* groups timed: upload; the subset kernels (one launch per product); download */
+#define TWXNS_I16 0                     /* dtype of the raw slab: packed short */
+#define TWXNS_F32 1                     /*   float */
+#define TWXNS_TILED 0                   /* layout: chunk-major [cy][cx][day][lev][4][4], edge chunks padded with the fill */
+#define TWXNS_PLAIN 1                   /*   [day][lev][lat][lon] */
+#define TWXNS_CONV_NONE 0
+#define TWXNS_CONV_K_TO_C 1             /* u - f32(273.15) */
+#define TWXNS_KIND_LEVELS 0             /* a product of nlev_out >= 1 level indices */
+#define TWXNS_KIND_THICK 1              /*   the difference of two levels: u[idx_up] - u[idx_low] */
+#define TWXNS_FILL 9.969209968386869e36f   /* netCDF4.default_fillvals['f4'] */
+#define TWXNS_MAX_LEV 32                /* level indices of a product (the reanalysis has 17 levels) */
+#define TWXNS_MAX_PROD 64               /* products of a call */
+#define TWXNS_MAX_DAYS (1 << 20)        /* days of the period (2870 years) */
+#define TWXNS_MAX_SIDE 4096             /* nlat_out, nlon_out */
+#define TWXNS_MAX_RAW ((int64_t)1 << 32)   /* values of the raw slab: 8 GiB of short, 16 GiB of float */
+#define TWXNS_MAX_OUT ((int64_t)1 << 31)   /* values of one product, padding included: 8 GiB */
+#define TWXNS_PD_SLOT 0                 /* words of a product descriptor: the slot, 0 / 1 / 2 = 12z / 18z / 24z */
+#define TWXNS_PD_KIND 1                 /*   TWXNS_KIND_* */
+#define TWXNS_PD_CONV 2                 /*   TWXNS_CONV_* */
+#define TWXNS_PD_NLEV 3                 /*   nlev_out of TWXNS_KIND_LEVELS (ignored for a thickness: its output has one level) */
+#define TWXNS_PD_LEV0 4                 /*   the level indices from here on; a thickness: idx_up, idx_low */
+#define TWXNS_PD_WORDS (TWXNS_PD_LEV0 + TWXNS_MAX_LEV)
+#define TWXNS_C_DAYS 0                  /* counts of a product: days that received a record */
+#define TWXNS_C_MARKED 1                /*   values written as fill because a raw datum equalled a mark */
+#define TWXNS_C_UNWRITTEN 2             /*   days of the period left unwritten (all fill) */
+#define TWXNS_C_N 3
+
+/*
+ * All years of one raw variable, every product made of it.  Stateless.
+ * raw [nrec][nl][ny][nx]     int16 (TWXNS_I16) or float32 (TWXNS_F32); nl = 1 for a variable without levels.  The caller may
+ *                            have cut the slab to the levels and rows in use: the entry only sees index lists.
+ * scale, offset              u = f32(f32(x) * scale) + offset, two roundings.  scale 1 with offset 0 leaves the datum as it
+ *                            is (a float -0 stays -0): what to pass for a variable without packing attributes.
+ * marks [2], has_mark [2]    missing_value and _FillValue in the raw dtype, and whether each exists.  A datum that EQUALS a
+ *                            present mark (floats by value: NaN equals nothing) gives the fill; a thickness is fill if either
+ *                            level is marked.
+ * rec_slot, rec_day [nrec]   0 / 1 / 2 or -1 (a record nobody uses); the output day 0 .. ndays - 1 or -1 (outside the period)
+ * lat_idx [nlat_out], lon_idx [nlon_out]   raw rows / columns of the output's; any order, repeats allowed
+ * prod [nprod][TWXNS_PD_WORDS]   the product descriptors (TWXNS_PD_*); Kelvin to Celsius is u - f32(273.15), after the
+ *                            difference of a thickness
+ * out [nprod]                host buffers of float32: TWXNS_TILED ceil(nlat_out / 4) ceil(nlon_out / 4) ndays nlev 16 values,
+ *                            TWXNS_PLAIN ndays nlev nlat_out nlon_out.  A day without a record is TWXNS_FILL, and so is the
+ *                            padding of an edge chunk: every byte is determined.
+ * counts [nprod][TWXNS_C_N]  int64
+ * kernel_ms (optional) [TWXNS_NKERNELS]
+ * Every output element is written by exactly one thread; the only atomics are integer additions to the mark counts: two
+ * calls give the same bytes.  Every argument is checked before anything touches the device: a dtype or layout flag, sizes
+ * beyond the TWXNS_MAX_* limits, an index outside the slab, nlev_out < 1, a thickness of one level twice, and two records
+ * that map to the same (slot, day) -- refused, naming both.
+ */
+int twxns_subset(int device, int dtype, const void *raw, int64_t nrec, int64_t nl, int64_t ny, int64_t nx, float scale,
+                 float offset, const void *marks, const int32_t *has_mark, const int32_t *rec_slot, const int32_t *rec_day,
+                 int64_t ndays, int64_t nlat_out, const int32_t *lat_idx, int64_t nlon_out, const int32_t *lon_idx,
+                 int64_t nprod, const int32_t *prod, int layout, float *const *out, int64_t *counts, float *kernel_ms,
+                 char *errbuf, int errlen);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1586,3 +1586,96 @@ class PinnedBuffer(object):
             self.close()
         except Exception:
             pass
+
+
+# ---- the reanalysis subsets of step12 (twxns_subset; TWXNS_* of include/twx_qa.h) ----
+NS_EXPORTS = ("twxns_subset",)
+NS_KERNELS = ("nsub_upload", "nsub_kernels", "nsub_download")          # TWXNS_NKERNELS
+NS_I16, NS_F32 = 0, 1                 # TWXNS_I16, TWXNS_F32
+NS_TILED, NS_PLAIN = 0, 1             # TWXNS_TILED, TWXNS_PLAIN
+NS_CONV = {"none": 0, "k_to_c": 1}    # TWXNS_CONV_*
+NS_KIND_LEVELS, NS_KIND_THICK = 0, 1  # TWXNS_KIND_*
+NS_MAX_LEV = 32                       # TWXNS_MAX_LEV
+NS_MAX_PROD = 64                      # TWXNS_MAX_PROD
+NS_MAX_DAYS = 1 << 20                 # TWXNS_MAX_DAYS
+NS_MAX_SIDE = 4096                    # TWXNS_MAX_SIDE
+NS_PD_WORDS = 4 + NS_MAX_LEV          # TWXNS_PD_WORDS
+NS_C_DAYS, NS_C_MARKED, NS_C_UNWRITTEN = 0, 1, 2                 # TWXNS_C_*
+NS_FILL = np.float32(9.969209968386869e36)                       # TWXNS_FILL
+
+
+def ns_out_shape(layout, ndays, nlev, nlat_out, nlon_out):
+    """The shape of one product of ``ns_subset`` in a layout."""
+    if layout == NS_TILED:
+        return ((nlat_out + 3) // 4, (nlon_out + 3) // 4, ndays, nlev, 4, 4)
+    return (ndays, nlev, nlat_out, nlon_out)
+
+
+def ns_subset(raw, scale, offset, marks, rec_slot, rec_day, ndays, lat_idx, lon_idx, products, layout=NS_TILED, dtype=None,
+              device=0, timing=None):
+    """``twxns_subset``: every product of one raw reanalysis variable from one upload of its records.
+
+    ``raw`` [nrec, nl, ny, nx] (or [nrec, ny, nx]) int16 or float32, the STORED values; ``scale`` / ``offset``: the packing
+    (1 and 0 for none); ``marks``: ``(missing_value, _FillValue)``, ``None`` for an absent one; ``rec_slot`` / ``rec_day``
+    [nrec]: 0 / 1 / 2 (12z, 18z, 24z) or -1, and the output day or -1; ``lat_idx`` / ``lon_idx``: raw rows / columns of the
+    output; ``products``: dicts with ``slot``, either ``levels`` (level indices) or ``thick`` = (idx_up, idx_low), and
+    ``conv`` ("none" / "k_to_c").  Returns ``(outs, counts)``: per product a float32 array of ``ns_out_shape`` and
+    ``counts`` [nprod, 3] int64 (days with a record, values filled for a mark, days unwritten).  What the library refuses
+    (include/twx_qa.h) raises ``QaError`` before anything touches the device."""
+    raw = np.asarray(raw)
+    if dtype is None:
+        if raw.dtype not in (np.dtype(np.int16), np.dtype(np.float32)):
+            raise ValueError("raw must be int16 or float32, not %s" % raw.dtype)
+        dtype = NS_I16 if raw.dtype == np.int16 else NS_F32
+    if raw.ndim == 3:
+        raw = raw[:, None]
+    if raw.ndim != 4 or not raw.flags.c_contiguous or raw.dtype.byteorder not in "=|":
+        raise ValueError("raw must be a C-contiguous native [nrec, nl, ny, nx] array")
+    nrec, nl, ny, nx = raw.shape
+    slot, day = _c(rec_slot, np.int32), _c(rec_day, np.int32)
+    lat, lon = _c(lat_idx, np.int32), _c(lon_idx, np.int32)
+    if slot.shape != (nrec,) or day.shape != (nrec,) or lat.ndim != 1 or lon.ndim != 1:
+        raise ValueError("rec_slot / rec_day must be [nrec], lat_idx / lon_idx 1-d")
+    mk = np.zeros(2, raw.dtype if raw.dtype.itemsize in (2, 4) else np.float32)
+    has = np.zeros(2, np.int32)
+    for k, m in enumerate(tuple(marks) + (None,) * (2 - len(tuple(marks)))):
+        if m is not None:
+            mk[k], has[k] = m, 1
+    nprod = len(products)
+    pd = np.zeros((max(nprod, 1), NS_PD_WORDS), np.int32)
+    nlevs = []
+    for p, d in enumerate(products):
+        if d.get("conv", "none") not in NS_CONV:
+            raise ValueError("conv must be 'none' or 'k_to_c'")
+        pd[p, 0], pd[p, 2] = int(d["slot"]), NS_CONV[d.get("conv", "none")]
+        if d.get("thick") is not None:
+            pd[p, 1], pd[p, 3] = NS_KIND_THICK, 1
+            pd[p, 4:6] = d["thick"]
+            nlevs.append(1)
+        else:
+            lv = np.asarray(d["levels"], np.int32).ravel()
+            pd[p, 1], pd[p, 3] = NS_KIND_LEVELS, lv.size
+            pd[p, 4:4 + min(lv.size, NS_MAX_LEV)] = lv[:NS_MAX_LEV]
+            nlevs.append(max(1, min(int(lv.size), NS_MAX_LEV)))
+    ndays = int(ndays)
+    big = not (1 <= ndays <= NS_MAX_DAYS and 1 <= lat.size <= NS_MAX_SIDE and 1 <= lon.size <= NS_MAX_SIDE and
+               1 <= nprod <= NS_MAX_PROD)                      # the library refuses these: no buffer of such a size is made
+    shapes = [(1,) if big else ns_out_shape(layout, ndays, n, lat.size, lon.size) if layout in (NS_TILED, NS_PLAIN) else (1,)
+              for n in nlevs]
+    outs = [np.empty(s, np.float32) for s in shapes] or [np.empty(1, np.float32)]
+    ptrs = (C.c_void_p * len(outs))(*[o.ctypes.data for o in outs])
+    counts = np.zeros((max(nprod, 1), 3), np.int64)
+    ms = (C.c_float * len(NS_KERNELS))()
+    fn = _pq_fn("twxns_subset", [C.c_int, C.c_int, C.c_void_p] + [C.c_int64] * 4 + [C.c_float, C.c_float] + [C.c_void_p] * 4 +
+                [C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int] + [C.c_void_p] * 3 +
+                [C.c_char_p, C.c_int])
+    buf512 = C.create_string_buffer(512)
+    rc = fn(int(device), int(dtype), raw.ctypes.data, nrec, nl, ny, nx, float(np.float32(scale)), float(np.float32(offset)),
+            mk.ctypes.data, has.ctypes.data, slot.ctypes.data, day.ctypes.data, ndays, lat.size, lat.ctypes.data, lon.size,
+            lon.ctypes.data, nprod, pd.ctypes.data, int(layout), C.addressof(ptrs), counts.ctypes.data, C.addressof(ms), buf512, 512)
+    if rc != 0:
+        raise QaError("twxns_subset failed: %s" % buf512.value.decode(errors="replace"))
+    if timing is not None:
+        for k, name in enumerate(NS_KERNELS):
+            timing[name + "_ms"] = timing.get(name + "_ms", 0.0) + float(ms[k])
+    return outs, counts[:nprod]

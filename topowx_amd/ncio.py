@@ -166,7 +166,7 @@ class _Classic(object):
     """``scipy.io.netcdf_file`` with netCDF4-python's method names (a variable's data stays in memory until close)."""
     _OWN = ("_nc", "path", "mode", "variables", "data_model")
 
-    def __init__(self, path, mode="r", version=2):
+    def __init__(self, path, mode="r", version=2, mmap=False):
         object.__setattr__(self, "path", os.fspath(path))
         object.__setattr__(self, "mode", mode)
         object.__setattr__(self, "data_model", "NETCDF3_64BIT" if version == 2 else "NETCDF3_CLASSIC")
@@ -175,7 +175,7 @@ class _Classic(object):
         elif mode == "w":
             nc = netcdf_file(self.path, "w", version=version, mmap=False)
         else:
-            nc = netcdf_file(self.path, "r", mmap=False)
+            nc = netcdf_file(self.path, "r", mmap=bool(mmap))
         object.__setattr__(self, "_nc", nc)
         object.__setattr__(self, "variables", {k: _ClassicVar(self, k, v) for k, v in nc.variables.items()})
 
@@ -227,6 +227,8 @@ class _Classic(object):
 
     def close(self):
         if self._nc is not None:
+            if getattr(self._nc, "use_mmap", False):            # the map closes once nothing refers to it
+                self.variables.clear()
             self._nc.close()
             object.__setattr__(self, "_nc", None)
 
@@ -248,9 +250,11 @@ class _Classic(object):
             self.setncattr(name, value)
 
 
-def open_dataset(path, mode="r", format=None, rdcc_nbytes=None, alignment=None):
+def open_dataset(path, mode="r", format=None, rdcc_nbytes=None, alignment=None, mmap=False):
     """``netCDF4.Dataset(path, mode)`` on either container.  'w': ``format`` or ``default_format()``; otherwise the file's
-    own format (magic bytes).  ``alignment``: see ``h5nc.Dataset`` (NETCDF4 only)."""
+    own format (magic bytes).  ``alignment``: see ``h5nc.Dataset`` (NETCDF4 only).  ``mmap`` (classic, mode 'r'): map the
+    file instead of reading all of it at once -- for a reader that takes a part of a large file (step12); what a variable
+    returns is a copy either way."""
     path = os.fspath(path)
     if mode == "w":
         fmt = format or default_format()
@@ -265,7 +269,7 @@ def open_dataset(path, mode="r", format=None, rdcc_nbytes=None, alignment=None):
             raise IOError("%s is a NetCDF-4 / HDF5 file and libhdf5 could not be loaded (TWX_HDF5_LIBDIR); see "
                           "python -m topowx_amd.ncio --convert-help" % path)
         return h5nc.Dataset(path, mode, rdcc_nbytes=rdcc_nbytes)
-    return _Classic(path, mode)
+    return _Classic(path, mode, mmap=mmap and mode == "r")
 
 
 def _is_nc4(ds):

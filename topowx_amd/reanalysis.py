@@ -2,10 +2,18 @@
 batched principal components of the columns it returns (``batched_components``: one call of libtwxqa's
 ``twxnr_components`` for every target and day group; include/twx_qa.h states the arithmetic).
 
-The files are the North American subsets ``nnr_<var>_<time>.nc`` that step12's ``create_nnr_subset*`` write: one float32
-variable on ``(time, level, lat, lon)`` or ``(time, lat, lon)``, a daily ``time`` axis, ``lat`` and ``lon``.  Writing them
-from the raw yearly reanalysis files (step12) and the time-zone lookup that gives a station its ``utc_offset`` (step13)
-are not ported.
+The files are the North American subsets ``nnr_<var>_<time>.nc``: one float32 variable on ``(time, level, lat, lon)`` or
+``(time, lat, lon)``, a daily ``time`` axis, ``lat`` and ``lon``.  Step12 writes them from the raw yearly reanalysis files:
+``create_nnr_subset``, ``create_nnr_subset_nolevel`` and ``create_thickness_nnr_subset`` (twx/db/reanalysis.py:45-305) with
+the reference's argument lists, each a thin call of ``create_nnr_subsets``, which reads the yearly files of a raw variable
+ONCE and makes every product of it in one call of libtwxqa's ``twxns_subset`` (``python -m topowx_amd.step12`` writes all
+21 files).  The time-zone lookup that gives a station its ``utc_offset`` (step13) is not ported.
+
+Deviations of step12.  ``valid_range`` / ``valid_min`` / ``valid_max`` are ignored: only ``missing_value`` and ``_FillValue``
+mask a datum (and not the type's default fill when there is no ``_FillValue``).  A yearly file whose ``time`` has a gap
+raises ``ValueError`` (the reference regenerates the axis and misaligns silently), and so does an epoch before 1583 (the
+mixed calendar of ``hours since 1-1-1`` needs cftime).  Packing attributes are taken as float32.  The yearly files of a
+variable must agree in type, packing and marks.  Nothing is downloaded.
 
 Deviations.  The reference's ``np.argsort`` of the cell distances leaves the order of exactly equidistant cells to the
 sort implementation; here the sort is stable: of equidistant cells the one of lower flat index (latitude-major, as
@@ -14,14 +22,18 @@ gives NaN scores or a division by zero in the reference; here ``get_nngh_matrix`
 fill value, and the result of ``batched_components`` raises it for either when the scores of such an item are asked for
 (``NnrBatch.scores``), naming the variable and the cell; an item nobody uses raises nothing, as on the host route.
 """
+import datetime as _dt
 import os
+import time as _time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
 from . import _qalib, ncio
-from .dates import YMD
+from .dates import DAY, MONTH, YEAR, YMD
 
-__all__ = ["NNRNghData", "NnrBatch", "grt_circle_dist", "NNR_STATUS"]
+__all__ = ["NNRNghData", "NnrBatch", "grt_circle_dist", "NNR_STATUS", "create_nnr_subset", "create_nnr_subset_nolevel",
+           "create_thickness_nnr_subset", "create_nnr_subsets", "record_slots_days", "BOUNDS"]
 
 RADIAN_CONVERSION_FACTOR = 0.017453292519943295         # util_geo.py:21
 AVG_EARTH_RADIUS_KM = 6371.009                          # util_geo.py:22
@@ -270,3 +282,318 @@ class NNRNghData(object):
             timing["nr_library_s"] = timing.get("nr_library_s", 0.0) + (time.perf_counter() - t1)
             timing["nr_sets"] = len(sets)
         return NnrBatch(set_of, sets, labels, res.max_var, res, self.grid_lons, self.grid_lats)
+
+
+# ---- step12: the North American subsets of the raw yearly files (twx/db/reanalysis.py:45-305) --------------------------
+BOUNDS = (60, 10, -135, -55)                  # LAT_TOP, LAT_BOTTOM, LON_LEFT, LON_RIGHT (reanalysis.py:41-42)
+SLOT_OF_UTC = {12: 0, 18: 1, 24: 2}           # the slots of twxns_subset; 24z is the 0z record, dated one day earlier
+MAX_READERS = 16
+INSTITUTION = "University of Montana Numerical Terradynamics Simulation Group"
+
+
+def _epoch(units, path):
+    """The epoch of ``hours since <date> [<time>]``; ``ValueError`` for other units or an epoch before 1583."""
+    parts = str(units).split()
+    try:
+        if len(parts) < 3 or not parts[0].lower().startswith("hour") or parts[1].lower() != "since":
+            raise ValueError
+        y, m, d = (int(x) for x in parts[2].split("-"))
+        hour = int(float(parts[3].split(":")[0])) if len(parts) > 3 else 0
+    except ValueError:
+        raise ValueError("%s: the units of time are %r, not 'hours since <date>'" % (path, units))
+    if y < 1583:
+        raise ValueError("%s: the epoch of time (%r) lies before 1583: its mixed Julian / Gregorian calendar cannot be "
+                         "decoded here (re-download the file: current ones count from 1800)" % (path, units))
+    return _dt.datetime(y, m, d, hour)
+
+
+def _period(days):
+    d0 = _dt.date(int(days[YEAR][0]), int(days[MONTH][0]), int(days[DAY][0]))
+    d1 = _dt.date(int(days[YEAR][-1]), int(days[MONTH][-1]), int(days[DAY][-1]))
+    if (d1 - d0).days + 1 != days.size:
+        raise ValueError("days must be consecutive calendar days")
+    return d0
+
+
+def record_slots_days(time_values, units, days, path="<time>"):
+    """(slot [nrec], day [nrec]) of a yearly file's records (reanalysis.py:106-124 restated).  The times are regenerated
+    as ``arange(time[0], time[-1] + 6, 6)``; ``ValueError`` naming ``path`` if the file's axis has another length.  The
+    hour selects the slot (12 -> 0, 18 -> 1, 0 -> 2, 6 -> -1); a 0z record is the 24z of the day before; a date outside
+    ``days`` is -1."""
+    t = np.asarray(time_values, np.float64).ravel()
+    epoch = _epoch(units, path)
+    if t.size < 1:
+        raise ValueError("%s: no records" % path)
+    reg = np.arange(t[0], t[-1] + 6, 6)
+    if reg.size != t.size:
+        raise ValueError("%s: time holds %d records, but %d lie between its first and last at 6-hour steps (a gap or a "
+                         "repeat): the records cannot be dated" % (path, t.size, reg.size))
+    if np.any(reg != np.floor(reg)):
+        raise ValueError("%s: the times are not whole hours" % path)
+    hours = reg.astype(np.int64) + epoch.hour
+    ordinal, hod = epoch.toordinal() + hours // 24, hours % 24
+    slot = np.full(t.size, -1, np.int32)
+    for h, s in ((12, 0), (18, 1), (0, 2)):
+        slot[hod == h] = s
+    day = ordinal - (slot == 2) - _period(days).toordinal()
+    day[(day < 0) | (day >= days.size)] = -1
+    return slot, day.astype(np.int32)
+
+
+def _mark(v, name, dtype):
+    """The attribute ``name`` of ``v`` in the variable's own type, ``None`` if absent or not representable in it (such a
+    mark equals no datum)."""
+    if name not in v.ncattrs():
+        return None
+    a = np.asarray(v.getncattr(name)).ravel()
+    if a.size < 1 or a.dtype.kind not in "iuf":
+        return None
+    with np.errstate(all="ignore"):
+        m = a[:1].astype(dtype)[0]
+    return m if (float(m) == float(a[0]) or (np.isnan(float(m)) and np.isnan(float(a[0])))) else None
+
+
+def _year_info(path, raw_var, days):
+    if not os.path.exists(path):
+        raise IOError("no reanalysis file %s" % path)
+    ds = ncio.open_dataset(path, mmap=True)
+    try:
+        if raw_var not in ds.variables or "time" not in ds.variables:
+            raise ValueError("%s has no variable %s on a time axis" % (path, raw_var))
+        v, tv = ds.variables[raw_var], ds.variables["time"]
+        dtype = np.dtype(v.dtype)
+        if dtype not in (np.dtype(np.int16), np.dtype(np.float32)):
+            raise ValueError("%s: %s is stored as %s; short and float are read" % (path, raw_var, dtype))
+        attrs = v.ncattrs()
+        scale = np.float32(np.asarray(v.getncattr("scale_factor")).ravel()[0]) if "scale_factor" in attrs else np.float32(1)
+        offset = np.float32(np.asarray(v.getncattr("add_offset")).ravel()[0]) if "add_offset" in attrs else np.float32(0)
+        marks = tuple(_mark(v, a, dtype) for a in ("missing_value", "_FillValue"))
+        slot, day = record_slots_days(tv[:], tv.getncattr("units"), days, path)
+        if v.shape[0] != slot.size:
+            raise ValueError("%s: %s has %d records, time %d" % (path, raw_var, v.shape[0], slot.size))
+        used = np.nonzero((slot >= 0) & (day >= 0))[0]
+        return dict(path=path, ds=ds, v=v, dtype=dtype, scale=scale, offset=offset, marks=marks, slot=slot[used], day=day[used],
+                    used=used, pack=(str(dtype), scale.tobytes(), offset.tobytes(),
+                                     tuple(None if m is None else m.tobytes() for m in marks), tuple(v.shape[1:])))
+    except Exception:
+        v = tv = None                                            # a mapped file closes once nothing refers to it
+        ds.close()
+        raise
+
+
+def _title(p):
+    if p.get("thick") is not None:
+        return "".join(["NCEP/NCAR Daily ", str(p["thick"][0]), "-", str(p["thick"][1]), " thickness ", str(p["utc_time"]), "Z Subset"])
+    return "".join(["NCEP/NCAR Daily ", p["varname_out"], " ", str(p["utc_time"]), "Z Subset"])
+
+
+def untile(a, nlat, nlon):
+    """[ndays, nlev, nlat, nlon] of a TWXNS_TILED product [cy, cx, ndays, nlev, 4, 4]."""
+    ncy, ncx, nd, nlev = a.shape[:4]
+    return np.ascontiguousarray(a.transpose(2, 3, 0, 4, 1, 5).reshape(nd, nlev, ncy * 4, ncx * 4)[:, :, :nlat, :nlon])
+
+
+def write_nnr_subset(fpath, title, varname_out, days, lons, lats, levels, data, tiled, format=None):
+    """One subset file as the reference's ``dbDataset`` helpers lay it out (create_db_all_stations.py:61-86,111-133).
+    ``levels``: the pressure levels of a ``(time, level, lat, lon)`` variable, ``None`` for ``(time, lat, lon)``.  ``data``:
+    the product of ``_qalib.ns_subset``, TWXNS_TILED (``tiled``) or TWXNS_PLAIN.  In NetCDF-4 the chunks are
+    ``(ndays, nlev, 4, 4)``, uncompressed, each written as the bytes it is."""
+    nd, nlat, nlon = int(days.size), len(lats), len(lons)
+    nlev = 1 if levels is None else len(levels)
+    ds = ncio.open_dataset(fpath, "w", format)
+    try:
+        ds.title, ds.institution = title, INSTITUTION
+        ds.history = "".join(["Created on: ", _dt.date.today().strftime("%Y-%m-%d")])
+        ds.createDimension("lon", nlon)
+        ds.createDimension("lat", nlat)
+        for name, long_name, units, vals in (("lon", "longitude", "degrees_east", lons), ("lat", "latitude", "degrees_north", lats)):
+            cv = ds.createVariable(name, "f8", (name,))
+            cv.long_name, cv.units, cv.standard_name = long_name, units, long_name
+            cv[:] = np.asarray(vals, np.float64)
+        ds.createDimension("time", nd)
+        tv = ds.createVariable("time", "f8", ("time",))
+        tv.long_name, tv.standard_name, tv.calendar = "time", "time", "standard"
+        y0 = int(np.min(days[YEAR]))
+        tv.units = "".join(["days since ", str(y0), "-1-1 0:0:0"])
+        tv[:] = float((_period(days) - _dt.date(y0, 1, 1)).days) + np.arange(nd, dtype=np.float64)
+        dims, chunks = ("time", "lat", "lon"), (nd, min(4, nlat), min(4, nlon))
+        if levels is not None:
+            ds.createDimension("level", nlev)
+            lv = ds.createVariable("level", "f8", ("level",))
+            lv.long_name, lv.units, lv.standard_name = "Level", "millibar", "level"
+            lv[:] = np.asarray(levels, np.float64)
+            dims, chunks = ("time", "level", "lat", "lon"), (nd, nlev, min(4, nlat), min(4, nlon))
+        shape = (nd, nlev, nlat, nlon) if levels is not None else (nd, nlat, nlon)
+        if ncio._is_nc4(ds):
+            v = ds.createVariable(varname_out, "f4", dims, fill_value=ncio.FILL_F4, chunksizes=chunks, zlib=False)
+            if tiled and nlat >= 4 and nlon >= 4:
+                lead = (0,) * (len(dims) - 2)
+                for cy in range(data.shape[0]):
+                    for cx in range(data.shape[1]):
+                        v.write_chunk_raw(lead + (4 * cy, 4 * cx), data[cy, cx])
+            else:
+                v[:] = (untile(data, nlat, nlon) if tiled else data).reshape(shape)
+        else:
+            v = ds.createVariable(varname_out, "f4", dims, fill_value=ncio.FILL_F4)
+            v[:] = (untile(data, nlat, nlon) if tiled else data).reshape(shape)
+    finally:
+        ds.close()
+    return fpath
+
+
+def create_nnr_subsets(path_nnr, path_out, yrs, days, raw_var, products, format=None, bounds=BOUNDS, suffix="", device=0,
+                       timing=None, pinned=True):
+    """Every product of the raw variable ``raw_var`` from ONE reading of its yearly files ``<raw_var><suffix>.<year>.nc``
+    in ``path_nnr``.  ``products``: dicts with ``fname`` (in ``path_out``), ``varname_out``, ``utc_time`` (12, 18, 24),
+    ``conv`` ("none" / "k_to_c") and either ``levels`` (the pressure levels of a subset with a level axis), ``thick`` =
+    (level_up, level_low), or neither (a variable without levels).  ``bounds`` = (lat top, lat bottom, lon left, lon right).
+    The years are read on at most 16 threads into one page-locked buffer (``pinned=False``: ordinary memory), cut to the
+    levels, rows and columns in use; ``twxns_subset`` forms every chunk once.  Returns the paths written; ``timing`` (a
+    dict) receives ``nsub_read_s``, ``nsub_library_s``, ``nsub_write_s`` and the library's milliseconds."""
+    t0 = _time.perf_counter()
+    yrs = [int(y) for y in np.asarray(yrs).ravel()]
+    if not yrs or not products:
+        raise ValueError("yrs and products must not be empty")
+    _period(days)
+    lat_top, lat_bottom, lon_left, lon_right = bounds
+    paths = [os.path.join(path_nnr, "%s%s.%d.nc" % (raw_var, suffix, y)) for y in yrs]
+    infos = []
+    try:
+        with ThreadPoolExecutor(max_workers=min(MAX_READERS, len(paths))) as pool:
+            futs = [pool.submit(_year_info, p, raw_var, days) for p in paths]
+            err = None
+            for f in futs:
+                try:
+                    infos.append(f.result())
+                except Exception as e:                               # the first failing year, the others closed below
+                    err = err or e
+            if err is not None:
+                raise err
+        first = infos[0]
+        for i in infos[1:]:
+            if i["pack"] != first["pack"]:
+                raise ValueError("%s and %s differ in the type, packing, marks or grid of %s: one call takes one kind"
+                                 % (first["path"], i["path"], raw_var))
+        ds = first["ds"]
+        has_level = first["v"].ndim == 4
+        if first["v"].ndim not in (3, 4):
+            raise ValueError("%s: %s must be on (time, level, lat, lon) or (time, lat, lon)" % (first["path"], raw_var))
+        levels = np.asarray(ds.variables["level"][:]) if has_level else None
+        lons = np.asarray(ds.variables["lon"][:], np.float64).copy()
+        lons[lons > 180] = lons[lons > 180] - 360.0
+        lats = np.asarray(ds.variables["lat"][:], np.float64)
+        mask_lons = np.logical_and(lons >= lon_left, lons <= lon_right)
+        mask_lats = np.logical_and(lats >= lat_bottom, lats <= lat_top)
+        iy, ix = np.nonzero(mask_lats)[0], np.nonzero(mask_lons)[0]
+        if iy.size < 1 or ix.size < 1:
+            raise ValueError("%s: no cell inside the bounds %r" % (first["path"], tuple(bounds)))
+        y0, y1, x0, x1 = int(iy[0]), int(iy[-1]) + 1, int(ix[0]), int(ix[-1]) + 1
+        # the products: level indices of the file, then of the cut slab
+        want, need = [], []
+        for p in products:
+            if p["utc_time"] not in SLOT_OF_UTC:
+                raise ValueError("utc_time must be 12, 18 or 24")
+            if p.get("thick") is not None or p.get("levels") is not None:
+                if not has_level:
+                    raise ValueError("%s has no level axis" % first["path"])
+                if p.get("thick") is not None:
+                    idx = []
+                    for lev in p["thick"]:
+                        k = np.nonzero(levels == lev)[0]
+                        if k.size < 1:
+                            raise ValueError("%s has no level %s" % (first["path"], lev))
+                        idx.append(int(k[0]))
+                    out_levels = None
+                else:
+                    mask_levels = np.isin(levels, np.asarray(p["levels"]), assume_unique=True)      # np.in1d(.., True)
+                    idx = [int(k) for k in np.nonzero(mask_levels)[0]]
+                    if not idx:
+                        raise ValueError("%s has none of the levels %r" % (first["path"], list(np.asarray(p["levels"]).ravel())))
+                    out_levels = levels[mask_levels]
+            else:
+                if has_level:
+                    raise ValueError("%s has a level axis: name the levels of %s" % (first["path"], p["fname"]))
+                idx, out_levels = [0], None
+            want.append((idx, out_levels))
+            need += idx
+        need = sorted(set(need))
+        pos = {k: j for j, k in enumerate(need)}
+        desc = []
+        for p, (idx, _) in zip(products, want):
+            d = dict(slot=SLOT_OF_UTC[p["utc_time"]], conv=p.get("conv", "none"))
+            if p.get("thick") is not None:
+                d["thick"] = (pos[idx[0]], pos[idx[1]])
+            else:
+                d["levels"] = [pos[k] for k in idx]
+            desc.append(d)
+        # one buffer for the records in use of every year
+        starts = np.concatenate([[0], np.cumsum([i["used"].size for i in infos])]).astype(np.int64)
+        nrec = int(starts[-1])
+        shape = (max(nrec, 1), len(need), y1 - y0, x1 - x0)
+        nbytes = int(np.prod(shape, dtype=np.int64)) * first["dtype"].itemsize
+        hold = _qalib.PinnedBuffer(nbytes) if pinned else None
+        try:
+            raw = (np.frombuffer(hold.view, first["dtype"]) if pinned else np.empty(nbytes // first["dtype"].itemsize,
+                                                                                     first["dtype"])).reshape(shape)
+
+            def fill(i, r0):
+                used = i["used"]
+                if used.size:
+                    lo, hi = int(used[0]), int(used[-1]) + 1
+                    for j, lev in enumerate(need):
+                        a = i["v"][lo:hi, lev, y0:y1, x0:x1] if has_level else i["v"][lo:hi, y0:y1, x0:x1]
+                        raw[r0:r0 + used.size, j] = a[used - lo]
+
+            with ThreadPoolExecutor(max_workers=min(MAX_READERS, len(infos))) as pool:
+                for f in [pool.submit(fill, i, int(starts[k])) for k, i in enumerate(infos)]:
+                    f.result()
+            if nrec:
+                slot, day = np.concatenate([i["slot"] for i in infos]), np.concatenate([i["day"] for i in infos])
+            else:                                                    # no record of these files lies in the period
+                raw[:] = 0
+                slot, day = np.array([-1], np.int32), np.array([-1], np.int32)
+            t1 = _time.perf_counter()
+            nc4 = (format or ncio.default_format()) == "NETCDF4"
+            outs, counts = _qalib.ns_subset(raw, first["scale"], first["offset"], first["marks"], slot, day, days.size, iy - y0,
+                                            ix - x0, desc, layout=_qalib.NS_TILED if nc4 else _qalib.NS_PLAIN, device=device,
+                                            timing=timing)
+            del raw
+        finally:
+            if hold is not None:
+                hold.close()
+    finally:
+        for i in infos:
+            i["v"] = None
+            i["ds"].close()
+    t2 = _time.perf_counter()
+    written = []
+    for p, (idx, out_levels), a in zip(products, want, outs):
+        written.append(write_nnr_subset(os.path.join(path_out, p["fname"]), _title(p), p["varname_out"], days, lons[mask_lons],
+                                        lats[mask_lats], out_levels, a, nc4, format="NETCDF4" if nc4 else format))
+    if timing is not None:
+        for k, v in (("nsub_read_s", t1 - t0), ("nsub_library_s", t2 - t1), ("nsub_write_s", _time.perf_counter() - t2)):
+            timing[k] = timing.get(k, 0.0) + v
+        timing["nsub_records"] = timing.get("nsub_records", 0) + nrec
+        timing.setdefault("nsub_counts", {}).update({p["fname"]: [int(c) for c in counts[k]] for k, p in enumerate(products)})
+    return written
+
+
+def create_nnr_subset(path_nnr, fpath_out, yrs, days, varname_in, varname_out, levels_subset, utc_time, conv="none", **kw):
+    """``create_nnr_subset`` (reanalysis.py:45-131); ``conv_func`` is ``conv``: "none" or "k_to_c"."""
+    return create_nnr_subsets(path_nnr, os.path.dirname(fpath_out), yrs, days, varname_in,
+                              [dict(fname=os.path.basename(fpath_out), varname_out=varname_out, utc_time=utc_time,
+                                    levels=np.asarray(levels_subset), conv=conv)], **kw)[0]
+
+
+def create_nnr_subset_nolevel(path_nnr, fpath_out, yrs, days, varname_in, varname_out, utc_time, conv="none", suffix="", **kw):
+    """``create_nnr_subset_nolevel`` (reanalysis.py:133-218); ``suffix`` follows the variable in the file names."""
+    return create_nnr_subsets(path_nnr, os.path.dirname(fpath_out), yrs, days, varname_in,
+                              [dict(fname=os.path.basename(fpath_out), varname_out=varname_out, utc_time=utc_time, conv=conv)],
+                              suffix=suffix, **kw)[0]
+
+
+def create_thickness_nnr_subset(path_nnr, fpath_out, yrs, days, level_up, level_low, utc_time, **kw):
+    """``create_thickness_nnr_subset`` (reanalysis.py:220-305): ``thick`` = hgt[level_up] - hgt[level_low]."""
+    return create_nnr_subsets(path_nnr, os.path.dirname(fpath_out), yrs, days, "hgt",
+                              [dict(fname=os.path.basename(fpath_out), varname_out="thick", utc_time=utc_time,
+                                    thick=(level_up, level_low))], **kw)[0]
