@@ -5,7 +5,10 @@
   exp, with the table in global memory and staged in LDS (the kernels use both);
 * ellip_pair_f64 (fp64 covariance build, tie guard) and ellip_pair_fast (fp32 tail: default build, k_stn_nn's routing
   bound) against the 40-digit arbiter (oracle/arbiter.py) on station half-angle sines / cosines formed as
-  twx_set_stations forms them.
+  twx_set_stations forms them;
+* ellip_pair_vario (twx_vario.h: the semivariogram's pair distance on the hardware reciprocal / reciprocal square root)
+  against the same arbiter and against ellip_pair_f64 on the same inputs, and its Newton helpers rcp_nr1 / sqrt_nr
+  against long-double 1 / x and sqrt(x).
 
 The compile-only test runs without a GPU, so a header change that breaks the probe shows up on a CPU box."""
 import math
@@ -165,8 +168,25 @@ def _exact_on_inputs(a, b):
         return 2 * w * arbiter.A_KM * (1 + f * H1 * (1 - cF2) * (1 - sG2) - f * H2 * cF2 * sG2)
 
 
+@pytest.fixture(scope="module")
+def pair_refs():
+    """The pairs of _pairs(), their half-angle values, S, and both 40-digit references -- once for the tests that share them."""
+    from oracle import arbiter
+    pairs = _pairs()
+    n = len(pairs)
+    tg = np.array([_trig(p[0], p[1]) + _trig(p[2], p[3]) for p in pairs])
+    kind = np.array([p[4] for p in pairs])
+    same = kind == "same"
+    ref = np.array([float(arbiter.ellip_dist(p[0], p[1], p[2], p[3])) if p[4] != "same" else 0.0 for p in pairs])
+    own = np.array([float(_exact_on_inputs(tg[i, :4], tg[i, 4:])) if not same[i] else 0.0 for i in range(n)])
+    sd = np.array([_sd(tg[i, :4], tg[i, 4:]) for i in range(n)])
+    for a in (tg, ref, own, sd):
+        a.setflags(write=False)
+    return dict(pairs=pairs, tg=tg, kind=kind, same=same, ref=ref, own=own, sd=sd)
+
+
 @pytest.mark.gpu
-def test_pair_distances_against_the_arbiter(probe, tmp_path):
+def test_pair_distances_against_the_arbiter(probe, tmp_path, pair_refs):
     """ellip_pair_f64 and ellip_pair_fast on ~1.8e4 pairs: 10 m .. 3000 km apart, latitudes -60 .. 80, pairs on both
     sides of each near / far switch (S = 4e-3 for the fp64 function, 0.01 for the fast one) and coincident points
     (exactly 0 in both).
@@ -180,17 +200,11 @@ def test_pair_distances_against_the_arbiter(probe, tmp_path):
         function sees them, which limits sin G and sin L to ~1e-16 absolute, i.e. the distance to ~2e-12 km
         ABSOLUTE at any separation -- ~3e-11 relative at 100 m (the ~5e-12 of the comment in twx_uk.h is the
         function's own arithmetic on those values, the figure above).  Bar: |d| <= 4e-12 km + 1e-13 h; measured 2.84e-12 km."""
-    from oracle import arbiter
-    pairs = _pairs()
+    pairs, tg, kind, same = (pair_refs[k] for k in ("pairs", "tg", "kind", "same"))
+    ref, own, sd = (pair_refs[k] for k in ("ref", "own", "sd"))
     n = len(pairs)
-    tg = np.array([_trig(p[0], p[1]) + _trig(p[2], p[3]) for p in pairs])
     h64, hf = _run(probe, tmp_path, "dist", tg, n)
-    kind = np.array([p[4] for p in pairs])
-    same = kind == "same"
     assert np.all(h64[same] == 0.0) and np.all(hf[same] == 0.0)
-    ref = np.array([float(arbiter.ellip_dist(p[0], p[1], p[2], p[3])) if p[4] != "same" else 0.0 for p in pairs])
-    own = np.array([float(_exact_on_inputs(tg[i, :4], tg[i, 4:])) if not same[i] else 0.0 for i in range(n)])
-    sd = np.array([_sd(tg[i, :4], tg[i, 4:]) for i in range(n)])
     for th, k in ((4e-3, "f64_switch"), (0.01, "fast_switch")):              # both sides of each switch reached
         s = sd[kind == k]
         assert (s < th).sum() > 500 and (s > th).sum() > 500, (k, (s < th).sum(), (s > th).sum())
@@ -209,3 +223,91 @@ def test_pair_distances_against_the_arbiter(probe, tmp_path):
     bound = 4e-12 + 1e-13 * ref[m]
     i = int(np.argmax(abs64 / bound))
     assert np.all(abs64 <= bound), (abs64[i], pairs[np.nonzero(m)[0][i]])
+
+
+@pytest.mark.gpu
+def test_vario_pair_distance_against_the_arbiter(probe, tmp_path, pair_refs):
+    """ellip_pair_vario (twx_vario.h: the semivariogram's pair distance, hardware reciprocal / reciprocal square root with
+    Newton steps) on the pairs of the test above, next to ellip_pair_f64 on the same inputs:
+
+      * coincident points: exactly 0;
+      * S >= 4e-3 (both functions call ellip_far_f64): the same bits;
+      * S < 4e-3: the bars ellip_pair_f64 is held to -- own arithmetic <= 1e-11 relative at >= 100 m, against the arbiter
+        from degrees |d| <= 4e-12 km + 1e-13 h -- and <= 1e-14 relative to ellip_pair_f64 at >= 100 m (the larger of the two
+        figures of the header's claim: "the main term to an ulp or two, the correction terms to ~1e-14").
+
+    Measured on gfx950: own max rel 6.09e-12 (>= 100 m), abs vs arbiter 2.84e-12 km -- ellip_pair_f64's own figures --,
+    max rel difference from ellip_pair_f64 3.67e-16 (>= 100 m): under two ulp, so the header's "a few ulp" holds and a
+    pair changes its 5 km bin with probability ~1e-15."""
+    pairs, tg, kind, same = (pair_refs[k] for k in ("pairs", "tg", "kind", "same"))
+    ref, own, sd = (pair_refs[k] for k in ("ref", "own", "sd"))
+    n = len(pairs)
+    hv, h64 = _run(probe, tmp_path, "vdist", tg, n)
+    assert np.all(hv[same] == 0.0) and not np.any(np.signbit(hv[same]))
+    s = sd[kind == "f64_switch"]
+    assert (s < 4e-3).sum() > 500 and (s >= 4e-3).sum() > 500, ((s < 4e-3).sum(), (s >= 4e-3).sum())
+    far_side, near_side = ~same & (sd >= 4e-3), ~same & (sd < 4e-3)
+    assert far_side.sum() > 500 and near_side.sum() > 500
+    assert np.array_equal(hv[far_side].view(np.uint64), h64[far_side].view(np.uint64))
+    m = ~same
+    assert ref[near_side].min() < 0.012 and ref[near_side].max() > 800.0
+    m100 = near_side & (ref >= 0.1)
+    rel_own = np.abs(hv[m100] - own[m100]) / own[m100]
+    rel_f64 = np.abs(hv[m100] - h64[m100]) / h64[m100]
+    absv = np.abs(hv[m] - ref[m])
+    print("ellip_pair_vario: own max rel %.3g (>= 100 m), abs vs arbiter %.3g km, vs ellip_pair_f64 max rel %.3g (>= 100 m)"
+          % (rel_own.max(), absv.max(), rel_f64.max()))
+    i = int(np.argmax(rel_own))
+    assert rel_own.max() <= 1e-11, (rel_own.max(), pairs[np.nonzero(m100)[0][i]])
+    bound = 4e-12 + 1e-13 * ref[m]
+    i = int(np.argmax(absv / bound))
+    assert np.all(absv <= bound), (absv[i], pairs[np.nonzero(m)[0][i]])
+    i = int(np.argmax(rel_f64))
+    assert rel_f64.max() <= 1e-14, (rel_f64.max(), pairs[np.nonzero(m100)[0][i]])
+
+
+def _newton_arguments():
+    rng = np.random.default_rng(13)
+    sd = 10.0 ** rng.uniform(-13.0, math.log10(4e-3), 40000)                  # what ellip_pair_vario hands them
+    P = np.full_like(sd, 0.01396484375)
+    for c in (0.017352764423076924, 0.022372159090909092, 0.030381944444444444, 0.044642857142857144, 0.075,
+              0.16666666666666666, 1.0):
+        P = P * sd + c
+    assert P.min() >= 1.0 and P.max() < 1.001
+    e = np.arange(-66, 11)                                                    # 2^-66 < 1e-20, 2^10 > 1e3
+    p2 = np.ldexp(1.0, e)
+    parts = [sd, 2.0 * sd, 2.0 * (1.0 - sd), P,
+             10.0 ** rng.uniform(-20.0, 3.0, 60000),
+             p2, np.nextafter(p2, 0.0), np.nextafter(p2, np.inf), np.nextafter(np.nextafter(p2, 0.0), 0.0),
+             np.nextafter(np.nextafter(p2, np.inf), np.inf)]
+    return np.concatenate(parts)
+
+
+def _ulps(got, ref):
+    _, e = np.frexp(ref)
+    ulp = np.ldexp(np.longdouble(1), e - 53)                                  # ulp of the binade of the exact value
+    return (np.abs(got.astype(np.longdouble) - ref) / ulp).astype(np.float64)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("helper", ("sqrt_nr", "rcp_nr1"))
+def test_vario_newton_helpers(probe, tmp_path, helper):
+    """rcp_nr1 and sqrt_nr (twx_vario.h) against long-double 1 / x and sqrt(x) on ~2.2e5 arguments: those
+    ellip_pair_vario gives them (S in [1e-13, 4e-3], 2 S, 2 C near 2, P in [1, 1.001]), log-uniform x in [1e-20, 1e3],
+    powers of two and their neighbours.  Bar: 2 ulp each ("an ulp or two").
+
+    Measured on gfx950: sqrt_nr max 0.500 ulp (and still 0.500 without its second Newton step: the closing correction
+    squares the error once more, so that step buys nothing the bar can see); rcp_nr1 max 0.500 ulp.
+
+    This test found rcp_nr1 at 10.598 ulp (x = 8.3e-17) with the single Newton step it had: the hardware reciprocal is
+    good to ~2^-25 here and one step leaves ~2^-50, 1.2e-15 relative -- inside the "~1e-14" twx_vario.h claims for the
+    correction terms the reciprocal serves, but not "an ulp or two".  It has a second step since (two fma per use, three
+    uses per pair of a point list)."""
+    x = _newton_arguments()
+    assert x.size > 200000 and x.min() > 0.0
+    rcp, sq = _run(probe, tmp_path, "vmath", x, x.size)
+    xl = x.astype(np.longdouble)
+    u = _ulps(sq, np.sqrt(xl)) if helper == "sqrt_nr" else _ulps(rcp, 1 / xl)
+    i = int(np.argmax(u))
+    print("%s: max %.3f ulp at %r" % (helper, u[i], float(x[i])))
+    assert u[i] <= 2.0, (helper, u[i], float(x[i]))

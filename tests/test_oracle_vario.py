@@ -1,5 +1,10 @@
 """Variogram estimation + range fit of the oracle (interp.R:54-113).
-Known-answer checks only: gstat cannot run here (PARITY UNPINNED)."""
+Known-answer checks only: gstat cannot run here (PARITY UNPINNED).
+
+CPU only.  The GPU side of the same stage (twx_vario.h) is held to this oracle in tests/test_gpu_vario.py (every k, one
+list with nested neighbourhoods, sparse tables, fallbacks, twx_krigall_points end to end) and its pair distance and Newton
+helpers to high-precision references in tests/test_gpu_devmath.py (test_vario_pair_distance_against_the_arbiter,
+test_vario_newton_helpers)."""
 import ctypes as C
 import os
 import sys

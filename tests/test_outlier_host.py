@@ -211,4 +211,4 @@ def test_qa_header_matches_binding():
 def test_kernel_sources_hash_unchanged():
     """libtwxqa lives outside topowx_amd/csrc and include/twx.h: the hash the committed profiles carry still holds."""
     import kernel_hash
-    assert kernel_hash.kernel_sources_sha16() == "85ae98e586e20c40"
+    assert kernel_hash.kernel_sources_sha16() == "051aca46034c8c88"      # (rcp_nr1's second Newton step: twx_vario.h)

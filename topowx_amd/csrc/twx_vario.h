@@ -23,9 +23,13 @@
 // Newton steps: the main term sqrt(S) to an ulp or two, the terms of the flattening correction (weight f = 1/298) to
 // ~1e-14 -- the distance differs from ellip_pair_f64's by a few ulp, which moves a pair across a 5 km bin boundary
 // with probability ~1e-15 and the bin's mean distance by less.  (Three quarters of k_vario's time was this loop.)
+// (rcp_nr1: the reciprocal to ~1 ulp.  One Newton step on the hardware value measured 10.6 ulp on gfx950, inside the ~1e-14
+// of the correction terms but not the "ulp or two" the helpers are held to: tests/test_gpu_devmath.py,
+// test_vario_newton_helpers.  The second step costs two fma per use, once per pair of a point LIST.)
 __device__ __forceinline__ double rcp_nr1(double x)
 {
     double y = __builtin_amdgcn_rcp(x);
+    y = fma(y, fma(-x, y, 1.0), y);
     return fma(y, fma(-x, y, 1.0), y);
 }
 __device__ __forceinline__ double sqrt_nr(double x)          // x > 0, normal
@@ -88,6 +92,8 @@ __device__ __forceinline__ double block_max(double v, double *s_tmp)
 // (upload_points, twx_hip.hip) from everything select_cell's ranking depends on per point -- location, the excluded station,
 // the further exclusion list of twx_set_exclusions --; rm_zero_dist and the station table are per call.  A new per-point
 // selection input must join that key, or k_vario would pair the first point's distances with another point's residuals.
+// Guarded by tests/test_gpu_vario.py, test_one_list_nested_neighbourhoods_and_lists_that_must_not_be_shared: 192 points of
+// one list and consecutive points whose keys differ in each of the three ways, every one against the oracle.
 __global__ __launch_bounds__(256) void k_group_dist64(StnDev st, CellSrc src, SelWs ws)
 {
     __shared__ double s_trig[5][TWX_KSEL_MAX];
