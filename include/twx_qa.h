@@ -1122,7 +1122,7 @@ int twxpc_pors_counts(int device, int64_t nstn, int64_t ndays, const float *vals
 /* ---- the GHCN-Daily ingest of step04: InsertGhcn.parse_stn_obs (twx/db/create_db_all_stations.py:1042-1103) for a batch
  * of .dly files, and create_tobs_db (twx/homog/tobs.py:121-157) for a batch of by-year CSV files; twx_ghcn.hip.  Both see
  * one byte buffer of files laid end to end: file_off [nfiles + 1] int64 from 0 to nbytes.  A last line without a newline is
- * a line; lines never span files.  Out of scope: InsertSnotel / InsertRaws, add_utc_offset, downloading. ---- */
+ * a line; lines never span files.  Out of scope: InsertSnotel / InsertRaws, downloading (add_utc_offset: twxtz_*). ---- */
 #define TWXGH_NKERNELS 4                /* kernel groups timed: fill; line index; claim pass; write pass */
 #define TWXGH_MAX_BYTES ((int64_t)2147483584)   /* of one call's buffer: a line's position + 1 is a uint32 */
 #define TWXGH_MAX_CELLS ((int64_t)1 << 31)      /* 3 nrows ndays of a .dly call, nstn nwin of a by-year call */
@@ -1180,7 +1180,7 @@ void twxgh_host_free(void *p);
 
 /* ---- the North American reanalysis subsets of step12: create_nnr_subset, create_nnr_subset_nolevel and
  * create_thickness_nnr_subset (twx/db/reanalysis.py:45-305) for every product of one raw variable in one call;
- * twx_nnrsub.hip.  Out of scope: step13's time-zone lookup, downloading, deflate of the subsets. ---- */
+ * twx_nnrsub.hip.  Out of scope: downloading, deflate of the subsets (step13's time-zone lookup: twxtz_*). ---- */
 #define TWXNS_NKERNELS 3                /* groups timed: upload; the subset kernels (one launch per product); download */
 #define TWXNS_I16 0                     /* dtype of the raw slab: packed short */
 #define TWXNS_F32 1                     /*   float */
@@ -1236,6 +1236,59 @@ int twxns_subset(int device, int dtype, const void *raw, int64_t nrec, int64_t n
                  int64_t ndays, int64_t nlat_out, const int32_t *lat_idx, int64_t nlon_out, const int32_t *lon_idx,
                  int64_t nprod, const int32_t *prod, int layout, float *const *out, int64_t *counts, float *kernel_ms,
                  char *errbuf, int errlen);
+
+/* ---- step13's time-zone lookup: add_utc_offset over UtcOffset (twx/db/create_db_all_stations.py:1333-1383,
+ * twx/db/stn_utc_offsets.py:43-117), tzwhere's tzNameAt(lat, lon, forceTZ=True) restated: the first polygon that contains
+ * the point, otherwise the nearest; twx_tzpoly.hip, the predicates in twx_tzpoly_pred.h.  Out of scope: the zone names and
+ * their offsets (Python), the Geonames client. ---- */
+#define TWXTZ_NPHASES 5                 /* groups timed */
+#define TWXTZ_T_UPLOAD 0
+#define TWXTZ_T_CANDIDATES 1            /*   count, the host's scan, scatter */
+#define TWXTZ_T_CONTAIN 2               /*   containment and the pick */
+#define TWXTZ_T_FORCED 3
+#define TWXTZ_T_DOWNLOAD 4
+#define TWXTZ_INSIDE 0                  /* status of a point: poly contains it (the lowest index that does) */
+#define TWXTZ_FORCED 1                  /*   nothing contains it; poly is the nearest within max_force_deg */
+#define TWXTZ_NONE 2                    /*   nothing contains it and nothing lies within max_force_deg; poly = -1 */
+#define TWXTZ_BAD_POINT 3               /*   lon or lat is not finite; poly = -1, no device work */
+#define TWXTZ_UNCERTAIN 4               /*   float64 could not decide it: the uncertain list says what to decide again */
+#define TWXTZ_PENDING 5                 /*   internal: waits for the forced search; never returned */
+#define TWXTZ_OVERFLOW 1                /* return value: the uncertain list was too small; counts say how many it needs */
+#define TWXTZ_CHUNK_EDGES 2048          /* edges of one work item of the containment kernel */
+#define TWXTZ_MAX_POINTS (1 << 30)
+#define TWXTZ_MAX_POLY (1 << 24)
+#define TWXTZ_MAX_EDGES ((int64_t)1 << 31)
+#define TWXTZ_MAX_ITEMS ((int64_t)1 << 31)     /* (pair, chunk) items of a call */
+#define TWXTZ_MAX_UNCERTAIN ((int64_t)1 << 28)
+#define TWXTZ_C_PAIRS 0                 /* counts: (point, polygon) pairs whose bbox holds the point */
+#define TWXTZ_C_ITEMS 1                 /*   work items they made */
+#define TWXTZ_C_PENDING 2               /*   points that went to the forced search */
+#define TWXTZ_C_UNCERTAIN 3             /*   entries the uncertain list needs */
+#define TWXTZ_C_N 4
+
+/*
+ * One call for all points.  Stateless.
+ * lon, lat [npt]              float64 degrees, as written: nothing wraps at +-180
+ * edge_off [npoly + 1]        int64, ascending from 0: polygon p owns edges edge_off[p] .. edge_off[p + 1] - 1 (all its rings;
+ *                             the even-odd rule over them makes the holes)
+ * bbox [npoly][4]             xmin, ymin, xmax, ymax, closed
+ * edges [nedge][4]            x1, y1, x2, y2, none of zero length
+ * max_force_deg               a point that nothing contains takes the nearest polygon if sqrt(d2) <= max_force_deg (infinity:
+ *                             always); d2 is the squared distance in degrees to the nearest edge, (d2, polygon) lexicographic
+ * poly, status [npt] int32, dist2 [npt] float64 (0 unless forced; of TWXTZ_NONE the distance found)
+ * uncertain [uncertain_cap][2]  int32 (point, polygon) sorted: pairs whose crossing parity float64 cannot certify (Shewchuk's
+ *                             static filter of orient2d) and that lie below the point's first inside polygon; (point, -1): a forced
+ *                             point with a second polygon within a relative 2^-40 of the nearest, an ill-conditioned distance,
+ *                             or a distance that close to max_force_deg.  Their points carry TWXTZ_UNCERTAIN and a provisional
+ *                             poly; the caller decides them exactly.
+ * counts [TWXTZ_C_N] int64; timing_ms (optional) [TWXTZ_NPHASES]
+ * Returns 0, TWXTZ_OVERFLOW (everything but the list is valid; call again with counts[TWXTZ_C_UNCERTAIN] entries), or -1
+ * with errbuf.  Integer atomics only (XOR / OR of a pair's parity word, the list's counter); the list is sorted before it is
+ * returned: two calls give the same bytes.  Every argument is checked before anything touches the device.
+ */
+int twxtz_locate(int device, int64_t npt, const double *lon, const double *lat, int64_t npoly, const int64_t *edge_off,
+                 const double *bbox, const double *edges, double max_force_deg, int32_t *poly, int32_t *status, double *dist2,
+                 int32_t *uncertain, int64_t uncertain_cap, int64_t *counts, float *timing_ms, char *errbuf, int errlen);
 
 #ifdef __cplusplus
 }

@@ -9,4 +9,7 @@ def __getattr__(name):
     if name == "NNRNghData":                 # the reanalysis reader (topowx_amd.reanalysis), imported at first use
         from .reanalysis import NNRNghData
         return NNRNghData
+    if name in ("UtcOffset", "add_utc_offset", "load_tz_polygons"):     # step13's time-zone lookup (topowx_amd.utc_offsets)
+        from . import utc_offsets
+        return getattr(utc_offsets, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

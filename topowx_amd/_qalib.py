@@ -1679,3 +1679,53 @@ def ns_subset(raw, scale, offset, marks, rec_slot, rec_day, ndays, lat_idx, lon_
         for k, name in enumerate(NS_KERNELS):
             timing[name + "_ms"] = timing.get(name + "_ms", 0.0) + float(ms[k])
     return outs, counts[:nprod]
+
+
+# ---- step13's time-zone lookup (twxtz_locate; TWXTZ_* of include/twx_qa.h) ----
+TZ_EXPORTS = ("twxtz_locate",)
+TZ_PHASES = ("tz_upload", "tz_candidates", "tz_contain", "tz_forced", "tz_download")          # TWXTZ_NPHASES
+TZ_INSIDE, TZ_FORCED, TZ_NONE, TZ_BAD_POINT, TZ_UNCERTAIN, TZ_PENDING = 0, 1, 2, 3, 4, 5     # TWXTZ_* statuses
+TZ_OVERFLOW = 1                       # TWXTZ_OVERFLOW
+TZ_CHUNK_EDGES = 2048                 # TWXTZ_CHUNK_EDGES
+TZ_C_PAIRS, TZ_C_ITEMS, TZ_C_PENDING, TZ_C_UNCERTAIN = 0, 1, 2, 3                            # TWXTZ_C_*
+
+
+def tz_locate(lon, lat, edge_off, bbox, edges, max_force_deg=1.0, uncertain_cap=4096, device=0, timing=None):
+    """``twxtz_locate``: for every point the first polygon that contains it (even-odd rule over the polygon's edges),
+    otherwise the nearest within ``max_force_deg`` degrees (``None``: any distance).
+
+    ``lon`` / ``lat`` [npt] float64; ``edge_off`` [npoly + 1] int64, ``bbox`` [npoly, 4], ``edges`` [nedge, 4] float64 as
+    ``utc_offsets.load_tz_polygons`` returns them.  Returns ``(poly, status, dist2, uncertain [n, 2], counts [4])`` as
+    include/twx_qa.h describes them: points with status ``TZ_UNCERTAIN`` are NOT decided, ``uncertain`` lists what the
+    caller has to decide exactly (``utc_offsets.UtcOffset`` does).  The call is repeated with room for every entry if
+    ``uncertain_cap`` was too small.  Arguments are checked before anything touches the device."""
+    lon, lat = _c(lon, np.float64).ravel(), _c(lat, np.float64).ravel()
+    off, bb, ed = _c(edge_off, np.int64), _c(bbox, np.float64), _c(edges, np.float64)
+    if lat.shape != lon.shape:
+        raise ValueError("lon / lat must be [npt]")
+    if off.ndim != 1 or off.size < 1 or bb.shape != (off.size - 1, 4) or ed.ndim != 2 or ed.shape[1:] != (4,) or \
+            (off.size and int(off[-1]) != ed.shape[0]):
+        raise ValueError("need edge_off [npoly + 1] ending at nedge, bbox [npoly, 4] and edges [nedge, 4]")
+    mf = float("inf") if max_force_deg is None else float(max_force_deg)
+    fn = _pq_fn("twxtz_locate", [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                 C.c_char_p, C.c_int])
+    npt, cap = lon.size, int(uncertain_cap)
+    while True:
+        poly, status, d2 = np.empty(npt, np.int32), np.empty(npt, np.int32), np.empty(npt, np.float64)
+        unc = np.zeros((max(cap, 1), 2), np.int32)
+        counts = np.zeros(4, np.int64)
+        ms = (C.c_float * len(TZ_PHASES))()
+        buf512 = C.create_string_buffer(512)
+        rc = fn(int(device), npt, lon.ctypes.data, lat.ctypes.data, off.size - 1, off.ctypes.data, bb.ctypes.data,
+                ed.ctypes.data if ed.size else None, mf, poly.ctypes.data, status.ctypes.data, d2.ctypes.data, unc.ctypes.data,
+                cap, counts.ctypes.data, C.addressof(ms), buf512, 512)
+        if rc not in (0, TZ_OVERFLOW):
+            raise QaError("twxtz_locate failed: %s" % buf512.value.decode(errors="replace"))
+        if timing is not None:
+            for k, name in enumerate(TZ_PHASES):
+                timing[name + "_ms"] = timing.get(name + "_ms", 0.0) + float(ms[k])
+            timing["tz_calls"] = timing.get("tz_calls", 0) + 1
+        if rc == 0:
+            return poly, status, d2, unc[:int(counts[TZ_C_UNCERTAIN])].copy(), counts
+        cap = int(counts[TZ_C_UNCERTAIN])

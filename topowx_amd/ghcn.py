@@ -6,7 +6,7 @@
 buffer on a thread pool and settles what only Python can: a value field that is not ``[+-]?[0-9]+`` goes through
 ``float()`` exactly as the reference's would, a header ``int()`` refuses raises ``ValueError`` naming the file and line.
 
-Out of scope: ``InsertSnotel`` / ``InsertRaws`` (their inputs are scrapes of web services), ``obsio``, ``add_utc_offset``,
+Out of scope: ``InsertSnotel`` / ``InsertRaws`` (their inputs are scrapes of web services), ``obsio``,
 deflate of the station variables (``zlib=False``: a station's kernel row IS a NetCDF-4 chunk and is written as one), and
 downloading anything.
 """

@@ -7,7 +7,7 @@ The files are the North American subsets ``nnr_<var>_<time>.nc``: one float32 va
 ``create_nnr_subset``, ``create_nnr_subset_nolevel`` and ``create_thickness_nnr_subset`` (twx/db/reanalysis.py:45-305) with
 the reference's argument lists, each a thin call of ``create_nnr_subsets``, which reads the yearly files of a raw variable
 ONCE and makes every product of it in one call of libtwxqa's ``twxns_subset`` (``python -m topowx_amd.step12`` writes all
-21 files).  The time-zone lookup that gives a station its ``utc_offset`` (step13) is not ported.
+21 files).  The time-zone lookup that gives a station its ``utc_offset`` (step13) is ``topowx_amd.utc_offsets``.
 
 Deviations of step12.  ``valid_range`` / ``valid_min`` / ``valid_max`` are ignored: only ``missing_value`` and ``_FillValue``
 mask a datum (and not the type's default fill when there is no ``_FillValue``).  A yearly file whose ``time`` has a gap

@@ -9,7 +9,7 @@ from step05 on takes as ``--db``.
 ``--start`` / ``--end``: ``yyyymmdd`` or ``yyyy-mm-dd``, inclusive.  US / CA / MX stations outside HI and AK that are not
 SNOTEL or RAWS sites are inserted; a station without a ``.dly`` file is an error unless ``--check-obs-exist`` drops it.
 ``--by-year DIR`` holds ``<year>.csv.gz`` (or ``<year>.csv``) for every year of the period.  The station variables are not
-compressed.  Out of scope: SNOTEL / RAWS inserts, ``add_utc_offset``, downloading.
+compressed.  Out of scope: SNOTEL / RAWS inserts, downloading (``add_utc_offset`` is step13: ``python -m topowx_amd.step13``).
 
 Prints one JSON line (stations, days, bytes, lines, values, fallback fields, seconds, kernel milliseconds).  Exits with 1
 if a file is missing, a date is bad or a line's header is not a number.
