@@ -27,7 +27,8 @@ python3 tests/tools/isa_resources.py "$LOG" > topowx_amd/libtwxhip.resources.txt
 # reanalysis columns of steps 14-16), twx_homog (step05, step09-11), twx_stnrast (step19, the front of step20) and
 # twx_prcpqa (the precipitation QA), the fifteenth, twx_prcpcorrob (its spatial corroboration check), and the sixteenth,
 # twx_ghcn (step04's GHCN-Daily ingest), the seventeenth, twx_nnrsub (step12's reanalysis subsets), and the eighteenth,
-# twx_tzpoly (step13's point-in-polygon time-zone lookup), are each named by a pattern that matches only it:
+# twx_tzpoly (step13's point-in-polygon time-zone lookup), and the nineteenth, twx_mosaic (step26/27's mosaics, deflated on
+# the device with the kernels of topowx_amd/csrc/twx_deflate.h), are each named by a pattern that matches only it:
 # tests/test_emnorm_host.py pins the number of unit names spelled out in this script to the units it knew
 if ! hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared -std=c++17 -Iinclude \
     -Rpass-analysis=kernel-resource-usage "$@" -o topowx_amd/libtwxqa.so topowx_amd/qa/twx_outlier.hip \
@@ -36,7 +37,8 @@ if ! hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared -std=c++17 
     topowx_amd/qa/twx_infillchk.[h]ip topowx_amd/qa/twx_xvalinfill.[h]ip topowx_amd/qa/twx_serial.[h]ip \
     topowx_amd/qa/twx_nnr.[h]ip topowx_amd/qa/twx_homog.[h]ip topowx_amd/qa/twx_stnrast.[h]ip \
     topowx_amd/qa/twx_prcpqa.[h]ip topowx_amd/qa/twx_prcpcorrob.[h]ip \
-    topowx_amd/qa/twx_ghcn.[h]ip topowx_amd/qa/twx_nnrsub.[h]ip topowx_amd/qa/twx_tzpoly.[h]ip 2> "$LOG"; then
+    topowx_amd/qa/twx_ghcn.[h]ip topowx_amd/qa/twx_nnrsub.[h]ip topowx_amd/qa/twx_tzpoly.[h]ip \
+    topowx_amd/qa/twx_mosaic.[h]ip 2> "$LOG"; then
     show_diagnostics "$LOG"
     rm -f "$LOG"
     exit 1

@@ -1290,6 +1290,87 @@ int twxtz_locate(int device, int64_t npt, const double *lon, const double *lat, 
                  const double *bbox, const double *edges, double max_force_deg, int32_t *poly, int32_t *status, double *dist2,
                  int32_t *uncertain, int64_t uncertain_cap, int64_t *counts, float *timing_ms, char *errbuf, int errlen);
 
+/* ---- step26 / step27: the daily and monthly mosaics with their chunks deflated on the device (twx_mosaic.hip; the host
+ * arithmetic in twx_mosaic_host.h).  TileMosaic.create_dly_ann_mosaics (twx/interp/tiling.py:567-780) and write_ds_mthly
+ * (:1169-1219) store int16 variables with zlib=True in chunks (1, 325, 700) (tiling.py:718-720, 892-894, 1035): THESE are the
+ * files the reference deflates -- the daily and normals mosaics and the monthly files.  Its tile files are NOT deflated
+ * (tiling.py:442-444).  A year of the mosaic is assembled in device memory from tile slabs, deflated there into one zlib stream
+ * per (day, chunk row, chunk column) that H5Dwrite_chunk appends as it is, and the monthly means come from the same resident
+ * year.
+ *
+ * The streams are those of topowx_amd/csrc/twx_deflate.h for a chunk whose time extent is one day: 78 01; the low bytes of the
+ * N = chunk_y * chunk_x values, element order (row, column), in ceil(N / 65535) stored blocks; the high bytes in
+ * dynamic-Huffman blocks of 16 384 input bytes, or stored where that is shorter; 01 00 00 FF FF; Adler-32 of the shuffled
+ * chunk.  ONE Huffman code per twxmo_deflate call, from the tokens of the first block of every chunk of every day of the call.
+ * oracle/deflate_oracle.py restates them byte for byte: the image [nd][Yp][Xp] as one layer of nd * Yp rows is a tile of
+ * (1, chunk_y, chunk_x) chunks.  Out of scope: inflating, a time extent other than 1, the normals mosaic. ---- */
+typedef struct twxmo_mosaic twxmo_mosaic;
+#define TWXMO_DAILY 0                   /* which image: int16 [max_days][Yp][Xp] */
+#define TWXMO_MONTHLY 1                 /*   int16 [12][Yp][Xp], written by twxmo_monthly */
+#define TWXMO_NGROUPS 7                 /* kernel groups timed */
+#define TWXMO_T_CLEAR 0
+#define TWXMO_T_PLACE 1                 /*   summed over the twxmo_place calls since the last twxmo_clear */
+#define TWXMO_T_HIST 2                  /*   token counts and the Huffman code */
+#define TWXMO_T_COUNT 3                 /*   block sizes, low planes, the per-chunk scan */
+#define TWXMO_T_EMIT 4
+#define TWXMO_T_COMPACT 5
+#define TWXMO_T_AGGREGATE 6
+#define TWXMO_S_YP 0                    /* twxmo_sizes: Y, X rounded up to whole chunks */
+#define TWXMO_S_XP 1
+#define TWXMO_S_NCHUNK 2                /*   chunks per layer */
+#define TWXMO_S_NSEG 3                  /*   high-plane blocks per chunk */
+#define TWXMO_S_SLOT_BYTES 4            /*   the longest stream of a chunk, rounded to 256 */
+#define TWXMO_S_DEVICE_BYTES 5          /*   device memory twxmo_create allocates (images, slots, workspace) */
+#define TWXMO_S_PINNED_BYTES 6          /*   pinned host memory twxmo_create allocates */
+#define TWXMO_S_VEC 7                   /*   2: chunk_x and Xp even, the coder loads two values at once; else 1 */
+#define TWXMO_S_N 8
+
+typedef struct twxmo_streams {
+    const uint8_t *data;                /* the streams one after the other (pinned; valid until the next twxmo_deflate) */
+    const int64_t *offset;              /* [nstreams + 1] byte offsets into data */
+    int64_t nstreams;                   /* layers * nchunk, in (layer, chunk row, chunk column) order */
+    int64_t slot_bytes;                 /* no stream is longer */
+    int32_t nchunk, chunk_y, chunk_x, reserved;
+} twxmo_streams;
+
+/* The sizes of an object with these arguments, without a device: sizes [TWXMO_S_N].  -1 with errbuf when the arguments are
+ * refused: max_days < 1, a chunk larger than the mosaic, a slot of 2^32 bytes or more, more chunks than a grid's x dimension. */
+int twxmo_sizes(int64_t max_days, int32_t Y, int32_t X, int32_t chunk_y, int32_t chunk_x, int64_t *sizes, char *errbuf, int errlen);
+
+/* Allocates the images, max(max_days, 12) * nchunk slots and the coder's workspace on `device`.  Refuses, naming both numbers,
+ * when hipMemGetInfo says that it does not fit: the caller asks for fewer days.  The arguments are checked first. */
+int twxmo_create(int device, int64_t max_days, int32_t Y, int32_t X, int32_t chunk_y, int32_t chunk_x, twxmo_mosaic **out,
+                 char *errbuf, int errlen);
+void twxmo_destroy(twxmo_mosaic *m);
+const char *twxmo_last_error(const twxmo_mosaic *m);
+
+/* Every later call returns 0 or -1 (twxmo_last_error has the text) and checks its arguments before it touches the device.
+ * twxmo_clear: layers 0 .. ndays - 1 of the daily image, padding included, hold TWX_FILL_I2; the timings start again. */
+int twxmo_clear(twxmo_mosaic *m, int64_t ndays);
+
+/* src int16 [nd][ty][tx] (host) is written at row y0, column x0 of layers 0 .. nd - 1.  A slab with any part outside Y x X (the
+ * padding is outside) is refused, not clipped.  Slabs are placed in call order: where two overlap, the later one wins.  The
+ * call returns once src has been copied to a staging buffer; the upload of the next slab runs under this one's placement.
+ * twxmo_staging hands out the staging buffer the NEXT twxmo_place will use (at least `bytes` long), so that a reader can fill
+ * it in place: pass that pointer as src. */
+int twxmo_place(twxmo_mosaic *m, const int16_t *src, int64_t nd, int32_t ty, int32_t tx, int32_t y0, int32_t x0);
+int twxmo_staging(twxmo_mosaic *m, int64_t bytes, void **ptr);
+
+/* The twelve monthly means of layers 0 .. ndays - 1 (day_month [ndays], 1..12) into the monthly image: twx_aggregate's kernel
+ * and its mthly_i16 output (np.ma.round(mean, 2) packed with scale_factor float32(0.01); a month without valid days is
+ * TWX_FILL_I2) on ncell = Yp * Xp. */
+int twxmo_monthly(twxmo_mosaic *m, int64_t ndays, const int32_t *day_month);
+
+/* Deflates layers 0 .. nlayers - 1 of image `which` (TWXMO_MONTHLY: nlayers <= 12).  Synchronous. */
+int twxmo_deflate(twxmo_mosaic *m, int which, int64_t nlayers, twxmo_streams *out);
+
+/* Debug / tests: layers 0 .. nlayers - 1 of image `which`, padded, int16 [nlayers][Yp][Xp]. */
+int twxmo_download(twxmo_mosaic *m, int which, int64_t nlayers, int16_t *dst);
+
+/* kernel_ms [TWXMO_NGROUPS] (HIP events; synchronises; every group summed over its runs since the last twxmo_clear), the device and the
+ * pinned host bytes the object holds now.  Any pointer may be NULL. */
+int twxmo_timing(twxmo_mosaic *m, float *kernel_ms, int64_t *device_bytes, int64_t *pinned_bytes);
+
 #ifdef __cplusplus
 }
 #endif

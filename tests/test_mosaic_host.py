@@ -1,0 +1,178 @@
+"""CPU: the file layer of ``TileMosaic.create_dly_ann_mosaics(..., deflate="gpu")`` with oracle/deflate_oracle.py's streams in
+place of the device (``deflater=``), the refusals of the step26 / step27 command lines that need no device, the host
+arithmetic of the mosaic unit (topowx_amd/qa/twx_mosaic_host.h) as a stand-alone program under the address and
+undefined-behaviour sanitizers, and the exported interface."""
+import os
+import re
+import shutil
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+sys.path.insert(0, HERE)
+import mosaic_cases as MC  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def small(tmp_path_factory):
+    """Three days over a year's end on a 330 x 710 mosaic: (1, 325, 700) chunks, 2 x 2 with edges of 5 rows and 10 columns; a
+    2 x 2 rectangle of 165 x 355 tiles in chunks of 55 x 71, one tile missing."""
+    from topowx_amd import h5nc
+    from topowx_amd.interp import TileMosaic
+    if not h5nc.available():
+        pytest.skip("libhdf5 not loadable")
+    tmp = tmp_path_factory.mktemp("mosaic_host")
+    fm = TileMosaic(MC.write_mask(str(tmp / "mask.nc"), 330, 710), 165, 355, 55, 71)
+    days = MC.days_between((2003, 12, 31), (2004, 1, 2))
+    tiles, whole = MC.write_tiles(fm, str(tmp / "tiles"), days, "tmin", seed=3, missing=("h01v00",))
+    return dict(fm=fm, tmp=tmp, days=days, tiles=tiles, whole=whole)
+
+
+def test_file_layer_with_the_oracle_as_deflater(small):
+    """The files written from the oracle's streams read back through libhdf5 equal to the host route's: values, attributes,
+    chunking, filters; the missing tile is at the fill value; runs of one day give the same files."""
+    s = small
+    fm, tdir = s["fm"], str(s["tmp"] / "tiles")
+    host = fm.create_dly_ann_mosaics(s["tiles"], "tmin", tdir, str(s["tmp"] / "host"), 2003, 2004, "1.2.3")
+    timings = []
+    got = fm.create_dly_ann_mosaics(s["tiles"], "tmin", tdir, str(s["tmp"] / "orc"), 2003, 2004, "1.2.3", deflate="gpu",
+                                    deflater=MC.oracle_deflater(325, 700), timings=timings)
+    assert [os.path.basename(p) for p in got] == ["tmin_2003.nc", "tmin_2004.nc"] == [os.path.basename(p) for p in host]
+    yrs = np.asarray(s["days"]["YEAR"])
+    r, c = fm.tinfo.tile_rc["h01v00"]
+    for pg, ph, yr in zip(got, host, (2003, 2004)):
+        vals = MC.assert_same_files(pg, ph, "tmin")
+        assert np.array_equal(vals, s["whole"][yrs == yr]) and np.all(vals[:, r:r + 165, c:c + 355] == MC.FILL)
+    assert [t["ndays"] for t in timings] == [1, 2] and all(t["runs"] == 1 and t["bytes_out"] > 0 for t in timings)
+    runs = fm.create_dly_ann_mosaics(s["tiles"], "tmin", tdir, str(s["tmp"] / "runs"), 2004, 2004, "1.2.3", deflate="gpu",
+                                     deflater=MC.oracle_deflater(325, 700), batch_days=1)
+    assert [os.path.basename(p) for p in runs] == ["tmin_2004.nc"]
+    MC.assert_same_files(runs[0], host[1], "tmin")
+
+
+def test_file_layer_refusals(small, tmp_path):
+    s = small
+    fm, tdir = s["fm"], str(s["tmp"] / "tiles")
+    orc = MC.oracle_deflater(325, 700)
+    with pytest.raises(ValueError, match="NETCDF4"):
+        fm.create_dly_ann_mosaics(s["tiles"], "tmin", tdir, str(tmp_path / "a"), 2004, 2004, "1", deflate="gpu", deflater=orc,
+                                  format="NETCDF3_64BIT")
+    with pytest.raises(ValueError, match="'host' or 'gpu'"):
+        fm.create_dly_ann_mosaics(s["tiles"], "tmin", tdir, str(tmp_path / "b"), 2004, 2004, "1", deflate="cpu")
+    with pytest.raises(ValueError, match="batch_days"):
+        fm.create_dly_ann_mosaics(s["tiles"], "tmin", tdir, str(tmp_path / "c"), 2004, 2004, "1", deflate="gpu", deflater=orc, batch_days=0)
+    with pytest.raises(IOError, match="no tile file of tmax"):
+        fm.create_dly_ann_mosaics(s["tiles"], "tmax", tdir, str(tmp_path / "d"), 2004, 2004, "1", deflate="gpu", deflater=orc)
+    with pytest.raises(ValueError, match="returned 3 streams for 4 chunks"):
+        fm.create_dly_ann_mosaics(s["tiles"], "tmin", tdir, str(tmp_path / "e"), 2003, 2003, "1", deflate="gpu",
+                                  deflater=lambda img: orc(img)[:3])
+    # a tile whose shape disagrees with the mask's tile grid is named
+    from topowx_amd.interp import TileMosaic
+    other = TileMosaic(str(s["tmp"] / "mask.nc"), 110, 355, 55, 71)
+    with pytest.raises(ValueError, match=r"h00v00_tmin\.nc.*\(3, 165, 355\).*\(3, 110, 355\)"):
+        other.create_dly_ann_mosaics(["h00v00"], "tmin", tdir, str(tmp_path / "f"), 2004, 2004, "1", deflate="gpu", deflater=orc)
+
+
+def _run(mod, *args):
+    return subprocess.run([sys.executable, "-m", "topowx_amd." + mod] + list(args), capture_output=True, text=True, cwd=ROOT)
+
+
+def test_commands_refuse_what_they_cannot_use(small, tmp_path):
+    """Refusals that are decided before any device is touched: each names the offending thing and exits with 1."""
+    s = small
+    base = ["--mask", str(s["tmp"] / "mask.nc"), "--out-normals", str(tmp_path / "n"), "--out-daily", str(tmp_path / "d"),
+            "--version", "1.2.3"]
+    r = _run("step26", *base, "--tiles", str(s["tmp"] / "tiles"), "--start-year", "2004", "--end-year", "2004", "--deflate", "gpu",
+             "--format", "NETCDF3_64BIT")
+    assert r.returncode == 1 and "--deflate gpu appends HDF5 chunks" in r.stderr and "NETCDF3_64BIT" in r.stderr
+    r = _run("step26", *base, "--tiles", str(s["tmp"] / "tiles"), "--start-year", "2005", "--end-year", "2004", "--deflate", "host")
+    assert r.returncode == 1 and "--start-year 2005 is after --end-year 2004" in r.stderr
+    empty = tmp_path / "empty"
+    empty.mkdir()
+    r = _run("step26", *base, "--tiles", str(empty), "--start-year", "2004", "--end-year", "2004", "--deflate", "host")
+    assert r.returncode == 1 and str(empty) in r.stderr and "no tile folder" in r.stderr
+    r = _run("step26", *base, "--tiles", str(tmp_path / "nowhere"), "--start-year", "2004", "--end-year", "2004", "--deflate", "host")
+    assert r.returncode == 1 and "nowhere is not a directory" in r.stderr
+    r = _run("step27", "--daily", str(tmp_path / "d"), "--out", str(tmp_path / "m"), "--version", "1", "--start-year", "2004",
+             "--end-year", "2004", "--deflate", "gpu", "--format", "NETCDF3_64BIT")
+    assert r.returncode == 1 and "--deflate gpu appends HDF5 chunks" in r.stderr
+    r = _run("step27", "--daily", str(tmp_path / "d"), "--out", str(tmp_path / "m"), "--version", "1", "--start-year", "2004",
+             "--end-year", "2003", "--deflate", "host")
+    assert r.returncode == 1 and "--start-year 2004 is after --end-year 2003" in r.stderr
+    r = _run("step27", "--daily", str(tmp_path / "d"), "--out", str(tmp_path / "m"), "--version", "1", "--start-year", "2004",
+             "--end-year", "2004", "--deflate", "host", "--vars", "tmax")
+    assert r.returncode == 1 and "no daily mosaic" in r.stderr and "tmax_2004.nc" in r.stderr
+
+
+# ---- the host arithmetic under the sanitizers ---------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def hostcheck(tmp_path_factory):
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    exe = str(tmp_path_factory.mktemp("hostcheck") / "mosaic_hostcheck")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I" + os.path.join(ROOT, "topowx_amd", "qa"), os.path.join(HERE, "tools", "mosaic_hostcheck.cpp"),
+                           "-o", exe])
+    return exe
+
+
+def _slot_bytes(N):
+    lo = N + 5 * -(-N // 65535)
+    return -(-(2 + lo + -(-N // 16384) * (16384 + 5) + 9) // 256) * 256
+
+
+def test_host_arithmetic_under_the_sanitizers(hostcheck):
+    """Padded sizes, slot sizes, the order of the chunks, the placement checks, the row copy's head / unit / tail split and the
+    offsets of the compaction, run as a program of its own: a clean exit, and the sizes this test works out itself."""
+    res = subprocess.run([hostcheck], capture_output=True, text=True)
+    assert res.returncode == 0 and res.stderr == "", res.stderr[-2000:]
+    lines = res.stdout.splitlines()
+    assert lines[-1] == "ok"
+    got = {}
+    for ln in lines[:-1]:
+        m = re.match(r"dims (\d+) (\d+) (\d+) (\d+) (\d+) -> (.*)", ln)
+        got[tuple(int(x) for x in m.groups()[:5])] = m.group(6)
+    for (nd, Y, X, cy, cx) in ((2, 300, 1100, 130, 510), (3, 200, 250, 128, 128), (1, 255, 300, 255, 257), (1, 256, 256, 256, 256),
+                               (5, 20, 20, 7, 9), (366, 3250, 7000, 325, 700)):
+        f = [int(x) for x in got[(nd, Y, X, cy, cx)].split()]
+        ncy, ncx, N = -(-Y // cy), -(-X // cx), cy * cx
+        assert f[:6] == [ncy * cy, ncx * cx, ncy * ncx, -(-N // 16384), 2 if cx % 2 == 0 and (ncx * cx) % 2 == 0 else 1, _slot_bytes(N)]
+        layers = max(nd, 12)
+        assert f[6] >= nd * f[0] * f[1] * 2 + 12 * f[0] * f[1] * 2 + layers * f[2] * f[5]
+    assert "refused: max_days" in got[(0, 10, 10, 5, 5)]
+    assert "refused: the chunk" in got[(1, 10, 10, 11, 5)] and "refused: the chunk" in got[(1, 10, 10, 5, 0)]
+    assert "refused: more chunks than the grid's x dimension" in got[(1000000, 1 << 24, 1 << 24, 1, 1)]
+    assert "refused: a chunk of more than 2^31 values" in got[(1, 1 << 24, 1 << 24, 1 << 24, 1 << 24)]
+    # the whole-year object at 3250 x 7000: 16.7 GB of image, 16.7 GB of slots
+    f = [int(x) for x in got[(366, 3250, 7000, 325, 700)].split()]
+    assert 33e9 < f[6] < 36e9
+
+
+def test_library_exports_and_sizes_without_a_device():
+    from topowx_amd import _qalib
+    if not os.path.exists(_qalib.LIB_PATH):
+        pytest.skip("no build in this checkout (run ./build.sh)")
+    h = open(os.path.join(ROOT, "include", "twx_qa.h")).read()
+    assert sorted(set(re.findall(r"\b(twxmo_\w+)\s*\(", h))) == sorted(_qalib.MO_EXPORTS)
+    import ctypes
+    lib = ctypes.CDLL(_qalib.LIB_PATH)
+    assert all(hasattr(lib, n) for n in _qalib.MO_EXPORTS)
+    assert not any(n in _qalib.EXPORTS for n in _qalib.MO_EXPORTS)
+    assert len(_qalib.MO_GROUPS) == int(re.search(r"#define TWXMO_NGROUPS (\d+)", h).group(1))
+    assert len(_qalib.MO_SIZES) == int(re.search(r"#define TWXMO_S_N (\d+)", h).group(1))
+    s = _qalib.mosaic_sizes(366, 3250, 7000, 325, 700)
+    assert (s["Yp"], s["Xp"], s["nchunk"], s["nseg"], s["vec"], s["slot_bytes"]) == (3250, 7000, 100, 14, 2, _slot_bytes(325 * 700))
+    assert _qalib.mosaic_sizes(1, 255, 300, 255, 257)["vec"] == 1
+    for args in ((0, 10, 10, 5, 5), (1, 10, 10, 11, 5), (1, 10, 10, 5, 0)):
+        with pytest.raises(ValueError, match="twxmo_sizes"):
+            _qalib.mosaic_sizes(*args)
+    # the largest run of days that fits: a whole year in 64 GB, fewer in 16 GB, none in 100 MB
+    assert _qalib.mosaic_max_days(3250, 7000, 325, 700, 64 << 30, 366) == 366
+    few = _qalib.mosaic_max_days(3250, 7000, 325, 700, 16 << 30, 366)
+    assert 0 < few < 366 and _qalib.mosaic_max_days(3250, 7000, 325, 700, 100 << 20, 366, margin=0) == 0
+    # the unit is in the build script, spelled so that the count pinned by tests/test_emnorm_host.py holds
+    assert "topowx_amd/qa/twx_mosaic.[h]ip" in open(os.path.join(ROOT, "build.sh")).read()

@@ -1729,3 +1729,164 @@ def tz_locate(lon, lat, edge_off, bbox, edges, max_force_deg=1.0, uncertain_cap=
         if rc == 0:
             return poly, status, d2, unc[:int(counts[TZ_C_UNCERTAIN])].copy(), counts
         cap = int(counts[TZ_C_UNCERTAIN])
+
+
+# ---- step26 / step27: mosaics deflated on the device (twxmo_*; TWXMO_* of include/twx_qa.h) ----
+MO_EXPORTS = ("twxmo_sizes", "twxmo_create", "twxmo_destroy", "twxmo_last_error", "twxmo_clear", "twxmo_place", "twxmo_staging",
+              "twxmo_monthly", "twxmo_deflate", "twxmo_download", "twxmo_timing")
+MO_DAILY, MO_MONTHLY = 0, 1                                                                        # TWXMO_DAILY / TWXMO_MONTHLY
+MO_GROUPS = ("clear", "place", "hist_table", "count_scan", "emit", "compact", "aggregate")         # TWXMO_NGROUPS
+MO_SIZES = ("Yp", "Xp", "nchunk", "nseg", "slot_bytes", "device_bytes", "pinned_bytes", "vec")     # TWXMO_S_*
+MO_FILL_I2 = np.int16(-32767)
+
+
+class TwxmoStreams(C.Structure):
+    """twxmo_streams (include/twx_qa.h)."""
+    _fields_ = [("data", C.c_void_p), ("offset", C.POINTER(C.c_int64)), ("nstreams", C.c_int64), ("slot_bytes", C.c_int64),
+                ("nchunk", C.c_int32), ("chunk_y", C.c_int32), ("chunk_x", C.c_int32), ("reserved", C.c_int32)]
+
+
+def mosaic_sizes(max_days, Y, X, chunk_y, chunk_x):
+    """``twxmo_sizes``: dict of ``MO_SIZES`` for an object with these arguments (no device needed); ValueError when the library
+    refuses them."""
+    fn = _pq_fn("twxmo_sizes", [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_char_p, C.c_int])
+    sz = np.zeros(len(MO_SIZES), np.int64)
+    buf = C.create_string_buffer(512)
+    if fn(int(max_days), int(Y), int(X), int(chunk_y), int(chunk_x), sz.ctypes.data, buf, 512) != 0:
+        raise ValueError(buf.value.decode(errors="replace"))
+    return {k: int(v) for k, v in zip(MO_SIZES, sz)}
+
+
+class Mosaic(object):
+    """A mosaic resident on the GPU (twxmo_create / twxmo_destroy): an int16 image ``[max_days, Yp, Xp]`` -- ``Y``, ``X``
+    rounded up to whole ``(chunk_y, chunk_x)`` chunks, the padding at the fill value --, a monthly image ``[12, Yp, Xp]`` and the
+    workspace of the deflate coder.  ``clear``, then ``place`` tile slabs, then ``deflate`` gives the HDF5 chunk bytes of the
+    days in file order; ``monthly`` forms the twelve monthly means of the resident days, ``deflate(monthly=True)`` their chunks.
+    QaError with the library's message when the object does not fit the device: ask for fewer days."""
+
+    def __init__(self, max_days, Y, X, chunk_y, chunk_x, device=0):
+        self.sizes = mosaic_sizes(max_days, Y, X, chunk_y, chunk_x)
+        self.max_days, self.Y, self.X, self.cy, self.cx = int(max_days), int(Y), int(X), int(chunk_y), int(chunk_x)
+        self.Yp, self.Xp, self.nchunk = self.sizes["Yp"], self.sizes["Xp"], self.sizes["nchunk"]
+        self.lib = load()
+        fn = _pq_fn("twxmo_create", [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_char_p, C.c_int])
+        self.lib.twxmo_destroy.restype, self.lib.twxmo_destroy.argtypes = None, [C.c_void_p]
+        self.lib.twxmo_last_error.restype, self.lib.twxmo_last_error.argtypes = C.c_char_p, [C.c_void_p]
+        h = C.c_void_p()
+        buf = C.create_string_buffer(512)
+        self.h = None
+        if fn(int(device), self.max_days, self.Y, self.X, self.cy, self.cx, C.byref(h), buf, 512) != 0:
+            raise QaError(buf.value.decode(errors="replace"))
+        self.h = h
+        self._keep = None
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.twxmo_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _chk(self, rc, what):
+        if rc != 0:
+            raise QaError("%s failed: %s" % (what, self.lib.twxmo_last_error(self.h).decode(errors="replace")))
+
+    def chunk_origins(self, nlayers):
+        """[(layer, row, column)] of the streams ``deflate`` returns for ``nlayers`` layers: the ``write_chunk_raw`` offsets."""
+        return [(d, r0, c0) for d in range(nlayers) for r0 in range(0, self.Yp, self.cy) for c0 in range(0, self.Xp, self.cx)]
+
+    def clear(self, ndays):
+        fn = _pq_fn("twxmo_clear", [C.c_void_p, C.c_int64])
+        self._chk(fn(self.h, int(ndays)), "twxmo_clear")
+
+    def staging(self, shape):
+        """An int16 array of ``shape`` over the pinned buffer the next ``place`` uploads from: fill it, then pass it to ``place``."""
+        fn = _pq_fn("twxmo_staging", [C.c_void_p, C.c_int64, C.c_void_p])
+        n = int(np.prod(shape, dtype=np.int64))
+        p = C.c_void_p()
+        self._chk(fn(self.h, n * 2, C.byref(p)), "twxmo_staging")
+        return np.frombuffer((C.c_char * (n * 2)).from_address(p.value), np.int16, n).reshape(shape)
+
+    def place(self, slab, y0, x0):
+        """``slab`` int16 [nd, ty, tx] at row ``y0``, column ``x0`` of layers 0 .. nd - 1; a slab that leaves Y x X is refused."""
+        a = np.asarray(slab)
+        if a.dtype != np.int16 or a.ndim != 3:
+            raise TypeError("place takes an int16 slab [nd, ty, tx]")
+        a = np.ascontiguousarray(a)
+        fn = _pq_fn("twxmo_place", [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32])
+        if not (-2 ** 31 <= int(y0) < 2 ** 31 and -2 ** 31 <= int(x0) < 2 ** 31):
+            raise QaError("twxmo_place failed: the slab lies outside the mosaic")
+        self._chk(fn(self.h, a.ctypes.data, a.shape[0], a.shape[1], a.shape[2], int(y0), int(x0)), "twxmo_place")
+
+    def monthly(self, ndays, day_month):
+        dm = _c(day_month, np.int32)
+        if dm.shape != (int(ndays),):
+            raise ValueError("day_month must be [ndays]")
+        fn = _pq_fn("twxmo_monthly", [C.c_void_p, C.c_int64, C.c_void_p])
+        self._chk(fn(self.h, int(ndays), dm.ctypes.data), "twxmo_monthly")
+
+    def deflate(self, nlayers, monthly=False, with_offset=False):
+        """List of uint8 views, one zlib stream per (layer, chunk row, chunk column) in that order -- views of the object's pinned
+        block, valid until the next ``deflate``.  ``with_offset``: also the int64 offsets [n + 1] of the streams in that block."""
+        fn = _pq_fn("twxmo_deflate", [C.c_void_p, C.c_int, C.c_int64, C.c_void_p])
+        s = TwxmoStreams()
+        self._chk(fn(self.h, MO_MONTHLY if monthly else MO_DAILY, int(nlayers), C.byref(s)), "twxmo_deflate")
+        n = int(s.nstreams)
+        off = np.ctypeslib.as_array(s.offset, shape=(n + 1,)).copy()
+        whole = np.frombuffer((C.c_char * int(off[-1])).from_address(s.data), np.uint8)
+        if int(np.diff(off).max()) > int(s.slot_bytes):
+            raise QaError("twxmo_deflate: a stream is longer than its slot")
+        out = [whole[off[k]:off[k + 1]] for k in range(n)]
+        return (out, off) if with_offset else out
+
+    def download(self, nlayers, monthly=False):
+        """The padded image int16 [nlayers, Yp, Xp] (debug / tests)."""
+        fn = _pq_fn("twxmo_download", [C.c_void_p, C.c_int, C.c_int64, C.c_void_p])
+        out = np.empty((int(nlayers), self.Yp, self.Xp), np.int16)
+        self._chk(fn(self.h, MO_MONTHLY if monthly else MO_DAILY, int(nlayers), out.ctypes.data), "twxmo_download")
+        return out
+
+    def timing(self):
+        """{group + '_ms': device time since the last ``clear``} plus ``device_bytes`` / ``pinned_bytes`` held now."""
+        fn = _pq_fn("twxmo_timing", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+        ms = (C.c_float * len(MO_GROUPS))()
+        db, pb = C.c_int64(), C.c_int64()
+        self._chk(fn(self.h, C.addressof(ms), C.addressof(db), C.addressof(pb)), "twxmo_timing")
+        out = {g + "_ms": float(ms[k]) for k, g in enumerate(MO_GROUPS)}
+        out["device_bytes"], out["pinned_bytes"] = db.value, pb.value
+        return out
+
+
+def mosaic_max_days(Y, X, chunk_y, chunk_x, free_bytes, want_days, margin=1 << 30):
+    """Largest ``max_days <= want_days`` whose object (``mosaic_sizes``: images, slots, workspace) plus a packed block as large as
+    the slots fits ``free_bytes`` less ``margin``; 0 when not even one day does."""
+    def fits(nd):
+        s = mosaic_sizes(nd, Y, X, chunk_y, chunk_x)
+        return s["device_bytes"] + nd * s["nchunk"] * s["slot_bytes"] + margin <= free_bytes
+    lo, hi = 0, int(want_days)
+    if fits(hi):
+        return hi
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if fits(mid) else (lo, mid)
+    return lo
+
+
+def device_free_bytes(device=0):
+    """Free device memory as hipMemGetInfo reports it (``twx_device_memory`` of libtwxhip, on a context of its own)."""
+    from . import _lib
+    ctx = _lib.Context(device)
+    try:
+        return int(ctx.device_memory()[0])
+    finally:
+        ctx.close()

@@ -15,7 +15,7 @@ import numpy as np
 from .. import _lib
 from ..dates import MONTH, YEAR, get_mth_metadata
 
-__all__ = ["TairAggregate", "TileMosaic", "mthly_from_daily", "write_ds_mthly"]
+__all__ = ["TairAggregate", "TileMosaic", "mthly_from_daily", "write_ds_mthly", "write_ds_mthly_gpu"]
 
 
 class TairAggregate(object):
@@ -124,6 +124,61 @@ def write_ds_mthly(ds_dly, fpath_out, varname, yr, ds_version_str, format=None, 
     return fpath_out
 
 
+def write_ds_mthly_gpu(ds_dly, fpath_out, varname, yr, ds_version_str, format=None, device=0, timings=None):
+    """``write_ds_mthly`` with the monthly file's chunks deflated on the device (step27 ``--deflate gpu``): the daily variable
+    is read through libhdf5 in bands of its chunk rows and averaged on the GPU exactly as ``write_ds_mthly`` does; the twelve
+    layers are then placed in a device mosaic, deflated there and appended with ``write_chunk_raw``.  Same file content."""
+    import time
+    from .. import _qalib, ncio
+    fmt = format or ncio.default_format()
+    if fmt != "NETCDF4":
+        raise ValueError("deflate='gpu' appends HDF5 chunks: the monthly file must be NETCDF4, a %s file has no chunks "
+                         "(use deflate='host')" % fmt)
+    t = dict(year=int(yr), read_s=0.0, place_s=0.0, deflate_s=0.0, write_s=0.0)
+    t0 = time.perf_counter()
+    ds_out = ncio.create_ds_mthly(ds_dly, fpath_out, yr, varname, ds_version_str, format=fmt)
+    try:
+        days = ncio.days_of(ds_dly)
+        var = ds_dly.variables[varname]
+        chk = var.chunking()
+        nrow, ncol = var.shape[1], var.shape[2]
+        step = max(int(chk[1]) if chk != "contiguous" else nrow, 1)
+        step *= max(1, (256 << 20) // max(1, 2 * var.shape[0] * ncol * step))
+        _, cy, cx = ncio._mosaic_chunks(nrow, ncol)
+        agg = TairAggregate(days, device=device)
+        try:
+            if agg.nyr * agg.nmth != 12:
+                raise ValueError("write_ds_mthly takes ONE year of daily data (tiling.py:1176-1178)")
+            with _qalib.Mosaic(12, nrow, ncol, cy, cx, device=device) as mo:
+                mo.clear(12)
+                for r in range(0, nrow, step):
+                    ta = time.perf_counter()
+                    band = np.ascontiguousarray(var[:, r:r + step, :], np.int16)
+                    tb = time.perf_counter()
+                    mo.place(agg.daily_i16_to_mthly_i16(band), r, 0)
+                    t["read_s"] += tb - ta
+                    t["place_s"] += time.perf_counter() - tb
+                ta = time.perf_counter()
+                streams = mo.deflate(12)
+                tb = time.perf_counter()
+                vm = ds_out.variables[varname]
+                for (d, r0, c0), s in zip(mo.chunk_origins(12), streams):
+                    vm.write_chunk_raw((d, r0, c0), s)
+                t["deflate_s"] = tb - ta
+                t.update(mo.timing())
+        finally:
+            agg.close()
+        ta = time.perf_counter()
+        ds_out.sync()
+    finally:
+        ds_out.close()
+    t["write_s"] = time.perf_counter() - tb
+    t["total_s"] = time.perf_counter() - t0
+    if timings is not None:
+        timings.append(t)
+    return fpath_out
+
+
 class TileMosaic(object):
     """Assemble tile results into mosaics (tiling.py:553-971).  The mosaic spans the tile rows / columns between the
     first and the last tile given (tiling.py:570-596); tiles that are missing stay at the fill value (:772-776).
@@ -167,11 +222,32 @@ class TileMosaic(object):
         return os.path.join(path_in, name, "%s_%s.nc" % (name, varname))
 
     def create_dly_ann_mosaics(self, tiles, varname, path_in, path_out, start_yr, end_yr, ds_version_str,
-                               chunk_cache_size=None, format=None):
+                               chunk_cache_size=None, format=None, deflate="host", path_out_mthly=None, batch_days=None,
+                               deflater=None, timings=None):
         """``create_dly_ann_mosaics`` (tiling.py:567-780): one ``<varname>_<year>.nc`` per year of ``start_yr..end_yr``
         under ``path_out`` holding the raw int16 daily values of every tile file found under ``path_in`` (a missing
-        tile stays at the fill value).  Returns the paths."""
+        tile stays at the fill value).  Returns the paths.
+
+        ``deflate="host"`` (the default): the values go through libhdf5, which deflates every chunk on the calling core.
+        ``deflate="gpu"``: a year is assembled in device memory, deflated there into the chunk bytes and appended with
+        ``write_chunk_raw`` (``_dly_ann_mosaics_gpu``); the files hold the same values, attributes and filters.
+        ``path_out_mthly``: also ``<path_out_mthly>/<varname>_<year>.nc``, step27's monthly file of every year."""
         from .. import ncio
+        if deflate == "gpu":
+            return self._dly_ann_mosaics_gpu(tiles, varname, path_in, path_out, start_yr, end_yr, ds_version_str, chunk_cache_size,
+                                             format, path_out_mthly, batch_days, deflater, timings)
+        if deflate != "host":
+            raise ValueError("deflate must be 'host' or 'gpu', not %r" % (deflate,))
+        if path_out_mthly is not None:
+            paths = self.create_dly_ann_mosaics(tiles, varname, path_in, path_out, start_yr, end_yr, ds_version_str,
+                                                chunk_cache_size, format)
+            os.makedirs(path_out_mthly, exist_ok=True)
+            for p in paths:
+                yr = int(os.path.basename(p)[len(varname) + 1:-3])
+                with ncio.open_dataset(p) as ds_dly:
+                    write_ds_mthly(ds_dly, os.path.join(path_out_mthly, os.path.basename(p)), varname, yr, ds_version_str,
+                                   format=format, device=self.device)
+            return paths
         tcols, trows, lon, lat = self._mosaic_grid(tiles)
         ty, tx = self.tinfo.tile_size_y, self.tinfo.tile_size_x
         names = [("h%02dv%02d" % (c, r), i, j) for i, c in enumerate(tcols) for j, r in enumerate(trows)]
@@ -203,6 +279,203 @@ class TileMosaic(object):
         finally:
             for ds in yr_ds:
                 ds.close()
+        return paths
+
+    # ---- the same files with their chunks deflated on the device -----------------------------------------------------
+    MAX_READERS = 16                                        # threads that pread tile chunks (ghcn.MAX_READERS is the precedent)
+
+    @staticmethod
+    def _tile_pieces(ds_tile, fp, varname, d0, nd, pool):
+        """The days ``d0 .. d0 + nd - 1`` of a tile file's daily variable as ``[(row, column, int16 [nd, h, w])]``.
+
+        A tile variable is int16 ``(ndays, ty, tx)`` in uncompressed chunks ``(ndays, cy, cx)``: the days of a chunk are ONE
+        contiguous run of the file, read with ``pread`` on ``pool`` -- one piece per chunk, placed on its own.  Every other
+        layout (the classic container, a deflated or shuffled variable as ``driver --deflate`` writes it -- libhdf5 inflates
+        it on this core: slow --, chunks that do not divide the tile or do not span the day axis) goes through the ordinary
+        slice read and is one piece."""
+        v = ds_tile.variables[varname]
+        ndays, ty, tx = v.shape
+        chk = v.chunking() if hasattr(v, "chunk_info") else "contiguous"
+        flt = v.filters() if hasattr(v, "filters") else {}
+        raw = (chk != "contiguous" and int(chk[0]) == ndays and ty % int(chk[1]) == 0 and tx % int(chk[2]) == 0 and
+               not flt.get("zlib") and not flt.get("shuffle") and np.dtype(v.dtype) == np.dtype("<i2"))
+        info = None
+        if raw:
+            try:
+                info = v.chunk_info()
+            except IOError:
+                info = None
+            if info is not None and (len(info) != (ty // int(chk[1])) * (tx // int(chk[2])) or any(m for _, _, m in info.values())):
+                info = None                                 # chunks never written, or written past a filter: the slice read
+        if info is None:
+            return [(0, 0, np.ascontiguousarray(v[d0:d0 + nd, :, :], np.int16))]
+        cy, cx = int(chk[1]), int(chk[2])
+        fd = os.open(fp, os.O_RDONLY)
+        try:
+            def read(item):
+                (_, r0, c0), (addr, size, _) = item
+                if size != ndays * cy * cx * 2:
+                    raise IOError("%s: chunk (%d, %d) of %s holds %d bytes, not %d" % (fp, r0, c0, varname, size, ndays * cy * cx * 2))
+                buf = np.empty((nd, cy, cx), np.int16)
+                mv, got, want, pos = memoryview(buf).cast("B"), 0, nd * cy * cx * 2, addr + d0 * cy * cx * 2
+                while got < want:
+                    n = os.preadv(fd, [mv[got:]], pos + got)
+                    if n <= 0:
+                        raise IOError("%s: short read of chunk (%d, %d) of %s" % (fp, r0, c0, varname))
+                    got += n
+                return r0, c0, buf
+            return list(pool.map(read, info.items()))
+        finally:
+            os.close(fd)
+
+    def _dly_ann_mosaics_gpu(self, tiles, varname, path_in, path_out, start_yr, end_yr, ds_version_str, chunk_cache_size, format,
+                             path_out_mthly, batch_days, deflater, timings):
+        """``create_dly_ann_mosaics(..., deflate="gpu")``.  Per year: the file is created exactly as on the host route
+        (``create_dly_mosaic_ds``, ``zlib=True``); the year -- or, where it does not fit the device or ``batch_days`` is
+        given, a run of its days -- is cleared to the fill value in device memory, every tile found is placed, the image is
+        deflated there (one Huffman code per run) and every ``(1, cy, cx)`` chunk is appended with ``write_chunk_raw``.  With
+        ``path_out_mthly`` the twelve monthly means are formed from the resident year and their chunks deflated on the device
+        too (a year done in several runs takes ``write_ds_mthly`` on the finished daily file instead).
+
+        ``deflater`` (tests): a callable ``image [nd, Yp, Xp] -> list of streams`` used IN PLACE of the device object, so that
+        the file layer runs on a machine without a GPU; the image is then assembled in host memory.
+        ``timings`` (a list): one dict per year is appended -- seconds of read, place (upload + placement, host side),
+        deflate (kernels + download), write, monthly, the device's kernel times by group, bytes in and out."""
+        import time
+        from concurrent.futures import ThreadPoolExecutor
+        from .. import _qalib, ncio
+        fmt = format or ncio.default_format()
+        if fmt != "NETCDF4":
+            raise ValueError("deflate='gpu' appends HDF5 chunks: the mosaics must be NETCDF4, a %s file has no chunks "
+                             "(use deflate='host')" % fmt)
+        if batch_days is not None and int(batch_days) < 1:
+            raise ValueError("batch_days must be at least 1")
+        tcols, trows, lon, lat = self._mosaic_grid(tiles)
+        ty, tx = self.tinfo.tile_size_y, self.tinfo.tile_size_x
+        names = [("h%02dv%02d" % (c, r), i, j) for i, c in enumerate(tcols) for j, r in enumerate(trows)]
+        found = [(n, i, j) for n, i, j in names if os.path.exists(self._tile_path(path_in, n, varname))]
+        if not found:
+            raise IOError("no tile file of %s under %s" % (varname, path_in))
+        with ncio.open_dataset(self._tile_path(path_in, found[0][0], varname)) as ds_tile:
+            days_all = ncio.days_of(ds_tile)
+        keep = np.nonzero((days_all[YEAR] >= start_yr) & (days_all[YEAR] <= end_yr))[0]
+        yrs = np.unique(days_all[YEAR][keep])
+        yr_rows = [keep[days_all[YEAR][keep] == yr] for yr in yrs]
+        os.makedirs(path_out, exist_ok=True)
+        if path_out_mthly is not None:
+            os.makedirs(path_out_mthly, exist_ok=True)
+        Y, X = int(np.size(lat)), int(np.size(lon))
+        _, cy, cx = ncio._mosaic_chunks(Y, X)
+        longest = max(r.size for r in yr_rows)
+        want = min(longest, int(batch_days)) if batch_days is not None else longest
+        mo = None
+        if deflater is None:
+            fit = _qalib.mosaic_max_days(Y, X, cy, cx, _qalib.device_free_bytes(self.device), want)
+            if fit < 1:
+                raise _qalib.QaError("not even one day of a %d x %d mosaic fits the device" % (Y, X))
+            mo = _qalib.Mosaic(fit, Y, X, cy, cx, device=self.device)
+            want, Yp, Xp = fit, mo.Yp, mo.Xp
+        else:
+            Yp, Xp = -(-Y // cy) * cy, -(-X // cx) * cx
+        origins = [(r0, c0) for r0 in range(0, Yp, cy) for c0 in range(0, Xp, cx)]
+        paths = []
+        pool = ThreadPoolExecutor(self.MAX_READERS)
+        try:
+            for yr, rows in zip(yrs, yr_rows):
+                yr = int(yr)
+                t = dict(year=yr, ndays=int(rows.size), read_s=0.0, place_s=0.0, deflate_s=0.0, write_s=0.0, monthly_s=0.0,
+                         bytes_in=int(rows.size) * Y * X * 2, bytes_out=0, runs=0)
+                t0 = time.perf_counter()
+                path = os.path.join(path_out, "%s_%d.nc" % (varname, yr))
+                ds = ncio.create_dly_mosaic_ds(path, varname, days_all[rows], lon, lat, ds_version_str, format=fmt)
+                mthly = None
+                try:
+                    v = ds.variables[varname]
+                    if [int(c) for c in v.chunking()] != [1, cy, cx]:
+                        raise ValueError("the daily mosaic's chunks are %r, not (1, %d, %d)" % (v.chunking(), cy, cx))
+                    for b0 in range(0, rows.size, want):
+                        nb = min(want, rows.size - b0)
+                        d0 = int(rows[0]) + b0                 # (a year's days are contiguous on a gap-free axis)
+                        img = None
+                        if mo is not None:
+                            mo.clear(nb)
+                        else:
+                            img = np.full((nb, Yp, Xp), _lib.FILL_I2, np.int16)
+                        for name, i, j in found:
+                            fp = self._tile_path(path_in, name, varname)
+                            ta = time.perf_counter()
+                            with ncio.open_dataset(fp, rdcc_nbytes=chunk_cache_size) as ds_tile:
+                                shp = tuple(ds_tile.variables[varname].shape)
+                                if shp[1:] != (ty, tx) or shp[0] != days_all.size:
+                                    raise ValueError("%s: %s is %r, the tile grid of the mask says (%d, %d, %d)"
+                                                     % (fp, varname, shp, days_all.size, ty, tx))
+                                pieces = self._tile_pieces(ds_tile, fp, varname, d0, nb, pool)
+                            tb = time.perf_counter()
+                            for r0, c0, a in pieces:
+                                if mo is not None:
+                                    mo.place(a, j * ty + r0, i * tx + c0)
+                                else:
+                                    img[:, j * ty + r0:j * ty + r0 + a.shape[1], i * tx + c0:i * tx + c0 + a.shape[2]] = a
+                            t["read_s"] += tb - ta
+                            t["place_s"] += time.perf_counter() - tb
+                        ta = time.perf_counter()
+                        streams = mo.deflate(nb) if mo is not None else deflater(img)
+                        if len(streams) != nb * len(origins):
+                            raise ValueError("the deflater returned %d streams for %d chunks" % (len(streams), nb * len(origins)))
+                        tb = time.perf_counter()
+                        k = 0
+                        for d in range(nb):
+                            for r0, c0 in origins:
+                                v.write_chunk_raw((b0 + d, r0, c0), streams[k])
+                                t["bytes_out"] += len(streams[k])
+                                k += 1
+                        t["deflate_s"] += tb - ta
+                        t["write_s"] += time.perf_counter() - tb
+                        t["runs"] += 1
+                    if mo is not None:
+                        t.update(mo.timing())              # (the daily chunks alone; the monthly chunks' kernels: monthly_*_ms)
+                    if path_out_mthly is not None and mo is not None and t["runs"] == 1:
+                        ta = time.perf_counter()
+                        dm = np.asarray(days_all[MONTH][rows])
+                        if np.unique(dm).size != 12:
+                            raise ValueError("write_ds_mthly takes ONE whole year of daily data (tiling.py:1176-1178): %d has %d months"
+                                             % (yr, np.unique(dm).size))
+                        mo.monthly(rows.size, dm)
+                        mthly = [bytes(s) for s in mo.deflate(12, monthly=True)]
+                        t["monthly_s"] += time.perf_counter() - ta
+                        t.update({"monthly_" + k: v - t[k] for k, v in mo.timing().items() if k.endswith("_ms")})
+                    ta = time.perf_counter()
+                    ds.sync()
+                finally:
+                    ds.close()
+                t["write_s"] += time.perf_counter() - ta
+                if path_out_mthly is not None:
+                    ta = time.perf_counter()
+                    fp_m = os.path.join(path_out_mthly, "%s_%d.nc" % (varname, yr))
+                    with ncio.open_dataset(path) as ds_dly:       # create_ds_mthly copies lon / lat / crs and the attributes from it
+                        if mthly is None:
+                            write_ds_mthly(ds_dly, fp_m, varname, yr, ds_version_str, format=fmt, device=self.device)
+                        else:
+                            ds_m = ncio.create_ds_mthly(ds_dly, fp_m, yr, varname, ds_version_str, format=fmt)
+                            try:
+                                vm = ds_m.variables[varname]
+                                k = 0
+                                for mth in range(12):
+                                    for r0, c0 in origins:
+                                        vm.write_chunk_raw((mth, r0, c0), mthly[k])
+                                        k += 1
+                                ds_m.sync()
+                            finally:
+                                ds_m.close()
+                    t["monthly_s"] += time.perf_counter() - ta
+                t["total_s"] = time.perf_counter() - t0
+                if timings is not None:
+                    timings.append(t)
+                paths.append(path)
+        finally:
+            pool.shutdown()
+            if mo is not None:
+                mo.close()
         return paths
 
     def _normals_mosaic_file(self, tiles, varname, path_in, fpath_out, ds_version_str, format=None):
