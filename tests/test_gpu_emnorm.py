@@ -121,7 +121,7 @@ def test_golden(gold, case, built):
     assert e.batches == 1 and e.rounds == -(-int(gold["iters"].max()) // 16)
     for k in ("em_prep_kernel_ms", "em_iter_kernel_ms", "em_upload_ms", "em_download_ms", "em_rounds", "em_batches",
               "assemble_s", "em_library_s"):
-        assert k in tm, k
+        assert k in tm and np.isfinite(tm[k]) and tm[k] >= 0, (k, tm)
     got, devs = as_items(e), []
     for i in range(576):
         want = {k: gold[k].ravel()[i] for k in ("mean", "variance", "iters", "status", "sd0", "margin")}

@@ -135,6 +135,7 @@ def test_seeded_pool(gold, tmp_path):
     assert sha == [str(s) for s in gold["pool/sha"]]
     assert stats["fallback"] == 0 and stats["values"] >= int(gold["pool/nvalues"].sum())
     assert stats["lines"] >= sum(d.count(b"\n") for _, d in pool["files"]) and set(tm) == {k + "_kernel_ms" for k in _qalib.GH_KERNELS}
+    assert all(np.isfinite(v) and v >= 0 for v in tm.values()), tm
     v2, q2 = ghcn.parse_dly_files(paths, pool["min_ymd"], pool["max_ymd"], batch_bytes=400000)
     assert v2.tobytes() == val.tobytes() and q2.tobytes() == flag.tobytes()
     # rows may be given in any order: file f fills row file_col[f]
@@ -165,10 +166,11 @@ def test_times_of_observation(gold, tmp_path):
             with pytest.raises(ValueError, match=r"tobs_bad_700_1948\.csv.*, line 6"):
                 ghcn.parse_tobs_files(files, case["ids"], case["min_ymd"], case["max_ymd"], element=case["element"])
             continue
-        stats = {}
+        stats, tm = {}, {}
         got = ghcn.parse_tobs_files(files, ["GHCN_" + s for s in case["ids"]], case["min_ymd"], case["max_ymd"],
-                                    element=case["element"], stats=stats)
+                                    element=case["element"], stats=stats, timing=tm)
         assert got.dtype == np.int16 and np.array_equal(got, r["tobs"]) and stats["outside"] == r["outside"], case["name"]
+        assert all(np.isfinite(tm[k + "_kernel_ms"]) and tm[k + "_kernel_ms"] >= 0 for k in _qalib.GH_KERNELS), tm
         if exc == "":
             assert np.array_equal(got, want), case["name"]
         else:                                                              # the one deviation: skipped and counted

@@ -43,12 +43,16 @@ def run_all(c, workspace_bytes=0, first_day=None, last_day=None):
     """The four entries on a case of ``HC.random_case``'s keys."""
     nd = c["obs"].shape[1]
     a, b = (0 if first_day is None else first_day), (nd - 1 if last_day is None else last_day)
-    out = dict(cnt=_qalib.obs_cnt(c["obs"], c["month"], a, b, workspace_bytes=workspace_bytes))
-    out["mean"], out["miss"] = _qalib.monthly_means(c["obs"], c["mth_first"], c["mth_ndays"], 9, workspace_bytes=workspace_bytes)
-    out["shift"], out["nshift"] = _qalib.tobs_shift(c["obs"], c["tobs"], workspace_bytes=workspace_bytes)
+    tm = {}
+    out = dict(cnt=_qalib.obs_cnt(c["obs"], c["month"], a, b, workspace_bytes=workspace_bytes, timing=tm))
+    out["mean"], out["miss"] = _qalib.monthly_means(c["obs"], c["mth_first"], c["mth_ndays"], 9, workspace_bytes=workspace_bytes,
+                                                    timing=tm)
+    out["shift"], out["nshift"] = _qalib.tobs_shift(c["obs"], c["tobs"], workspace_bytes=workspace_bytes, timing=tm)
     out.update(_qalib.homog_daily(c["obs"], c["mth_mean"], c["mth_miss"], c["pha"], c["mth_ymd"], c["mth_first"],
                                   c["mth_ndays"], c["adj_off"], c["adj_start"], c["adj_end"], c["adj"],
-                                  workspace_bytes=workspace_bytes))
+                                  workspace_bytes=workspace_bytes, timing=tm))
+    times = [k + "_kernel_ms" for k in _qalib.HM_KERNELS] + ["hm_upload_ms", "hm_download_ms"]
+    assert tm["hm_calls"] == 4 and all(np.isfinite(tm[k]) and tm[k] >= 0 for k in times), tm
     return out
 
 

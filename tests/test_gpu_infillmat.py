@@ -89,6 +89,7 @@ def test_golden(gold, case, built):
     assert (m.status == 0).all() and m.ngroups == 12 and m.rounds == int(gold["nrings"].max())
     assert sorted(tm) == ["compact_kernel_ms", "download_ms", "item_kernel_ms", "library_s", "pair_kernel_ms", "ring_kernel_ms",
                           "rounds", "thresholds_s", "transpose_s", "upload_ms"]
+    assert all(np.isfinite(tm[k]) and tm[k] >= 0 for k in tm if k.endswith("_ms")), tm
     assert np.array_equal(m.nnghs, gold["nnghs"]) and np.array_equal(m.max_dist, gold["max_dist"])
     assert np.array_equal(m.off, gold["off"]) and np.array_equal(m.idx, gold["idx"]) and np.array_equal(m.keep, gold["keep"])
     print("max |ioa - golden| %.3g, max |dist - golden| %.3g" % (np.abs(m.ioa - gold["ioa"]).max(),

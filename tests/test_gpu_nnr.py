@@ -61,7 +61,7 @@ def test_case_against_the_executed_reference(batch, gold, case):
     b, tm = batch
     assert b.set_of.tolist() == gold["stn_set"].tolist() and len(b.sets) == 11 and tm["nr_sets"] == 11
     for k in ("nr_gram_kernel_ms", "nr_eig_kernel_ms", "nr_scores_kernel_ms", "nr_upload_ms", "nr_download_ms", "nr_select_s"):
-        assert k in tm, k
+        assert k in tm and np.isfinite(tm[k]) and tm[k] >= 0, (k, tm)
     assert (b.res.status == _qalib.NR_OK).all() and (b.res.sweeps > 0).all() and (b.res.sweeps < _qalib.NR_MAX_SWEEPS).all()
     worst_sc, worst_ve, nsc, worst_re, nre = 0.0, 0.0, 0, 0.0, 0
     rd = case.reader()

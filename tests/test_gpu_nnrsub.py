@@ -63,7 +63,9 @@ def test_entry_equals_the_restatement_byte_for_byte(ndays, nlat, nlon):
         assert case["marks"] != (None, None) or want_counts[:, 1].sum() == 0
         assert ndays * nlat * nlon < 1000 or case["marks"] == (None, None) or want_counts[:, 1].min() > 0
         for layout in (_qalib.NS_TILED, _qalib.NS_PLAIN):
-            outs, counts = _qalib.ns_subset(layout=layout, **case)
+            tm = {}
+            outs, counts = _qalib.ns_subset(layout=layout, timing=tm, **case)
+            assert all(np.isfinite(tm[k + "_ms"]) and tm[k + "_ms"] >= 0 for k in _qalib.NS_KERNELS), tm
             again, counts2 = _qalib.ns_subset(layout=layout, **case)
             assert np.array_equal(counts, want_counts) and np.array_equal(counts2, counts)
             for p, (a, b, w) in enumerate(zip(outs, again, want)):

@@ -102,6 +102,7 @@ def test_single_station_is_its_batch_row_bit_for_bit(cases):
         many = xo.run_xval_many(ids)
         again = xo.run_xval_many(ids)
         assert np.array_equal(many.view(np.uint64), again.view(np.uint64))
+        assert np.isfinite(xo.last_timing["wls_kernel_ms"]) and xo.last_timing["wls_kernel_ms"] >= 0
         for r in (0, 17, 95, 208, ids.size - 1):
             one = xo.run_xval_stn(ids[r])
             assert one.shape == (13,)

@@ -213,6 +213,9 @@ def test_two_calls_give_identical_bytes(case):
     for k in ("flags", "status", "abs_dif", "pctile", "thres"):
         assert a[k].tobytes() == b[k].tobytes(), k
     assert qa_prcp.pors_counts(pool.prcp, pool.days).tobytes() == qa_prcp.pors_counts(pool.prcp, pool.days).tobytes()
+    tm = {}
+    _qalib.prcp_pors_counts(np.ascontiguousarray(pool.prcp.T), pool.days[YMD], timing=tm)
+    assert np.isfinite(tm["pc_rowcounts_kernel_ms"]) and tm["pc_rowcounts_kernel_ms"] >= 0
 
 
 def test_record_of_366_days_from_29_february():

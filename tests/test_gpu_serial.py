@@ -103,8 +103,11 @@ def test_select_300_series_in_batches():
     gf, gn = SC.simple_groups(nd)
     kw = dict(run_threshold=40, group_first=gf, group_ndays=gn, max_miss=3)
     one = _qalib.serial_complete(tair, tinf, flag, **kw)
-    many = _qalib.serial_complete(tair, tinf, flag, workspace_bytes=37 * nd * 14, **kw)
+    tm = {}
+    many = _qalib.serial_complete(tair, tinf, flag, workspace_bytes=37 * nd * 14, timing=tm, **kw)
     assert one["batches"] == 1 and many["batches"] == 9
+    times = [k + "_kernel_ms" for k in _qalib.SC_KERNELS] + [k + "_ms" for k in _qalib.SC_HOST_TIMES]
+    assert tm["sc_batches"] == 9 and all(np.isfinite(tm[k]) and tm[k] >= 0 for k in times), tm
     want = RS.serial_complete(tair, tinf, flag, **kw)
     same_select(one, want, "300 series")
     for name in ("serial", "flag_infilled", "max_run", "nmissing", "all_infill", "norm", "norm_nmths"):

@@ -37,6 +37,11 @@ def _runs(G):
                 yield str(name), str(combo)
 
 
+def _times_ok(t, kernel):
+    """The times an entry reported: its kernel's and the two host-clock ones, each finite and not negative."""
+    return all(np.isfinite(t[k]) and t[k] >= 0 for k in (kernel + "_kernel_ms", "rv_upload_ms", "rv_download_ms"))
+
+
 def test_sample_and_ring_against_the_golden(G):
     from topowx_amd import _qalib
     assert (_qalib.RV_OK, _qalib.RV_NEAREST, _qalib.RV_NODATA, _qalib.RV_NEEDS_FORCE, _qalib.RV_NO_DATA_ANYWHERE) == \
@@ -53,17 +58,19 @@ def test_sample_and_ring_against_the_golden(G):
         lon, lat = G[name + "_lon"][sel], G[name + "_lat"][sel]
         want = {k: G["%s_%s_%s" % (name, combo, k)] for k in ("value", "status", "row", "col", "forced", "ring_value", "ring_dist",
                                                                "ring_r", "ring_winner", "ring_runner_up")}
+        tm = {}
         got = _qalib.raster_sample(data, geo_t, ndata, lon, lat, band_ndata=band, extract_method=method, revert_nn=revert,
-                                   force_data_value=force)
+                                   force_data_value=force, timing=tm)
         what = (name, combo)
+        assert _times_ok(tm, _qalib.RV_KERNELS[0]), (what, tm)
         assert np.array_equal(got["status"], want["status"]), (what, "status", np.nonzero(got["status"] != want["status"])[0])
         assert np.array_equal(got["row"], want["row"]) and np.array_equal(got["col"], want["col"]), (what, "row / col")
         forced = np.nonzero(got["status"] == _qalib.RV_NEEDS_FORCE)[0]
         assert np.array_equal(forced, want["forced"]), (what, "forced")
         value = got["value"].copy()
         if forced.size:
-            nn = _qalib.raster_nearest_data(data, geo_t, ndata, got["row"][forced], got["col"][forced])
-            assert (nn["status"] == _qalib.RV_OK).all(), what
+            nn = _qalib.raster_nearest_data(data, geo_t, ndata, got["row"][forced], got["col"][forced], timing=tm)
+            assert (nn["status"] == _qalib.RV_OK).all() and _times_ok(tm, _qalib.RV_KERNELS[1]), (what, tm)
             assert np.array_equal(nn["ring"], want["ring_r"]), (what, "ring", nn["ring"], want["ring_r"])
             assert np.array_equal(nn["winner"], want["ring_winner"]), (what, "winner")
             assert nn["value"].tobytes() == want["ring_value"].tobytes(), (what, "ring value")
@@ -160,9 +167,11 @@ def test_dup_classes(nstn, G):
         lon[3], lat[3] = -lon[100], lat[100]
         lat[200] = np.nextafter(lat[100], 90.0)                       # one ulp away: by the products, whichever way they fall
         lon[200] = lon[100]
-    cls, size = _qalib.dup_classes(lon, lat)
+    tm = {}
+    cls, size = _qalib.dup_classes(lon, lat, timing=tm)
     wc, ws = RR.dup_classes(lon, lat)
     assert np.array_equal(cls, wc) and np.array_equal(size, ws), (nstn, np.nonzero(cls != wc)[0])
+    assert _times_ok(tm, _qalib.RV_KERNELS[2]), tm
     if nstn >= 2:
         assert cls[-1] == 0 and size[0] >= 2
     if nstn == 257:                                                   # and against the executed reference on the golden table
@@ -195,7 +204,7 @@ def test_col_count(nstn):
                 assert a.dtype == np.int32 and np.array_equal(a, want), (nstn, ndays, data.dtype, cols)
                 assert a.tobytes() == b.tobytes(), (nstn, ndays, "the batches change nothing")
                 if ndays >= 3 and (cols is None or len(cols)):
-                    assert t["rv_batches"] == 3, t
+                    assert t["rv_batches"] == 3 and _times_ok(t, _qalib.RV_KERNELS[3]), t
     with pytest.raises(ValueError, match="outside"):
         _qalib.col_count(np.zeros((3, nstn), np.int8), [nstn])
 

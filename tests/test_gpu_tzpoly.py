@@ -174,6 +174,7 @@ def test_two_calls_give_the_same_bytes(tmp_path):
         poly, status, d2, unc, counts = _qalib.tz_locate(lon, lat, tz.edge_off, tz.bbox, tz.edges, 1.0, cap)
         _qalib.tz_locate(lon, lat, tz.edge_off, tz.bbox, tz.edges, 1.0, cap, timing=tm)
         assert tm["tz_calls"] == (2 if cap == 1 else 1)            # the overflow-and-retry path was taken
+        assert all(np.isfinite(tm[k + "_ms"]) and tm[k + "_ms"] >= 0 for k in _qalib.TZ_PHASES), tm
         assert unc.shape[0] == counts[_qalib.TZ_C_UNCERTAIN] > 1 and np.array_equal(unc, unc[np.lexsort((unc[:, 1], unc[:, 0]))])
         outs.append(b"".join(a.tobytes() for a in (poly, status, d2, unc, counts)))
     assert outs[0] == outs[1] == outs[2] == outs[3]

@@ -37,7 +37,9 @@ def test_holdout_smallest_shapes(ndays):
     rows = XC.holdout_rows(ndays)
     idx = np.arange(len(rows), dtype=np.int32)[::-1].copy()         # the rows in another order than the table's
     for nkeep in XC.holdout_nkeeps(rows):
-        got = _qalib.holdout(rows, idx, nkeep)
+        tm = {}
+        got = _qalib.holdout(rows, idx, nkeep, timing=tm)
+        assert np.isfinite(tm["xv_holdout_kernel_ms"]) and tm["xv_holdout_kernel_ms"] >= 0
         held, train, nheld, nfin = XC.want_holdout(rows[idx], nkeep)
         assert np.array_equal(got["held"], held), (ndays, nkeep)
         assert got["train_obs"].tobytes() == train.tobytes(), (ndays, nkeep)
@@ -67,8 +69,11 @@ def _same(a, b):
 
 def test_exclusion_of_nothing_is_the_old_entry(infill_case):
     args, old = infill_case
-    new = _qalib.infill_matrix(exclude_idx=np.full(args["lon"].size, -1, np.int32), **args)
+    tm = {}
+    new = _qalib.infill_matrix(exclude_idx=np.full(args["lon"].size, -1, np.int32), timing=tm, **args)
     assert _same(old, new) == [] and new["rounds"] == old["rounds"]
+    times = [k for k in tm if k.endswith("_ms")]
+    assert len(times) >= 4 and all(np.isfinite(tm[k]) and tm[k] >= 0 for k in times), tm
 
 
 def test_exclusion_of_one_station_per_target(infill_case):
@@ -174,7 +179,9 @@ def test_isolation_on_the_facade_pool():
 @pytest.mark.parametrize("n", CC.GRID_N)
 def test_score(n):
     infill, obs, held, group = XC.score_series(n)
-    got = _qalib.xval_score(infill, obs, held, group)
+    tm = {}
+    got = _qalib.xval_score(infill, obs, held, group, timing=tm)
+    assert np.isfinite(tm["xv_score_kernel_ms"]) and tm["xv_score_kernel_ms"] >= 0
     again = _qalib.xval_score(infill, obs, held, group)
     for k in got:
         assert got[k].tobytes() == again[k].tobytes(), k

@@ -39,9 +39,8 @@
 #include <vector>
 
 #include "twx_qa.h"
+#include "twx_qa_common.h"
 
-#define CB_RADIAN 0.017453292519943295       // util_geo.py:21
-#define CB_EARTH_KM 6371.009                 // util_geo.py:22
 #define CB_NJOBS 380                         // 365 rows + the 15 leap rows whose window holds Feb 29
 #define CB_LEAP_FIRST 52                     // Feb 22 of the 366-row table
 #define CB_BIWEIGHT_C 7.5                    // qa_temp.py:1173
@@ -195,7 +194,7 @@ __global__ __launch_bounds__(64) void k_radius_dist(int64_t nstn, const double *
     const int lane = threadIdx.x;
     const int64_t t = blockIdx.x;
     const int32_t self = target_idx[t];
-    const double lat1rad = lat[self] * CB_RADIAN, lon1rad = lon[self] * CB_RADIAN;
+    const double lat1rad = lat[self] * QA_RADIAN, lon1rad = lon[self] * QA_RADIAN;
     const double cos1 = cos(lat1rad);
     int64_t pos = 0;
     int room = 0;
@@ -210,10 +209,7 @@ __global__ __launch_bounds__(64) void k_radius_dist(int64_t nstn, const double *
         bool in = false;
         double dist = 0.0;
         if (j < nstn && j != self) {
-            const double lat2rad = lat[j] * CB_RADIAN, lon2rad = lon[j] * CB_RADIAN;
-            const double s1 = sin((lat1rad - lat2rad) / 2.0), s2 = sin((lon1rad - lon2rad) / 2.0);
-            const double a = s1 * s1 + (cos1 * cos(lat2rad)) * (s2 * s2);
-            dist = CB_EARTH_KM * (2.0 * asin(sqrt(a)));
+            dist = qa_dist_km(lat1rad, lon1rad, cos1, lat[j], lon[j]);
             in = dist <= TWXQA_NGH_RADIUS_KM;
         }
         const uint64_t b = __ballot(in);
@@ -358,46 +354,6 @@ __global__ __launch_bounds__(256) void k_mega_final(int64_t ndays, const float *
 // ---------------------------------------------------------------------------------
 namespace {
 
-int cb_fail(char *errbuf, int errlen, const char *what, hipError_t e = hipSuccess)
-{
-    if (errbuf && errlen > 0) {
-        if (e != hipSuccess) snprintf(errbuf, (size_t)errlen, "%s: %s", what, hipGetErrorString(e));
-        else snprintf(errbuf, (size_t)errlen, "%s", what);
-    }
-    return -1;
-}
-
-struct CbBuf {
-    void *p = nullptr;
-    ~CbBuf() { if (p) (void)hipFree(p); }
-};
-
-struct CbTimer {                                                 // HIP-event time of a run of launches on the null stream
-    hipEvent_t a = nullptr, b = nullptr;
-    ~CbTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    hipError_t init() { hipError_t e = hipEventCreate(&a); return e != hipSuccess ? e : hipEventCreate(&b); }
-    hipError_t start() { return hipEventRecord(a, nullptr); }
-    hipError_t stop(float *ms)
-    {
-        hipError_t e = hipEventRecord(b, nullptr);
-        if (e == hipSuccess) e = hipEventSynchronize(b);
-        if (e == hipSuccess) e = hipEventElapsedTime(ms, a, b);
-        return e;
-    }
-};
-
-int64_t cb_days_from_civil(int64_t y, int mth, int day)           // days since 1970-01-01, proleptic Gregorian
-{
-    y -= mth <= 2;
-    const int64_t era = (y >= 0 ? y : y - 399) / 400;
-    const int64_t yoe = y - era * 400;
-    const int64_t doy = (153 * (mth + (mth > 2 ? -3 : 9)) + 2) / 5 + day - 1;
-    const int64_t doe = yoe * 365 + yoe / 4 - yoe / 100 + doy;
-    return era * 146097 + doe - 719468;
-}
-
-bool cb_leap(int y) { return (y % 4 == 0 && y % 100 != 0) || y % 400 == 0; }
-
 // The calendar tables of a day axis of consecutive days (checked): per year of the series (Jan 1's series index,
 // leap), per day the row of the 731-row normals (365-row table first) and the month.  -1 and a message on failure.
 struct CbCalendar {
@@ -414,30 +370,30 @@ int cb_calendar(const char *fn, int64_t ndays, const int32_t *ymd, CbCalendar &c
     const int y0 = a / 10000, m0 = (a / 100) % 100, d0 = a % 100;
     if (a < 10101 || m0 < 1 || m0 > 12 || d0 < 1 || d0 > 31) {
         snprintf(msg, sizeof msg, "%s: ymd[0] is not a date", fn);
-        return cb_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
-    const int64_t z0 = cb_days_from_civil(y0, m0, d0);
+    const int64_t z0 = qa_days_from_civil(y0, m0, d0);
     c.normrow.resize((size_t)ndays);
     c.month.resize((size_t)ndays);
     int y = y0, mth = m0, day = d0;
     static const int mlen[12] = {31, 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31};
-    int64_t jan1 = cb_days_from_civil(y0, 1, 1) - z0;
-    c.yr.assign({(int32_t)jan1, cb_leap(y0) ? 1 : 0});
+    int64_t jan1 = qa_days_from_civil(y0, 1, 1) - z0;
+    c.yr.assign({(int32_t)jan1, qa_leap(y0) ? 1 : 0});
     for (int64_t i = 0; i < ndays; ++i) {
         if (ymd[i] != y * 10000 + mth * 100 + day) {
             snprintf(msg, sizeof msg, "%s: ymd[%lld] = %d: the days are not consecutive calendar days", fn, (long long)i,
                      (int)ymd[i]);
-            return cb_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
-        c.normrow[(size_t)i] = (int32_t)(i - jan1) + (cb_leap(y) ? 365 : 0);
+        c.normrow[(size_t)i] = (int32_t)(i - jan1) + (qa_leap(y) ? 365 : 0);
         c.month[(size_t)i] = (uint8_t)mth;
-        if (++day > mlen[mth - 1] + ((mth == 2 && cb_leap(y)) ? 1 : 0)) {
+        if (++day > mlen[mth - 1] + ((mth == 2 && qa_leap(y)) ? 1 : 0)) {
             day = 1;
             if (++mth > 12) {
                 mth = 1;
                 ++y;
                 jan1 = i + 1;
-                if (i + 1 < ndays) { c.yr.push_back((int32_t)jan1); c.yr.push_back(cb_leap(y) ? 1 : 0); }
+                if (i + 1 < ndays) { c.yr.push_back((int32_t)jan1); c.yr.push_back(qa_leap(y) ? 1 : 0); }
             }
         }
     }
@@ -446,51 +402,45 @@ int cb_calendar(const char *fn, int64_t ndays, const int32_t *ymd, CbCalendar &c
         snprintf(msg, sizeof msg, "%s: the series touches %d years; a row of the day-of-year normals holds at most "
                  "TWXQA_MAX_NORM_VALUES = %d values (15 per year, %d years)", fn, c.nyears, TWXQA_MAX_NORM_VALUES,
                  TWXQA_MAX_NORM_VALUES / 15);
-        return cb_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     return 0;
 }
 
 }  // namespace
 
-#define CBCHK(call)                                                                     \
-    do {                                                                                \
-        hipError_t e_ = (call);                                                         \
-        if (e_ != hipSuccess) return cb_fail(errbuf, errlen, #call, e_);                \
-    } while (0)
-
 extern "C" int twxqa_doy_norms(int device, int64_t nseries, int64_t ndays, const float *series, const int32_t *ymd,
                                double *norms, float *kernel_ms, char *errbuf, int errlen)
 {
     if (errbuf && errlen > 0) errbuf[0] = 0;
     if (nseries < 1 || ndays < 1 || ndays > INT32_MAX - 64 || nseries * CB_NJOBS > INT32_MAX)
-        return cb_fail(errbuf, errlen, "twxqa_doy_norms: need nseries >= 1, ndays >= 1 and nseries * 380 < 2^31");
-    if (!series || !ymd || !norms) return cb_fail(errbuf, errlen, "twxqa_doy_norms: null buffer");
+        return qa_fail(errbuf, errlen, "twxqa_doy_norms: need nseries >= 1, ndays >= 1 and nseries * 380 < 2^31");
+    if (!series || !ymd || !norms) return qa_fail(errbuf, errlen, "twxqa_doy_norms: null buffer");
     CbCalendar cal;
     if (cb_calendar("twxqa_doy_norms", ndays, ymd, cal, errbuf, errlen) != 0) return -1;
     const size_t ns = (size_t)nseries, nd = (size_t)ndays;
-    CBCHK(hipSetDevice(device));
-    CbBuf b_obs, b_yr, b_rows, b_out;
-    CbTimer tm;
-    CBCHK(tm.init());
-    CBCHK(hipMalloc(&b_obs.p, ns * nd * 4));
-    CBCHK(hipMemcpy(b_obs.p, series, ns * nd * 4, hipMemcpyHostToDevice));
-    CBCHK(hipMalloc(&b_yr.p, cal.yr.size() * 4));
-    CBCHK(hipMemcpy(b_yr.p, cal.yr.data(), cal.yr.size() * 4, hipMemcpyHostToDevice));
+    QACHK(hipSetDevice(device));
+    QaBuf b_obs, b_yr, b_rows, b_out;
+    QaTimer tm;
+    QACHK(tm.init());
+    QACHK(hipMalloc(&b_obs.p, ns * nd * 4));
+    QACHK(hipMemcpy(b_obs.p, series, ns * nd * 4, hipMemcpyHostToDevice));
+    QACHK(hipMalloc(&b_yr.p, cal.yr.size() * 4));
+    QACHK(hipMemcpy(b_yr.p, cal.yr.data(), cal.yr.size() * 4, hipMemcpyHostToDevice));
     std::vector<int32_t> rows(ns);
     for (size_t i = 0; i < ns; ++i) rows[i] = (int32_t)i;
-    CBCHK(hipMalloc(&b_rows.p, ns * 4));
-    CBCHK(hipMemcpy(b_rows.p, rows.data(), ns * 4, hipMemcpyHostToDevice));
-    CBCHK(hipMalloc(&b_out.p, ns * TWXQA_NORM_ROWS * 8));
+    QACHK(hipMalloc(&b_rows.p, ns * 4));
+    QACHK(hipMemcpy(b_rows.p, rows.data(), ns * 4, hipMemcpyHostToDevice));
+    QACHK(hipMalloc(&b_out.p, ns * TWXQA_NORM_ROWS * 8));
     float ms = 0.0f;
-    CBCHK(tm.start());
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_doy_norms, dim3((unsigned)(ns * CB_NJOBS)), dim3(256), 0, nullptr, ndays, cal.nyears,
                        (const int2 *)b_yr.p, (const float *)b_obs.p, (const int32_t *)b_rows.p, (const uint8_t *)nullptr,
                        (double *)b_out.p, 1, 0);
-    CBCHK(hipGetLastError());
-    CBCHK(tm.stop(&ms));
+    QACHK(hipGetLastError());
+    QACHK(tm.stop_set(&ms));
     if (kernel_ms) kernel_ms[0] = ms;
-    CBCHK(hipMemcpy(norms, b_out.p, ns * TWXQA_NORM_ROWS * 8, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(norms, b_out.p, ns * TWXQA_NORM_ROWS * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -501,15 +451,15 @@ extern "C" int twxqa_spatial_only(int device, int64_t nstn, int64_t ndays, const
 {
     if (errbuf && errlen > 0) errbuf[0] = 0;
     if (nstn < 1 || ndays < 1 || ntarget < 1 || nstn > INT32_MAX || ndays > INT32_MAX - 64 || ntarget > INT32_MAX)
-        return cb_fail(errbuf, errlen, "twxqa_spatial_only: need nstn >= 1, ndays >= 1 and ntarget >= 1");
+        return qa_fail(errbuf, errlen, "twxqa_spatial_only: need nstn >= 1, ndays >= 1 and ntarget >= 1");
     if (!lon || !lat || !tmin || !tmax || !ymd || !target_idx || !flag_tmin || !flag_tmax)
-        return cb_fail(errbuf, errlen, "twxqa_spatial_only: null buffer");
+        return qa_fail(errbuf, errlen, "twxqa_spatial_only: null buffer");
     CbCalendar cal;
     if (cb_calendar("twxqa_spatial_only", ndays, ymd, cal, errbuf, errlen) != 0) return -1;
     const size_t nt = (size_t)ntarget, ns = (size_t)nstn, nd = (size_t)ndays;
     const int nblk = (int)((ndays + 63) / 64);
     if ((int64_t)nblk * 2 * ntarget > INT32_MAX || (2 * nstn + 2 * ntarget) * CB_NJOBS > INT32_MAX)
-        return cb_fail(errbuf, errlen, "twxqa_spatial_only: more than 2^31 - 1 work items in one call");
+        return qa_fail(errbuf, errlen, "twxqa_spatial_only: more than 2^31 - 1 work items in one call");
 
     // ---- 1. the regression check, as it stands (it validates the coordinates and the target list) -----------------
     float ms[6] = {0, 0, 0, 0, 0, 0};
@@ -518,52 +468,52 @@ extern "C" int twxqa_spatial_only(int device, int64_t nstn, int64_t ndays, const
                               reg.data() + nt * nd, nullptr, nullptr, nullptr, nullptr, ms, errbuf, errlen) != 0)
         return -1;
 
-    CBCHK(hipSetDevice(device));
-    CbBuf b_geo, b_obs, b_tgt, b_csr, b_cal, b_slot, b_rows, b_nnorm, b_tnorm, b_flag;
-    CbTimer tm;
-    CBCHK(tm.init());
-    CBCHK(hipMalloc(&b_geo.p, ns * 16));
+    QACHK(hipSetDevice(device));
+    QaBuf b_geo, b_obs, b_tgt, b_csr, b_cal, b_slot, b_rows, b_nnorm, b_tnorm, b_flag;
+    QaTimer tm;
+    QACHK(tm.init());
+    QACHK(hipMalloc(&b_geo.p, ns * 16));
     double *d_lon = static_cast<double *>(b_geo.p), *d_lat = d_lon + ns;
-    CBCHK(hipMemcpy(d_lon, lon, ns * 8, hipMemcpyHostToDevice));
-    CBCHK(hipMemcpy(d_lat, lat, ns * 8, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_lon, lon, ns * 8, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_lat, lat, ns * 8, hipMemcpyHostToDevice));
     // per target: csr offsets (int64, nt + 1), index, count
-    CBCHK(hipMalloc(&b_tgt.p, (nt + 1) * 8 + nt * 8));
+    QACHK(hipMalloc(&b_tgt.p, (nt + 1) * 8 + nt * 8));
     int64_t *d_off = static_cast<int64_t *>(b_tgt.p);
     int32_t *d_idx = (int32_t *)(d_off + nt + 1), *d_cnt = d_idx + nt;
-    CBCHK(hipMemcpy(d_idx, target_idx, nt * 4, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_idx, target_idx, nt * 4, hipMemcpyHostToDevice));
 
     // ---- 2. the radius lists in distance order: count, scan on the host, fill + sort ------------------------------
     float ms_a = 0.0f, ms_b = 0.0f;
-    CBCHK(tm.start());
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_radius_dist, dim3((unsigned)nt), dim3(64), 0, nullptr, nstn, (const double *)d_lon,
                        (const double *)d_lat, (const int32_t *)d_idx, 0, d_cnt, (const int64_t *)nullptr, (int32_t *)nullptr,
                        (double *)nullptr);
-    CBCHK(hipGetLastError());
-    CBCHK(tm.stop(&ms_a));
+    QACHK(hipGetLastError());
+    QACHK(tm.stop_set(&ms_a));
     std::vector<int32_t> cnt(nt), tst(nt);
     std::vector<int64_t> off(nt + 1);
-    CBCHK(hipMemcpy(cnt.data(), d_cnt, nt * 4, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(cnt.data(), d_cnt, nt * 4, hipMemcpyDeviceToHost));
     off[0] = 0;
     for (size_t i = 0; i < nt; ++i) {                            // a list above the cap is not built: the target says so
         tst[i] = cnt[i] > TWXQA_MAX_RADIUS_NGH ? TWXQA_SP_NGH_CAP : (cnt[i] < TWXQA_MIN_NGHS ? TWXQA_SP_FEW_NGHS : TWXQA_SP_OK);
         off[i + 1] = off[i] + (tst[i] == TWXQA_SP_NGH_CAP ? 0 : cnt[i]);
     }
-    CBCHK(hipMemcpy(d_off, off.data(), (nt + 1) * 8, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_off, off.data(), (nt + 1) * 8, hipMemcpyHostToDevice));
     const size_t ncsr = (size_t)off[nt];
-    CBCHK(hipMalloc(&b_csr.p, std::max<size_t>(16, ncsr * 12)));
+    QACHK(hipMalloc(&b_csr.p, std::max<size_t>(16, ncsr * 12)));
     double *d_dist = static_cast<double *>(b_csr.p);
     int32_t *d_csr = (int32_t *)(d_dist + ncsr);
     if (ncsr > 0) {
-        CBCHK(tm.start());
+        QACHK(tm.start());
         hipLaunchKernelGGL(k_radius_dist, dim3((unsigned)nt), dim3(64), 0, nullptr, nstn, (const double *)d_lon,
                            (const double *)d_lat, (const int32_t *)d_idx, 1, d_cnt, (const int64_t *)d_off, d_csr, d_dist);
-        CBCHK(hipGetLastError());
-        CBCHK(tm.stop(&ms_b));
+        QACHK(hipGetLastError());
+        QACHK(tm.stop_set(&ms_b));
     }
     ms[2] = ms_a + ms_b;
     // the stations that are somebody's neighbour get normals: their slot in the table, -1 for the rest
     std::vector<int32_t> csr(ncsr), slot(ns, -1), rows;
-    if (ncsr > 0) CBCHK(hipMemcpy(csr.data(), d_csr, ncsr * 4, hipMemcpyDeviceToHost));
+    if (ncsr > 0) QACHK(hipMemcpy(csr.data(), d_csr, ncsr * 4, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < nt; ++i) {
         if (tst[i] != TWXQA_SP_OK) continue;                     // (a list shorter than 3 is never walked)
         for (int64_t k = off[i]; k < off[i + 1]; ++k) slot[(size_t)csr[(size_t)k]] = 0;
@@ -573,67 +523,67 @@ extern "C" int twxqa_spatial_only(int device, int64_t nstn, int64_t ndays, const
     const size_t nslot = rows.size();
 
     // ---- 3. the normals: neighbours from the pool as it is, targets without the days the regression check removed --
-    CBCHK(hipMalloc(&b_obs.p, 2 * ns * nd * 4));
+    QACHK(hipMalloc(&b_obs.p, 2 * ns * nd * 4));
     float *d_tmin = static_cast<float *>(b_obs.p), *d_tmax = d_tmin + ns * nd;
-    CBCHK(hipMemcpy(d_tmin, tmin, ns * nd * 4, hipMemcpyHostToDevice));
-    CBCHK(hipMemcpy(d_tmax, tmax, ns * nd * 4, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_tmin, tmin, ns * nd * 4, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_tmax, tmax, ns * nd * 4, hipMemcpyHostToDevice));
     // calendar: years (int2), normrow (int32), month (uint8)
     const size_t cal_yr = 0, cal_row = cal_yr + cal.yr.size() * 4, cal_mth = cal_row + nd * 4;
-    CBCHK(hipMalloc(&b_cal.p, cal_mth + nd));
+    QACHK(hipMalloc(&b_cal.p, cal_mth + nd));
     char *dc = static_cast<char *>(b_cal.p);
-    CBCHK(hipMemcpy(dc + cal_yr, cal.yr.data(), cal.yr.size() * 4, hipMemcpyHostToDevice));
-    CBCHK(hipMemcpy(dc + cal_row, cal.normrow.data(), nd * 4, hipMemcpyHostToDevice));
-    CBCHK(hipMemcpy(dc + cal_mth, cal.month.data(), nd, hipMemcpyHostToDevice));
-    CBCHK(hipMalloc(&b_slot.p, ns * 4));
-    CBCHK(hipMemcpy(b_slot.p, slot.data(), ns * 4, hipMemcpyHostToDevice));
-    CBCHK(hipMalloc(&b_rows.p, std::max<size_t>(4, nslot * 4)));
-    if (nslot > 0) CBCHK(hipMemcpy(b_rows.p, rows.data(), nslot * 4, hipMemcpyHostToDevice));
-    CBCHK(hipMalloc(&b_nnorm.p, std::max<size_t>(8, 2 * nslot * TWXQA_NORM_ROWS * 8)));
+    QACHK(hipMemcpy(dc + cal_yr, cal.yr.data(), cal.yr.size() * 4, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(dc + cal_row, cal.normrow.data(), nd * 4, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(dc + cal_mth, cal.month.data(), nd, hipMemcpyHostToDevice));
+    QACHK(hipMalloc(&b_slot.p, ns * 4));
+    QACHK(hipMemcpy(b_slot.p, slot.data(), ns * 4, hipMemcpyHostToDevice));
+    QACHK(hipMalloc(&b_rows.p, std::max<size_t>(4, nslot * 4)));
+    if (nslot > 0) QACHK(hipMemcpy(b_rows.p, rows.data(), nslot * 4, hipMemcpyHostToDevice));
+    QACHK(hipMalloc(&b_nnorm.p, std::max<size_t>(8, 2 * nslot * TWXQA_NORM_ROWS * 8)));
     double *d_nnorm = static_cast<double *>(b_nnorm.p);
-    CBCHK(hipMalloc(&b_tnorm.p, 2 * nt * TWXQA_NORM_ROWS * 8));   // [nt][2][731]
+    QACHK(hipMalloc(&b_tnorm.p, 2 * nt * TWXQA_NORM_ROWS * 8));   // [nt][2][731]
     double *d_tnorm = static_cast<double *>(b_tnorm.p);
     // flags: regress (2), corrob (2), final (2), each [nt][nd]
-    CBCHK(hipMalloc(&b_flag.p, 6 * nt * nd));
+    QACHK(hipMalloc(&b_flag.p, 6 * nt * nd));
     uint8_t *d_reg = static_cast<uint8_t *>(b_flag.p), *d_cor = d_reg + 2 * nt * nd, *d_fin = d_cor + 2 * nt * nd;
-    CBCHK(hipMemcpy(d_reg, reg.data(), 2 * nt * nd, hipMemcpyHostToDevice));
-    CBCHK(hipMemset(d_cor, 0, 2 * nt * nd));
-    CBCHK(tm.start());
+    QACHK(hipMemcpy(d_reg, reg.data(), 2 * nt * nd, hipMemcpyHostToDevice));
+    QACHK(hipMemset(d_cor, 0, 2 * nt * nd));
+    QACHK(tm.start());
     for (int v = 0; v < 2; ++v) {
         const float *d_obs = v ? d_tmax : d_tmin;
         if (nslot > 0) {
             hipLaunchKernelGGL(k_doy_norms, dim3((unsigned)(nslot * CB_NJOBS)), dim3(256), 0, nullptr, ndays, cal.nyears,
                                (const int2 *)(dc + cal_yr), d_obs, (const int32_t *)b_rows.p, (const uint8_t *)nullptr,
                                d_nnorm + (size_t)v * nslot * TWXQA_NORM_ROWS, 1, 0);
-            CBCHK(hipGetLastError());
+            QACHK(hipGetLastError());
         }
         hipLaunchKernelGGL(k_doy_norms, dim3((unsigned)(nt * CB_NJOBS)), dim3(256), 0, nullptr, ndays, cal.nyears,
                            (const int2 *)(dc + cal_yr), d_obs, (const int32_t *)d_idx, (const uint8_t *)(d_reg + (size_t)v * nt * nd),
                            d_tnorm, 2, v);
-        CBCHK(hipGetLastError());
+        QACHK(hipGetLastError());
     }
-    CBCHK(tm.stop(&ms[3]));
+    QACHK(tm.stop_set(&ms[3]));
 
     // ---- 4. the corroboration check -----------------------------------------------------------------------------
-    if (norms) CBCHK(hipMemcpy(norms, d_tnorm, 2 * nt * TWXQA_NORM_ROWS * 8, hipMemcpyDeviceToHost));
-    CBCHK(tm.start());
+    if (norms) QACHK(hipMemcpy(norms, d_tnorm, 2 * nt * TWXQA_NORM_ROWS * 8, hipMemcpyDeviceToHost));
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_corrob, dim3((unsigned)(nt * 2 * (size_t)nblk)), dim3(64), 0, nullptr, ndays, nblk,
                        (const float *)d_tmin, (const float *)d_tmax, (const int32_t *)(dc + cal_row), (const int32_t *)d_idx,
                        (const int64_t *)d_off, (const int32_t *)d_csr, (const int32_t *)b_slot.p, (int64_t)nslot,
                        (const double *)d_nnorm, (const double *)d_tnorm, (const uint8_t *)d_reg,
                        (const uint8_t *)(d_reg + nt * nd), d_cor, d_cor + nt * nd);
-    CBCHK(hipGetLastError());
-    CBCHK(tm.stop(&ms[4]));
+    QACHK(hipGetLastError());
+    QACHK(tm.stop_set(&ms[4]));
 
     // ---- 5. mega-inconsistency and the final flag numbers --------------------------------------------------------
-    CBCHK(tm.start());
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_mega_final, dim3((unsigned)nt), dim3(256), 0, nullptr, ndays, (const float *)d_tmin,
                        (const float *)d_tmax, (const uint8_t *)(dc + cal_mth), (const int32_t *)d_idx, (const uint8_t *)d_reg,
                        (const uint8_t *)(d_reg + nt * nd), (const uint8_t *)d_cor, (const uint8_t *)(d_cor + nt * nd), d_fin,
                        d_fin + nt * nd);
-    CBCHK(hipGetLastError());
-    CBCHK(tm.stop(&ms[5]));
-    CBCHK(hipMemcpy(flag_tmin, d_fin, nt * nd, hipMemcpyDeviceToHost));
-    CBCHK(hipMemcpy(flag_tmax, d_fin + nt * nd, nt * nd, hipMemcpyDeviceToHost));
+    QACHK(hipGetLastError());
+    QACHK(tm.stop_set(&ms[5]));
+    QACHK(hipMemcpy(flag_tmin, d_fin, nt * nd, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(flag_tmax, d_fin + nt * nd, nt * nd, hipMemcpyDeviceToHost));
     if (status) memcpy(status, tst.data(), nt * 4);
     if (kernel_ms) memcpy(kernel_ms, ms, sizeof ms);
     return 0;

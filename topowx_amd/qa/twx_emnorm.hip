@@ -1,7 +1,7 @@
 // twx_emnorm.hip -- libtwxqa.so: the mean / variance estimator of step14 (twx/infill/rpy/norm_infill.R: prelim.norm,
 // em.norm, getparam.norm, of which the reference keeps mu[1] and sigma[1, 1]) restated from Schafer (1997, section 5.3)
-// for every (target, day group) item of one call (include/twx_qa.h, twxem_mean_variance).  Its own translation unit:
-// the helpers it shares with twx_infillmat.hip (the buffer list, the event timer) are restated, nothing there is edited.
+// for every (target, day group) item of one call (include/twx_qa.h, twxem_mean_variance).  Its own translation unit;
+// the helpers it shares with the other units (the wave sums, the buffer list, the event timer) are twx_qa_common.h's.
 //
 // An item is a matrix of up to TWXEM_MAX_ROWS days by P <= 31 columns: the target, its station columns (float32 rows of
 // the station-major observations) and the columns of one optional extra set (float64).  theta is the symmetric
@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "twx_qa.h"
+#include "twx_qa_common.h"
 
 #define EM_D 32                              // theta is EM_D x EM_D: the constant and up to 31 columns
 #define EM_NW 4                              // wavefronts of a k_em_iter workgroup
@@ -55,20 +56,6 @@ __device__ __forceinline__ void wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ double em_wave_sum(double v)
-{
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v = v + __shfl_xor(v, m, 64);
-    return v;
-}
-
-__device__ __forceinline__ double em_wave_max(double v)
-{
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
-    return v;
 }
 
 // what a kernel needs to find the columns of an item
@@ -146,7 +133,7 @@ __global__ __launch_bounds__(256) void k_em_prep(EmIn in, int first_item, const 
                 atomicOr((unsigned *)&keys[r] + 1, 1u << (c + 1));
             }
         }
-        cnt = em_wave_sum(cnt); s1 = em_wave_sum(s1); s2 = em_wave_sum(s2);
+        cnt = qa_wave_sum(cnt); s1 = qa_wave_sum(s1); s2 = qa_wave_sum(s2);
         if (lane == 0) {
             const double xbar = s1 / cnt;
             double sdv = sqrt((s2 - s1 * s1 / cnt) / cnt);
@@ -348,7 +335,7 @@ __global__ __launch_bounds__(EM_THREADS) void k_em_iter(EmIn in, int first_item,
             dmax = fmax(dmax, ch);
             s_theta[e] = v;
         }
-        dmax = em_wave_max(dmax);
+        dmax = qa_wave_max(dmax);
         if (lane == 0) s_red[wave] = dmax;
         __syncthreads();
         dl = fmax(fmax(s_red[0], s_red[1]), fmax(s_red[2], s_red[3]));
@@ -384,57 +371,6 @@ __global__ __launch_bounds__(EM_THREADS) void k_em_iter(EmIn in, int first_item,
     }
 }
 
-namespace {
-
-int em_fail(char *errbuf, int errlen, const char *what, hipError_t e = hipSuccess)
-{
-    if (errbuf && errlen > 0) {
-        if (e != hipSuccess) snprintf(errbuf, (size_t)errlen, "%s: %s", what, hipGetErrorString(e));
-        else snprintf(errbuf, (size_t)errlen, "%s", what);
-    }
-    return -1;
-}
-
-struct EmBufs {                                                  // every device allocation of a call, freed together
-    std::vector<void *> p;
-    ~EmBufs() { for (void *x : p) if (x) (void)hipFree(x); }
-    hipError_t get(void **out, size_t bytes)
-    {
-        hipError_t e = hipMalloc(out, bytes ? bytes : 1);
-        if (e == hipSuccess) p.push_back(*out);
-        return e;
-    }
-};
-
-struct EmTimer {                                                 // HIP-event time of a run of launches on the null stream
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EmTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    hipError_t init() { hipError_t e = hipEventCreate(&a); return e != hipSuccess ? e : hipEventCreate(&b); }
-    hipError_t start() { return hipEventRecord(a, nullptr); }
-    hipError_t stop(float *acc)
-    {
-        float ms = 0.0f;
-        hipError_t e = hipEventRecord(b, nullptr);
-        if (e == hipSuccess) e = hipEventSynchronize(b);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
-        *acc += ms;
-        return e;
-    }
-};
-
-}  // namespace
-
-#define EMCHK(call)                                                                     \
-    do {                                                                                \
-        hipError_t e_ = (call);                                                         \
-        if (e_ != hipSuccess) return em_fail(errbuf, errlen, #call, e_);                \
-    } while (0)
-#define EMALLOC(bufs, ptr, type, count) EMCHK((bufs).get((void **)&(ptr), (size_t)(count) * sizeof(type)))
-#define EMUP(dst, src, type, count)                                                                         \
-    do {                                                                                                    \
-        if ((count) > 0) EMCHK(hipMemcpy((dst), (src), (size_t)(count) * sizeof(type), hipMemcpyHostToDevice)); \
-    } while (0)
-
 extern "C" int twxem_mean_variance(int device, int64_t nstn, int64_t ndays, const float *obs, int32_t ngroups,
                                    const int8_t *group, int64_t nitem, const int32_t *item_target,
                                    const int32_t *item_group, const int32_t *item_matrix_status, const int64_t *col_off,
@@ -450,16 +386,16 @@ extern "C" int twxem_mean_variance(int device, int64_t nstn, int64_t ndays, cons
     if (nstn < 1 || ndays < 1 || nitem < 1 || nstn > INT32_MAX || ndays > INT32_MAX || nitem > INT32_MAX / 2 ||
         ngroups < 1 || ngroups > 127 || nset < 0 || nset > INT32_MAX) {
         snprintf(msg, sizeof msg, "%s: need nstn, ndays, nitem >= 1, 1 <= ngroups <= 127 and nset >= 0", fn);
-        return em_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (!obs || !group || !item_target || !item_group || !col_off || !mean || !variance || !iters || !delta || !status ||
         (nset > 0 && (!set_group || !set_ncol || !set_vals || !item_set)) || ((mu == nullptr) != (sigma == nullptr))) {
         snprintf(msg, sizeof msg, "%s: null buffer (mu and sigma go together)", fn);
-        return em_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (!(criterion > 0.0) || !std::isfinite(criterion) || maxits < 1) {
         snprintf(msg, sizeof msg, "%s: criterion and maxits must be positive (defaults: TWXEM_DEFAULT_CRITERION, TWXEM_DEFAULT_MAXITS)", fn);
-        return em_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (iters_per_launch <= 0) iters_per_launch = TWXEM_ITERS_PER_LAUNCH;
     if (workspace_bytes <= 0) workspace_bytes = TWXEM_WORKSPACE_BYTES;
@@ -468,7 +404,7 @@ extern "C" int twxem_mean_variance(int device, int64_t nstn, int64_t ndays, cons
     for (int64_t d = 0; d < ndays; ++d) {
         if (group[d] < -1 || group[d] >= ngroups) {
             snprintf(msg, sizeof msg, "%s: group[%lld] = %d outside -1 .. %d", fn, (long long)d, (int)group[d], ngroups - 1);
-            return em_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         if (group[d] >= 0) ++goff[(size_t)group[d] + 1];
     }
@@ -481,7 +417,7 @@ extern "C" int twxem_mean_variance(int device, int64_t nstn, int64_t ndays, cons
         if (set_group[s] < 0 || set_group[s] >= ngroups || set_ncol[s] < 0 || set_ncol[s] > TWXEM_MAX_COLS) {
             snprintf(msg, sizeof msg, "%s: extra-column set %lld: group %d, %d columns (at most TWXEM_MAX_COLS = %d in all)",
                      fn, (long long)s, (int)set_group[s], (int)set_ncol[s], TWXEM_MAX_COLS);
-            return em_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         const int64_t rows = goff[(size_t)set_group[s] + 1] - goff[(size_t)set_group[s]];
         set_off[(size_t)s + 1] = set_off[(size_t)s] + rows * set_ncol[s];
@@ -493,30 +429,30 @@ extern "C" int twxem_mean_variance(int device, int64_t nstn, int64_t ndays, cons
         if (item_target[i] < 0 || item_target[i] >= nstn || item_group[i] < 0 || item_group[i] >= ngroups) {
             snprintf(msg, sizeof msg, "%s: item %lld: target %d outside [0, %lld) or group %d outside [0, %d)", fn,
                      (long long)i, (int)item_target[i], (long long)nstn, (int)item_group[i], ngroups);
-            return em_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         if (col_off[i + 1] < col_off[i] || (i == 0 && col_off[0] != 0) || (col_off[i + 1] > col_off[i] && !col_idx)) {
             snprintf(msg, sizeof msg, "%s: col_off is not a CSR offset array at item %lld", fn, (long long)i);
-            return em_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         const int64_t s = item_set ? item_set[i] : -1;
         if (s < -1 || s >= nset || (s >= 0 && set_group[s] != item_group[i])) {
             snprintf(msg, sizeof msg, "%s: item %lld names extra-column set %lld (of %lld; it must be of the item's group)", fn,
                      (long long)i, (long long)s, (long long)nset);
-            return em_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         h_iset[(size_t)i] = (int32_t)s;
         const int64_t ncol = 1 + (col_off[i + 1] - col_off[i]) + (s >= 0 ? set_ncol[s] : 0);
         if (ncol > TWXEM_MAX_COLS) {
             snprintf(msg, sizeof msg, "%s: item %lld has %lld columns, TWXEM_MAX_COLS is %d", fn, (long long)i,
                      (long long)ncol, TWXEM_MAX_COLS);
-            return em_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         for (int64_t c = col_off[i]; c < col_off[i + 1]; ++c)
             if (col_idx[c] < 0 || col_idx[c] >= nstn) {
                 snprintf(msg, sizeof msg, "%s: item %lld: column index %d outside [0, %lld)", fn, (long long)i,
                          (int)col_idx[c], (long long)nstn);
-                return em_fail(errbuf, errlen, msg);
+                return qa_fail(errbuf, errlen, msg);
             }
         const int64_t rows = goff[(size_t)item_group[i] + 1] - goff[(size_t)item_group[i]];
         if (item_matrix_status && item_matrix_status[i] != TWXIF_OK) { h_status[(size_t)i] = TWXEM_NO_MATRIX; h_done[(size_t)i] = 1; }
@@ -524,9 +460,9 @@ extern "C" int twxem_mean_variance(int device, int64_t nstn, int64_t ndays, cons
     }
     const int64_t ncolidx = col_off[nitem];
 
-    EMCHK(hipSetDevice(device));
+    QACHK(hipSetDevice(device));
     const auto t_up = std::chrono::steady_clock::now();
-    EmBufs bufs;
+    QaPool bufs;
     float *d_obs;
     int32_t *d_gdays, *d_goff, *d_itarget, *d_igroup, *d_iset, *d_colidx, *d_setncol, *d_iters, *d_status;
     int64_t *d_coloff, *d_setoff;
@@ -534,43 +470,43 @@ extern "C" int twxem_mean_variance(int device, int64_t nstn, int64_t ndays, cons
     uint8_t *d_done;
     const size_t NS = (size_t)nstn, ND = (size_t)ndays, G = (size_t)ngroups, NSET = (size_t)nset;
     const size_t C = TWXEM_MAX_COLS;
-    EMALLOC(bufs, d_obs, float, NS * ND);
-    EMALLOC(bufs, d_gdays, int32_t, gdays.size()); EMALLOC(bufs, d_goff, int32_t, G + 1);
-    EMALLOC(bufs, d_itarget, int32_t, NI); EMALLOC(bufs, d_igroup, int32_t, NI); EMALLOC(bufs, d_iset, int32_t, NI);
-    EMALLOC(bufs, d_coloff, int64_t, NI + 1); EMALLOC(bufs, d_colidx, int32_t, ncolidx);
-    EMALLOC(bufs, d_setncol, int32_t, NSET); EMALLOC(bufs, d_setoff, int64_t, NSET + 1);
-    EMALLOC(bufs, d_setvals, double, set_off[NSET]);
-    EMALLOC(bufs, d_iters, int32_t, NI); EMALLOC(bufs, d_status, int32_t, NI); EMALLOC(bufs, d_done, uint8_t, NI);
-    EMALLOC(bufs, d_mean, double, NI); EMALLOC(bufs, d_var, double, NI); EMALLOC(bufs, d_delta, double, NI);
-    EMUP(d_obs, obs, float, NS * ND);
-    EMUP(d_gdays, gdays.data(), int32_t, gdays.size());
-    EMUP(d_goff, goff.data(), int32_t, G + 1);
-    EMUP(d_itarget, item_target, int32_t, NI);
-    EMUP(d_igroup, item_group, int32_t, NI);
-    EMUP(d_iset, h_iset.data(), int32_t, NI);
-    EMUP(d_coloff, col_off, int64_t, NI + 1);
-    EMUP(d_colidx, col_idx, int32_t, ncolidx);
-    EMUP(d_setncol, set_ncol, int32_t, NSET);
-    EMUP(d_setoff, set_off.data(), int64_t, NSET + 1);
-    EMUP(d_setvals, set_vals, double, set_off[NSET]);
-    EMUP(d_status, h_status.data(), int32_t, NI);
-    EMUP(d_done, h_done.data(), uint8_t, NI);
-    EMCHK(hipMemset(d_iters, 0, NI * 4));
-    EMCHK(hipMemset(d_mean, 0xff, NI * 8));                      // all bits set: a NaN
-    EMCHK(hipMemset(d_var, 0xff, NI * 8));
-    EMCHK(hipMemset(d_delta, 0xff, NI * 8));
+    QAALLOC(bufs, d_obs, float, NS * ND);
+    QAALLOC(bufs, d_gdays, int32_t, gdays.size()); QAALLOC(bufs, d_goff, int32_t, G + 1);
+    QAALLOC(bufs, d_itarget, int32_t, NI); QAALLOC(bufs, d_igroup, int32_t, NI); QAALLOC(bufs, d_iset, int32_t, NI);
+    QAALLOC(bufs, d_coloff, int64_t, NI + 1); QAALLOC(bufs, d_colidx, int32_t, ncolidx);
+    QAALLOC(bufs, d_setncol, int32_t, NSET); QAALLOC(bufs, d_setoff, int64_t, NSET + 1);
+    QAALLOC(bufs, d_setvals, double, set_off[NSET]);
+    QAALLOC(bufs, d_iters, int32_t, NI); QAALLOC(bufs, d_status, int32_t, NI); QAALLOC(bufs, d_done, uint8_t, NI);
+    QAALLOC(bufs, d_mean, double, NI); QAALLOC(bufs, d_var, double, NI); QAALLOC(bufs, d_delta, double, NI);
+    QAUP_NZ(d_obs, obs, float, NS * ND);
+    QAUP_NZ(d_gdays, gdays.data(), int32_t, gdays.size());
+    QAUP_NZ(d_goff, goff.data(), int32_t, G + 1);
+    QAUP_NZ(d_itarget, item_target, int32_t, NI);
+    QAUP_NZ(d_igroup, item_group, int32_t, NI);
+    QAUP_NZ(d_iset, h_iset.data(), int32_t, NI);
+    QAUP_NZ(d_coloff, col_off, int64_t, NI + 1);
+    QAUP_NZ(d_colidx, col_idx, int32_t, ncolidx);
+    QAUP_NZ(d_setncol, set_ncol, int32_t, NSET);
+    QAUP_NZ(d_setoff, set_off.data(), int64_t, NSET + 1);
+    QAUP_NZ(d_setvals, set_vals, double, set_off[NSET]);
+    QAUP_NZ(d_status, h_status.data(), int32_t, NI);
+    QAUP_NZ(d_done, h_done.data(), uint8_t, NI);
+    QACHK(hipMemset(d_iters, 0, NI * 4));
+    QACHK(hipMemset(d_mean, 0xff, NI * 8));                      // all bits set: a NaN
+    QACHK(hipMemset(d_var, 0xff, NI * 8));
+    QACHK(hipMemset(d_delta, 0xff, NI * 8));
     if (mu) {
-        EMALLOC(bufs, d_mu, double, NI * C); EMALLOC(bufs, d_sigma, double, NI * C * C);
-        EMCHK(hipMemset(d_mu, 0xff, NI * C * 8));
-        EMCHK(hipMemset(d_sigma, 0xff, NI * C * C * 8));
+        QAALLOC(bufs, d_mu, double, NI * C); QAALLOC(bufs, d_sigma, double, NI * C * C);
+        QACHK(hipMemset(d_mu, 0xff, NI * C * 8));
+        QACHK(hipMemset(d_sigma, 0xff, NI * C * C * 8));
     }
     EmIn in = {d_obs, ndays, d_gdays, d_goff, d_itarget, d_igroup, d_iset, d_coloff, d_colidx, d_setncol, d_setoff, d_setvals};
 
-    EmTimer tm;
+    QaTimer tm;
     float ms[TWXEM_NTIMES] = {0.0f, 0.0f, 0.0f, 0.0f};
     if (kernel_ms) {
-        EMCHK(tm.init());
-        EMCHK(hipDeviceSynchronize());
+        QACHK(tm.init());
+        QACHK(hipDeviceSynchronize());
         ms[2] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_up).count();
     }
     // batches of consecutive items under the workspace budget (at least one item each)
@@ -592,54 +528,54 @@ extern "C" int twxem_mean_variance(int device, int64_t nstn, int64_t ndays, cons
         }
         const size_t NB = (size_t)(last - first);
         ++nbatches;
-        EmBufs ws;                                               // freed at the end of the batch
+        QaPool ws;                                               // freed at the end of the batch
         int64_t *w_rowoff;
         int32_t *w_perm, *w_runs, *w_nruns, *w_act;
         double *w_stat, *w_theta;
-        EMALLOC(ws, w_rowoff, int64_t, NB); EMALLOC(ws, w_perm, int32_t, rows_total);
-        EMALLOC(ws, w_runs, int32_t, (size_t)rows_total + NB); EMALLOC(ws, w_nruns, int32_t, NB); EMALLOC(ws, w_act, int32_t, NB);
-        EMALLOC(ws, w_stat, double, NB * 2 * EM_D); EMALLOC(ws, w_theta, double, NB * EM_D * EM_D);
-        EMUP(w_rowoff, row_off.data(), int64_t, NB);
-        EMCHK(hipMemset(w_nruns, 0, NB * 4));
-        if (kernel_ms) EMCHK(tm.start());
+        QAALLOC(ws, w_rowoff, int64_t, NB); QAALLOC(ws, w_perm, int32_t, rows_total);
+        QAALLOC(ws, w_runs, int32_t, (size_t)rows_total + NB); QAALLOC(ws, w_nruns, int32_t, NB); QAALLOC(ws, w_act, int32_t, NB);
+        QAALLOC(ws, w_stat, double, NB * 2 * EM_D); QAALLOC(ws, w_theta, double, NB * EM_D * EM_D);
+        QAUP_NZ(w_rowoff, row_off.data(), int64_t, NB);
+        QACHK(hipMemset(w_nruns, 0, NB * 4));
+        if (kernel_ms) QACHK(tm.start());
         hipLaunchKernelGGL(k_em_prep, dim3((unsigned)NB), dim3(256), 0, nullptr, in, (int)first, (const int64_t *)w_rowoff,
                            w_perm, w_runs, w_nruns, w_stat, w_theta, d_done, d_status);
-        EMCHK(hipGetLastError());
-        if (kernel_ms) EMCHK(tm.stop(&ms[0]));
+        QACHK(hipGetLastError());
+        if (kernel_ms) QACHK(tm.stop_add(&ms[0]));
         bdone.resize(NB);
         const int64_t max_rounds = ((int64_t)maxits + iters_per_launch - 1) / iters_per_launch;
         for (int64_t round = 0;; ++round) {
-            EMCHK(hipMemcpy(bdone.data(), d_done + first, NB, hipMemcpyDeviceToHost));
+            QACHK(hipMemcpy(bdone.data(), d_done + first, NB, hipMemcpyDeviceToHost));
             act.clear();
             for (size_t b = 0; b < NB; ++b)
                 if (!bdone[b]) act.push_back((int32_t)b);
             if (act.empty()) break;
             if (round >= max_rounds) {                           // every launch advances each of its items or ends it
                 snprintf(msg, sizeof msg, "%s: internal error: %lld launches for maxits %d", fn, (long long)round, (int)maxits);
-                return em_fail(errbuf, errlen, msg);
+                return qa_fail(errbuf, errlen, msg);
             }
-            EMUP(w_act, act.data(), int32_t, act.size());
-            if (kernel_ms) EMCHK(tm.start());
+            QAUP_NZ(w_act, act.data(), int32_t, act.size());
+            if (kernel_ms) QACHK(tm.start());
             hipLaunchKernelGGL(k_em_iter, dim3((unsigned)act.size()), dim3(EM_THREADS), 0, nullptr, in, (int)first,
                                (const int32_t *)w_act, (const int64_t *)w_rowoff, (const int32_t *)w_perm,
                                (const int32_t *)w_runs, (const int32_t *)w_nruns, (const double *)w_stat, w_theta, criterion,
                                (int)maxits, (int)iters_per_launch, d_done, d_status, d_iters, d_delta, d_mean, d_var, d_mu,
                                d_sigma);
-            EMCHK(hipGetLastError());
-            if (kernel_ms) EMCHK(tm.stop(&ms[1]));
+            QACHK(hipGetLastError());
+            if (kernel_ms) QACHK(tm.stop_add(&ms[1]));
             ++rounds;
         }
         first = last;
     }
     const auto t_down = std::chrono::steady_clock::now();
-    EMCHK(hipMemcpy(mean, d_mean, NI * 8, hipMemcpyDeviceToHost));
-    EMCHK(hipMemcpy(variance, d_var, NI * 8, hipMemcpyDeviceToHost));
-    EMCHK(hipMemcpy(delta, d_delta, NI * 8, hipMemcpyDeviceToHost));
-    EMCHK(hipMemcpy(iters, d_iters, NI * 4, hipMemcpyDeviceToHost));
-    EMCHK(hipMemcpy(status, d_status, NI * 4, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(mean, d_mean, NI * 8, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(variance, d_var, NI * 8, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(delta, d_delta, NI * 8, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(iters, d_iters, NI * 4, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(status, d_status, NI * 4, hipMemcpyDeviceToHost));
     if (mu) {
-        EMCHK(hipMemcpy(mu, d_mu, NI * C * 8, hipMemcpyDeviceToHost));
-        EMCHK(hipMemcpy(sigma, d_sigma, NI * C * C * 8, hipMemcpyDeviceToHost));
+        QACHK(hipMemcpy(mu, d_mu, NI * C * 8, hipMemcpyDeviceToHost));
+        QACHK(hipMemcpy(sigma, d_sigma, NI * C * C * 8, hipMemcpyDeviceToHost));
     }
     ms[3] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_down).count();
     if (counts) { counts[0] = rounds; counts[1] = nbatches; }

@@ -33,6 +33,7 @@
 
 #include "twx_ghcn_field.h"
 #include "twx_qa.h"
+#include "twx_qa_common.h"
 
 #define GH_CHUNK 4096                        // bytes per workgroup of k_gh_count / k_gh_starts
 #define GH_LINES_PER_WG 8
@@ -304,34 +305,6 @@ __global__ __launch_bounds__(256) void k_gh_tobs(const uint8_t *__restrict__ buf
 // ---------------------------------------------------------------------------------
 namespace {
 
-int gh_fail(char *errbuf, int errlen, const char *what, hipError_t e = hipSuccess)
-{
-    if (errbuf && errlen > 0) {
-        if (e != hipSuccess) snprintf(errbuf, (size_t)errlen, "%s: %s", what, hipGetErrorString(e));
-        else snprintf(errbuf, (size_t)errlen, "%s", what);
-    }
-    return -1;
-}
-
-struct GhBuf {
-    void *p = nullptr;
-    ~GhBuf() { if (p) (void)hipFree(p); }
-};
-
-struct GhTimer {                                                 // HIP-event time of a run of launches on the null stream
-    hipEvent_t a = nullptr, b = nullptr;
-    ~GhTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    hipError_t init() { hipError_t e = hipEventCreate(&a); return e != hipSuccess ? e : hipEventCreate(&b); }
-    hipError_t start() { return hipEventRecord(a, nullptr); }
-    hipError_t stop(float *ms)
-    {
-        hipError_t e = hipEventRecord(b, nullptr);
-        if (e == hipSuccess) e = hipEventSynchronize(b);
-        if (e == hipSuccess) e = hipEventElapsedTime(ms, a, b);
-        return e;
-    }
-};
-
 // The arguments both entries share, checked before anything touches the device.  *ndays_out: days of the period.
 int gh_check(const char *who, int64_t nbytes, int64_t nfiles, const int64_t *file_off, int32_t min_ymd, int32_t max_ymd,
              int64_t *day0, int64_t *ndays_out, char *errbuf, int errlen)
@@ -339,68 +312,58 @@ int gh_check(const char *who, int64_t nbytes, int64_t nfiles, const int64_t *fil
     char msg[320];
     if (nfiles < 1 || nfiles > INT32_MAX / 2 || nbytes < 0 || nbytes > TWXGH_MAX_BYTES) {
         snprintf(msg, sizeof msg, "%s: need nfiles >= 1 and 0 <= nbytes <= TWXGH_MAX_BYTES = %lld", who, (long long)TWXGH_MAX_BYTES);
-        return gh_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (!file_off || file_off[0] != 0 || file_off[nfiles] != nbytes) {
         snprintf(msg, sizeof msg, "%s: file_off must run from 0 to nbytes", who);
-        return gh_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     for (int64_t f = 0; f < nfiles; ++f)
         if (file_off[f + 1] < file_off[f]) {
             snprintf(msg, sizeof msg, "%s: file_off[%lld] decreases", who, (long long)(f + 1));
-            return gh_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
     const int64_t y0 = min_ymd / 10000, m0 = (min_ymd / 100) % 100, d0 = min_ymd % 100;
     const int64_t y1 = max_ymd / 10000, m1 = (max_ymd / 100) % 100, d1 = max_ymd % 100;
     if (min_ymd < 0 || max_ymd < min_ymd || !gh_valid_date(y0, m0, d0) || !gh_valid_date(y1, m1, d1)) {
         snprintf(msg, sizeof msg, "%s: min_ymd = %d, max_ymd = %d is not a period of calendar days", who, (int)min_ymd, (int)max_ymd);
-        return gh_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     *day0 = gh_days_from_civil(y0, m0, d0);
     *ndays_out = gh_days_from_civil(y1, m1, d1) - *day0 + 1;
     return 0;
 }
 
-}  // namespace
-
-#define GHCHK(call)                                                                     \
-    do {                                                                                \
-        hipError_t e_ = (call);                                                         \
-        if (e_ != hipSuccess) return gh_fail(errbuf, errlen, #call, e_);                \
-    } while (0)
-
-namespace {
-
 // Upload the buffer (padded to 16 bytes, the pad zeroed) and the offsets, build the candidate list.  ms: the three kernels.
-int gh_index(const uint8_t *buf, int64_t nbytes, int64_t nfiles, const int64_t *file_off, GhBuf &b_buf, GhBuf &b_off,
-             GhBuf &b_cand, GhBuf &b_blk, uint32_t *ncand_out, GhTimer &tm, float *ms, char *errbuf, int errlen)
+int gh_index(const uint8_t *buf, int64_t nbytes, int64_t nfiles, const int64_t *file_off, QaBuf &b_buf, QaBuf &b_off,
+             QaBuf &b_cand, QaBuf &b_blk, uint32_t *ncand_out, QaTimer &tm, float *ms, char *errbuf, int errlen)
 {
     const size_t padded = ((size_t)nbytes + 15) / 16 * 16 + 16;
-    GHCHK(hipMalloc(&b_buf.p, padded));
-    GHCHK(hipMemset(static_cast<uint8_t *>(b_buf.p) + (padded - 32), 0, 32));
-    if (nbytes > 0) GHCHK(hipMemcpy(b_buf.p, buf, (size_t)nbytes, hipMemcpyHostToDevice));
-    GHCHK(hipMalloc(&b_off.p, (size_t)(nfiles + 1) * 8));
-    GHCHK(hipMemcpy(b_off.p, file_off, (size_t)(nfiles + 1) * 8, hipMemcpyHostToDevice));
+    QACHK(hipMalloc(&b_buf.p, padded));
+    QACHK(hipMemset(static_cast<uint8_t *>(b_buf.p) + (padded - 32), 0, 32));
+    if (nbytes > 0) QACHK(hipMemcpy(b_buf.p, buf, (size_t)nbytes, hipMemcpyHostToDevice));
+    QACHK(hipMalloc(&b_off.p, (size_t)(nfiles + 1) * 8));
+    QACHK(hipMemcpy(b_off.p, file_off, (size_t)(nfiles + 1) * 8, hipMemcpyHostToDevice));
     const int64_t nblk = std::max<int64_t>(1, (nbytes + GH_CHUNK - 1) / GH_CHUNK);
-    GHCHK(hipMalloc(&b_blk.p, (size_t)(2 * nblk + 1) * 4));
+    QACHK(hipMalloc(&b_blk.p, (size_t)(2 * nblk + 1) * 4));
     uint32_t *d_cnt = static_cast<uint32_t *>(b_blk.p), *d_boff = d_cnt + nblk, *d_total = d_boff + nblk;
     const uint8_t *d_buf = static_cast<const uint8_t *>(b_buf.p);
     float a = 0.0f, b = 0.0f;
-    GHCHK(tm.start());
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_gh_count, dim3((unsigned)nblk), dim3(256), 0, nullptr, d_buf, nbytes, d_cnt);
-    GHCHK(hipGetLastError());
+    QACHK(hipGetLastError());
     hipLaunchKernelGGL(k_gh_scan, dim3(1), dim3(1024), 0, nullptr, (const uint32_t *)d_cnt, nblk, d_boff, d_total);
-    GHCHK(hipGetLastError());
-    GHCHK(tm.stop(&a));
+    QACHK(hipGetLastError());
+    QACHK(tm.stop_set(&a));
     uint32_t ncand = 0;
-    GHCHK(hipMemcpy(&ncand, d_total, 4, hipMemcpyDeviceToHost));
-    GHCHK(hipMalloc(&b_cand.p, std::max<size_t>(16, (size_t)ncand * 4)));
+    QACHK(hipMemcpy(&ncand, d_total, 4, hipMemcpyDeviceToHost));
+    QACHK(hipMalloc(&b_cand.p, std::max<size_t>(16, (size_t)ncand * 4)));
     if (ncand > 0) {
-        GHCHK(tm.start());
+        QACHK(tm.start());
         hipLaunchKernelGGL(k_gh_starts, dim3((unsigned)nblk), dim3(256), 0, nullptr, d_buf, nbytes, (const uint32_t *)d_boff, ncand,
                            static_cast<uint32_t *>(b_cand.p));
-        GHCHK(hipGetLastError());
-        GHCHK(tm.stop(&b));
+        QACHK(hipGetLastError());
+        QACHK(tm.stop_set(&b));
     }
     *ncand_out = ncand;
     *ms = a + b;
@@ -417,17 +380,17 @@ extern "C" int twxgh_parse_dly(int device, const uint8_t *buf, int64_t nbytes, i
     if (errbuf && errlen > 0) errbuf[0] = 0;
     int64_t day0 = 0, nd = 0;
     if (gh_check("twxgh_parse_dly", nbytes, nfiles, file_off, min_ymd, max_ymd, &day0, &nd, errbuf, errlen) != 0) return -1;
-    if (nd != ndays) return gh_fail(errbuf, errlen, "twxgh_parse_dly: ndays is not the number of days from min_ymd to max_ymd");
+    if (nd != ndays) return qa_fail(errbuf, errlen, "twxgh_parse_dly: ndays is not the number of days from min_ymd to max_ymd");
     if ((nbytes > 0 && !buf) || !file_col || !val || !qflag || !bad_header || !counts || (fallback_cap > 0 && !fallback))
-        return gh_fail(errbuf, errlen, "twxgh_parse_dly: null buffer");
+        return qa_fail(errbuf, errlen, "twxgh_parse_dly: null buffer");
     if (nrows < 1 || nrows > INT32_MAX || fallback_cap < 0 || fallback_cap > INT32_MAX ||
         (double)nrows * (double)ndays * 3.0 > (double)TWXGH_MAX_CELLS)
-        return gh_fail(errbuf, errlen, "twxgh_parse_dly: need 1 <= nrows, 3 nrows ndays <= TWXGH_MAX_CELLS, 0 <= fallback_cap");
+        return qa_fail(errbuf, errlen, "twxgh_parse_dly: need 1 <= nrows, 3 nrows ndays <= TWXGH_MAX_CELLS, 0 <= fallback_cap");
     {
         std::vector<uint8_t> seen((size_t)nrows, 0);
         for (int64_t f = 0; f < nfiles; ++f) {
             if (file_col[f] < 0 || file_col[f] >= nrows || seen[(size_t)file_col[f]])
-                return gh_fail(errbuf, errlen, "twxgh_parse_dly: file_col must be distinct rows in 0 .. nrows - 1");
+                return qa_fail(errbuf, errlen, "twxgh_parse_dly: file_col must be distinct rows in 0 .. nrows - 1");
             seen[(size_t)file_col[f]] = 1;
         }
     }
@@ -435,22 +398,22 @@ extern "C" int twxgh_parse_dly(int device, const uint8_t *buf, int64_t nbytes, i
     float ms[TWXGH_NKERNELS];
     for (int i = 0; i < TWXGH_NKERNELS; ++i) ms[i] = 0.0f;
 
-    GHCHK(hipSetDevice(device));
-    GhBuf b_buf, b_off, b_cand, b_blk, b_col, b_win, b_val, b_q, b_bad, b_fb, b_cnt;
-    GhTimer tm;
-    GHCHK(tm.init());
-    GHCHK(hipMalloc(&b_val.p, cells * 4));
-    GHCHK(hipMalloc(&b_q.p, cells));
-    GHCHK(hipMemset(b_q.p, 0, cells));
-    GHCHK(tm.start());
+    QACHK(hipSetDevice(device));
+    QaBuf b_buf, b_off, b_cand, b_blk, b_col, b_win, b_val, b_q, b_bad, b_fb, b_cnt;
+    QaTimer tm;
+    QACHK(tm.init());
+    QACHK(hipMalloc(&b_val.p, cells * 4));
+    QACHK(hipMalloc(&b_q.p, cells));
+    QACHK(hipMemset(b_q.p, 0, cells));
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_gh_fill, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, nullptr, static_cast<float *>(b_val.p),
                        (int64_t)cells, (float)GH_MISSING);
-    GHCHK(hipGetLastError());
-    GHCHK(tm.stop(&ms[0]));
-    GHCHK(hipMalloc(&b_bad.p, (size_t)nfiles * 4));
-    GHCHK(hipMemset(b_bad.p, 0xff, (size_t)nfiles * 4));
-    GHCHK(hipMalloc(&b_cnt.p, 16));
-    GHCHK(hipMemset(b_cnt.p, 0, 16));
+    QACHK(hipGetLastError());
+    QACHK(tm.stop_set(&ms[0]));
+    QACHK(hipMalloc(&b_bad.p, (size_t)nfiles * 4));
+    QACHK(hipMemset(b_bad.p, 0xff, (size_t)nfiles * 4));
+    QACHK(hipMalloc(&b_cnt.p, 16));
+    QACHK(hipMemset(b_cnt.p, 0, 16));
     unsigned long long *d_nw = static_cast<unsigned long long *>(b_cnt.p);
     uint32_t *d_fbn = reinterpret_cast<uint32_t *>(d_nw + 1);
     uint32_t ncand = 0;
@@ -458,11 +421,11 @@ extern "C" int twxgh_parse_dly(int device, const uint8_t *buf, int64_t nbytes, i
     if (nbytes > 0) {
         if (gh_index(buf, nbytes, nfiles, file_off, b_buf, b_off, b_cand, b_blk, &ncand, tm, &ms[1], errbuf, errlen) != 0) return -1;
         nlines = nfiles + (int64_t)ncand;
-        GHCHK(hipMalloc(&b_col.p, (size_t)nfiles * 4));
-        GHCHK(hipMemcpy(b_col.p, file_col, (size_t)nfiles * 4, hipMemcpyHostToDevice));
-        GHCHK(hipMalloc(&b_win.p, cells * 4));
-        GHCHK(hipMemset(b_win.p, 0, cells * 4));
-        GHCHK(hipMalloc(&b_fb.p, std::max<size_t>(16, (size_t)fallback_cap * TWXGH_FB_WORDS * 4)));
+        QACHK(hipMalloc(&b_col.p, (size_t)nfiles * 4));
+        QACHK(hipMemcpy(b_col.p, file_col, (size_t)nfiles * 4, hipMemcpyHostToDevice));
+        QACHK(hipMalloc(&b_win.p, cells * 4));
+        QACHK(hipMemset(b_win.p, 0, cells * 4));
+        QACHK(hipMalloc(&b_fb.p, std::max<size_t>(16, (size_t)fallback_cap * TWXGH_FB_WORDS * 4)));
         const unsigned grid = (unsigned)((nlines + GH_LINES_PER_WG - 1) / GH_LINES_PER_WG);
 #define GH_DLY_ARGS                                                                                                          \
     static_cast<const uint8_t *>(b_buf.p), (int)nfiles, static_cast<const int64_t *>(b_off.p),                             \
@@ -470,26 +433,26 @@ extern "C" int twxgh_parse_dly(int device, const uint8_t *buf, int64_t nbytes, i
         (int64_t)min_ymd, (int64_t)max_ymd, day0, static_cast<uint32_t *>(b_win.p), static_cast<float *>(b_val.p),         \
         static_cast<uint8_t *>(b_q.p), static_cast<uint32_t *>(b_bad.p), static_cast<uint32_t *>(b_fb.p),                  \
         (uint32_t)fallback_cap, d_fbn, d_nw
-        GHCHK(tm.start());
+        QACHK(tm.start());
         hipLaunchKernelGGL(k_gh_dly<0>, dim3(grid), dim3(256), 0, nullptr, GH_DLY_ARGS);
-        GHCHK(hipGetLastError());
-        GHCHK(tm.stop(&ms[2]));
-        GHCHK(tm.start());
+        QACHK(hipGetLastError());
+        QACHK(tm.stop_set(&ms[2]));
+        QACHK(tm.start());
         hipLaunchKernelGGL(k_gh_dly<1>, dim3(grid), dim3(256), 0, nullptr, GH_DLY_ARGS);
-        GHCHK(hipGetLastError());
-        GHCHK(tm.stop(&ms[3]));
+        QACHK(hipGetLastError());
+        QACHK(tm.stop_set(&ms[3]));
 #undef GH_DLY_ARGS
     }
     unsigned long long nw = 0;
     uint32_t nfb = 0;
-    GHCHK(hipMemcpy(&nw, d_nw, 8, hipMemcpyDeviceToHost));
-    GHCHK(hipMemcpy(&nfb, d_fbn, 4, hipMemcpyDeviceToHost));
-    GHCHK(hipMemcpy(val, b_val.p, cells * 4, hipMemcpyDeviceToHost));
-    GHCHK(hipMemcpy(qflag, b_q.p, cells, hipMemcpyDeviceToHost));
-    GHCHK(hipMemcpy(bad_header, b_bad.p, (size_t)nfiles * 4, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(&nw, d_nw, 8, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(&nfb, d_fbn, 4, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(val, b_val.p, cells * 4, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(qflag, b_q.p, cells, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(bad_header, b_bad.p, (size_t)nfiles * 4, hipMemcpyDeviceToHost));
     const size_t nget = (size_t)std::min<int64_t>(nfb, fallback_cap);
     if (nget > 0) {
-        GHCHK(hipMemcpy(fallback, b_fb.p, nget * TWXGH_FB_WORDS * 4, hipMemcpyDeviceToHost));
+        QACHK(hipMemcpy(fallback, b_fb.p, nget * TWXGH_FB_WORDS * 4, hipMemcpyDeviceToHost));
         struct Row { uint32_t w[TWXGH_FB_WORDS]; };
         Row *r = reinterpret_cast<Row *>(fallback);                // buffer order, then day: the slots the atomics gave are gone
         std::sort(r, r + nget, [](const Row &x, const Row &y) { return x.w[7] != y.w[7] ? x.w[7] < y.w[7] : x.w[3] < y.w[3]; });
@@ -510,15 +473,15 @@ extern "C" int twxgh_parse_tobs(int device, const uint8_t *buf, int64_t nbytes, 
     int64_t day0 = 0, nd = 0;
     if (gh_check("twxgh_parse_tobs", nbytes, nfiles, file_off, min_ymd, max_ymd, &day0, &nd, errbuf, errlen) != 0) return -1;
     if ((nbytes > 0 && !buf) || !ids || !element || !tobs || !counts || (bad_cap > 0 && !bad))
-        return gh_fail(errbuf, errlen, "twxgh_parse_tobs: null buffer");
-    if (strlen(element) != 4) return gh_fail(errbuf, errlen, "twxgh_parse_tobs: the element is four characters");
+        return qa_fail(errbuf, errlen, "twxgh_parse_tobs: null buffer");
+    if (strlen(element) != 4) return qa_fail(errbuf, errlen, "twxgh_parse_tobs: the element is four characters");
     if (nstn < 1 || nstn > INT32_MAX || win0 < 0 || nwin < 1 || win0 + nwin > nd || bad_cap < 0 || bad_cap > INT32_MAX ||
         (double)nstn * (double)nwin > (double)TWXGH_MAX_CELLS)
-        return gh_fail(errbuf, errlen, "twxgh_parse_tobs: need nstn >= 1, a window of days inside the period, nstn nwin <= "
+        return qa_fail(errbuf, errlen, "twxgh_parse_tobs: need nstn >= 1, a window of days inside the period, nstn nwin <= "
                                        "TWXGH_MAX_CELLS and bad_cap >= 0");
     for (int64_t s = 1; s < nstn; ++s)
         if (memcmp(ids + (s - 1) * 11, ids + s * 11, 11) >= 0)
-            return gh_fail(errbuf, errlen, "twxgh_parse_tobs: the id table must be sorted and without duplicates");
+            return qa_fail(errbuf, errlen, "twxgh_parse_tobs: the id table must be sorted and without duplicates");
     const size_t cells = (size_t)nstn * (size_t)nwin;
     float ms[TWXGH_NKERNELS];
     for (int i = 0; i < TWXGH_NKERNELS; ++i) ms[i] = 0.0f;
@@ -526,22 +489,22 @@ extern "C" int twxgh_parse_tobs(int device, const uint8_t *buf, int64_t nbytes, 
     memset(cnt, 0, sizeof cnt);
     int64_t nlines = 0;
     if (nbytes > 0) {
-        GHCHK(hipSetDevice(device));
-        GhBuf b_buf, b_off, b_cand, b_blk, b_ids, b_win, b_out, b_bad, b_cnt;
-        GhTimer tm;
-        GHCHK(tm.init());
+        QACHK(hipSetDevice(device));
+        QaBuf b_buf, b_off, b_cand, b_blk, b_ids, b_win, b_out, b_bad, b_cnt;
+        QaTimer tm;
+        QACHK(tm.init());
         uint32_t ncand = 0;
         if (gh_index(buf, nbytes, nfiles, file_off, b_buf, b_off, b_cand, b_blk, &ncand, tm, &ms[1], errbuf, errlen) != 0) return -1;
         nlines = nfiles + (int64_t)ncand;
-        GHCHK(hipMalloc(&b_ids.p, (size_t)nstn * 11));
-        GHCHK(hipMemcpy(b_ids.p, ids, (size_t)nstn * 11, hipMemcpyHostToDevice));
-        GHCHK(hipMalloc(&b_win.p, cells * 4));
-        GHCHK(hipMemset(b_win.p, 0, cells * 4));
-        GHCHK(hipMalloc(&b_out.p, cells * 2));
-        GHCHK(hipMemcpy(b_out.p, tobs, cells * 2, hipMemcpyHostToDevice));
-        GHCHK(hipMalloc(&b_bad.p, std::max<size_t>(16, (size_t)bad_cap * 8)));
-        GHCHK(hipMalloc(&b_cnt.p, sizeof cnt));
-        GHCHK(hipMemset(b_cnt.p, 0, sizeof cnt));
+        QACHK(hipMalloc(&b_ids.p, (size_t)nstn * 11));
+        QACHK(hipMemcpy(b_ids.p, ids, (size_t)nstn * 11, hipMemcpyHostToDevice));
+        QACHK(hipMalloc(&b_win.p, cells * 4));
+        QACHK(hipMemset(b_win.p, 0, cells * 4));
+        QACHK(hipMalloc(&b_out.p, cells * 2));
+        QACHK(hipMemcpy(b_out.p, tobs, cells * 2, hipMemcpyHostToDevice));
+        QACHK(hipMalloc(&b_bad.p, std::max<size_t>(16, (size_t)bad_cap * 8)));
+        QACHK(hipMalloc(&b_cnt.p, sizeof cnt));
+        QACHK(hipMemset(b_cnt.p, 0, sizeof cnt));
         uint32_t ew = 0;
         memcpy(&ew, element, 4);
         const unsigned grid = (unsigned)((nlines + 255) / 256);
@@ -550,20 +513,20 @@ extern "C" int twxgh_parse_tobs(int device, const uint8_t *buf, int64_t nbytes, 
         static_cast<const uint32_t *>(b_cand.p), nlines, static_cast<const uint8_t *>(b_ids.p), (int)nstn, ew,             \
         (int64_t)min_ymd, (int64_t)max_ymd, day0, win0, nwin, static_cast<uint32_t *>(b_win.p),                            \
         static_cast<int16_t *>(b_out.p), static_cast<uint32_t *>(b_bad.p), (uint32_t)bad_cap, static_cast<uint32_t *>(b_cnt.p)
-        GHCHK(tm.start());
+        QACHK(tm.start());
         hipLaunchKernelGGL(k_gh_tobs<0>, dim3(grid), dim3(256), 0, nullptr, GH_TOBS_ARGS);
-        GHCHK(hipGetLastError());
-        GHCHK(tm.stop(&ms[2]));
-        GHCHK(tm.start());
+        QACHK(hipGetLastError());
+        QACHK(tm.stop_set(&ms[2]));
+        QACHK(tm.start());
         hipLaunchKernelGGL(k_gh_tobs<1>, dim3(grid), dim3(256), 0, nullptr, GH_TOBS_ARGS);
-        GHCHK(hipGetLastError());
-        GHCHK(tm.stop(&ms[3]));
+        QACHK(hipGetLastError());
+        QACHK(tm.stop_set(&ms[3]));
 #undef GH_TOBS_ARGS
-        GHCHK(hipMemcpy(cnt, b_cnt.p, sizeof cnt, hipMemcpyDeviceToHost));
-        GHCHK(hipMemcpy(tobs, b_out.p, cells * 2, hipMemcpyDeviceToHost));
+        QACHK(hipMemcpy(cnt, b_cnt.p, sizeof cnt, hipMemcpyDeviceToHost));
+        QACHK(hipMemcpy(tobs, b_out.p, cells * 2, hipMemcpyDeviceToHost));
         const size_t nget = (size_t)std::min<int64_t>(cnt[TWXGH_TC_BAD], bad_cap);
         if (nget > 0) {
-            GHCHK(hipMemcpy(bad, b_bad.p, nget * 8, hipMemcpyDeviceToHost));
+            QACHK(hipMemcpy(bad, b_bad.p, nget * 8, hipMemcpyDeviceToHost));
             struct Row { uint32_t f, pos; };
             Row *r = reinterpret_cast<Row *>(bad);
             std::sort(r, r + nget, [](const Row &x, const Row &y) { return x.f != y.f ? x.f < y.f : x.pos < y.pos; });

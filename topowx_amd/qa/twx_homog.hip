@@ -1,7 +1,7 @@
 // twx_homog.hip -- libtwxqa.so: the array work on either side of the external PHA program, as include/twx_qa.h states it:
 // twxhm_obs_cnt (add_obs_cnt), twxhm_monthly_means (add_monthly_means / TairAggregate.daily_to_mthly), twxhm_tobs_shift
-// (_tobs_shift_tmax) and twxhm_homog_daily (HomogDaily.homog_stn).  Its own translation unit: the buffer list and the event
-// timer it shares with twx_serial.hip are restated, nothing there is edited.
+// (_tobs_shift_tmax) and twxhm_homog_daily (HomogDaily.homog_stn).  Its own translation unit; the buffer list and the event
+// timer it shares with the other units are twx_qa_common.h's.
 //
 // A record is station-major, [nstn][ndays] float32 with NaN for "no value"; an entry walks it in batches of whole stations
 // that fit workspace_bytes.
@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "twx_qa.h"
+#include "twx_qa_common.h"
 
 #define HM_THREADS 256
 #define HM_NW (HM_THREADS / 64)
@@ -291,47 +292,6 @@ __global__ __launch_bounds__(HM_THREADS) void k_hm_apply(const float *__restrict
 
 namespace {
 
-int hm_fail(char *errbuf, int errlen, const char *what, hipError_t e = hipSuccess)
-{
-    if (errbuf && errlen > 0) {
-        if (e != hipSuccess) snprintf(errbuf, (size_t)errlen, "%s: %s", what, hipGetErrorString(e));
-        else snprintf(errbuf, (size_t)errlen, "%s", what);
-    }
-    return -1;
-}
-
-struct HmBufs {                                                  // every device allocation of a call, freed together
-    std::vector<void *> p;
-    ~HmBufs() { for (void *x : p) if (x) (void)hipFree(x); }
-    hipError_t get(void **out, size_t bytes)
-    {
-        hipError_t e = hipMalloc(out, bytes ? bytes : 1);
-        if (e == hipSuccess) p.push_back(*out);
-        return e;
-    }
-};
-
-struct HmTimer {                                                 // HIP-event time of a run of launches on the null stream
-    hipEvent_t a = nullptr, b = nullptr;
-    ~HmTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    hipError_t init() { hipError_t e = hipEventCreate(&a); return e != hipSuccess ? e : hipEventCreate(&b); }
-    hipError_t start() { return hipEventRecord(a, nullptr); }
-    hipError_t stop(float *acc)
-    {
-        float ms = 0.0f;
-        hipError_t e = hipEventRecord(b, nullptr);
-        if (e == hipSuccess) e = hipEventSynchronize(b);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
-        *acc += ms;
-        return e;
-    }
-};
-
-float hm_since(std::chrono::steady_clock::time_point t)
-{
-    return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t).count();
-}
-
 // the stations of one batch: as many as fit the budget, at least one, fewer than 2^31 floats
 int64_t hm_batch(int64_t workspace_bytes, int64_t ndays, int64_t bytes_a_day)
 {
@@ -348,7 +308,7 @@ int hm_shape(const char *fn, int64_t nstn, int64_t ndays, char *errbuf, int errl
     char msg[256];
     if (nstn < 1 || nstn > INT32_MAX / 2 || ndays < 1 || ndays > TWXSC_MAX_DAYS) {
         snprintf(msg, sizeof msg, "%s: need 1 <= nstn <= %d and 1 <= ndays <= %d", fn, INT32_MAX / 2, TWXSC_MAX_DAYS);
-        return hm_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     return 0;
 }
@@ -360,32 +320,23 @@ int hm_months(const char *fn, int64_t ndays, int32_t nmth, const int32_t *mth_fi
     char msg[256];
     if (nmth < 1 || nmth > TWXHM_MAX_MONTHS) {
         snprintf(msg, sizeof msg, "%s: need 1 <= nmth <= %d", fn, TWXHM_MAX_MONTHS);
-        return hm_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     for (int32_t g = 0; g < nmth; ++g) {
         const int64_t d0 = mth_first[g], nd = mth_ndays[g];
         if (nd < 1 || nd > 31 || d0 < 0 || d0 + nd > ndays) {
             snprintf(msg, sizeof msg, "%s: month %d lies outside the day axis or has not 1 .. 31 days", fn, (int)g);
-            return hm_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         if (g > 0 && d0 != (int64_t)mth_first[g - 1] + mth_ndays[g - 1]) {
             snprintf(msg, sizeof msg, "%s: month %d does not start where month %d ends", fn, (int)g, (int)g - 1);
-            return hm_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
     }
     return 0;
 }
 
 }  // namespace
-
-#define HMCHK(call)                                                                     \
-    do {                                                                                \
-        hipError_t e_ = (call);                                                         \
-        if (e_ != hipSuccess) return hm_fail(errbuf, errlen, #call, e_);                \
-    } while (0)
-#define HMALLOC(bufs, ptr, type, count) HMCHK((bufs).get((void **)&(ptr), (size_t)(count) * sizeof(type)))
-#define HMUP(dst, src, type, count) HMCHK(hipMemcpy((dst), (src), (size_t)(count) * sizeof(type), hipMemcpyHostToDevice))
-#define HMDOWN(dst, src, type, count) HMCHK(hipMemcpy((dst), (src), (size_t)(count) * sizeof(type), hipMemcpyDeviceToHost))
 
 extern "C" int twxhm_obs_cnt(int device, int64_t nstn, int64_t ndays, const float *obs, const int8_t *day_month,
                              int64_t first_day, int64_t last_day, int64_t workspace_bytes, int32_t *cnt, int32_t *counts,
@@ -397,49 +348,49 @@ extern "C" int twxhm_obs_cnt(int device, int64_t nstn, int64_t ndays, const floa
     if (hm_shape(fn, nstn, ndays, errbuf, errlen)) return -1;
     if (!obs || !day_month || !cnt) {
         snprintf(msg, sizeof msg, "%s: null buffer", fn);
-        return hm_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (first_day < 0 || last_day >= ndays || first_day > last_day) {
         snprintf(msg, sizeof msg, "%s: need 0 <= first_day <= last_day < ndays", fn);
-        return hm_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     for (int64_t d = 0; d < ndays; ++d) {
         if (day_month[d] < 1 || day_month[d] > HM_NMONTHS) {
             snprintf(msg, sizeof msg, "%s: day_month[%lld] is outside 1 .. 12", fn, (long long)d);
-            return hm_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
     }
     const size_t NS = (size_t)nstn, ND = (size_t)ndays;
     const int64_t per = hm_batch(workspace_bytes, ndays, 4);
     const size_t NBMAX = (size_t)(per < nstn ? per : nstn);
 
-    HMCHK(hipSetDevice(device));
-    HmBufs bufs;
+    QACHK(hipSetDevice(device));
+    QaPool bufs;
     float *w_obs;
     int8_t *d_mon;
     int32_t *d_cnt;
     const auto t_alloc = std::chrono::steady_clock::now();
-    HMALLOC(bufs, w_obs, float, NBMAX * ND); HMALLOC(bufs, d_mon, int8_t, ND); HMALLOC(bufs, d_cnt, int32_t, NS * HM_NMONTHS);
-    HMUP(d_mon, day_month, int8_t, ND);
-    HmTimer tm;
+    QAALLOC(bufs, w_obs, float, NBMAX * ND); QAALLOC(bufs, d_mon, int8_t, ND); QAALLOC(bufs, d_cnt, int32_t, NS * HM_NMONTHS);
+    QAUP(d_mon, day_month, int8_t, ND);
+    QaTimer tm;
     float ms[TWXHM_NTIMES] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (kernel_ms) { HMCHK(tm.init()); ms[2] = hm_since(t_alloc); }
+    if (kernel_ms) { QACHK(tm.init()); ms[2] = qa_since(t_alloc); }
     int nbatches = 0;
     for (int64_t first = 0; first < nstn; first += per) {
         const size_t NB = (size_t)(nstn - first < per ? nstn - first : per);
         const auto t_up = std::chrono::steady_clock::now();
-        HMUP(w_obs, obs + (size_t)first * ND, float, NB * ND);
+        QAUP(w_obs, obs + (size_t)first * ND, float, NB * ND);
         ++nbatches;
-        if (kernel_ms) { HMCHK(hipDeviceSynchronize()); ms[2] += hm_since(t_up); HMCHK(tm.start()); }
+        if (kernel_ms) { QACHK(hipDeviceSynchronize()); ms[2] += qa_since(t_up); QACHK(tm.start()); }
         hipLaunchKernelGGL(k_hm_cnt, dim3((unsigned)NB), dim3(HM_THREADS), 0, nullptr, (const float *)w_obs,
                            (const int8_t *)d_mon, (int)ndays, (int)first_day, (int)last_day, first, d_cnt);
-        HMCHK(hipGetLastError());
-        if (kernel_ms) HMCHK(tm.stop(&ms[0]));
-        else HMCHK(hipDeviceSynchronize());                      // the next batch overwrites the rows
+        QACHK(hipGetLastError());
+        if (kernel_ms) QACHK(tm.stop_add(&ms[0]));
+        else QACHK(hipDeviceSynchronize());                      // the next batch overwrites the rows
     }
     const auto t_down = std::chrono::steady_clock::now();
-    HMDOWN(cnt, d_cnt, int32_t, NS * HM_NMONTHS);
-    ms[3] = hm_since(t_down);
+    QADOWN(cnt, d_cnt, int32_t, NS * HM_NMONTHS);
+    ms[3] = qa_since(t_down);
     if (counts) { counts[0] = nbatches; counts[1] = nbatches; }
     if (kernel_ms) memcpy(kernel_ms, ms, sizeof ms);
     return 0;
@@ -456,7 +407,7 @@ extern "C" int twxhm_monthly_means(int device, int64_t nstn, int64_t ndays, cons
     if (hm_shape(fn, nstn, ndays, errbuf, errlen)) return -1;
     if (!obs || !mth_first || !mth_ndays || !mth_mean || !mth_miss) {
         snprintf(msg, sizeof msg, "%s: null buffer", fn);
-        return hm_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (hm_months(fn, ndays, nmth, mth_first, mth_ndays, errbuf, errlen)) return -1;
     const size_t NS = (size_t)nstn, ND = (size_t)ndays, NM = (size_t)nmth;
@@ -465,37 +416,37 @@ extern "C" int twxhm_monthly_means(int device, int64_t nstn, int64_t ndays, cons
     const size_t NBMAX = (size_t)(per < nstn ? per : nstn);
     const unsigned ngrp = (unsigned)((nmth + HM_MM - 1) / HM_MM);
 
-    HMCHK(hipSetDevice(device));
-    HmBufs bufs;
+    QACHK(hipSetDevice(device));
+    QaPool bufs;
     float *w_obs, *d_mean;
     int16_t *d_miss;
     int32_t *d_mf, *d_mn;
     const auto t_alloc = std::chrono::steady_clock::now();
-    HMALLOC(bufs, w_obs, float, NBMAX * ND); HMALLOC(bufs, d_mean, float, NS * NM); HMALLOC(bufs, d_miss, int16_t, NS * NM);
-    HMALLOC(bufs, d_mf, int32_t, NM); HMALLOC(bufs, d_mn, int32_t, NM);
-    HMUP(d_mf, mth_first, int32_t, NM);
-    HMUP(d_mn, mth_ndays, int32_t, NM);
-    HmTimer tm;
+    QAALLOC(bufs, w_obs, float, NBMAX * ND); QAALLOC(bufs, d_mean, float, NS * NM); QAALLOC(bufs, d_miss, int16_t, NS * NM);
+    QAALLOC(bufs, d_mf, int32_t, NM); QAALLOC(bufs, d_mn, int32_t, NM);
+    QAUP(d_mf, mth_first, int32_t, NM);
+    QAUP(d_mn, mth_ndays, int32_t, NM);
+    QaTimer tm;
     float ms[TWXHM_NTIMES] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (kernel_ms) { HMCHK(tm.init()); ms[2] = hm_since(t_alloc); }
+    if (kernel_ms) { QACHK(tm.init()); ms[2] = qa_since(t_alloc); }
     int nbatches = 0;
     for (int64_t first = 0; first < nstn; first += per) {
         const size_t NB = (size_t)(nstn - first < per ? nstn - first : per);
         const auto t_up = std::chrono::steady_clock::now();
-        HMUP(w_obs, obs + (size_t)first * ND, float, NB * ND);
+        QAUP(w_obs, obs + (size_t)first * ND, float, NB * ND);
         ++nbatches;
-        if (kernel_ms) { HMCHK(hipDeviceSynchronize()); ms[2] += hm_since(t_up); HMCHK(tm.start()); }
+        if (kernel_ms) { QACHK(hipDeviceSynchronize()); ms[2] += qa_since(t_up); QACHK(tm.start()); }
         hipLaunchKernelGGL(k_hm_means, dim3(ngrp, (unsigned)NB), dim3(HM_MM), 0, nullptr, (const float *)w_obs,
                            (int64_t)(NB * ND), (int)ndays, (int)nmth, (const int32_t *)d_mf, (const int32_t *)d_mn,
                            (int)max_miss, first, d_mean, d_miss);
-        HMCHK(hipGetLastError());
-        if (kernel_ms) HMCHK(tm.stop(&ms[0]));
-        else HMCHK(hipDeviceSynchronize());                      // the next batch overwrites the rows
+        QACHK(hipGetLastError());
+        if (kernel_ms) QACHK(tm.stop_add(&ms[0]));
+        else QACHK(hipDeviceSynchronize());                      // the next batch overwrites the rows
     }
     const auto t_down = std::chrono::steady_clock::now();
-    HMDOWN(mth_mean, d_mean, float, NS * NM);
-    HMDOWN(mth_miss, d_miss, int16_t, NS * NM);
-    ms[3] = hm_since(t_down);
+    QADOWN(mth_mean, d_mean, float, NS * NM);
+    QADOWN(mth_miss, d_miss, int16_t, NS * NM);
+    ms[3] = qa_since(t_down);
     if (counts) { counts[0] = nbatches; counts[1] = nbatches; }
     if (kernel_ms) memcpy(kernel_ms, ms, sizeof ms);
     return 0;
@@ -511,42 +462,42 @@ extern "C" int twxhm_tobs_shift(int device, int64_t nstn, int64_t ndays, const f
     if (hm_shape(fn, nstn, ndays, errbuf, errlen)) return -1;
     if (!tmax || !tobs || !out || !nshift) {
         snprintf(msg, sizeof msg, "%s: null buffer", fn);
-        return hm_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     const size_t NS = (size_t)nstn, ND = (size_t)ndays;
     const int64_t per = hm_batch(workspace_bytes, ndays, 12);
     const size_t NBMAX = (size_t)(per < nstn ? per : nstn);
 
-    HMCHK(hipSetDevice(device));
-    HmBufs bufs;
+    QACHK(hipSetDevice(device));
+    QaPool bufs;
     float *w_tmax, *w_tobs, *w_out;
     int32_t *d_ns;
     const auto t_alloc = std::chrono::steady_clock::now();
-    HMALLOC(bufs, w_tmax, float, NBMAX * ND); HMALLOC(bufs, w_tobs, float, NBMAX * ND); HMALLOC(bufs, w_out, float, NBMAX * ND);
-    HMALLOC(bufs, d_ns, int32_t, NS);
-    HmTimer tm;
+    QAALLOC(bufs, w_tmax, float, NBMAX * ND); QAALLOC(bufs, w_tobs, float, NBMAX * ND); QAALLOC(bufs, w_out, float, NBMAX * ND);
+    QAALLOC(bufs, d_ns, int32_t, NS);
+    QaTimer tm;
     float ms[TWXHM_NTIMES] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (kernel_ms) { HMCHK(tm.init()); ms[2] = hm_since(t_alloc); }
+    if (kernel_ms) { QACHK(tm.init()); ms[2] = qa_since(t_alloc); }
     int nbatches = 0;
     for (int64_t first = 0; first < nstn; first += per) {
         const size_t NB = (size_t)(nstn - first < per ? nstn - first : per);
         const size_t at = (size_t)first * ND;
         const auto t_up = std::chrono::steady_clock::now();
-        HMUP(w_tmax, tmax + at, float, NB * ND);
-        HMUP(w_tobs, tobs + at, float, NB * ND);
+        QAUP(w_tmax, tmax + at, float, NB * ND);
+        QAUP(w_tobs, tobs + at, float, NB * ND);
         ++nbatches;
-        if (kernel_ms) { HMCHK(hipDeviceSynchronize()); ms[2] += hm_since(t_up); HMCHK(tm.start()); }
+        if (kernel_ms) { QACHK(hipDeviceSynchronize()); ms[2] += qa_since(t_up); QACHK(tm.start()); }
         hipLaunchKernelGGL(k_hm_tobs, dim3((unsigned)NB), dim3(HM_THREADS), 0, nullptr, (const float *)w_tmax,
                            (const float *)w_tobs, (int)ndays, first, w_out, d_ns);
-        HMCHK(hipGetLastError());
-        if (kernel_ms) HMCHK(tm.stop(&ms[0]));
+        QACHK(hipGetLastError());
+        if (kernel_ms) QACHK(tm.stop_add(&ms[0]));
         const auto t_down = std::chrono::steady_clock::now();    // the copy waits for the launch (null stream)
-        HMDOWN(out + at, w_out, float, NB * ND);
-        ms[3] += hm_since(t_down);
+        QADOWN(out + at, w_out, float, NB * ND);
+        ms[3] += qa_since(t_down);
     }
     const auto t_down = std::chrono::steady_clock::now();
-    HMDOWN(nshift, d_ns, int32_t, NS);
-    ms[3] += hm_since(t_down);
+    QADOWN(nshift, d_ns, int32_t, NS);
+    ms[3] += qa_since(t_down);
     if (counts) { counts[0] = nbatches; counts[1] = nbatches; }
     if (kernel_ms) memcpy(kernel_ms, ms, sizeof ms);
     return 0;
@@ -566,29 +517,29 @@ extern "C" int twxhm_homog_daily(int device, int64_t nstn, int64_t ndays, const 
     if (!obs || !mth_mean || !mth_miss || !pha || !mth_ymd || !mth_first || !mth_ndays || !adj_off || !delta || !out ||
         !status || !nchanged) {
         snprintf(msg, sizeof msg, "%s: null buffer", fn);
-        return hm_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (hm_months(fn, ndays, nmth, mth_first, mth_ndays, errbuf, errlen)) return -1;
     if (adj_off[0] != 0) {
         snprintf(msg, sizeof msg, "%s: adj_off must start at 0", fn);
-        return hm_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     for (int64_t s = 0; s < nstn; ++s) {
         if (adj_off[s + 1] < adj_off[s]) {
             snprintf(msg, sizeof msg, "%s: adj_off must ascend (station %lld)", fn, (long long)s);
-            return hm_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
     }
     const int64_t nadj = adj_off[nstn];
     if (nadj > 0 && (!adj_ymd_start || !adj_ymd_end || !adj)) {
         snprintf(msg, sizeof msg, "%s: null adjustment list", fn);
-        return hm_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     for (int64_t s = 0; s < nstn; ++s) {
         for (int64_t a = adj_off[s] + 1; a < adj_off[s + 1]; ++a) {
             if (adj_ymd_start[a] < adj_ymd_start[a - 1]) {
                 snprintf(msg, sizeof msg, "%s: the adjustments of station %lld are not sorted by ymd_start", fn, (long long)s);
-                return hm_fail(errbuf, errlen, msg);
+                return qa_fail(errbuf, errlen, msg);
             }
         }
     }
@@ -599,56 +550,56 @@ extern "C" int twxhm_homog_daily(int device, int64_t nstn, int64_t ndays, const 
     for (int32_t g = 0; g < nmth; ++g)
         for (int32_t j = 0; j < mth_ndays[g]; ++j) day_mth[(size_t)mth_first[g] + j] = g;
 
-    HMCHK(hipSetDevice(device));
-    HmBufs bufs;
+    QACHK(hipSetDevice(device));
+    QaPool bufs;
     float *w_obs, *w_out, *d_mean;
     int16_t *d_miss;
     int32_t *d_pha, *d_ymd, *d_mn, *d_dm, *d_as, *d_ae, *d_status, *d_nch;
     int64_t *d_off;
     double *d_adj, *d_delta;
     const auto t_alloc = std::chrono::steady_clock::now();
-    HMALLOC(bufs, w_obs, float, NBMAX * ND); HMALLOC(bufs, w_out, float, NBMAX * ND);
-    HMALLOC(bufs, d_mean, float, NS * NM); HMALLOC(bufs, d_miss, int16_t, NS * NM); HMALLOC(bufs, d_pha, int32_t, NS * NM);
-    HMALLOC(bufs, d_ymd, int32_t, NM); HMALLOC(bufs, d_mn, int32_t, NM); HMALLOC(bufs, d_dm, int32_t, ND);
-    HMALLOC(bufs, d_off, int64_t, NS + 1); HMALLOC(bufs, d_as, int32_t, NA); HMALLOC(bufs, d_ae, int32_t, NA);
-    HMALLOC(bufs, d_adj, double, NA); HMALLOC(bufs, d_delta, double, NS * NM);
-    HMALLOC(bufs, d_status, int32_t, NS); HMALLOC(bufs, d_nch, int32_t, NS);
-    HMUP(d_mean, mth_mean, float, NS * NM); HMUP(d_miss, mth_miss, int16_t, NS * NM); HMUP(d_pha, pha, int32_t, NS * NM);
-    HMUP(d_ymd, mth_ymd, int32_t, NM); HMUP(d_mn, mth_ndays, int32_t, NM); HMUP(d_dm, day_mth.data(), int32_t, ND);
-    HMUP(d_off, adj_off, int64_t, NS + 1);
-    if (NA) { HMUP(d_as, adj_ymd_start, int32_t, NA); HMUP(d_ae, adj_ymd_end, int32_t, NA); HMUP(d_adj, adj, double, NA); }
-    HmTimer tm;
+    QAALLOC(bufs, w_obs, float, NBMAX * ND); QAALLOC(bufs, w_out, float, NBMAX * ND);
+    QAALLOC(bufs, d_mean, float, NS * NM); QAALLOC(bufs, d_miss, int16_t, NS * NM); QAALLOC(bufs, d_pha, int32_t, NS * NM);
+    QAALLOC(bufs, d_ymd, int32_t, NM); QAALLOC(bufs, d_mn, int32_t, NM); QAALLOC(bufs, d_dm, int32_t, ND);
+    QAALLOC(bufs, d_off, int64_t, NS + 1); QAALLOC(bufs, d_as, int32_t, NA); QAALLOC(bufs, d_ae, int32_t, NA);
+    QAALLOC(bufs, d_adj, double, NA); QAALLOC(bufs, d_delta, double, NS * NM);
+    QAALLOC(bufs, d_status, int32_t, NS); QAALLOC(bufs, d_nch, int32_t, NS);
+    QAUP(d_mean, mth_mean, float, NS * NM); QAUP(d_miss, mth_miss, int16_t, NS * NM); QAUP(d_pha, pha, int32_t, NS * NM);
+    QAUP(d_ymd, mth_ymd, int32_t, NM); QAUP(d_mn, mth_ndays, int32_t, NM); QAUP(d_dm, day_mth.data(), int32_t, ND);
+    QAUP(d_off, adj_off, int64_t, NS + 1);
+    if (NA) { QAUP(d_as, adj_ymd_start, int32_t, NA); QAUP(d_ae, adj_ymd_end, int32_t, NA); QAUP(d_adj, adj, double, NA); }
+    QaTimer tm;
     float ms[TWXHM_NTIMES] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (kernel_ms) { HMCHK(tm.init()); HMCHK(hipDeviceSynchronize()); ms[2] = hm_since(t_alloc); HMCHK(tm.start()); }
+    if (kernel_ms) { QACHK(tm.init()); QACHK(hipDeviceSynchronize()); ms[2] = qa_since(t_alloc); QACHK(tm.start()); }
     hipLaunchKernelGGL(k_hm_delta, dim3((unsigned)NS), dim3(HM_THREADS), 0, nullptr, (int)nmth, (const float *)d_mean,
                        (const int16_t *)d_miss, (const int32_t *)d_pha, (const int32_t *)d_ymd, (const int32_t *)d_mn,
                        (const int64_t *)d_off, (const int32_t *)d_as, (const int32_t *)d_ae, (const double *)d_adj, d_delta,
                        d_status, d_nch);
-    HMCHK(hipGetLastError());
-    if (kernel_ms) HMCHK(tm.stop(&ms[0]));
+    QACHK(hipGetLastError());
+    if (kernel_ms) QACHK(tm.stop_add(&ms[0]));
     int nbatches = 0;
     for (int64_t first = 0; first < nstn; first += per) {
         const size_t NB = (size_t)(nstn - first < per ? nstn - first : per);
         const size_t at = (size_t)first * ND;
         const int total = (int)(NB * ND);                        // < 2^31 by hm_batch
         const auto t_up = std::chrono::steady_clock::now();
-        HMUP(w_obs, obs + at, float, NB * ND);
+        QAUP(w_obs, obs + at, float, NB * ND);
         ++nbatches;
-        if (kernel_ms) { HMCHK(hipDeviceSynchronize()); ms[2] += hm_since(t_up); HMCHK(tm.start()); }
+        if (kernel_ms) { QACHK(hipDeviceSynchronize()); ms[2] += qa_since(t_up); QACHK(tm.start()); }
         const unsigned nblk = (unsigned)(((int64_t)total + 4 * HM_THREADS - 1) / (4 * HM_THREADS));
         hipLaunchKernelGGL(k_hm_apply, dim3(nblk), dim3(HM_THREADS), 0, nullptr, (const float *)w_obs, total, (int)ndays,
                            (int)nmth, (const int32_t *)d_dm, (const double *)d_delta, (const int32_t *)d_status, first, w_out);
-        HMCHK(hipGetLastError());
-        if (kernel_ms) HMCHK(tm.stop(&ms[1]));
+        QACHK(hipGetLastError());
+        if (kernel_ms) QACHK(tm.stop_add(&ms[1]));
         const auto t_down = std::chrono::steady_clock::now();    // the copy waits for the launch (null stream)
-        HMDOWN(out + at, w_out, float, NB * ND);
-        ms[3] += hm_since(t_down);
+        QADOWN(out + at, w_out, float, NB * ND);
+        ms[3] += qa_since(t_down);
     }
     const auto t_down = std::chrono::steady_clock::now();
-    HMDOWN(delta, d_delta, double, NS * NM);
-    HMDOWN(status, d_status, int32_t, NS);
-    HMDOWN(nchanged, d_nch, int32_t, NS);
-    ms[3] += hm_since(t_down);
+    QADOWN(delta, d_delta, double, NS * NM);
+    QADOWN(status, d_status, int32_t, NS);
+    QADOWN(nchanged, d_nch, int32_t, NS);
+    ms[3] += qa_since(t_down);
     if (counts) { counts[0] = nbatches + 1; counts[1] = nbatches; }
     if (kernel_ms) memcpy(kernel_ms, ms, sizeof ms);
     return 0;

@@ -1,7 +1,7 @@
 // twx_infillchk.hip -- libtwxqa.so: the check of step16's fits (_is_nonoptimal_infill, twx/infill/infill_daily.py:563-595,
 // with hasVarChgPt of twx/infill/rpy/pca_infill.R:306-310) restated as include/twx_qa.h states it, for every item of one
-// call (twxck_infill_check).  Its own translation unit: the buffer list and the event timer it shares with twx_ppca.hip
-// are restated, nothing there is edited.
+// call (twxck_infill_check).  Its own translation unit; the buffer list and the event timer it shares with the other
+// units are twx_qa_common.h's.
 //
 // An item is a fitted series and the target's observations on the same N <= TWXCK_MAX_ROWS days.  One workgroup of 256 (4
 // wavefronts) per item; thread k owns the contiguous rows k c .. k c + c - 1, c = ceil(N / 256), so a prefix sum over the
@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "twx_qa.h"
+#include "twx_qa_common.h"
 
 #define CK_NW 4                              // wavefronts of a workgroup
 #define CK_THREADS (64 * CK_NW)
@@ -240,57 +241,6 @@ __global__ __launch_bounds__(CK_THREADS) void k_ck_check(const int64_t *__restri
     }
 }
 
-namespace {
-
-int ck_fail(char *errbuf, int errlen, const char *what, hipError_t e = hipSuccess)
-{
-    if (errbuf && errlen > 0) {
-        if (e != hipSuccess) snprintf(errbuf, (size_t)errlen, "%s: %s", what, hipGetErrorString(e));
-        else snprintf(errbuf, (size_t)errlen, "%s", what);
-    }
-    return -1;
-}
-
-struct CkBufs {                                                  // every device allocation of a call, freed together
-    std::vector<void *> p;
-    ~CkBufs() { for (void *x : p) if (x) (void)hipFree(x); }
-    hipError_t get(void **out, size_t bytes)
-    {
-        hipError_t e = hipMalloc(out, bytes ? bytes : 1);
-        if (e == hipSuccess) p.push_back(*out);
-        return e;
-    }
-};
-
-struct CkTimer {                                                 // HIP-event time of a run of launches on the null stream
-    hipEvent_t a = nullptr, b = nullptr;
-    ~CkTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    hipError_t init() { hipError_t e = hipEventCreate(&a); return e != hipSuccess ? e : hipEventCreate(&b); }
-    hipError_t start() { return hipEventRecord(a, nullptr); }
-    hipError_t stop(float *acc)
-    {
-        float ms = 0.0f;
-        hipError_t e = hipEventRecord(b, nullptr);
-        if (e == hipSuccess) e = hipEventSynchronize(b);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
-        *acc += ms;
-        return e;
-    }
-};
-
-}  // namespace
-
-#define CKCHK(call)                                                                     \
-    do {                                                                                \
-        hipError_t e_ = (call);                                                         \
-        if (e_ != hipSuccess) return ck_fail(errbuf, errlen, #call, e_);                \
-    } while (0)
-#define CKALLOC(bufs, ptr, type, count) CKCHK((bufs).get((void **)&(ptr), (size_t)(count) * sizeof(type)))
-#define CKUP(dst, src, type, count)                                                                         \
-    do {                                                                                                    \
-        if ((count) > 0) CKCHK(hipMemcpy((dst), (src), (size_t)(count) * sizeof(type), hipMemcpyHostToDevice)); \
-    } while (0)
-
 extern "C" int twxck_infill_check(int device, int64_t nitem, const int64_t *off, const double *fit, const double *obs,
                                   const double *pen, double mae_max, double r2_min, double impossible_high,
                                   double impossible_low, int64_t workspace_bytes, int32_t *nobs, double *mae, double *r2,
@@ -302,46 +252,46 @@ extern "C" int twxck_infill_check(int device, int64_t nitem, const int64_t *off,
     if (errbuf && errlen > 0) errbuf[0] = 0;
     if (nitem < 1 || nitem > INT32_MAX / 2) {
         snprintf(msg, sizeof msg, "%s: need 1 <= nitem <= %d", fn, INT32_MAX / 2);
-        return ck_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (!off || !pen || !nobs || !mae || !r2 || !nimpossible || !cpt_stat || !cpt_tau || !reasons || !status) {
         snprintf(msg, sizeof msg, "%s: null buffer", fn);
-        return ck_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (!std::isfinite(mae_max) || !std::isfinite(r2_min) || !std::isfinite(impossible_high) || !std::isfinite(impossible_low)) {
         snprintf(msg, sizeof msg, "%s: mae_max, r2_min, impossible_high and impossible_low must be finite (defaults: "
                  "TWXCK_DEFAULT_*)", fn);
-        return ck_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (off[0] != 0) {
         snprintf(msg, sizeof msg, "%s: off[0] = %lld, not 0", fn, (long long)off[0]);
-        return ck_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     for (int64_t i = 0; i < nitem; ++i)
         if (off[i + 1] < off[i]) {
             snprintf(msg, sizeof msg, "%s: off decreases at item %lld", fn, (long long)i);
-            return ck_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
     if (off[nitem] > 0 && (!fit || !obs)) {
         snprintf(msg, sizeof msg, "%s: null buffer", fn);
-        return ck_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (workspace_bytes <= 0) workspace_bytes = TWXCK_WORKSPACE_BYTES;
     const size_t NI = (size_t)nitem;
 
-    CKCHK(hipSetDevice(device));
-    CkBufs bufs;
+    QACHK(hipSetDevice(device));
+    QaPool bufs;
     CkOut d_out;
     double *d_pen;
-    CKALLOC(bufs, d_pen, double, NI);
-    CKALLOC(bufs, d_out.nobs, int32_t, NI); CKALLOC(bufs, d_out.nimpossible, int32_t, NI);
-    CKALLOC(bufs, d_out.cpt_tau, int32_t, NI); CKALLOC(bufs, d_out.reasons, int32_t, NI);
-    CKALLOC(bufs, d_out.status, int32_t, NI);
-    CKALLOC(bufs, d_out.mae, double, NI); CKALLOC(bufs, d_out.r2, double, NI); CKALLOC(bufs, d_out.cpt_stat, double, NI);
-    CKUP(d_pen, pen, double, NI);
-    CkTimer tm;
+    QAALLOC(bufs, d_pen, double, NI);
+    QAALLOC(bufs, d_out.nobs, int32_t, NI); QAALLOC(bufs, d_out.nimpossible, int32_t, NI);
+    QAALLOC(bufs, d_out.cpt_tau, int32_t, NI); QAALLOC(bufs, d_out.reasons, int32_t, NI);
+    QAALLOC(bufs, d_out.status, int32_t, NI);
+    QAALLOC(bufs, d_out.mae, double, NI); QAALLOC(bufs, d_out.r2, double, NI); QAALLOC(bufs, d_out.cpt_stat, double, NI);
+    QAUP_NZ(d_pen, pen, double, NI);
+    QaTimer tm;
     float ms[TWXCK_NTIMES] = {0.0f, 0.0f, 0.0f};
-    if (kernel_ms) CKCHK(tm.init());
+    if (kernel_ms) QACHK(tm.init());
     // batches of consecutive items whose rows fit the budget (at least one item each); an item above the cap has no rows
     int nbatches = 0;
     std::vector<int64_t> boff;
@@ -370,38 +320,38 @@ extern "C" int twxck_infill_check(int device, int64_t nitem, const int64_t *off,
             }
         }
         ++nbatches;
-        CkBufs ws;                                               // freed at the end of the batch
+        QaPool ws;                                               // freed at the end of the batch
         int64_t *w_off;
         int32_t *w_n;
         double *w_fit, *w_obs;
-        CKALLOC(ws, w_off, int64_t, NB + 1); CKALLOC(ws, w_n, int32_t, NB);
-        CKALLOC(ws, w_fit, double, NR); CKALLOC(ws, w_obs, double, NR);
-        CKUP(w_off, boff.data(), int64_t, NB + 1);
-        CKUP(w_n, bn.data(), int32_t, NB);
-        CKUP(w_fit, hfit.data(), double, NR);
-        CKUP(w_obs, hobs.data(), double, NR);
+        QAALLOC(ws, w_off, int64_t, NB + 1); QAALLOC(ws, w_n, int32_t, NB);
+        QAALLOC(ws, w_fit, double, NR); QAALLOC(ws, w_obs, double, NR);
+        QAUP_NZ(w_off, boff.data(), int64_t, NB + 1);
+        QAUP_NZ(w_n, bn.data(), int32_t, NB);
+        QAUP_NZ(w_fit, hfit.data(), double, NR);
+        QAUP_NZ(w_obs, hobs.data(), double, NR);
         if (kernel_ms) {
-            CKCHK(hipDeviceSynchronize());
+            QACHK(hipDeviceSynchronize());
             ms[1] += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_up).count();
-            CKCHK(tm.start());
+            QACHK(tm.start());
         }
         hipLaunchKernelGGL(k_ck_check, dim3((unsigned)NB), dim3(CK_THREADS), 0, nullptr, (const int64_t *)w_off,
                            (const int32_t *)w_n, (const double *)w_fit, (const double *)w_obs, (const double *)d_pen, first,
                            mae_max, r2_min, impossible_high, impossible_low, d_out);
-        CKCHK(hipGetLastError());
-        if (kernel_ms) CKCHK(tm.stop(&ms[0]));
-        else CKCHK(hipDeviceSynchronize());                      // the batch's buffers are freed next
+        QACHK(hipGetLastError());
+        if (kernel_ms) QACHK(tm.stop_add(&ms[0]));
+        else QACHK(hipDeviceSynchronize());                      // the batch's buffers are freed next
         first = last;
     }
     const auto t_down = std::chrono::steady_clock::now();
-    CKCHK(hipMemcpy(nobs, d_out.nobs, NI * 4, hipMemcpyDeviceToHost));
-    CKCHK(hipMemcpy(nimpossible, d_out.nimpossible, NI * 4, hipMemcpyDeviceToHost));
-    CKCHK(hipMemcpy(cpt_tau, d_out.cpt_tau, NI * 4, hipMemcpyDeviceToHost));
-    CKCHK(hipMemcpy(reasons, d_out.reasons, NI * 4, hipMemcpyDeviceToHost));
-    CKCHK(hipMemcpy(status, d_out.status, NI * 4, hipMemcpyDeviceToHost));
-    CKCHK(hipMemcpy(mae, d_out.mae, NI * 8, hipMemcpyDeviceToHost));
-    CKCHK(hipMemcpy(r2, d_out.r2, NI * 8, hipMemcpyDeviceToHost));
-    CKCHK(hipMemcpy(cpt_stat, d_out.cpt_stat, NI * 8, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(nobs, d_out.nobs, NI * 4, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(nimpossible, d_out.nimpossible, NI * 4, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(cpt_tau, d_out.cpt_tau, NI * 4, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(reasons, d_out.reasons, NI * 4, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(status, d_out.status, NI * 4, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(mae, d_out.mae, NI * 8, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(r2, d_out.r2, NI * 8, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(cpt_stat, d_out.cpt_stat, NI * 8, hipMemcpyDeviceToHost));
     ms[2] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_down).count();
     if (counts) { counts[0] = nbatches; counts[1] = nbatches; }
     if (kernel_ms) memcpy(kernel_ms, ms, sizeof ms);

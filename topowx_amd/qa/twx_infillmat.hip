@@ -1,8 +1,8 @@
 // twx_infillmat.hip -- libtwxqa.so: the neighbour matrices of the infill family (step14 / step15 / step16): the first
 // pass of _InfillMatrix (twx/infill/infill_normals.py:52-237), the widening loop of _InfillMatrix.infill (:324-343 with
 // __extend_ngh_radius / __merge / __has_min_daily_nghs) and _shrink_matrix (:391-420), for all targets and day groups
-// of one call (include/twx_qa.h, twxif_infill_matrix).  Its own translation unit: the helpers it shares with the other
-// units of the library (the haversine of k_radius_dist, the event timer) are restated, nothing there is edited.
+// of one call (include/twx_qa.h, twxif_infill_matrix).  Its own translation unit; the helpers it shares with the
+// other units of the library (the haversine, the wave sums, the buffer list, the event timer) are twx_qa_common.h's.
 //
 // An item is (target, day group).  The rings of a target -- (−1, 75], (75, 112.5], ... with an empty ring grown by
 // 37.5 km until it holds a station -- depend on distances only, so every item of a target sees the same sequence of
@@ -48,9 +48,8 @@
 #include <vector>
 
 #include "twx_qa.h"
+#include "twx_qa_common.h"
 
-#define IF_RADIAN 0.017453292519943295       // util_geo.py:21
-#define IF_EARTH_KM 6371.009                 // util_geo.py:22
 #define IF_CAP TWXQA_MAX_RADIUS_NGH
 #define IF_IOA_DENOM0 (-2.0)                 // pair marker: the d1 denominator is 0 (d1 itself lies in [0, 1])
 #define IF_RING_EXHAUSTED (-1)
@@ -60,28 +59,6 @@
 namespace {
 
 __device__ __forceinline__ bool if_finitef(float v) { return fabsf(v) <= 3.40282346638528859812e38f; }
-
-__device__ __forceinline__ double if_dist(double lat1rad, double lon1rad, double cos1, double lat2, double lon2)
-{
-    const double lat2rad = lat2 * IF_RADIAN, lon2rad = lon2 * IF_RADIAN;
-    const double s1 = sin((lat1rad - lat2rad) / 2.0), s2 = sin((lon1rad - lon2rad) / 2.0);
-    const double a = s1 * s1 + (cos1 * cos(lat2rad)) * (s2 * s2);
-    return IF_EARTH_KM * (2.0 * asin(sqrt(a)));
-}
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v = v + __shfl_xor(v, m, 64);
-    return v;
-}
-
-__device__ __forceinline__ int wave_sum_i(int v)
-{
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v = v + __shfl_xor(v, m, 64);
-    return v;
-}
 
 }  // namespace
 
@@ -97,7 +74,7 @@ __global__ __launch_bounds__(64) void k_if_ring(int64_t nstn, const double *__re
     const int lane = threadIdx.x;
     const int64_t t = act_t[blockIdx.x];
     const int32_t self = target_idx[t], excl = exclude_idx[t];   // excl: -1 (no row has it) or the row twxxv_ leaves out
-    const double lat1rad = lat[self] * IF_RADIAN, lon1rad = lon[self] * IF_RADIAN;
+    const double lat1rad = lat[self] * QA_RADIAN, lon1rad = lon[self] * QA_RADIAN;
     const double cos1 = cos(lat1rad);
     const double rin = first ? -1.0 : cur_max[t];                // the reference's dists > min_dist, min_dist = -1
     // ---- pass A: the nearest eligible station beyond rin --------------------------------------------------------
@@ -105,7 +82,7 @@ __global__ __launch_bounds__(64) void k_if_ring(int64_t nstn, const double *__re
     for (int64_t j0 = 0; j0 < nstn; j0 += 64) {                  // uniform
         const int64_t j = j0 + lane;
         if (j < nstn && j != self && j != excl && elig[j]) {
-            const double d = if_dist(lat1rad, lon1rad, cos1, lat[j], lon[j]);
+            const double d = qa_dist_km(lat1rad, lon1rad, cos1, lat[j], lon[j]);
             if (d > rin && d < dmin) dmin = d;
         }
     }
@@ -124,7 +101,7 @@ __global__ __launch_bounds__(64) void k_if_ring(int64_t nstn, const double *__re
         bool in = false;
         double d = 0.0;
         if (j < nstn && j != self && j != excl && elig[j]) {
-            d = if_dist(lat1rad, lon1rad, cos1, lat[j], lon[j]);
+            d = qa_dist_km(lat1rad, lon1rad, cos1, lat[j], lon[j]);
             in = d > rin && d <= rout;
         }
         const uint64_t b = __ballot(in);
@@ -182,11 +159,11 @@ __global__ __launch_bounds__(256) void k_if_pair(int64_t ndays, const float *__r
             nst += fb ? 1 : 0;
             if (fb) so = so + (double)o;
         }
-        nlap = wave_sum_i(nlap);
-        nst = wave_sum_i(nst);
+        nlap = qa_wave_sum_i(nlap);
+        nst = qa_wave_sum_i(nst);
         double ioa = __builtin_nan("");                          // not needed: below the target's threshold
         if (nst > 0 && nst >= thr_por[t * ngroups + g]) {        // uniform
-            const double mean = wave_sum(so) / (double)nst;      // np.mean of the overlap
+            const double mean = qa_wave_sum(so) / (double)nst;      // np.mean of the overlap
             double num = 0.0, den = 0.0;
             for (int i = a + lane; i < b; i += 64) {
                 const int d = perm[i];
@@ -197,8 +174,8 @@ __global__ __launch_bounds__(256) void k_if_pair(int64_t ndays, const float *__r
                     den = den + (fabs(p - mean) + fabs(o - mean));
                 }
             }
-            num = wave_sum(num);
-            den = wave_sum(den);
+            num = qa_wave_sum(num);
+            den = qa_wave_sum(den);
             ioa = den == 0.0 ? IF_IOA_DENOM0 : 1.0 - num / den;  // perf_metrics.py:59-62
         }
         if (lane == 0) { p_nlap[out] = nlap; p_nst[out] = nst; p_ioa[out] = ioa; }
@@ -374,53 +351,15 @@ __global__ __launch_bounds__(256) void k_if_compact(const int32_t *__restrict__ 
 // ---------------------------------------------------------------------------------
 namespace {
 
-int if_fail(char *errbuf, int errlen, const char *what, hipError_t e = hipSuccess)
-{
-    if (errbuf && errlen > 0) {
-        if (e != hipSuccess) snprintf(errbuf, (size_t)errlen, "%s: %s", what, hipGetErrorString(e));
-        else snprintf(errbuf, (size_t)errlen, "%s", what);
-    }
-    return -1;
-}
-
-struct IfBufs {                                                  // every device allocation of a call, freed together
-    std::vector<void *> p;
-    ~IfBufs() { for (void *x : p) if (x) (void)hipFree(x); }
-    hipError_t get(void **out, size_t bytes)
-    {
-        hipError_t e = hipMalloc(out, bytes ? bytes : 1);
-        if (e == hipSuccess) p.push_back(*out);
-        return e;
-    }
-};
-
-struct IfTimer {                                                 // HIP-event time of a run of launches on the null stream
-    hipEvent_t a = nullptr, b = nullptr;
-    ~IfTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    hipError_t init() { hipError_t e = hipEventCreate(&a); return e != hipSuccess ? e : hipEventCreate(&b); }
-    hipError_t start() { return hipEventRecord(a, nullptr); }
-    hipError_t stop(float *acc)
-    {
-        float ms = 0.0f;
-        hipError_t e = hipEventRecord(b, nullptr);
-        if (e == hipSuccess) e = hipEventSynchronize(b);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
-        *acc += ms;
-        return e;
-    }
-};
-
-bool if_leap(int y) { return (y % 4 == 0 && y % 100 != 0) || y % 400 == 0; }
-
 // the first index whose date is not the day after the one before it; -1: consecutive calendar days
 int64_t if_first_gap(int64_t ndays, const int32_t *ymd)
 {
     static const int mlen[12] = {31, 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31};
     int y = ymd[0] / 10000, mth = (ymd[0] / 100) % 100, day = ymd[0] % 100;
-    if (ymd[0] < 10101 || mth < 1 || mth > 12 || day < 1 || day > mlen[mth - 1] + ((mth == 2 && if_leap(y)) ? 1 : 0)) return 0;
+    if (ymd[0] < 10101 || mth < 1 || mth > 12 || day < 1 || day > mlen[mth - 1] + ((mth == 2 && qa_leap(y)) ? 1 : 0)) return 0;
     for (int64_t i = 0; i < ndays; ++i) {
         if (ymd[i] != y * 10000 + mth * 100 + day) return i;
-        if (++day > mlen[mth - 1] + ((mth == 2 && if_leap(y)) ? 1 : 0)) {
+        if (++day > mlen[mth - 1] + ((mth == 2 && qa_leap(y)) ? 1 : 0)) {
             day = 1;
             if (++mth > 12) { mth = 1; ++y; }
         }
@@ -429,13 +368,6 @@ int64_t if_first_gap(int64_t ndays, const int32_t *ymd)
 }
 
 }  // namespace
-
-#define IFCHK(call)                                                                     \
-    do {                                                                                \
-        hipError_t e_ = (call);                                                         \
-        if (e_ != hipSuccess) return if_fail(errbuf, errlen, #call, e_);                \
-    } while (0)
-#define IFALLOC(ptr, type, count) IFCHK(bufs.get((void **)&(ptr), (size_t)(count) * sizeof(type)))
 
 // the driver of twxif_infill_matrix and twxxv_infill_matrix; exclude_idx: nullptr (no exclusion) or [ntarget]
 static int if_matrix(const char *fn, int device, int64_t nstn, int64_t ndays, const double *lon, const double *lat,
@@ -453,41 +385,41 @@ static int if_matrix(const char *fn, int device, int64_t nstn, int64_t ndays, co
         ntarget * (int64_t)ngroups > INT32_MAX / 2) {
         snprintf(msg, sizeof msg, "%s: need nstn, ndays, ntarget >= 1, 1 <= ngroups <= %d and 1 <= min_daily_nnghs <= %d",
                  fn, TWXIF_MAX_GROUPS, TWXIF_MAX_MIN_NNGHS);
-        return if_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (!lon || !lat || !obs || !ymd || !eligible || !target_idx || !group || !nthres_all || !nthres_target_por ||
         !status || !nnghs || !max_dist || !csr_off || !ngh_idx || !ngh_ioa || !ngh_dist || !ngh_nlap || !ngh_nlap_stn ||
         !keep || csr_cap < 0) {
         snprintf(msg, sizeof msg, "%s: null buffer", fn);
-        return if_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     const int64_t gap = if_first_gap(ndays, ymd);
     if (gap >= 0) {
         snprintf(msg, sizeof msg, "%s: ymd[%lld] = %d: the days are not consecutive calendar days", fn, (long long)gap,
                  (int)ymd[gap]);
-        return if_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     for (int64_t j = 0; j < nstn; ++j)
         if (!std::isfinite(lon[j]) || !std::isfinite(lat[j])) {
             snprintf(msg, sizeof msg, "%s: station %lld has a non-finite longitude / latitude", fn, (long long)j);
-            return if_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
     for (int64_t t = 0; t < ntarget; ++t)
         if (target_idx[t] < 0 || target_idx[t] >= nstn) {
             snprintf(msg, sizeof msg, "%s: target index %d outside [0, %lld)", fn, (int)target_idx[t], (long long)nstn);
-            return if_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
     for (int64_t t = 0; exclude_idx && t < ntarget; ++t)
         if (exclude_idx[t] < -1 || exclude_idx[t] >= nstn) {
             snprintf(msg, sizeof msg, "%s: exclude index %d outside -1 .. %lld", fn, (int)exclude_idx[t], (long long)nstn - 1);
-            return if_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
     // the used days sorted by group, in day order within a group
     std::vector<int32_t> goff((size_t)ngroups + 1, 0);
     for (int64_t d = 0; d < ndays; ++d) {
         if (group[d] < -1 || group[d] >= ngroups) {
             snprintf(msg, sizeof msg, "%s: group[%lld] = %d outside -1 .. %d", fn, (long long)d, (int)group[d], ngroups - 1);
-            return if_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         if (group[d] >= 0) ++goff[(size_t)group[d] + 1];
     }
@@ -503,57 +435,58 @@ static int if_matrix(const char *fn, int device, int64_t nstn, int64_t ndays, co
     for (int64_t i = 0; i < ni; ++i) {
         if (nthres_target_por[i] < 0 || nthres_all[i % ngroups] < 0) {
             snprintf(msg, sizeof msg, "%s: negative threshold of item %lld", fn, (long long)i);
-            return if_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         if (nthres_target_por[i] == 0) { done[(size_t)i] = 1; h_status[(size_t)i] = TWXIF_NO_TARGET_OBS; }
     }
 
-    IFCHK(hipSetDevice(device));
+    QACHK(hipSetDevice(device));
     const auto t_up = std::chrono::steady_clock::now();
-    IfBufs bufs;
+    QaPool bufs;
     double *d_lon, *d_lat, *d_curmax, *d_rdist, *d_pioa, *d_maxdist, *d_lioa, *d_ldist;
     float *d_obs;
     uint8_t *d_elig, *d_done, *d_lkeep, *d_daycnt;
     int32_t *d_tidx, *d_excl, *d_actt, *d_acti, *d_perm, *d_goff, *d_thrall, *d_thrpor, *d_ringn, *d_ridx, *d_pnlap, *d_pnst,
         *d_status, *d_nnghs, *d_n, *d_lidx, *d_lnlap, *d_lnst;
     const size_t NS = (size_t)nstn, ND = (size_t)ndays, NT = (size_t)ntarget, NI = (size_t)ni, G = (size_t)ngroups;
-    IFALLOC(d_lon, double, NS); IFALLOC(d_lat, double, NS); IFALLOC(d_elig, uint8_t, NS);
-    IFALLOC(d_obs, float, NS * ND);
-    IFALLOC(d_tidx, int32_t, NT); IFALLOC(d_excl, int32_t, NT); IFALLOC(d_actt, int32_t, NT); IFALLOC(d_acti, int32_t, NI);
-    IFALLOC(d_perm, int32_t, perm.size()); IFALLOC(d_goff, int32_t, G + 1);
-    IFALLOC(d_thrall, int32_t, G); IFALLOC(d_thrpor, int32_t, NI);
-    IFALLOC(d_curmax, double, NT); IFALLOC(d_ringn, int32_t, NT);
-    IFALLOC(d_ridx, int32_t, NT * IF_CAP); IFALLOC(d_rdist, double, NT * IF_CAP);
-    IFALLOC(d_pnlap, int32_t, NT * IF_CAP * G); IFALLOC(d_pnst, int32_t, NT * IF_CAP * G);
-    IFALLOC(d_pioa, double, NT * IF_CAP * G);
-    IFALLOC(d_done, uint8_t, NI); IFALLOC(d_status, int32_t, NI); IFALLOC(d_nnghs, int32_t, NI);
-    IFALLOC(d_maxdist, double, NI); IFALLOC(d_n, int32_t, NI);
-    IFALLOC(d_lidx, int32_t, NI * IF_CAP); IFALLOC(d_lioa, double, NI * IF_CAP); IFALLOC(d_ldist, double, NI * IF_CAP);
-    IFALLOC(d_lnlap, int32_t, NI * IF_CAP); IFALLOC(d_lnst, int32_t, NI * IF_CAP); IFALLOC(d_lkeep, uint8_t, NI * IF_CAP);
-    IFALLOC(d_daycnt, uint8_t, NT * ND);
-    IFCHK(hipMemcpy(d_lon, lon, NS * 8, hipMemcpyHostToDevice));
-    IFCHK(hipMemcpy(d_lat, lat, NS * 8, hipMemcpyHostToDevice));
-    IFCHK(hipMemcpy(d_elig, eligible, NS, hipMemcpyHostToDevice));
-    IFCHK(hipMemcpy(d_obs, obs, NS * ND * 4, hipMemcpyHostToDevice));
-    IFCHK(hipMemcpy(d_tidx, target_idx, NT * 4, hipMemcpyHostToDevice));
-    if (exclude_idx) IFCHK(hipMemcpy(d_excl, exclude_idx, NT * 4, hipMemcpyHostToDevice));
-    else IFCHK(hipMemset(d_excl, 0xff, NT * 4));                 // -1: no station has that row
-    if (!perm.empty()) IFCHK(hipMemcpy(d_perm, perm.data(), perm.size() * 4, hipMemcpyHostToDevice));
-    IFCHK(hipMemcpy(d_goff, goff.data(), (G + 1) * 4, hipMemcpyHostToDevice));
-    IFCHK(hipMemcpy(d_thrall, nthres_all, G * 4, hipMemcpyHostToDevice));
-    IFCHK(hipMemcpy(d_thrpor, nthres_target_por, NI * 4, hipMemcpyHostToDevice));
-    IFCHK(hipMemcpy(d_done, done.data(), NI, hipMemcpyHostToDevice));
-    IFCHK(hipMemcpy(d_status, h_status.data(), NI * 4, hipMemcpyHostToDevice));
-    IFCHK(hipMemcpy(d_nnghs, h_nnghs.data(), NI * 4, hipMemcpyHostToDevice));
-    IFCHK(hipMemcpy(d_maxdist, h_maxdist.data(), NI * 8, hipMemcpyHostToDevice));
-    IFCHK(hipMemset(d_n, 0, NI * 4));
-    IFCHK(hipMemset(d_lkeep, 0, NI * IF_CAP));
+    QAALLOC(bufs, d_lon, double, NS); QAALLOC(bufs, d_lat, double, NS); QAALLOC(bufs, d_elig, uint8_t, NS);
+    QAALLOC(bufs, d_obs, float, NS * ND);
+    QAALLOC(bufs, d_tidx, int32_t, NT); QAALLOC(bufs, d_excl, int32_t, NT); QAALLOC(bufs, d_actt, int32_t, NT);
+    QAALLOC(bufs, d_acti, int32_t, NI);
+    QAALLOC(bufs, d_perm, int32_t, perm.size()); QAALLOC(bufs, d_goff, int32_t, G + 1);
+    QAALLOC(bufs, d_thrall, int32_t, G); QAALLOC(bufs, d_thrpor, int32_t, NI);
+    QAALLOC(bufs, d_curmax, double, NT); QAALLOC(bufs, d_ringn, int32_t, NT);
+    QAALLOC(bufs, d_ridx, int32_t, NT * IF_CAP); QAALLOC(bufs, d_rdist, double, NT * IF_CAP);
+    QAALLOC(bufs, d_pnlap, int32_t, NT * IF_CAP * G); QAALLOC(bufs, d_pnst, int32_t, NT * IF_CAP * G);
+    QAALLOC(bufs, d_pioa, double, NT * IF_CAP * G);
+    QAALLOC(bufs, d_done, uint8_t, NI); QAALLOC(bufs, d_status, int32_t, NI); QAALLOC(bufs, d_nnghs, int32_t, NI);
+    QAALLOC(bufs, d_maxdist, double, NI); QAALLOC(bufs, d_n, int32_t, NI);
+    QAALLOC(bufs, d_lidx, int32_t, NI * IF_CAP); QAALLOC(bufs, d_lioa, double, NI * IF_CAP); QAALLOC(bufs, d_ldist, double, NI * IF_CAP);
+    QAALLOC(bufs, d_lnlap, int32_t, NI * IF_CAP); QAALLOC(bufs, d_lnst, int32_t, NI * IF_CAP); QAALLOC(bufs, d_lkeep, uint8_t, NI * IF_CAP);
+    QAALLOC(bufs, d_daycnt, uint8_t, NT * ND);
+    QACHK(hipMemcpy(d_lon, lon, NS * 8, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_lat, lat, NS * 8, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_elig, eligible, NS, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_obs, obs, NS * ND * 4, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_tidx, target_idx, NT * 4, hipMemcpyHostToDevice));
+    if (exclude_idx) QACHK(hipMemcpy(d_excl, exclude_idx, NT * 4, hipMemcpyHostToDevice));
+    else QACHK(hipMemset(d_excl, 0xff, NT * 4));                 // -1: no station has that row
+    if (!perm.empty()) QACHK(hipMemcpy(d_perm, perm.data(), perm.size() * 4, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_goff, goff.data(), (G + 1) * 4, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_thrall, nthres_all, G * 4, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_thrpor, nthres_target_por, NI * 4, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_done, done.data(), NI, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_status, h_status.data(), NI * 4, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_nnghs, h_nnghs.data(), NI * 4, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_maxdist, h_maxdist.data(), NI * 8, hipMemcpyHostToDevice));
+    QACHK(hipMemset(d_n, 0, NI * 4));
+    QACHK(hipMemset(d_lkeep, 0, NI * IF_CAP));
 
-    IfTimer tm;
+    QaTimer tm;
     float ms[TWXIF_NTIMES] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     if (kernel_ms) {
-        IFCHK(tm.init());
-        IFCHK(hipDeviceSynchronize());
+        QACHK(tm.init());
+        QACHK(hipDeviceSynchronize());
         ms[4] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_up).count();
     }
     std::vector<int32_t> h_ringn((size_t)ntarget, 0);
@@ -571,23 +504,23 @@ static int if_matrix(const char *fn, int device, int64_t nstn, int64_t ndays, co
         if (act_t.empty()) break;
         if (rounds > nstn + 1) {                                 // every round takes a station of each active target, or ends it
             snprintf(msg, sizeof msg, "%s: internal error: %d rounds for %lld stations", fn, rounds, (long long)nstn);
-            return if_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         const int first = rounds == 0 ? 1 : 0;
-        IFCHK(hipMemcpy(d_actt, act_t.data(), act_t.size() * 4, hipMemcpyHostToDevice));
-        IFCHK(hipMemcpy(d_acti, act_i.data(), act_i.size() * 4, hipMemcpyHostToDevice));
-        if (kernel_ms) IFCHK(tm.start());
+        QACHK(hipMemcpy(d_actt, act_t.data(), act_t.size() * 4, hipMemcpyHostToDevice));
+        QACHK(hipMemcpy(d_acti, act_i.data(), act_i.size() * 4, hipMemcpyHostToDevice));
+        if (kernel_ms) QACHK(tm.start());
         hipLaunchKernelGGL(k_if_ring, dim3((unsigned)act_t.size()), dim3(64), 0, nullptr, nstn, (const double *)d_lon,
                            (const double *)d_lat, (const uint8_t *)d_elig, (const int32_t *)d_tidx,
                            (const int32_t *)d_excl, (const int32_t *)d_actt, first, d_curmax, d_ringn, d_ridx, d_rdist);
-        IFCHK(hipGetLastError());
-        if (kernel_ms) IFCHK(tm.stop(&ms[0]));
+        QACHK(hipGetLastError());
+        if (kernel_ms) QACHK(tm.stop_add(&ms[0]));
         // the pair grid is sized by the round's largest ring (about 26 stations on a real pool, not the cap of 256)
-        IFCHK(hipMemcpy(h_ringn.data(), d_ringn, NT * 4, hipMemcpyDeviceToHost));
+        QACHK(hipMemcpy(h_ringn.data(), d_ringn, NT * 4, hipMemcpyDeviceToHost));
         int ring_max = 0;
         for (int32_t t : act_t) ring_max = h_ringn[(size_t)t] > ring_max ? h_ringn[(size_t)t] : ring_max;
         const unsigned pair_rows = (unsigned)((ring_max + 3) / 4);
-        if (kernel_ms) IFCHK(tm.start());
+        if (kernel_ms) QACHK(tm.start());
         if (pair_rows > 0) {
             hipLaunchKernelGGL(k_if_pair, dim3((unsigned)act_t.size(), pair_rows), dim3(256), 0, nullptr, ndays,
                                (const float *)d_obs, (const int32_t *)d_tidx, (const int32_t *)d_actt, (int)ngroups,
@@ -595,8 +528,8 @@ static int if_matrix(const char *fn, int device, int64_t nstn, int64_t ndays, co
                                (const uint8_t *)d_done, (const int32_t *)d_ringn, (const int32_t *)d_ridx, d_pnlap, d_pnst,
                                d_pioa);
         }
-        IFCHK(hipGetLastError());
-        if (kernel_ms) { IFCHK(tm.stop(&ms[1])); IFCHK(tm.start()); }
+        QACHK(hipGetLastError());
+        if (kernel_ms) { QACHK(tm.stop_add(&ms[1])); QACHK(tm.start()); }
         hipLaunchKernelGGL(k_if_item, dim3((unsigned)act_i.size()), dim3(256), 0, nullptr, ndays, (const float *)d_obs,
                            (int)ngroups, (const int32_t *)d_acti, (const int32_t *)d_perm, (const int32_t *)d_goff,
                            (const int32_t *)d_thrall, (const int32_t *)d_thrpor, first, (int)min_daily_nnghs,
@@ -604,16 +537,16 @@ static int if_matrix(const char *fn, int device, int64_t nstn, int64_t ndays, co
                            (const double *)d_rdist, (const int32_t *)d_pnlap, (const int32_t *)d_pnst,
                            (const double *)d_pioa, d_done, d_status, d_nnghs, d_maxdist, d_n, d_lidx, d_lioa, d_ldist,
                            d_lnlap, d_lnst, d_lkeep, d_daycnt);
-        IFCHK(hipGetLastError());
-        if (kernel_ms) IFCHK(tm.stop(&ms[2]));
-        IFCHK(hipMemcpy(done.data(), d_done, NI, hipMemcpyDeviceToHost));
+        QACHK(hipGetLastError());
+        if (kernel_ms) QACHK(tm.stop_add(&ms[2]));
+        QACHK(hipMemcpy(done.data(), d_done, NI, hipMemcpyDeviceToHost));
     }
-    IFCHK(hipMemcpy(h_n.data(), d_n, NI * 4, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(h_n.data(), d_n, NI * 4, hipMemcpyDeviceToHost));
     csr_off[0] = 0;
     for (int64_t i = 0; i < ni; ++i) {
         if (h_n[(size_t)i] < 0 || h_n[(size_t)i] > IF_CAP) {
             snprintf(msg, sizeof msg, "%s: internal error: list length %d of item %lld", fn, (int)h_n[(size_t)i], (long long)i);
-            return if_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         csr_off[i + 1] = csr_off[i] + h_n[(size_t)i];
     }
@@ -621,7 +554,7 @@ static int if_matrix(const char *fn, int device, int64_t nstn, int64_t ndays, co
     if (total > csr_cap) {
         snprintf(msg, sizeof msg, "%s: the ranked lists hold %lld entries, csr_cap is %lld (ntarget * ngroups * "
                  "TWXQA_MAX_RADIUS_NGH always suffices)", fn, (long long)total, (long long)csr_cap);
-        return if_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     const auto t_down = std::chrono::steady_clock::now();
     float compact_ms = 0.0f;
@@ -631,27 +564,27 @@ static int if_matrix(const char *fn, int device, int64_t nstn, int64_t ndays, co
         double *o_ioa, *o_dist;
         uint8_t *o_keep;
         const size_t T = (size_t)total;
-        IFALLOC(d_off, int64_t, NI + 1);
-        IFALLOC(o_idx, int32_t, T); IFALLOC(o_nlap, int32_t, T); IFALLOC(o_nst, int32_t, T);
-        IFALLOC(o_ioa, double, T); IFALLOC(o_dist, double, T); IFALLOC(o_keep, uint8_t, T);
-        IFCHK(hipMemcpy(d_off, csr_off, (NI + 1) * 8, hipMemcpyHostToDevice));
-        if (kernel_ms) IFCHK(tm.start());
+        QAALLOC(bufs, d_off, int64_t, NI + 1);
+        QAALLOC(bufs, o_idx, int32_t, T); QAALLOC(bufs, o_nlap, int32_t, T); QAALLOC(bufs, o_nst, int32_t, T);
+        QAALLOC(bufs, o_ioa, double, T); QAALLOC(bufs, o_dist, double, T); QAALLOC(bufs, o_keep, uint8_t, T);
+        QACHK(hipMemcpy(d_off, csr_off, (NI + 1) * 8, hipMemcpyHostToDevice));
+        if (kernel_ms) QACHK(tm.start());
         hipLaunchKernelGGL(k_if_compact, dim3((unsigned)ni), dim3(256), 0, nullptr, (const int32_t *)d_n,
                            (const int64_t *)d_off, (const int32_t *)d_lidx, (const double *)d_lioa,
                            (const double *)d_ldist, (const int32_t *)d_lnlap, (const int32_t *)d_lnst,
                            (const uint8_t *)d_lkeep, o_idx, o_ioa, o_dist, o_nlap, o_nst, o_keep);
-        IFCHK(hipGetLastError());
-        if (kernel_ms) { IFCHK(tm.stop(&ms[3])); compact_ms = ms[3]; }
-        IFCHK(hipMemcpy(ngh_idx, o_idx, T * 4, hipMemcpyDeviceToHost));
-        IFCHK(hipMemcpy(ngh_ioa, o_ioa, T * 8, hipMemcpyDeviceToHost));
-        IFCHK(hipMemcpy(ngh_dist, o_dist, T * 8, hipMemcpyDeviceToHost));
-        IFCHK(hipMemcpy(ngh_nlap, o_nlap, T * 4, hipMemcpyDeviceToHost));
-        IFCHK(hipMemcpy(ngh_nlap_stn, o_nst, T * 4, hipMemcpyDeviceToHost));
-        IFCHK(hipMemcpy(keep, o_keep, T, hipMemcpyDeviceToHost));
+        QACHK(hipGetLastError());
+        if (kernel_ms) { QACHK(tm.stop_add(&ms[3])); compact_ms = ms[3]; }
+        QACHK(hipMemcpy(ngh_idx, o_idx, T * 4, hipMemcpyDeviceToHost));
+        QACHK(hipMemcpy(ngh_ioa, o_ioa, T * 8, hipMemcpyDeviceToHost));
+        QACHK(hipMemcpy(ngh_dist, o_dist, T * 8, hipMemcpyDeviceToHost));
+        QACHK(hipMemcpy(ngh_nlap, o_nlap, T * 4, hipMemcpyDeviceToHost));
+        QACHK(hipMemcpy(ngh_nlap_stn, o_nst, T * 4, hipMemcpyDeviceToHost));
+        QACHK(hipMemcpy(keep, o_keep, T, hipMemcpyDeviceToHost));
     }
-    IFCHK(hipMemcpy(status, d_status, NI * 4, hipMemcpyDeviceToHost));
-    IFCHK(hipMemcpy(nnghs, d_nnghs, NI * 4, hipMemcpyDeviceToHost));
-    IFCHK(hipMemcpy(max_dist, d_maxdist, NI * 8, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(status, d_status, NI * 4, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(nnghs, d_nnghs, NI * 4, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(max_dist, d_maxdist, NI * 8, hipMemcpyDeviceToHost));
     if (nrounds) *nrounds = rounds;
     ms[5] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_down).count() - compact_ms;
     if (kernel_ms) memcpy(kernel_ms, ms, sizeof ms);

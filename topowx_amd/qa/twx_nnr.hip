@@ -1,8 +1,8 @@
 // twx_nnr.hip -- libtwxqa.so: the principal components of the reanalysis columns of the infill family (pca_svd of
 // twx/utils/pca.py:26-76 as _InfillMatrix.infill calls it, twx/infill/infill_normals.py:347-356, and its step16
 // counterpart), as include/twx_qa.h states it, for every (column set, day group) item of one call (twxnr_components).
-// Its own translation unit: the buffer list and the event timer it shares with the other units are restated, nothing
-// there is edited.
+// Its own translation unit; the wave sum, the buffer list and the event timer it shares with the other units are
+// twx_qa_common.h's.
 //
 // The route is the eigen-decomposition of the P x P Gram matrix of the standardised columns, not an SVD of the N x P
 // matrix: N x P float64 (2200 x 32 in the reference's shape) does not fit in LDS, P x P does.  The price is accuracy in
@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "twx_qa.h"
+#include "twx_qa_common.h"
 
 #define NR_NW 4                              // wavefronts of a workgroup of k_nr_gram / k_nr_scores
 #define NR_THREADS (64 * NR_NW)
@@ -52,13 +53,6 @@
 namespace {
 
 __device__ __forceinline__ bool nr_finite(double v) { return fabs(v) <= NR_DBL_MAX; }
-
-__device__ __forceinline__ double nr_wave_sum(double v)
-{
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) v = v + __shfl_xor(v, s, 64);
-    return v;
-}
 
 struct NrTab {                               // the items of a call: item = set * ngroups + group
     const float *cols;                       // [ncol][ndays]
@@ -147,15 +141,15 @@ __global__ __launch_bounds__(NR_THREADS) void k_nr_gram(NrTab t, int64_t ms_tota
             if (!nr_finite(v)) nbad = nbad + 1.0;
             sum = sum + v;
         }
-        sum = nr_wave_sum(sum);
-        nbad = nr_wave_sum(nbad);
+        sum = qa_wave_sum(sum);
+        nbad = qa_wave_sum(nbad);
         const double mean = sum / (double)n;
         double ss = 0.0;
         for (int r = lane; r < n; r += 64) {
             const double d = (double)x[t.grp_day[r0 + r]] - mean;
             ss = ss + d * d;
         }
-        ss = nr_wave_sum(ss);
+        ss = qa_wave_sum(ss);
         const double sd = sqrt(ss / (double)(n - 1));
         if (lane == 0) {
             s_mean[j] = mean;
@@ -219,7 +213,7 @@ __global__ __launch_bounds__(64) void k_nr_eig(NrTab t, int32_t pmax, const doub
         double off2 = 0.0;
         for (int x = lane; x < PP2; x += 64)
             if (x / P != x % P) off2 = off2 + A[x] * A[x];
-        off2 = nr_wave_sum(off2);                                // the same in every lane
+        off2 = qa_wave_sum(off2);                                // the same in every lane
         if (off2 <= tol2) { conv = true; break; }
         if (nsweep == TWXNR_MAX_SWEEPS) break;
         ++nsweep;
@@ -358,64 +352,10 @@ __global__ __launch_bounds__(NR_THREADS) void k_nr_scores(NrTab t, int64_t ms_to
     }
 }
 
-namespace {
-
-int nr_fail(char *errbuf, int errlen, const char *what, hipError_t e = hipSuccess)
-{
-    if (errbuf && errlen > 0) {
-        if (e != hipSuccess) snprintf(errbuf, (size_t)errlen, "%s: %s", what, hipGetErrorString(e));
-        else snprintf(errbuf, (size_t)errlen, "%s", what);
-    }
-    return -1;
-}
-
-struct NrBufs {                                                  // every device allocation of a call, freed together
-    std::vector<void *> p;
-    ~NrBufs() { for (void *x : p) if (x) (void)hipFree(x); }
-    hipError_t get(void **out, size_t bytes)
-    {
-        hipError_t e = hipMalloc(out, bytes ? bytes : 1);
-        if (e == hipSuccess) p.push_back(*out);
-        return e;
-    }
-};
-
-struct NrTimer {                                                 // HIP-event time of a run of launches on the null stream
-    hipEvent_t a = nullptr, b = nullptr;
-    ~NrTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    hipError_t init() { hipError_t e = hipEventCreate(&a); return e != hipSuccess ? e : hipEventCreate(&b); }
-    hipError_t start() { return hipEventRecord(a, nullptr); }
-    hipError_t stop(float *acc)
-    {
-        float ms = 0.0f;
-        hipError_t e = hipEventRecord(b, nullptr);
-        if (e == hipSuccess) e = hipEventSynchronize(b);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
-        *acc += ms;
-        return e;
-    }
-};
-
-}  // namespace
-
-#define NRCHK(call)                                                                     \
-    do {                                                                                \
-        hipError_t e_ = (call);                                                         \
-        if (e_ != hipSuccess) return nr_fail(errbuf, errlen, #call, e_);                \
-    } while (0)
-#define NRALLOC(bufs, ptr, type, count) NRCHK((bufs).get((void **)&(ptr), (size_t)(count) * sizeof(type)))
-#define NRUP(dst, src, type, count)                                                                         \
-    do {                                                                                                    \
-        if ((count) > 0) NRCHK(hipMemcpy((dst), (src), (size_t)(count) * sizeof(type), hipMemcpyHostToDevice)); \
-    } while (0)
-#define NRDOWN(dst, src, type, count)                                                                       \
-    do {                                                                                                    \
-        if ((count) > 0) NRCHK(hipMemcpy((dst), (src), (size_t)(count) * sizeof(type), hipMemcpyDeviceToHost)); \
-    } while (0)
 #define NRBAD(...)                                                                      \
     do {                                                                                \
         snprintf(msg, sizeof msg, __VA_ARGS__);                                         \
-        return nr_fail(errbuf, errlen, msg);                                            \
+        return qa_fail(errbuf, errlen, msg);                                            \
     } while (0)
 
 extern "C" int twxnr_components(int device, int64_t ndays, int64_t ncol, const float *cols, int64_t nset,
@@ -472,54 +412,54 @@ extern "C" int twxnr_components(int device, int64_t ndays, int64_t ncol, const f
     }
     const size_t NI = (size_t)nitem, MS = (size_t)(ntot * ngroups), SQ = (size_t)(h_sq_off[(size_t)nset] * ngroups);
 
-    NRCHK(hipSetDevice(device));
+    QACHK(hipSetDevice(device));
     float ms[TWXNR_NTIMES] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     const auto t_up = std::chrono::steady_clock::now();
-    NrBufs bufs;
+    QaPool bufs;
     NrTab tab;
     float *d_cols;
     int32_t *d_set_off, *d_set_col, *d_grp_off, *d_grp_day, *d_status, *d_bad, *d_ncomp, *d_sweeps, *d_keep;
     int64_t *d_sq_off, *d_score_off;
     double *d_max_var, *d_ms, *d_gram, *d_ve, *d_ev, *d_load, *d_scores = nullptr;
-    NRALLOC(bufs, d_cols, float, (size_t)ncol * (size_t)ndays);
-    NRALLOC(bufs, d_set_off, int32_t, (size_t)nset + 1); NRALLOC(bufs, d_set_col, int32_t, (size_t)ntot);
-    NRALLOC(bufs, d_sq_off, int64_t, (size_t)nset + 1);
-    NRALLOC(bufs, d_grp_off, int32_t, (size_t)ngroups + 1); NRALLOC(bufs, d_grp_day, int32_t, grp_day.size());
-    NRALLOC(bufs, d_max_var, double, (size_t)nthr);
-    NRALLOC(bufs, d_status, int32_t, NI); NRALLOC(bufs, d_bad, int32_t, NI); NRALLOC(bufs, d_sweeps, int32_t, NI);
-    NRALLOC(bufs, d_keep, int32_t, NI); NRALLOC(bufs, d_ncomp, int32_t, NI * (size_t)nthr);
-    NRALLOC(bufs, d_score_off, int64_t, NI + 1);
-    NRALLOC(bufs, d_ms, double, 2 * MS); NRALLOC(bufs, d_ve, double, MS); NRALLOC(bufs, d_ev, double, MS);
-    NRALLOC(bufs, d_gram, double, SQ); NRALLOC(bufs, d_load, double, SQ);
-    NRUP(d_cols, cols, float, (size_t)ncol * (size_t)ndays);
-    NRUP(d_set_off, h_set_off.data(), int32_t, (size_t)nset + 1); NRUP(d_set_col, set_col, int32_t, (size_t)ntot);
-    NRUP(d_sq_off, h_sq_off.data(), int64_t, (size_t)nset + 1);
-    NRUP(d_grp_off, grp_off.data(), int32_t, (size_t)ngroups + 1); NRUP(d_grp_day, grp_day.data(), int32_t, grp_day.size());
-    NRUP(d_max_var, max_var, double, (size_t)nthr);
+    QAALLOC(bufs, d_cols, float, (size_t)ncol * (size_t)ndays);
+    QAALLOC(bufs, d_set_off, int32_t, (size_t)nset + 1); QAALLOC(bufs, d_set_col, int32_t, (size_t)ntot);
+    QAALLOC(bufs, d_sq_off, int64_t, (size_t)nset + 1);
+    QAALLOC(bufs, d_grp_off, int32_t, (size_t)ngroups + 1); QAALLOC(bufs, d_grp_day, int32_t, grp_day.size());
+    QAALLOC(bufs, d_max_var, double, (size_t)nthr);
+    QAALLOC(bufs, d_status, int32_t, NI); QAALLOC(bufs, d_bad, int32_t, NI); QAALLOC(bufs, d_sweeps, int32_t, NI);
+    QAALLOC(bufs, d_keep, int32_t, NI); QAALLOC(bufs, d_ncomp, int32_t, NI * (size_t)nthr);
+    QAALLOC(bufs, d_score_off, int64_t, NI + 1);
+    QAALLOC(bufs, d_ms, double, 2 * MS); QAALLOC(bufs, d_ve, double, MS); QAALLOC(bufs, d_ev, double, MS);
+    QAALLOC(bufs, d_gram, double, SQ); QAALLOC(bufs, d_load, double, SQ);
+    QAUP_NZ(d_cols, cols, float, (size_t)ncol * (size_t)ndays);
+    QAUP_NZ(d_set_off, h_set_off.data(), int32_t, (size_t)nset + 1); QAUP_NZ(d_set_col, set_col, int32_t, (size_t)ntot);
+    QAUP_NZ(d_sq_off, h_sq_off.data(), int64_t, (size_t)nset + 1);
+    QAUP_NZ(d_grp_off, grp_off.data(), int32_t, (size_t)ngroups + 1); QAUP_NZ(d_grp_day, grp_day.data(), int32_t, grp_day.size());
+    QAUP_NZ(d_max_var, max_var, double, (size_t)nthr);
     // an item that is not decomposed leaves its slots of the packed outputs NaN
-    NRCHK(hipMemset(d_ms, 0xff, 2 * MS * 8)); NRCHK(hipMemset(d_ve, 0xff, MS * 8)); NRCHK(hipMemset(d_ev, 0xff, MS * 8));
-    NRCHK(hipMemset(d_load, 0xff, SQ * 8));
+    QACHK(hipMemset(d_ms, 0xff, 2 * MS * 8)); QACHK(hipMemset(d_ve, 0xff, MS * 8)); QACHK(hipMemset(d_ev, 0xff, MS * 8));
+    QACHK(hipMemset(d_load, 0xff, SQ * 8));
     tab.cols = d_cols; tab.set_off = d_set_off; tab.set_col = d_set_col; tab.sq_off = d_sq_off; tab.grp_off = d_grp_off;
     tab.grp_day = d_grp_day; tab.ndays = ndays; tab.ngroups = ngroups;
-    NrTimer tm;
+    QaTimer tm;
     if (kernel_ms) {
-        NRCHK(tm.init());
-        NRCHK(hipDeviceSynchronize());
+        QACHK(tm.init());
+        QACHK(hipDeviceSynchronize());
         ms[3] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_up).count();
-        NRCHK(tm.start());
+        QACHK(tm.start());
     }
     hipLaunchKernelGGL(k_nr_gram, dim3((unsigned)NI), dim3(NR_THREADS), 0, nullptr, tab, (int64_t)MS, d_ms, d_gram, d_status,
                        d_bad);
-    NRCHK(hipGetLastError());
-    if (kernel_ms) { NRCHK(tm.stop(&ms[0])); NRCHK(tm.start()); }
+    QACHK(hipGetLastError());
+    if (kernel_ms) { QACHK(tm.stop_add(&ms[0])); QACHK(tm.start()); }
     hipLaunchKernelGGL(k_nr_eig, dim3((unsigned)NI), dim3(64), (size_t)2 * pmax * pmax * sizeof(double), nullptr, tab,
                        (int32_t)pmax, (const double *)d_gram, nthr, (const double *)d_max_var, d_status, d_ncomp, d_sweeps,
                        d_ve, d_ev, d_load);
-    NRCHK(hipGetLastError());
-    if (kernel_ms) NRCHK(tm.stop(&ms[1]));
+    QACHK(hipGetLastError());
+    if (kernel_ms) QACHK(tm.stop_add(&ms[1]));
     // the host lays the scores out: per item the components of its largest cut
-    NRDOWN(status, d_status, int32_t, NI);
-    NRDOWN(ncomp, d_ncomp, int32_t, NI * (size_t)nthr);
+    QADOWN_NZ(status, d_status, int32_t, NI);
+    QADOWN_NZ(ncomp, d_ncomp, int32_t, NI * (size_t)nthr);
     std::vector<int32_t> keep(NI, 0);
     score_off[0] = 0;
     for (size_t i = 0; i < NI; ++i) {
@@ -531,27 +471,27 @@ extern "C" int twxnr_components(int device, int64_t ndays, int64_t ncol, const f
     if (score_off[NI] > score_cap)
         NRBAD("%s: the scores need %lld entries, score_cap is %lld", fn, (long long)score_off[NI], (long long)score_cap);
     if (score_off[NI] > 0) {
-        NRALLOC(bufs, d_scores, double, (size_t)score_off[NI]);
-        NRUP(d_keep, keep.data(), int32_t, NI);
-        NRUP(d_score_off, score_off, int64_t, NI + 1);
-        if (kernel_ms) NRCHK(tm.start());
+        QAALLOC(bufs, d_scores, double, (size_t)score_off[NI]);
+        QAUP_NZ(d_keep, keep.data(), int32_t, NI);
+        QAUP_NZ(d_score_off, score_off, int64_t, NI + 1);
+        if (kernel_ms) QACHK(tm.start());
         hipLaunchKernelGGL(k_nr_scores, dim3((unsigned)NI), dim3(NR_THREADS), 0, nullptr, tab, (int64_t)MS,
                            (const double *)d_ms, (const double *)d_load, (const int32_t *)d_keep,
                            (const int64_t *)d_score_off, d_scores);
-        NRCHK(hipGetLastError());
-        if (kernel_ms) NRCHK(tm.stop(&ms[2]));
+        QACHK(hipGetLastError());
+        if (kernel_ms) QACHK(tm.stop_add(&ms[2]));
     }
-    NRCHK(hipDeviceSynchronize());
+    QACHK(hipDeviceSynchronize());
     const auto t_down = std::chrono::steady_clock::now();
-    NRDOWN(status, d_status, int32_t, NI);
-    NRDOWN(bad_col, d_bad, int32_t, NI);
-    NRDOWN(sweeps, d_sweeps, int32_t, NI);
-    NRDOWN(mean, d_ms, double, MS);
-    NRDOWN(sd, d_ms + MS, double, MS);
-    NRDOWN(var_explain, d_ve, double, MS);
-    NRDOWN(eigval, d_ev, double, MS);
-    NRDOWN(loadings, d_load, double, SQ);
-    NRDOWN(scores, d_scores, double, (size_t)score_off[NI]);
+    QADOWN_NZ(status, d_status, int32_t, NI);
+    QADOWN_NZ(bad_col, d_bad, int32_t, NI);
+    QADOWN_NZ(sweeps, d_sweeps, int32_t, NI);
+    QADOWN_NZ(mean, d_ms, double, MS);
+    QADOWN_NZ(sd, d_ms + MS, double, MS);
+    QADOWN_NZ(var_explain, d_ve, double, MS);
+    QADOWN_NZ(eigval, d_ev, double, MS);
+    QADOWN_NZ(loadings, d_load, double, SQ);
+    QADOWN_NZ(scores, d_scores, double, (size_t)score_off[NI]);
     ms[4] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_down).count();
     if (kernel_ms) memcpy(kernel_ms, ms, sizeof ms);
     return 0;

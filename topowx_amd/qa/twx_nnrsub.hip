@@ -22,6 +22,7 @@
 
 #include "twx_nnrsub_map.h"
 #include "twx_qa.h"
+#include "twx_qa_common.h"
 
 namespace {
 
@@ -126,34 +127,6 @@ __global__ __launch_bounds__(256) void k_nsub_plain(const T *__restrict__ raw, N
 // ---------------------------------------------------------------------------------
 namespace {
 
-int ns_fail(char *errbuf, int errlen, const char *what, hipError_t e = hipSuccess)
-{
-    if (errbuf && errlen > 0) {
-        if (e != hipSuccess) snprintf(errbuf, (size_t)errlen, "%s: %s", what, hipGetErrorString(e));
-        else snprintf(errbuf, (size_t)errlen, "%s", what);
-    }
-    return -1;
-}
-
-struct NsBuf {
-    void *p = nullptr;
-    ~NsBuf() { if (p) (void)hipFree(p); }
-};
-
-struct NsTimer {                                                 // HIP-event time of work on the null stream
-    hipEvent_t a = nullptr, b = nullptr;
-    ~NsTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    hipError_t init() { hipError_t e = hipEventCreate(&a); return e != hipSuccess ? e : hipEventCreate(&b); }
-    hipError_t start() { return hipEventRecord(a, nullptr); }
-    hipError_t stop(float *ms)
-    {
-        hipError_t e = hipEventRecord(b, nullptr);
-        if (e == hipSuccess) e = hipEventSynchronize(b);
-        if (e == hipSuccess) e = hipEventElapsedTime(ms, a, b);
-        return e;
-    }
-};
-
 bool ns_indices_ok(const int32_t *idx, int64_t n, int64_t bound)
 {
     for (int64_t i = 0; i < n; ++i)
@@ -183,12 +156,6 @@ hipError_t ns_launch(int layout, const void *raw, const NsArgs &a, const void *m
 
 }  // namespace
 
-#define NSCHK(call)                                                                     \
-    do {                                                                                \
-        hipError_t e_ = (call);                                                         \
-        if (e_ != hipSuccess) return ns_fail(errbuf, errlen, #call, e_);                \
-    } while (0)
-
 extern "C" int twxns_subset(int device, int dtype, const void *raw, int64_t nrec, int64_t nl, int64_t ny, int64_t nx, float scale,
                             float offset, const void *marks, const int32_t *has_mark, const int32_t *rec_slot,
                             const int32_t *rec_day, int64_t ndays, int64_t nlat_out, const int32_t *lat_idx, int64_t nlon_out,
@@ -198,29 +165,29 @@ extern "C" int twxns_subset(int device, int dtype, const void *raw, int64_t nrec
     if (errbuf && errlen > 0) errbuf[0] = 0;
     char msg[320];
     if (dtype != TWXNS_I16 && dtype != TWXNS_F32)
-        return ns_fail(errbuf, errlen, "twxns_subset: dtype must be TWXNS_I16 or TWXNS_F32");
+        return qa_fail(errbuf, errlen, "twxns_subset: dtype must be TWXNS_I16 or TWXNS_F32");
     if (layout != TWXNS_TILED && layout != TWXNS_PLAIN)
-        return ns_fail(errbuf, errlen, "twxns_subset: layout must be TWXNS_TILED or TWXNS_PLAIN");
+        return qa_fail(errbuf, errlen, "twxns_subset: layout must be TWXNS_TILED or TWXNS_PLAIN");
     if (!raw || !marks || !has_mark || !rec_slot || !rec_day || !lat_idx || !lon_idx || !prod || !out || !counts)
-        return ns_fail(errbuf, errlen, "twxns_subset: null buffer");
+        return qa_fail(errbuf, errlen, "twxns_subset: null buffer");
     if (nrec < 1 || nl < 1 || ny < 1 || nx < 1 || nrec > INT32_MAX || nl > INT32_MAX || ny > INT32_MAX || nx > INT32_MAX ||
         (double)nrec * (double)nl * (double)ny * (double)nx > (double)TWXNS_MAX_RAW) {
         snprintf(msg, sizeof msg, "twxns_subset: need a raw slab [nrec][nl][ny][nx] of 1 .. TWXNS_MAX_RAW = %lld values",
                  (long long)TWXNS_MAX_RAW);
-        return ns_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (ndays < 1 || ndays > TWXNS_MAX_DAYS || nlat_out < 1 || nlat_out > TWXNS_MAX_SIDE || nlon_out < 1 ||
         nlon_out > TWXNS_MAX_SIDE) {
         snprintf(msg, sizeof msg, "twxns_subset: need 1 <= ndays <= TWXNS_MAX_DAYS = %d and 1 <= nlat_out, nlon_out <= "
                                   "TWXNS_MAX_SIDE = %d", TWXNS_MAX_DAYS, TWXNS_MAX_SIDE);
-        return ns_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (nprod < 1 || nprod > TWXNS_MAX_PROD) {
         snprintf(msg, sizeof msg, "twxns_subset: need 1 <= nprod <= TWXNS_MAX_PROD = %d", TWXNS_MAX_PROD);
-        return ns_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
-    if (!ns_indices_ok(lat_idx, nlat_out, ny)) return ns_fail(errbuf, errlen, "twxns_subset: a lat_idx entry is out of range 0 .. ny - 1");
-    if (!ns_indices_ok(lon_idx, nlon_out, nx)) return ns_fail(errbuf, errlen, "twxns_subset: a lon_idx entry is out of range 0 .. nx - 1");
+    if (!ns_indices_ok(lat_idx, nlat_out, ny)) return qa_fail(errbuf, errlen, "twxns_subset: a lat_idx entry is out of range 0 .. ny - 1");
+    if (!ns_indices_ok(lon_idx, nlon_out, nx)) return qa_fail(errbuf, errlen, "twxns_subset: a lon_idx entry is out of range 0 .. nx - 1");
     NsShape s;
     s.nrec = nrec, s.nl = nl, s.ny = ny, s.nx = nx, s.ndays = ndays, s.nlat_out = nlat_out, s.nlon_out = nlon_out;
     std::vector<NsProd> prods((size_t)nprod);
@@ -231,11 +198,11 @@ extern "C" int twxns_subset(int device, int dtype, const void *raw, int64_t nrec
         memset(&q, 0, sizeof q);
         if (d[TWXNS_PD_SLOT] < 0 || d[TWXNS_PD_SLOT] > 2) {
             snprintf(msg, sizeof msg, "twxns_subset: product %lld: the slot must be 0, 1 or 2", (long long)p);
-            return ns_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         if (d[TWXNS_PD_CONV] != TWXNS_CONV_NONE && d[TWXNS_PD_CONV] != TWXNS_CONV_K_TO_C) {
             snprintf(msg, sizeof msg, "twxns_subset: product %lld: unknown conversion %d", (long long)p, (int)d[TWXNS_PD_CONV]);
-            return ns_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         q.conv = d[TWXNS_PD_CONV];
         int nidx = 0;
@@ -243,7 +210,7 @@ extern "C" int twxns_subset(int device, int dtype, const void *raw, int64_t nrec
             if (d[TWXNS_PD_NLEV] < 1 || d[TWXNS_PD_NLEV] > TWXNS_MAX_LEV) {
                 snprintf(msg, sizeof msg, "twxns_subset: product %lld: need 1 <= nlev_out <= TWXNS_MAX_LEV = %d, got %d",
                          (long long)p, TWXNS_MAX_LEV, (int)d[TWXNS_PD_NLEV]);
-                return ns_fail(errbuf, errlen, msg);
+                return qa_fail(errbuf, errlen, msg);
             }
             q.kind = NS_KIND_LEVELS, q.nlev = nidx = d[TWXNS_PD_NLEV];
         } else if (d[TWXNS_PD_KIND] == TWXNS_KIND_THICK) {
@@ -251,26 +218,26 @@ extern "C" int twxns_subset(int device, int dtype, const void *raw, int64_t nrec
             if (d[TWXNS_PD_LEV0] == d[TWXNS_PD_LEV0 + 1]) {
                 snprintf(msg, sizeof msg, "twxns_subset: product %lld: a thickness needs two different levels, got index %d twice",
                          (long long)p, (int)d[TWXNS_PD_LEV0]);
-                return ns_fail(errbuf, errlen, msg);
+                return qa_fail(errbuf, errlen, msg);
             }
         } else {
             snprintf(msg, sizeof msg, "twxns_subset: product %lld: the kind must be TWXNS_KIND_LEVELS or TWXNS_KIND_THICK", (long long)p);
-            return ns_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         for (int k = 0; k < nidx; ++k) {
             q.lev[k] = d[TWXNS_PD_LEV0 + k];
             if (q.lev[k] < 0 || q.lev[k] >= nl) {
                 snprintf(msg, sizeof msg, "twxns_subset: product %lld: level index %d is out of range 0 .. nl - 1 = %lld", (long long)p,
                          (int)q.lev[k], (long long)(nl - 1));
-                return ns_fail(errbuf, errlen, msg);
+                return qa_fail(errbuf, errlen, msg);
             }
         }
-        if (!out[p]) return ns_fail(errbuf, errlen, "twxns_subset: null output buffer");
+        if (!out[p]) return qa_fail(errbuf, errlen, "twxns_subset: null output buffer");
         const int64_t n = layout == TWXNS_TILED ? ns_tiled_size(s, q.nlev) : ns_plain_size(s, q.nlev);
         if (n > TWXNS_MAX_OUT) {
             snprintf(msg, sizeof msg, "twxns_subset: product %lld has %lld values, more than TWXNS_MAX_OUT = %lld", (long long)p,
                      (long long)n, (long long)TWXNS_MAX_OUT);
-            return ns_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         off[(size_t)p + 1] = off[(size_t)p] + (n + 3) / 4 * 4;
     }
@@ -280,14 +247,14 @@ extern "C" int twxns_subset(int device, int dtype, const void *raw, int64_t nrec
         if (rec_slot[r] < -1 || rec_slot[r] > 2 || rec_day[r] < -1 || rec_day[r] >= ndays) {
             snprintf(msg, sizeof msg, "twxns_subset: record %lld: slot %d, day %d (need -1 .. 2 and -1 .. ndays - 1)", (long long)r,
                      (int)rec_slot[r], (int)rec_day[r]);
-            return ns_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         if (rec_slot[r] < 0 || rec_day[r] < 0) continue;
         int32_t &e = day_rec[(size_t)rec_slot[r] * (size_t)ndays + (size_t)rec_day[r]];
         if (e >= 0) {
             snprintf(msg, sizeof msg, "twxns_subset: records %d and %lld both map to slot %d, day %d", (int)e, (long long)r,
                      (int)rec_slot[r], (int)rec_day[r]);
-            return ns_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         e = (int32_t)r;
         ++got[rec_slot[r]];
@@ -297,24 +264,24 @@ extern "C" int twxns_subset(int device, int dtype, const void *raw, int64_t nrec
     const size_t raw_bytes = (size_t)nrec * (size_t)nl * (size_t)ny * (size_t)nx * esize;
     float ms[TWXNS_NKERNELS];
     for (int i = 0; i < TWXNS_NKERNELS; ++i) ms[i] = 0.0f;
-    NSCHK(hipSetDevice(device));
-    NsBuf b_raw, b_rec, b_lat, b_lon, b_out, b_cnt;
-    NsTimer tm;
-    NSCHK(tm.init());
-    NSCHK(hipMalloc(&b_raw.p, raw_bytes));
-    NSCHK(hipMalloc(&b_rec.p, day_rec.size() * 4));
-    NSCHK(hipMalloc(&b_lat.p, (size_t)nlat_out * 4));
-    NSCHK(hipMalloc(&b_lon.p, (size_t)nlon_out * 4));
-    NSCHK(hipMalloc(&b_out.p, (size_t)off[(size_t)nprod] * 4));
-    NSCHK(hipMalloc(&b_cnt.p, (size_t)nprod * 8));
-    NSCHK(hipMemset(b_cnt.p, 0, (size_t)nprod * 8));
-    NSCHK(tm.start());
-    NSCHK(hipMemcpy(b_raw.p, raw, raw_bytes, hipMemcpyHostToDevice));
-    NSCHK(hipMemcpy(b_rec.p, day_rec.data(), day_rec.size() * 4, hipMemcpyHostToDevice));
-    NSCHK(hipMemcpy(b_lat.p, lat_idx, (size_t)nlat_out * 4, hipMemcpyHostToDevice));
-    NSCHK(hipMemcpy(b_lon.p, lon_idx, (size_t)nlon_out * 4, hipMemcpyHostToDevice));
-    NSCHK(tm.stop(&ms[0]));
-    NSCHK(tm.start());
+    QACHK(hipSetDevice(device));
+    QaBuf b_raw, b_rec, b_lat, b_lon, b_out, b_cnt;
+    QaTimer tm;
+    QACHK(tm.init());
+    QACHK(hipMalloc(&b_raw.p, raw_bytes));
+    QACHK(hipMalloc(&b_rec.p, day_rec.size() * 4));
+    QACHK(hipMalloc(&b_lat.p, (size_t)nlat_out * 4));
+    QACHK(hipMalloc(&b_lon.p, (size_t)nlon_out * 4));
+    QACHK(hipMalloc(&b_out.p, (size_t)off[(size_t)nprod] * 4));
+    QACHK(hipMalloc(&b_cnt.p, (size_t)nprod * 8));
+    QACHK(hipMemset(b_cnt.p, 0, (size_t)nprod * 8));
+    QACHK(tm.start());
+    QACHK(hipMemcpy(b_raw.p, raw, raw_bytes, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(b_rec.p, day_rec.data(), day_rec.size() * 4, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(b_lat.p, lat_idx, (size_t)nlat_out * 4, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(b_lon.p, lon_idx, (size_t)nlon_out * 4, hipMemcpyHostToDevice));
+    QACHK(tm.stop_set(&ms[0]));
+    QACHK(tm.start());
     for (int64_t p = 0; p < nprod; ++p) {
         NsArgs a;
         a.s = s, a.p = prods[(size_t)p], a.scale = scale, a.offset = offset;
@@ -323,18 +290,18 @@ extern "C" int twxns_subset(int device, int dtype, const void *raw, int64_t nrec
         float *d_out = static_cast<float *>(b_out.p) + off[(size_t)p];
         unsigned long long *d_cnt = static_cast<unsigned long long *>(b_cnt.p) + p;
         const int32_t *d_lat = static_cast<const int32_t *>(b_lat.p), *d_lon = static_cast<const int32_t *>(b_lon.p);
-        if (dtype == TWXNS_I16) NSCHK(ns_launch<int16_t>(layout, b_raw.p, a, marks, has_mark, d_rec, d_lat, d_lon, d_out, d_cnt));
-        else NSCHK(ns_launch<float>(layout, b_raw.p, a, marks, has_mark, d_rec, d_lat, d_lon, d_out, d_cnt));
+        if (dtype == TWXNS_I16) QACHK(ns_launch<int16_t>(layout, b_raw.p, a, marks, has_mark, d_rec, d_lat, d_lon, d_out, d_cnt));
+        else QACHK(ns_launch<float>(layout, b_raw.p, a, marks, has_mark, d_rec, d_lat, d_lon, d_out, d_cnt));
     }
-    NSCHK(tm.stop(&ms[1]));
+    QACHK(tm.stop_set(&ms[1]));
     std::vector<unsigned long long> nmarked((size_t)nprod, 0);
-    NSCHK(tm.start());
+    QACHK(tm.start());
     for (int64_t p = 0; p < nprod; ++p) {
         const int64_t n = layout == TWXNS_TILED ? ns_tiled_size(s, prods[(size_t)p].nlev) : ns_plain_size(s, prods[(size_t)p].nlev);
-        NSCHK(hipMemcpy(out[p], static_cast<const float *>(b_out.p) + off[(size_t)p], (size_t)n * 4, hipMemcpyDeviceToHost));
+        QACHK(hipMemcpy(out[p], static_cast<const float *>(b_out.p) + off[(size_t)p], (size_t)n * 4, hipMemcpyDeviceToHost));
     }
-    NSCHK(hipMemcpy(nmarked.data(), b_cnt.p, (size_t)nprod * 8, hipMemcpyDeviceToHost));
-    NSCHK(tm.stop(&ms[2]));
+    QACHK(hipMemcpy(nmarked.data(), b_cnt.p, (size_t)nprod * 8, hipMemcpyDeviceToHost));
+    QACHK(tm.stop_set(&ms[2]));
     for (int64_t p = 0; p < nprod; ++p) {
         const int64_t g = got[prod[p * TWXNS_PD_WORDS + TWXNS_PD_SLOT]];
         counts[p * TWXNS_C_N + TWXNS_C_DAYS] = g;

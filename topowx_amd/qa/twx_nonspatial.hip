@@ -42,6 +42,7 @@
 #include <vector>
 
 #include "twx_qa.h"
+#include "twx_qa_common.h"
 
 #define NS_NJOBS 380                         // 365 rows + the 15 leap rows whose window holds Feb 29
 #define NS_LEAP_FIRST 52                     // Feb 22 of the 366-row table
@@ -548,46 +549,6 @@ __global__ __launch_bounds__(256) void k_ns_mega(int64_t ndays, const uint8_t *_
 // ---------------------------------------------------------------------------------
 namespace {
 
-int ns_fail(char *errbuf, int errlen, const char *what, hipError_t e = hipSuccess)
-{
-    if (errbuf && errlen > 0) {
-        if (e != hipSuccess) snprintf(errbuf, (size_t)errlen, "%s: %s", what, hipGetErrorString(e));
-        else snprintf(errbuf, (size_t)errlen, "%s", what);
-    }
-    return -1;
-}
-
-struct NsBuf {
-    void *p = nullptr;
-    ~NsBuf() { if (p) (void)hipFree(p); }
-};
-
-struct NsTimer {                                                 // HIP-event time of a run of launches on the null stream
-    hipEvent_t a = nullptr, b = nullptr;
-    ~NsTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    hipError_t init() { hipError_t e = hipEventCreate(&a); return e != hipSuccess ? e : hipEventCreate(&b); }
-    hipError_t start() { return hipEventRecord(a, nullptr); }
-    hipError_t stop(float *ms)
-    {
-        hipError_t e = hipEventRecord(b, nullptr);
-        if (e == hipSuccess) e = hipEventSynchronize(b);
-        if (e == hipSuccess) e = hipEventElapsedTime(ms, a, b);
-        return e;
-    }
-};
-
-int64_t ns_days_from_civil(int64_t y, int mth, int day)           // days since 1970-01-01, proleptic Gregorian
-{
-    y -= mth <= 2;
-    const int64_t era = (y >= 0 ? y : y - 399) / 400;
-    const int64_t yoe = y - era * 400;
-    const int64_t doy = (153 * (mth + (mth > 2 ? -3 : 9)) + 2) / 5 + day - 1;
-    const int64_t doe = yoe * 365 + yoe / 4 - yoe / 100 + doy;
-    return era * 146097 + doe - 719468;
-}
-
-bool ns_leap(int y) { return (y % 4 == 0 && y % 100 != 0) || y % 400 == 0; }
-
 // The calendar tables of a day axis of consecutive days (checked).  -1 and a message on failure.
 struct NsCalendar {
     int nyears = 0, ndistinct = 0;
@@ -603,23 +564,23 @@ int ns_calendar(int64_t ndays, const int32_t *ymd, NsCalendar &c, char *errbuf, 
     char msg[256];
     const int32_t a = ymd[0];
     const int y0 = a / 10000, m0 = (a / 100) % 100, d0 = a % 100;
-    if (a < 10101 || m0 < 1 || m0 > 12 || d0 < 1 || d0 > 31) return ns_fail(errbuf, errlen, "twxqa_non_spatial: ymd[0] is not a date");
+    if (a < 10101 || m0 < 1 || m0 > 12 || d0 < 1 || d0 > 31) return qa_fail(errbuf, errlen, "twxqa_non_spatial: ymd[0] is not a date");
     // the years the axis touches, before anything is sized by them
-    const int64_t zlast = ns_days_from_civil(y0, m0, d0) + ndays - 1;
+    const int64_t zlast = qa_days_from_civil(y0, m0, d0) + ndays - 1;
     int64_t ylast = y0 + (ndays - 1) / 366;
-    while (ns_days_from_civil(ylast + 1, 1, 1) <= zlast) ++ylast;
+    while (qa_days_from_civil(ylast + 1, 1, 1) <= zlast) ++ylast;
     const int64_t nyears = ylast - y0 + 1;
     if (nyears * 31 > TWXQA_MAX_GAP_VALUES) {
         snprintf(msg, sizeof msg, "twxqa_non_spatial: the series touches %lld years; the gap check sorts at most "
                  "TWXQA_MAX_GAP_VALUES = %d values of a calendar month (31 per year, %d years)", (long long)nyears,
                  TWXQA_MAX_GAP_VALUES, TWXQA_MAX_GAP_VALUES / 31);
-        return ns_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (nyears * 15 > TWXQA_MAX_NORM_VALUES) {
         snprintf(msg, sizeof msg, "twxqa_non_spatial: the series touches %lld years; a row of the day-of-year normals "
                  "holds at most TWXQA_MAX_NORM_VALUES = %d values (15 per year, %d years)", (long long)nyears,
                  TWXQA_MAX_NORM_VALUES, TWXQA_MAX_NORM_VALUES / 15);
-        return ns_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     c.nyears = (int)nyears;
     c.normrow.resize((size_t)ndays);
@@ -632,43 +593,37 @@ int ns_calendar(int64_t ndays, const int32_t *ymd, NsCalendar &c, char *errbuf, 
     static const int mlen[12] = {31, 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31};
     int y = y0, mth = m0, day = d0, k = 0;
     bool seen[12] = {false, false, false, false, false, false, false, false, false, false, false, false};
-    int64_t jan1 = ns_days_from_civil(y0, 1, 1) - ns_days_from_civil(y0, m0, d0);
-    c.yr.assign({(int32_t)jan1, ns_leap(y0) ? 1 : 0});
+    int64_t jan1 = qa_days_from_civil(y0, 1, 1) - qa_days_from_civil(y0, m0, d0);
+    c.yr.assign({(int32_t)jan1, qa_leap(y0) ? 1 : 0});
     for (int64_t i = 0; i < ndays; ++i) {
         if (ymd[i] != y * 10000 + mth * 100 + day) {
             snprintf(msg, sizeof msg, "twxqa_non_spatial: ymd[%lld] = %d: the days are not consecutive calendar days",
                      (long long)i, (int)ymd[i]);
-            return ns_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
-        c.normrow[(size_t)i] = (int32_t)(i - jan1) + (ns_leap(y) ? 365 : 0);
+        c.normrow[(size_t)i] = (int32_t)(i - jan1) + (qa_leap(y) ? 365 : 0);
         c.month[(size_t)i] = (uint8_t)mth;
         c.yidx[(size_t)i] = (uint8_t)k;
         seen[mth - 1] = true;
         if (c.ylen[(size_t)k]++ == 0) c.ystart[(size_t)k] = (int32_t)i;
         const size_t seg = (size_t)k * 12 + (size_t)(mth - 1);
         if (c.mlen[seg]++ == 0) c.mstart[seg] = (int32_t)i;
-        if (++day > mlen[mth - 1] + ((mth == 2 && ns_leap(y)) ? 1 : 0)) {
+        if (++day > mlen[mth - 1] + ((mth == 2 && qa_leap(y)) ? 1 : 0)) {
             day = 1;
             if (++mth > 12) {
                 mth = 1;
                 ++y;
                 jan1 = i + 1;
-                if (i + 1 < ndays) { ++k; c.yr.push_back((int32_t)jan1); c.yr.push_back(ns_leap(y) ? 1 : 0); }
+                if (i + 1 < ndays) { ++k; c.yr.push_back((int32_t)jan1); c.yr.push_back(qa_leap(y) ? 1 : 0); }
             }
         }
     }
     for (int m = 0; m < 12; ++m) c.ndistinct += seen[m] ? 1 : 0;
-    if ((int)(c.yr.size() / 2) != c.nyears) return ns_fail(errbuf, errlen, "twxqa_non_spatial: calendar count mismatch");
+    if ((int)(c.yr.size() / 2) != c.nyears) return qa_fail(errbuf, errlen, "twxqa_non_spatial: calendar count mismatch");
     return 0;
 }
 
 }  // namespace
-
-#define NSCHK(call)                                                                     \
-    do {                                                                                \
-        hipError_t e_ = (call);                                                         \
-        if (e_ != hipSuccess) return ns_fail(errbuf, errlen, #call, e_);                \
-    } while (0)
 
 extern "C" int twxqa_non_spatial(int device, int64_t nstn, int64_t ndays, const float *tmin, const float *tmax,
                                  const int32_t *ymd, uint8_t *flag_tmin, uint8_t *flag_tmax, double *norms,
@@ -677,34 +632,34 @@ extern "C" int twxqa_non_spatial(int device, int64_t nstn, int64_t ndays, const 
     if (errbuf && errlen > 0) errbuf[0] = 0;
     if (nstn < 1 || ndays < 1 || ndays > INT32_MAX - 64 || nstn > INT32_MAX / (2 * NS_NJOBS) ||
         (nstn * ndays + 255) / 256 * 2 > INT32_MAX)
-        return ns_fail(errbuf, errlen, "twxqa_non_spatial: need nstn >= 1, ndays >= 1 and fewer than 2^31 work items in one call");
-    if (!tmin || !tmax || !ymd || !flag_tmin || !flag_tmax) return ns_fail(errbuf, errlen, "twxqa_non_spatial: null buffer");
+        return qa_fail(errbuf, errlen, "twxqa_non_spatial: need nstn >= 1, ndays >= 1 and fewer than 2^31 work items in one call");
+    if (!tmin || !tmax || !ymd || !flag_tmin || !flag_tmax) return qa_fail(errbuf, errlen, "twxqa_non_spatial: null buffer");
     NsCalendar cal;
     if (ns_calendar(ndays, ymd, cal, errbuf, errlen) != 0) return -1;
     const size_t ns = (size_t)nstn, nd = (size_t)ndays, ny = (size_t)cal.nyears;
-    NSCHK(hipSetDevice(device));
-    NsBuf b_obs, b_flag, b_cal, b_norm;
-    NsTimer tm;
-    NSCHK(tm.init());
-    NSCHK(hipMalloc(&b_obs.p, 2 * ns * nd * 4));                  // [2][nstn][ndays]
+    QACHK(hipSetDevice(device));
+    QaBuf b_obs, b_flag, b_cal, b_norm;
+    QaTimer tm;
+    QACHK(tm.init());
+    QACHK(hipMalloc(&b_obs.p, 2 * ns * nd * 4));                  // [2][nstn][ndays]
     float *d_tmin = static_cast<float *>(b_obs.p), *d_tmax = d_tmin + ns * nd;
-    NSCHK(hipMemcpy(d_tmin, tmin, ns * nd * 4, hipMemcpyHostToDevice));
-    NSCHK(hipMemcpy(d_tmax, tmax, ns * nd * 4, hipMemcpyHostToDevice));
-    NSCHK(hipMalloc(&b_flag.p, 2 * ns * nd));
+    QACHK(hipMemcpy(d_tmin, tmin, ns * nd * 4, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_tmax, tmax, ns * nd * 4, hipMemcpyHostToDevice));
+    QACHK(hipMalloc(&b_flag.p, 2 * ns * nd));
     uint8_t *d_f0 = static_cast<uint8_t *>(b_flag.p), *d_f1 = d_f0 + ns * nd;
     // calendar: int32 tables first (yr, normrow, ystart, ylen, mstart, mlen), then the bytes (month, yidx)
     const size_t o_yr = 0, o_row = o_yr + ny * 8, o_ys = o_row + nd * 4, o_yl = o_ys + ny * 4, o_ms = o_yl + ny * 4,
                  o_ml = o_ms + ny * 48, o_mth = o_ml + ny * 48, o_yi = o_mth + nd;
-    NSCHK(hipMalloc(&b_cal.p, o_yi + nd));
+    QACHK(hipMalloc(&b_cal.p, o_yi + nd));
     char *dc = static_cast<char *>(b_cal.p);
-    NSCHK(hipMemcpy(dc + o_yr, cal.yr.data(), ny * 8, hipMemcpyHostToDevice));
-    NSCHK(hipMemcpy(dc + o_row, cal.normrow.data(), nd * 4, hipMemcpyHostToDevice));
-    NSCHK(hipMemcpy(dc + o_ys, cal.ystart.data(), ny * 4, hipMemcpyHostToDevice));
-    NSCHK(hipMemcpy(dc + o_yl, cal.ylen.data(), ny * 4, hipMemcpyHostToDevice));
-    NSCHK(hipMemcpy(dc + o_ms, cal.mstart.data(), ny * 48, hipMemcpyHostToDevice));
-    NSCHK(hipMemcpy(dc + o_ml, cal.mlen.data(), ny * 48, hipMemcpyHostToDevice));
-    NSCHK(hipMemcpy(dc + o_mth, cal.month.data(), nd, hipMemcpyHostToDevice));
-    NSCHK(hipMemcpy(dc + o_yi, cal.yidx.data(), nd, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(dc + o_yr, cal.yr.data(), ny * 8, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(dc + o_row, cal.normrow.data(), nd * 4, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(dc + o_ys, cal.ystart.data(), ny * 4, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(dc + o_yl, cal.ylen.data(), ny * 4, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(dc + o_ms, cal.mstart.data(), ny * 48, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(dc + o_ml, cal.mlen.data(), ny * 48, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(dc + o_mth, cal.month.data(), nd, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(dc + o_yi, cal.yidx.data(), nd, hipMemcpyHostToDevice));
     NsCal k;
     k.month = (const uint8_t *)(dc + o_mth);
     k.yidx = (const uint8_t *)(dc + o_yi);
@@ -716,61 +671,61 @@ extern "C" int twxqa_non_spatial(int device, int64_t nstn, int64_t ndays, const 
     k.yr = (const int2 *)(dc + o_yr);
     k.nyears = cal.nyears;
     k.skip_month = cal.ndistinct - 1;
-    NSCHK(hipMalloc(&b_norm.p, ns * 2 * TWXQA_NORM_ROWS * 2 * 8)); // [nstn][2][731][2]
+    QACHK(hipMalloc(&b_norm.p, ns * 2 * TWXQA_NORM_ROWS * 2 * 8)); // [nstn][2][731][2]
     double *d_norm = static_cast<double *>(b_norm.p);
 
     float ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const unsigned g_day = (unsigned)((ns * nd + 255) / 256), g_day2 = (unsigned)((2 * ns * nd + 255) / 256);
     // ---- missing (2), naught (3) ---------------------------------------------------------------------------------------------
-    NSCHK(tm.start());
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_ns_init, dim3(g_day), dim3(256), 0, nullptr, (int64_t)(ns * nd), (const float *)d_tmin,
                        (const float *)d_tmax, d_f0, d_f1);
-    NSCHK(hipGetLastError());
-    NSCHK(tm.stop(&ms[0]));
+    QACHK(hipGetLastError());
+    QACHK(tm.stop_set(&ms[0]));
     // ---- the duplicates (4, 6, 5, 7), impossible values (8) ----------------------------------------------------------
-    NSCHK(tm.start());
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_ns_dups, dim3((unsigned)ns), dim3(256), 0, nullptr, ndays, k, (const float *)d_tmin,
                        (const float *)d_tmax, d_f0, d_f1);
-    NSCHK(hipGetLastError());
-    NSCHK(tm.stop(&ms[1]));
+    QACHK(hipGetLastError());
+    QACHK(tm.stop_set(&ms[1]));
     // ---- streaks (9) -------------------------------------------------------------------------------------------------
-    NSCHK(tm.start());
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_ns_streak, dim3((unsigned)(2 * ns)), dim3(64), 0, nullptr, ndays, (const float *)d_tmin, d_f0);
-    NSCHK(hipGetLastError());
-    NSCHK(tm.stop(&ms[2]));
+    QACHK(hipGetLastError());
+    QACHK(tm.stop_set(&ms[2]));
     // ---- gaps (10) ---------------------------------------------------------------------------------------------------
-    NSCHK(tm.start());
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_ns_gap, dim3((unsigned)(2 * ns * 12)), dim3(256), 0, nullptr, ndays, k, (const float *)d_tmin, d_f0);
-    NSCHK(hipGetLastError());
-    NSCHK(tm.stop(&ms[3]));
+    QACHK(hipGetLastError());
+    QACHK(tm.stop_set(&ms[3]));
     // ---- the day-of-year rows of what is left, then the outliers (15) and Tmin > Tmax (11) ---------------------------
-    NSCHK(tm.start());
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_ns_norms, dim3((unsigned)(2 * ns * NS_NJOBS)), dim3(256), 0, nullptr, ndays, nstn, cal.nyears,
                        k.yr, (const float *)d_tmin, (const uint8_t *)d_f0, d_norm);
-    NSCHK(hipGetLastError());
-    NSCHK(tm.stop(&ms[4]));
-    if (norms) NSCHK(hipMemcpy(norms, d_norm, ns * 2 * TWXQA_NORM_ROWS * 2 * 8, hipMemcpyDeviceToHost));
-    NSCHK(tm.start());
+    QACHK(hipGetLastError());
+    QACHK(tm.stop_set(&ms[4]));
+    if (norms) QACHK(hipMemcpy(norms, d_norm, ns * 2 * TWXQA_NORM_ROWS * 2 * 8, hipMemcpyDeviceToHost));
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_ns_clim, dim3(g_day), dim3(256), 0, nullptr, ndays, nstn, k.normrow, (const float *)d_tmin,
                        (const float *)d_tmax, (const double *)d_norm, d_f0, d_f1);
-    NSCHK(hipGetLastError());
-    NSCHK(tm.stop(&ms[5]));
+    QACHK(hipGetLastError());
+    QACHK(tm.stop_set(&ms[5]));
     // ---- spike / dip (13), then the lagged range (12) on what it left ------------------------------------------------
-    NSCHK(tm.start());
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_ns_spike, dim3(g_day2), dim3(256), 0, nullptr, ndays, (int64_t)(2 * ns), (const float *)d_tmin, d_f0);
-    NSCHK(hipGetLastError());
+    QACHK(hipGetLastError());
     hipLaunchKernelGGL(k_ns_lagrange, dim3(g_day), dim3(256), 0, nullptr, ndays, nstn, (const float *)d_tmin,
                        (const float *)d_tmax, d_f0, d_f1);
-    NSCHK(hipGetLastError());
-    NSCHK(tm.stop(&ms[6]));
+    QACHK(hipGetLastError());
+    QACHK(tm.stop_set(&ms[6]));
     // ---- mega-inconsistency (18) ---------------------------------------------------------------------------------------
-    NSCHK(tm.start());
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_ns_mega, dim3((unsigned)ns), dim3(256), 0, nullptr, ndays, k.month, (const float *)d_tmin,
                        (const float *)d_tmax, d_f0, d_f1);
-    NSCHK(hipGetLastError());
-    NSCHK(tm.stop(&ms[7]));
-    NSCHK(hipMemcpy(flag_tmin, d_f0, ns * nd, hipMemcpyDeviceToHost));
-    NSCHK(hipMemcpy(flag_tmax, d_f1, ns * nd, hipMemcpyDeviceToHost));
+    QACHK(hipGetLastError());
+    QACHK(tm.stop_set(&ms[7]));
+    QACHK(hipMemcpy(flag_tmin, d_f0, ns * nd, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(flag_tmax, d_f1, ns * nd, hipMemcpyDeviceToHost));
     if (kernel_ms) memcpy(kernel_ms, ms, sizeof ms);
     return 0;
 }

@@ -1,6 +1,7 @@
 // twx_outlier.hip -- libtwxqa.so: step20's leave-one-out outlier screen (XvalOutlier, twx/interp/optimize.py:84-207;
 // include/twx_qa.h).  Its own translation unit and library: the kriging / daily kernels of libtwxhip are not rebuilt
-// or touched, and none of their headers is included (the few helpers needed are restated below).
+// or touched, and none of their headers is included (the few device helpers needed are restated below; the host scaffold
+// is twx_qa_common.h's).
 //
 // k_outlier_wls: one wavefront per left-out station, one 16-lane DPP row per (station, target) item, four targets at a
 // time (13 targets = 4 rounds; the fourth round holds one).  The design of k_gwr_z (csrc/twx_daily.h): a lane walks
@@ -22,6 +23,7 @@
 #include <vector>
 
 #include "twx_qa.h"
+#include "twx_qa_common.h"
 
 #define QA_SLOTS ((TWXQA_MAX_K + 15) / 16)   // neighbours per lane
 // a pivot below this fraction of its column's diagonal is a column (numerically) inside the span of the previous ones:
@@ -181,35 +183,6 @@ __global__ __launch_bounds__(256) void k_outlier_wls(int64_t nstn, const double 
 // ---------------------------------------------------------------------------------
 // host entry
 // ---------------------------------------------------------------------------------
-namespace {
-
-int qa_fail(char *errbuf, int errlen, const char *what, hipError_t e = hipSuccess)
-{
-    if (errbuf && errlen > 0) {
-        if (e != hipSuccess) snprintf(errbuf, (size_t)errlen, "%s: %s", what, hipGetErrorString(e));
-        else snprintf(errbuf, (size_t)errlen, "%s", what);
-    }
-    return -1;
-}
-
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
-
-struct Events {
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-};
-
-}  // namespace
-
-#define QACHK(call)                                                                     \
-    do {                                                                                \
-        hipError_t e_ = (call);                                                         \
-        if (e_ != hipSuccess) return qa_fail(errbuf, errlen, #call, e_);                \
-    } while (0)
-
 extern "C" int twxqa_outlier_wls(int device, int64_t nstn, const double *lon, const double *lat, const double *elev,
                                  const double *lst13, const double *norm13, int64_t npts, const double *pt, int32_t k,
                                  const int32_t *idx, const double *wgt, const int32_t *knn_status, double *err,
@@ -239,7 +212,7 @@ extern "C" int twxqa_outlier_wls(int device, int64_t nstn, const double *lon, co
                  off_norm = off_lst + 13 * n * 8, off_pt = off_norm + 13 * n * 8, off_wgt = off_pt + np * TWXQA_PT_STRIDE * 8,
                  off_err = off_wgt + nk * 8, off_idx = off_err + np * TWXQA_NTARGET * 8, off_kst = off_idx + nk * 4,
                  off_st = off_kst + np * 4, total = off_st + np * TWXQA_NTARGET * 4;
-    DevBuf buf;
+    QaBuf buf;
     QACHK(hipMalloc(&buf.p, total));
     char *d = static_cast<char *>(buf.p);
     QACHK(hipMemcpy(d + off_lon, lon, n * 8, hipMemcpyHostToDevice));
@@ -251,11 +224,10 @@ extern "C" int twxqa_outlier_wls(int device, int64_t nstn, const double *lon, co
     QACHK(hipMemcpy(d + off_wgt, wgt, nk * 8, hipMemcpyHostToDevice));
     QACHK(hipMemcpy(d + off_idx, idx, nk * 4, hipMemcpyHostToDevice));
     QACHK(hipMemcpy(d + off_kst, knn_status, np * 4, hipMemcpyHostToDevice));
-    Events ev;
+    QaTimer tm;
     if (kernel_ms) {
-        QACHK(hipEventCreate(&ev.e[0]));
-        QACHK(hipEventCreate(&ev.e[1]));
-        QACHK(hipEventRecord(ev.e[0], nullptr));
+        QACHK(tm.init());
+        QACHK(tm.start());
     }
     hipLaunchKernelGGL(k_outlier_wls, dim3((unsigned)((npts + 3) / 4)), dim3(256), 0, nullptr, (int64_t)nstn,
                        (const double *)(d + off_lon), (const double *)(d + off_lat), (const double *)(d + off_elev),
@@ -264,11 +236,7 @@ extern "C" int twxqa_outlier_wls(int device, int64_t nstn, const double *lon, co
                        (const double *)(d + off_wgt), (const int32_t *)(d + off_kst), (double *)(d + off_err),
                        (int32_t *)(d + off_st));
     QACHK(hipGetLastError());
-    if (kernel_ms) {
-        QACHK(hipEventRecord(ev.e[1], nullptr));
-        QACHK(hipEventSynchronize(ev.e[1]));
-        QACHK(hipEventElapsedTime(kernel_ms, ev.e[0], ev.e[1]));
-    }
+    if (kernel_ms) QACHK(tm.stop_set(kernel_ms));
     QACHK(hipMemcpy(err, d + off_err, np * TWXQA_NTARGET * 8, hipMemcpyDeviceToHost));
     QACHK(hipMemcpy(status, d + off_st, np * TWXQA_NTARGET * 4, hipMemcpyDeviceToHost));
     return 0;

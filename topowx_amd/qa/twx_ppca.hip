@@ -1,7 +1,7 @@
 // twx_ppca.hip -- libtwxqa.so: the estimator of step16 (twx/infill/rpy/pca_infill.R: pcaMethods' pca(method = 'ppca'), EM
 // for probabilistic PCA with missing values) restated as include/twx_qa.h states it, for every item of one call
-// (twxpp_ppca_fit).  Its own translation unit: the helpers it shares with twx_emnorm.hip (the column gather, the buffer
-// list, the event timer) are restated, nothing there is edited.
+// (twxpp_ppca_fit).  Its own translation unit: the column gather it shares with twx_emnorm.hip is restated, nothing
+// there is edited; the wave sum, the buffer list and the event timer are twx_qa_common.h's.
 //
 // An item is a matrix of N <= TWXPP_MAX_ROWS days by D <= TWXPP_MAX_COLS columns (the target, its station columns as
 // float32 rows of the station-major observations, the float64 columns of one optional extra set), standardised with the
@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "twx_qa.h"
+#include "twx_qa_common.h"
 
 #define PP_D TWXPP_MAX_COLS                  // 64: one lane per column
 #define PP_K TWXPP_MAX_PCS                   // 32: the stride of every d-indexed array
@@ -59,13 +60,6 @@ __device__ __forceinline__ void wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ double pp_wave_sum(double v)
-{
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v = v + __shfl_xor(v, m, 64);
-    return v;
 }
 
 struct PpIn {
@@ -191,7 +185,7 @@ __device__ __forceinline__ double pp_dot_dd(const double *A, const double *B, in
             else if (i == c) acc = acc + A[e];
         }
     }
-    return pp_wave_sum(acc);
+    return qa_wave_sum(acc);
 }
 
 // CtC = C'C over the rows j < D, by the workgroup
@@ -247,7 +241,7 @@ __global__ __launch_bounds__(PP_THREADS) void k_pp_prep(PpIn in, int first_item,
             const double y = pp_value(col, days, r);
             if (pp_finite(y)) { cnt = cnt + 1.0; s1 = s1 + y; }
         }
-        cnt = pp_wave_sum(cnt); s1 = pp_wave_sum(s1);
+        cnt = qa_wave_sum(cnt); s1 = qa_wave_sum(s1);
         if (lane == 0) { sCnt[c] = cnt; sM[c] = s1 / cnt; }
     }
     __syncthreads();
@@ -303,7 +297,7 @@ __global__ __launch_bounds__(PP_THREADS) void k_pp_prep(PpIn in, int first_item,
         }
         wave_sync();
     }
-    racc = pp_wave_sum(racc);
+    racc = qa_wave_sum(racc);
     if (lane == 0) sRed[wave] = racc;
     __syncthreads();
     const double ss = (((sRed[0] + sRed[1]) + sRed[2]) + sRed[3]) / ((double)N * (double)D - missing);
@@ -451,7 +445,7 @@ __global__ __launch_bounds__(PP_THREADS) void k_pp_iter(PpIn in, int first_item,
             }
             wave_sync();
         }
-        racc = pp_wave_sum(racc);
+        racc = qa_wave_sum(racc);
         if (lane == 0) sRed[wave][0] = racc;
         __syncthreads();
         const double res = ((sRed[0][0] + sRed[1][0]) + sRed[2][0]) + sRed[3][0];
@@ -491,10 +485,10 @@ __global__ __launch_bounds__(PP_THREADS) void k_pp_iter(PpIn in, int first_item,
             for (int pass = 0; pass < 2; ++pass)
                 for (int m = 0; m < c; ++m) {
                     const double qm = sB[lane * PP_CS + m];
-                    const double dot = pp_wave_sum(qm * ck);
+                    const double dot = qa_wave_sum(qm * ck);
                     ck = ck - dot * qm;
                 }
-            const double nrm = sqrt(pp_wave_sum(ck * ck));
+            const double nrm = sqrt(qa_wave_sum(ck * ck));
             if (!(nrm > 0.0) || !pp_finite(nrm)) bad = true;
             else sB[lane * PP_CS + c] = ck / nrm;
         }
@@ -547,7 +541,7 @@ __global__ __launch_bounds__(PP_THREADS) void k_pp_iter(PpIn in, int first_item,
                     else off = off + sW[e] * sW[e];
                 }
             }
-            off = pp_wave_sum(off); dia = pp_wave_sum(dia);
+            off = qa_wave_sum(off); dia = qa_wave_sum(dia);
             if (!(off > 1e-40 * dia)) break;
             for (int p = 0; p < d - 1; ++p)
                 for (int q = p + 1; q < d; ++q) {
@@ -635,10 +629,10 @@ __global__ __launch_bounds__(PP_THREADS) void k_pp_iter(PpIn in, int first_item,
 #pragma unroll
         for (int t = 0; t < PP_K; ++t)
             if (t < d) {
-                const double v = pp_wave_sum(err[t]);
+                const double v = qa_wave_sum(err[t]);
                 if (lane == 0) sRed[wave][t] = v;
             }
-        den = pp_wave_sum(den);
+        den = qa_wave_sum(den);
         if (lane == 0) sRed[wave][PP_K] = den;
         __syncthreads();
         if (tid < d) {
@@ -653,57 +647,6 @@ __global__ __launch_bounds__(PP_THREADS) void k_pp_iter(PpIn in, int first_item,
     if (m_out && tid < D) m_out[(int64_t)item * PP_D + tid] = fx[PP_WS_C + tid];
     if (tid == 0) { done[item] = 1; status[item] = state; iters[item] = it; rel_out[item] = rel; }
 }
-
-namespace {
-
-int pp_fail(char *errbuf, int errlen, const char *what, hipError_t e = hipSuccess)
-{
-    if (errbuf && errlen > 0) {
-        if (e != hipSuccess) snprintf(errbuf, (size_t)errlen, "%s: %s", what, hipGetErrorString(e));
-        else snprintf(errbuf, (size_t)errlen, "%s", what);
-    }
-    return -1;
-}
-
-struct PpBufs {                                                  // every device allocation of a call, freed together
-    std::vector<void *> p;
-    ~PpBufs() { for (void *x : p) if (x) (void)hipFree(x); }
-    hipError_t get(void **out, size_t bytes)
-    {
-        hipError_t e = hipMalloc(out, bytes ? bytes : 1);
-        if (e == hipSuccess) p.push_back(*out);
-        return e;
-    }
-};
-
-struct PpTimer {                                                 // HIP-event time of a run of launches on the null stream
-    hipEvent_t a = nullptr, b = nullptr;
-    ~PpTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    hipError_t init() { hipError_t e = hipEventCreate(&a); return e != hipSuccess ? e : hipEventCreate(&b); }
-    hipError_t start() { return hipEventRecord(a, nullptr); }
-    hipError_t stop(float *acc)
-    {
-        float ms = 0.0f;
-        hipError_t e = hipEventRecord(b, nullptr);
-        if (e == hipSuccess) e = hipEventSynchronize(b);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
-        *acc += ms;
-        return e;
-    }
-};
-
-}  // namespace
-
-#define PPCHK(call)                                                                     \
-    do {                                                                                \
-        hipError_t e_ = (call);                                                         \
-        if (e_ != hipSuccess) return pp_fail(errbuf, errlen, #call, e_);                \
-    } while (0)
-#define PPALLOC(bufs, ptr, type, count) PPCHK((bufs).get((void **)&(ptr), (size_t)(count) * sizeof(type)))
-#define PPUP(dst, src, type, count)                                                                         \
-    do {                                                                                                    \
-        if ((count) > 0) PPCHK(hipMemcpy((dst), (src), (size_t)(count) * sizeof(type), hipMemcpyHostToDevice)); \
-    } while (0)
 
 extern "C" int twxpp_ppca_fit(int device, int64_t nstn, int64_t ndays, const float *obs, int32_t ngroups,
                               const int8_t *group, int64_t nitem, const int32_t *item_target, const int32_t *item_group,
@@ -721,16 +664,16 @@ extern "C" int twxpp_ppca_fit(int device, int64_t nstn, int64_t ndays, const flo
     if (nstn < 1 || ndays < 1 || nitem < 1 || nstn > INT32_MAX || ndays > INT32_MAX || nitem > INT32_MAX / 2 ||
         ngroups < 1 || ngroups > 127 || nset < 0 || nset > INT32_MAX) {
         snprintf(msg, sizeof msg, "%s: need nstn, ndays, nitem >= 1, 1 <= ngroups <= 127 and nset >= 0", fn);
-        return pp_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (!obs || !group || !item_target || !item_group || !item_npcs || !col_off || !norms || !stds || !c0 || !fit ||
         !r2cum || !iters || !rel || !status || (nset > 0 && (!set_group || !set_ncol || !set_vals || !item_set))) {
         snprintf(msg, sizeof msg, "%s: null buffer", fn);
-        return pp_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (!(threshold > 0.0) || !std::isfinite(threshold) || maxits < 1) {
         snprintf(msg, sizeof msg, "%s: threshold and maxits must be positive (defaults: TWXPP_DEFAULT_THRESHOLD, TWXPP_DEFAULT_MAXITS)", fn);
-        return pp_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (iters_per_launch <= 0) iters_per_launch = TWXPP_ITERS_PER_LAUNCH;
     if (workspace_bytes <= 0) workspace_bytes = TWXPP_WORKSPACE_BYTES;
@@ -739,7 +682,7 @@ extern "C" int twxpp_ppca_fit(int device, int64_t nstn, int64_t ndays, const flo
     for (int64_t d = 0; d < ndays; ++d) {
         if (group[d] < -1 || group[d] >= ngroups) {
             snprintf(msg, sizeof msg, "%s: group[%lld] = %d outside -1 .. %d", fn, (long long)d, (int)group[d], ngroups - 1);
-            return pp_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         if (group[d] >= 0) ++goff[(size_t)group[d] + 1];
     }
@@ -752,7 +695,7 @@ extern "C" int twxpp_ppca_fit(int device, int64_t nstn, int64_t ndays, const flo
         if (set_group[s] < 0 || set_group[s] >= ngroups || set_ncol[s] < 0) {
             snprintf(msg, sizeof msg, "%s: extra-column set %lld: group %d, %d columns", fn, (long long)s, (int)set_group[s],
                      (int)set_ncol[s]);
-            return pp_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         const int64_t rows = goff[(size_t)set_group[s] + 1] - goff[(size_t)set_group[s]];
         set_off[(size_t)s + 1] = set_off[(size_t)s] + rows * set_ncol[s];
@@ -765,24 +708,24 @@ extern "C" int twxpp_ppca_fit(int device, int64_t nstn, int64_t ndays, const flo
         if (item_target[i] < 0 || item_target[i] >= nstn || item_group[i] < 0 || item_group[i] >= ngroups) {
             snprintf(msg, sizeof msg, "%s: item %lld: target %d outside [0, %lld) or group %d outside [0, %d)", fn,
                      (long long)i, (int)item_target[i], (long long)nstn, (int)item_group[i], ngroups);
-            return pp_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         if (col_off[i + 1] < col_off[i] || (i == 0 && col_off[0] != 0) || (col_off[i + 1] > col_off[i] && !col_idx)) {
             snprintf(msg, sizeof msg, "%s: col_off is not a CSR offset array at item %lld", fn, (long long)i);
-            return pp_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         const int64_t s = item_set ? item_set[i] : -1;
         if (s < -1 || s >= nset || (s >= 0 && set_group[s] != item_group[i])) {
             snprintf(msg, sizeof msg, "%s: item %lld names extra-column set %lld (of %lld; it must be of the item's group)", fn,
                      (long long)i, (long long)s, (long long)nset);
-            return pp_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         h_iset[(size_t)i] = (int32_t)s;
         for (int64_t c = col_off[i]; c < col_off[i + 1]; ++c)
             if (col_idx[c] < 0 || col_idx[c] >= nstn) {
                 snprintf(msg, sizeof msg, "%s: item %lld: column index %d outside [0, %lld)", fn, (long long)i,
                          (int)col_idx[c], (long long)nstn);
-                return pp_fail(errbuf, errlen, msg);
+                return qa_fail(errbuf, errlen, msg);
             }
         const int64_t D = 1 + (col_off[i + 1] - col_off[i]) + (s >= 0 ? set_ncol[s] : 0);
         const int64_t d = item_npcs[i];
@@ -791,7 +734,7 @@ extern "C" int twxpp_ppca_fit(int device, int64_t nstn, int64_t ndays, const flo
         if (!nomat && (d < 1 || d > D || rows <= d)) {
             snprintf(msg, sizeof msg, "%s: item %lld: %lld components for %lld rows by %lld columns (need 1 <= d <= D and N > d)",
                      fn, (long long)i, (long long)d, (long long)rows, (long long)D);
-            return pp_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         par_off[(size_t)i + 1] = par_off[(size_t)i] + D;
         c0_off[(size_t)i + 1] = c0_off[(size_t)i] + (nomat ? 0 : D * d);
@@ -805,60 +748,60 @@ extern "C" int twxpp_ppca_fit(int device, int64_t nstn, int64_t ndays, const flo
     }
     const int64_t ncolidx = col_off[nitem], npar = par_off[NI], nc0 = c0_off[NI], nfit = fit_off[NI];
 
-    PPCHK(hipSetDevice(device));
+    QACHK(hipSetDevice(device));
     const auto t_up = std::chrono::steady_clock::now();
-    PpBufs bufs;
+    QaPool bufs;
     float *d_obs;
     int32_t *d_gdays, *d_goff, *d_itarget, *d_igroup, *d_iset, *d_inpcs, *d_colidx, *d_setncol, *d_iters, *d_status;
     int64_t *d_coloff, *d_setoff, *d_paroff, *d_c0off, *d_fitoff;
     double *d_setvals, *d_norms, *d_stds, *d_c0, *d_fit, *d_r2, *d_rel, *d_cout = nullptr, *d_mout = nullptr;
     uint8_t *d_done;
     const size_t NS = (size_t)nstn, ND = (size_t)ndays, G = (size_t)ngroups, NSET = (size_t)nset;
-    PPALLOC(bufs, d_obs, float, NS * ND);
-    PPALLOC(bufs, d_gdays, int32_t, gdays.size()); PPALLOC(bufs, d_goff, int32_t, G + 1);
-    PPALLOC(bufs, d_itarget, int32_t, NI); PPALLOC(bufs, d_igroup, int32_t, NI); PPALLOC(bufs, d_iset, int32_t, NI);
-    PPALLOC(bufs, d_inpcs, int32_t, NI);
-    PPALLOC(bufs, d_coloff, int64_t, NI + 1); PPALLOC(bufs, d_colidx, int32_t, ncolidx);
-    PPALLOC(bufs, d_setncol, int32_t, NSET); PPALLOC(bufs, d_setoff, int64_t, NSET + 1);
-    PPALLOC(bufs, d_setvals, double, set_off[NSET]);
-    PPALLOC(bufs, d_paroff, int64_t, NI + 1); PPALLOC(bufs, d_c0off, int64_t, NI + 1); PPALLOC(bufs, d_fitoff, int64_t, NI + 1);
-    PPALLOC(bufs, d_norms, double, npar); PPALLOC(bufs, d_stds, double, npar); PPALLOC(bufs, d_c0, double, nc0);
-    PPALLOC(bufs, d_iters, int32_t, NI); PPALLOC(bufs, d_status, int32_t, NI); PPALLOC(bufs, d_done, uint8_t, NI);
-    PPALLOC(bufs, d_fit, double, nfit); PPALLOC(bufs, d_r2, double, NI * PP_K); PPALLOC(bufs, d_rel, double, NI);
-    PPUP(d_obs, obs, float, NS * ND);
-    PPUP(d_gdays, gdays.data(), int32_t, gdays.size());
-    PPUP(d_goff, goff.data(), int32_t, G + 1);
-    PPUP(d_itarget, item_target, int32_t, NI);
-    PPUP(d_igroup, item_group, int32_t, NI);
-    PPUP(d_iset, h_iset.data(), int32_t, NI);
-    PPUP(d_inpcs, item_npcs, int32_t, NI);
-    PPUP(d_coloff, col_off, int64_t, NI + 1);
-    PPUP(d_colidx, col_idx, int32_t, ncolidx);
-    PPUP(d_setncol, set_ncol, int32_t, NSET);
-    PPUP(d_setoff, set_off.data(), int64_t, NSET + 1);
-    PPUP(d_setvals, set_vals, double, set_off[NSET]);
-    PPUP(d_paroff, par_off.data(), int64_t, NI + 1);
-    PPUP(d_c0off, c0_off.data(), int64_t, NI + 1);
-    PPUP(d_fitoff, fit_off.data(), int64_t, NI + 1);
-    PPUP(d_norms, norms, double, npar);
-    PPUP(d_stds, stds, double, npar);
-    PPUP(d_c0, c0, double, nc0);
-    PPUP(d_status, h_status.data(), int32_t, NI);
-    PPUP(d_done, h_done.data(), uint8_t, NI);
-    PPCHK(hipMemset(d_iters, 0, NI * 4));
-    PPCHK(hipMemset(d_fit, 0xff, (size_t)nfit * 8));             // all bits set: a NaN
-    PPCHK(hipMemset(d_r2, 0xff, NI * PP_K * 8));
-    PPCHK(hipMemset(d_rel, 0xff, NI * 8));
-    if (c_out) { PPALLOC(bufs, d_cout, double, NI * PP_D * PP_K); PPCHK(hipMemset(d_cout, 0xff, NI * PP_D * PP_K * 8)); }
-    if (m_out) { PPALLOC(bufs, d_mout, double, NI * PP_D); PPCHK(hipMemset(d_mout, 0xff, NI * PP_D * 8)); }
+    QAALLOC(bufs, d_obs, float, NS * ND);
+    QAALLOC(bufs, d_gdays, int32_t, gdays.size()); QAALLOC(bufs, d_goff, int32_t, G + 1);
+    QAALLOC(bufs, d_itarget, int32_t, NI); QAALLOC(bufs, d_igroup, int32_t, NI); QAALLOC(bufs, d_iset, int32_t, NI);
+    QAALLOC(bufs, d_inpcs, int32_t, NI);
+    QAALLOC(bufs, d_coloff, int64_t, NI + 1); QAALLOC(bufs, d_colidx, int32_t, ncolidx);
+    QAALLOC(bufs, d_setncol, int32_t, NSET); QAALLOC(bufs, d_setoff, int64_t, NSET + 1);
+    QAALLOC(bufs, d_setvals, double, set_off[NSET]);
+    QAALLOC(bufs, d_paroff, int64_t, NI + 1); QAALLOC(bufs, d_c0off, int64_t, NI + 1); QAALLOC(bufs, d_fitoff, int64_t, NI + 1);
+    QAALLOC(bufs, d_norms, double, npar); QAALLOC(bufs, d_stds, double, npar); QAALLOC(bufs, d_c0, double, nc0);
+    QAALLOC(bufs, d_iters, int32_t, NI); QAALLOC(bufs, d_status, int32_t, NI); QAALLOC(bufs, d_done, uint8_t, NI);
+    QAALLOC(bufs, d_fit, double, nfit); QAALLOC(bufs, d_r2, double, NI * PP_K); QAALLOC(bufs, d_rel, double, NI);
+    QAUP_NZ(d_obs, obs, float, NS * ND);
+    QAUP_NZ(d_gdays, gdays.data(), int32_t, gdays.size());
+    QAUP_NZ(d_goff, goff.data(), int32_t, G + 1);
+    QAUP_NZ(d_itarget, item_target, int32_t, NI);
+    QAUP_NZ(d_igroup, item_group, int32_t, NI);
+    QAUP_NZ(d_iset, h_iset.data(), int32_t, NI);
+    QAUP_NZ(d_inpcs, item_npcs, int32_t, NI);
+    QAUP_NZ(d_coloff, col_off, int64_t, NI + 1);
+    QAUP_NZ(d_colidx, col_idx, int32_t, ncolidx);
+    QAUP_NZ(d_setncol, set_ncol, int32_t, NSET);
+    QAUP_NZ(d_setoff, set_off.data(), int64_t, NSET + 1);
+    QAUP_NZ(d_setvals, set_vals, double, set_off[NSET]);
+    QAUP_NZ(d_paroff, par_off.data(), int64_t, NI + 1);
+    QAUP_NZ(d_c0off, c0_off.data(), int64_t, NI + 1);
+    QAUP_NZ(d_fitoff, fit_off.data(), int64_t, NI + 1);
+    QAUP_NZ(d_norms, norms, double, npar);
+    QAUP_NZ(d_stds, stds, double, npar);
+    QAUP_NZ(d_c0, c0, double, nc0);
+    QAUP_NZ(d_status, h_status.data(), int32_t, NI);
+    QAUP_NZ(d_done, h_done.data(), uint8_t, NI);
+    QACHK(hipMemset(d_iters, 0, NI * 4));
+    QACHK(hipMemset(d_fit, 0xff, (size_t)nfit * 8));             // all bits set: a NaN
+    QACHK(hipMemset(d_r2, 0xff, NI * PP_K * 8));
+    QACHK(hipMemset(d_rel, 0xff, NI * 8));
+    if (c_out) { QAALLOC(bufs, d_cout, double, NI * PP_D * PP_K); QACHK(hipMemset(d_cout, 0xff, NI * PP_D * PP_K * 8)); }
+    if (m_out) { QAALLOC(bufs, d_mout, double, NI * PP_D); QACHK(hipMemset(d_mout, 0xff, NI * PP_D * 8)); }
     PpIn in = {d_obs, ndays, d_gdays, d_goff, d_itarget, d_igroup, d_iset, d_inpcs, d_coloff, d_colidx, d_setncol, d_setoff,
                d_setvals, d_paroff, d_norms, d_stds, d_c0off, d_c0};
 
-    PpTimer tm;
+    QaTimer tm;
     float ms[TWXPP_NTIMES] = {0.0f, 0.0f, 0.0f, 0.0f};
     if (kernel_ms) {
-        PPCHK(tm.init());
-        PPCHK(hipDeviceSynchronize());
+        QACHK(tm.init());
+        QACHK(hipDeviceSynchronize());
         ms[2] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_up).count();
     }
     // batches of consecutive items under the workspace budget (at least one item each)
@@ -880,50 +823,50 @@ extern "C" int twxpp_ppca_fit(int device, int64_t nstn, int64_t ndays, const flo
         }
         const size_t NB = (size_t)(last - first);
         ++nbatches;
-        PpBufs ws;                                               // freed at the end of the batch
+        QaPool ws;                                               // freed at the end of the batch
         int64_t *w_xoff;
         int32_t *w_act;
         double *w_fixed, *w_x;
-        PPALLOC(ws, w_xoff, int64_t, NB); PPALLOC(ws, w_act, int32_t, NB);
-        PPALLOC(ws, w_fixed, double, NB * PP_WS_FIXED); PPALLOC(ws, w_x, double, x_total);
-        PPUP(w_xoff, xoff.data(), int64_t, NB);
-        if (kernel_ms) PPCHK(tm.start());
+        QAALLOC(ws, w_xoff, int64_t, NB); QAALLOC(ws, w_act, int32_t, NB);
+        QAALLOC(ws, w_fixed, double, NB * PP_WS_FIXED); QAALLOC(ws, w_x, double, x_total);
+        QAUP_NZ(w_xoff, xoff.data(), int64_t, NB);
+        if (kernel_ms) QACHK(tm.start());
         hipLaunchKernelGGL(k_pp_prep, dim3((unsigned)NB), dim3(PP_THREADS), 0, nullptr, in, (int)first,
                            (const int64_t *)w_xoff, w_fixed, w_x, d_done, d_status);
-        PPCHK(hipGetLastError());
-        if (kernel_ms) PPCHK(tm.stop(&ms[0]));
+        QACHK(hipGetLastError());
+        if (kernel_ms) QACHK(tm.stop_add(&ms[0]));
         bdone.resize(NB);
         const int64_t max_rounds = ((int64_t)maxits + iters_per_launch - 1) / iters_per_launch;
         for (int64_t round = 0;; ++round) {
-            PPCHK(hipMemcpy(bdone.data(), d_done + first, NB, hipMemcpyDeviceToHost));
+            QACHK(hipMemcpy(bdone.data(), d_done + first, NB, hipMemcpyDeviceToHost));
             act.clear();
             for (size_t b = 0; b < NB; ++b)
                 if (!bdone[b]) act.push_back((int32_t)b);
             if (act.empty()) break;
             if (round >= max_rounds) {                           // every launch advances each of its items or ends it
                 snprintf(msg, sizeof msg, "%s: internal error: %lld launches for maxits %d", fn, (long long)round, (int)maxits);
-                return pp_fail(errbuf, errlen, msg);
+                return qa_fail(errbuf, errlen, msg);
             }
-            PPUP(w_act, act.data(), int32_t, act.size());
-            if (kernel_ms) PPCHK(tm.start());
+            QAUP_NZ(w_act, act.data(), int32_t, act.size());
+            if (kernel_ms) QACHK(tm.start());
             hipLaunchKernelGGL(k_pp_iter, dim3((unsigned)act.size()), dim3(PP_THREADS), 0, nullptr, in, (int)first,
                                (const int32_t *)w_act, (const int64_t *)w_xoff, w_fixed, w_x, (const int64_t *)d_fitoff,
                                threshold, (int)maxits, (int)iters_per_launch, d_done, d_status, d_iters, d_rel, d_fit, d_r2,
                                d_cout, d_mout);
-            PPCHK(hipGetLastError());
-            if (kernel_ms) PPCHK(tm.stop(&ms[1]));
+            QACHK(hipGetLastError());
+            if (kernel_ms) QACHK(tm.stop_add(&ms[1]));
             ++rounds;
         }
         first = last;
     }
     const auto t_down = std::chrono::steady_clock::now();
-    PPCHK(hipMemcpy(fit, d_fit, (size_t)nfit * 8, hipMemcpyDeviceToHost));
-    PPCHK(hipMemcpy(r2cum, d_r2, NI * PP_K * 8, hipMemcpyDeviceToHost));
-    PPCHK(hipMemcpy(rel, d_rel, NI * 8, hipMemcpyDeviceToHost));
-    PPCHK(hipMemcpy(iters, d_iters, NI * 4, hipMemcpyDeviceToHost));
-    PPCHK(hipMemcpy(status, d_status, NI * 4, hipMemcpyDeviceToHost));
-    if (c_out) PPCHK(hipMemcpy(c_out, d_cout, NI * PP_D * PP_K * 8, hipMemcpyDeviceToHost));
-    if (m_out) PPCHK(hipMemcpy(m_out, d_mout, NI * PP_D * 8, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(fit, d_fit, (size_t)nfit * 8, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(r2cum, d_r2, NI * PP_K * 8, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(rel, d_rel, NI * 8, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(iters, d_iters, NI * 4, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(status, d_status, NI * 4, hipMemcpyDeviceToHost));
+    if (c_out) QACHK(hipMemcpy(c_out, d_cout, NI * PP_D * PP_K * 8, hipMemcpyDeviceToHost));
+    if (m_out) QACHK(hipMemcpy(m_out, d_mout, NI * PP_D * 8, hipMemcpyDeviceToHost));
     ms[3] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_down).count();
     if (counts) { counts[0] = rounds; counts[1] = nbatches; }
     if (kernel_ms) memcpy(kernel_ms, ms, sizeof ms);

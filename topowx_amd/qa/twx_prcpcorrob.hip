@@ -47,9 +47,8 @@
 #include <vector>
 
 #include "twx_qa.h"
+#include "twx_qa_common.h"
 
-#define PC_RADIAN 0.017453292519943295       // util_geo.py:21
-#define PC_EARTH_KM 6371.009                 // util_geo.py:22
 #define PC_OK 1                              // qa_prcp.py:37-57
 #define PC_SPATIAL_CORROB 17
 #define PC_ROWS TWXPQ_PCTILE_ROWS
@@ -78,7 +77,7 @@ __global__ __launch_bounds__(64) void k_pc_radius(int64_t nstn, const double *__
     const int lane = threadIdx.x;
     const int64_t t = blockIdx.x;
     const int32_t self = target_idx[t];
-    const double lat1rad = lat[self] * PC_RADIAN, lon1rad = lon[self] * PC_RADIAN;
+    const double lat1rad = lat[self] * QA_RADIAN, lon1rad = lon[self] * QA_RADIAN;
     const double cos1 = cos(lat1rad);
     int64_t pos = 0;
     int room = 0;
@@ -93,10 +92,7 @@ __global__ __launch_bounds__(64) void k_pc_radius(int64_t nstn, const double *__
         bool in = false;
         double dist = 0.0;
         if (j < nstn && j != self) {
-            const double lat2rad = lat[j] * PC_RADIAN, lon2rad = lon[j] * PC_RADIAN;
-            const double s1 = sin((lat1rad - lat2rad) / 2.0), s2 = sin((lon1rad - lon2rad) / 2.0);
-            const double a = s1 * s1 + (cos1 * cos(lat2rad)) * (s2 * s2);
-            dist = PC_EARTH_KM * (2.0 * asin(sqrt(a)));
+            dist = qa_dist_km(lat1rad, lon1rad, cos1, lat[j], lon[j]);
             in = dist <= TWXQA_NGH_RADIUS_KM;
         }
         const uint64_t b = __ballot(in);
@@ -291,46 +287,6 @@ __global__ __launch_bounds__(256) void k_pc_apply(int64_t total, const uint8_t *
 // ---------------------------------------------------------------------------------
 namespace {
 
-int pc_fail(char *errbuf, int errlen, const char *what, hipError_t e = hipSuccess)
-{
-    if (errbuf && errlen > 0) {
-        if (e != hipSuccess) snprintf(errbuf, (size_t)errlen, "%s: %s", what, hipGetErrorString(e));
-        else snprintf(errbuf, (size_t)errlen, "%s", what);
-    }
-    return -1;
-}
-
-struct PcBuf {
-    void *p = nullptr;
-    ~PcBuf() { if (p) (void)hipFree(p); }
-};
-
-struct PcTimer {                                                 // HIP-event time of a run of launches on the null stream
-    hipEvent_t a = nullptr, b = nullptr;
-    ~PcTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    hipError_t init() { hipError_t e = hipEventCreate(&a); return e != hipSuccess ? e : hipEventCreate(&b); }
-    hipError_t start() { return hipEventRecord(a, nullptr); }
-    hipError_t stop(float *ms)
-    {
-        hipError_t e = hipEventRecord(b, nullptr);
-        if (e == hipSuccess) e = hipEventSynchronize(b);
-        if (e == hipSuccess) e = hipEventElapsedTime(ms, a, b);
-        return e;
-    }
-};
-
-int64_t pc_days_from_civil(int64_t y, int mth, int day)           // days since 1970-01-01, proleptic Gregorian
-{
-    y -= mth <= 2;
-    const int64_t era = (y >= 0 ? y : y - 399) / 400;
-    const int64_t yoe = y - era * 400;
-    const int64_t doy = (153 * (mth + (mth > 2 ? -3 : 9)) + 2) / 5 + day - 1;
-    const int64_t doe = yoe * 365 + yoe / 4 - yoe / 100 + doy;
-    return era * 146097 + doe - 719468;
-}
-
-bool pc_leap(int y) { return (y % 4 == 0 && y % 100 != 0) || y % 400 == 0; }
-
 struct PcCalendar {
     int nyears = 0;
     std::vector<int32_t> yr;        // [nyears][2]: Jan 1's series index (may lie before the axis), leap
@@ -346,17 +302,17 @@ int pc_calendar(const char *who, int64_t ndays, const int32_t *ymd, PcCalendar &
     const int y0 = a / 10000, m0 = (a / 100) % 100, d0 = a % 100;
     if (a < 10101 || m0 < 1 || m0 > 12 || d0 < 1 || d0 > 31) {
         snprintf(msg, sizeof msg, "%s: ymd[0] is not a date", who);
-        return pc_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
-    const int64_t zlast = pc_days_from_civil(y0, m0, d0) + ndays - 1;
+    const int64_t zlast = qa_days_from_civil(y0, m0, d0) + ndays - 1;
     int64_t ylast = y0 + (ndays - 1) / 366;
-    while (pc_days_from_civil(ylast + 1, 1, 1) <= zlast) ++ylast;
+    while (qa_days_from_civil(ylast + 1, 1, 1) <= zlast) ++ylast;
     const int64_t nyears = ylast - y0 + 1;
     if (nyears * 29 > TWXPQ_MAX_WINDOW_VALUES) {
         snprintf(msg, sizeof msg, "%s: the series touches %lld years; a row of the percentile basis holds at most "
                  "TWXPQ_MAX_WINDOW_VALUES = %d values (29 per year, %d years)", who, (long long)nyears,
                  TWXPQ_MAX_WINDOW_VALUES, TWXPQ_MAX_WINDOW_VALUES / 29);
-        return pc_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     c.nyears = (int)nyears;
     c.row.resize((size_t)ndays);
@@ -364,40 +320,34 @@ int pc_calendar(const char *who, int64_t ndays, const int32_t *ymd, PcCalendar &
     static const int mlen[12] = {31, 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31};
     static const int cum[12] = {0, 31, 60, 91, 121, 152, 182, 213, 244, 274, 305, 335};    // a leap year's
     int y = y0, mth = m0, day = d0;
-    int64_t jan1 = pc_days_from_civil(y0, 1, 1) - pc_days_from_civil(y0, m0, d0);
-    c.yr.assign({(int32_t)jan1, pc_leap(y0) ? 1 : 0});
+    int64_t jan1 = qa_days_from_civil(y0, 1, 1) - qa_days_from_civil(y0, m0, d0);
+    c.yr.assign({(int32_t)jan1, qa_leap(y0) ? 1 : 0});
     for (int64_t i = 0; i < ndays; ++i) {
         if (ymd[i] != y * 10000 + mth * 100 + day) {
             snprintf(msg, sizeof msg, "%s: ymd[%lld] = %d: the days are not consecutive calendar days", who, (long long)i,
                      (int)ymd[i]);
-            return pc_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         c.row[(size_t)i] = (uint16_t)(i - jan1);                  // 0 .. 365
         c.mday[(size_t)i] = (uint16_t)(cum[mth - 1] + day - 1);   // 0 .. 365
-        if (++day > mlen[mth - 1] + ((mth == 2 && pc_leap(y)) ? 1 : 0)) {
+        if (++day > mlen[mth - 1] + ((mth == 2 && qa_leap(y)) ? 1 : 0)) {
             day = 1;
             if (++mth > 12) {
                 mth = 1;
                 ++y;
                 jan1 = i + 1;
-                if (i + 1 < ndays) { c.yr.push_back((int32_t)jan1); c.yr.push_back(pc_leap(y) ? 1 : 0); }
+                if (i + 1 < ndays) { c.yr.push_back((int32_t)jan1); c.yr.push_back(qa_leap(y) ? 1 : 0); }
             }
         }
     }
     if ((int)(c.yr.size() / 2) != c.nyears) {
         snprintf(msg, sizeof msg, "%s: calendar count mismatch", who);
-        return pc_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     return 0;
 }
 
 }  // namespace
-
-#define PCCHK(call)                                                                     \
-    do {                                                                                \
-        hipError_t e_ = (call);                                                         \
-        if (e_ != hipSuccess) return pc_fail(errbuf, errlen, #call, e_);                \
-    } while (0)
 
 extern "C" int twxpc_spatial_corrob(int device, int64_t nstn, int64_t ndays, const double *lon, const double *lat,
                                     const float *prcp, const int32_t *ymd, int64_t ntarget, const int32_t *target_idx,
@@ -406,11 +356,11 @@ extern "C" int twxpc_spatial_corrob(int device, int64_t nstn, int64_t ndays, con
 {
     if (errbuf && errlen > 0) errbuf[0] = 0;
     if (nstn < 1 || ndays < 1 || ntarget < 1 || nstn > INT32_MAX || ndays > INT32_MAX - 256 || ntarget > INT32_MAX / PC_ROWS)
-        return pc_fail(errbuf, errlen, "twxpc_spatial_corrob: need nstn >= 1, ndays >= 1 and ntarget >= 1");
-    if (!lon || !lat || !prcp || !ymd || !target_idx || !flags) return pc_fail(errbuf, errlen, "twxpc_spatial_corrob: null buffer");
+        return qa_fail(errbuf, errlen, "twxpc_spatial_corrob: need nstn >= 1, ndays >= 1 and ntarget >= 1");
+    if (!lon || !lat || !prcp || !ymd || !target_idx || !flags) return qa_fail(errbuf, errlen, "twxpc_spatial_corrob: null buffer");
     const int64_t nblk64 = (ndays + 63) / 64;
     if (nblk64 * ntarget > INT32_MAX || (ntarget * ndays + 255) / 256 > INT32_MAX || (nstn + ntarget) > INT32_MAX)
-        return pc_fail(errbuf, errlen, "twxpc_spatial_corrob: more than 2^31 - 1 work items in one call");
+        return qa_fail(errbuf, errlen, "twxpc_spatial_corrob: more than 2^31 - 1 work items in one call");
     PcCalendar cal;
     if (pc_calendar("twxpc_spatial_corrob", ndays, ymd, cal, errbuf, errlen) != 0) return -1;
     for (int64_t i = 0; i < ntarget; ++i) {
@@ -418,7 +368,7 @@ extern "C" int twxpc_spatial_corrob(int device, int64_t nstn, int64_t ndays, con
             char msg[160];
             snprintf(msg, sizeof msg, "twxpc_spatial_corrob: target_idx[%lld] = %d is not a row of the pool (nstn = %lld)",
                      (long long)i, (int)target_idx[i], (long long)nstn);
-            return pc_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
     }
     const size_t nt = (size_t)ntarget, ns = (size_t)nstn, nd = (size_t)ndays;
@@ -426,50 +376,50 @@ extern "C" int twxpc_spatial_corrob(int device, int64_t nstn, int64_t ndays, con
     float ms[TWXPC_NKERNELS];
     for (int i = 0; i < TWXPC_NKERNELS; ++i) ms[i] = 0.0f;
 
-    PCCHK(hipSetDevice(device));
-    PcBuf b_geo, b_tgt, b_csr, b_obs, b_flag, b_cal, b_slot, b_rows, b_cnt, b_state, b_work, b_out;
-    PcTimer tm;
-    PCCHK(tm.init());
-    PCCHK(hipMalloc(&b_geo.p, ns * 16));
+    QACHK(hipSetDevice(device));
+    QaBuf b_geo, b_tgt, b_csr, b_obs, b_flag, b_cal, b_slot, b_rows, b_cnt, b_state, b_work, b_out;
+    QaTimer tm;
+    QACHK(tm.init());
+    QACHK(hipMalloc(&b_geo.p, ns * 16));
     double *d_lon = static_cast<double *>(b_geo.p), *d_lat = d_lon + ns;
-    PCCHK(hipMemcpy(d_lon, lon, ns * 8, hipMemcpyHostToDevice));
-    PCCHK(hipMemcpy(d_lat, lat, ns * 8, hipMemcpyHostToDevice));
-    PCCHK(hipMalloc(&b_tgt.p, (nt + 1) * 8 + nt * 8));           // csr offsets (int64, nt + 1), index, count
+    QACHK(hipMemcpy(d_lon, lon, ns * 8, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_lat, lat, ns * 8, hipMemcpyHostToDevice));
+    QACHK(hipMalloc(&b_tgt.p, (nt + 1) * 8 + nt * 8));           // csr offsets (int64, nt + 1), index, count
     int64_t *d_off = static_cast<int64_t *>(b_tgt.p);
     int32_t *d_idx = (int32_t *)(d_off + nt + 1), *d_ncnt = d_idx + nt;
-    PCCHK(hipMemcpy(d_idx, target_idx, nt * 4, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_idx, target_idx, nt * 4, hipMemcpyHostToDevice));
 
     // ---- 1. the radius lists in distance order: count, scan on the host, fill + sort ----------------------------------
     float ms_a = 0.0f, ms_b = 0.0f;
-    PCCHK(tm.start());
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_pc_radius, dim3((unsigned)nt), dim3(64), 0, nullptr, nstn, (const double *)d_lon,
                        (const double *)d_lat, (const int32_t *)d_idx, 0, d_ncnt, (const int64_t *)nullptr, (int32_t *)nullptr);
-    PCCHK(hipGetLastError());
-    PCCHK(tm.stop(&ms_a));
+    QACHK(hipGetLastError());
+    QACHK(tm.stop_set(&ms_a));
     std::vector<int32_t> ncnt(nt), tst(nt);
     std::vector<int64_t> off(nt + 1);
-    PCCHK(hipMemcpy(ncnt.data(), d_ncnt, nt * 4, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(ncnt.data(), d_ncnt, nt * 4, hipMemcpyDeviceToHost));
     off[0] = 0;
     for (size_t i = 0; i < nt; ++i) {                            // a list above the cap is not built: the target says so
         tst[i] = ncnt[i] > TWXQA_MAX_RADIUS_NGH ? TWXQA_SP_NGH_CAP : (ncnt[i] < PC_MIN_NGHS ? TWXQA_SP_FEW_NGHS : TWXQA_SP_OK);
         off[i + 1] = off[i] + (tst[i] == TWXQA_SP_NGH_CAP ? 0 : ncnt[i]);
     }
     if (status) memcpy(status, tst.data(), nt * 4);
-    PCCHK(hipMemcpy(d_off, off.data(), (nt + 1) * 8, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_off, off.data(), (nt + 1) * 8, hipMemcpyHostToDevice));
     const size_t ncsr = (size_t)off[nt];
-    PCCHK(hipMalloc(&b_csr.p, std::max<size_t>(16, ncsr * 4)));
+    QACHK(hipMalloc(&b_csr.p, std::max<size_t>(16, ncsr * 4)));
     int32_t *d_csr = static_cast<int32_t *>(b_csr.p);
     if (ncsr > 0) {
-        PCCHK(tm.start());
+        QACHK(tm.start());
         hipLaunchKernelGGL(k_pc_radius, dim3((unsigned)nt), dim3(64), 0, nullptr, nstn, (const double *)d_lon,
                            (const double *)d_lat, (const int32_t *)d_idx, 1, d_ncnt, (const int64_t *)d_off, d_csr);
-        PCCHK(hipGetLastError());
-        PCCHK(tm.stop(&ms_b));
+        QACHK(hipGetLastError());
+        QACHK(tm.stop_set(&ms_b));
     }
     ms[0] = ms_a + ms_b;
     // the stations that are a walked target's neighbour get row counts: their slot, -1 for the rest
     std::vector<int32_t> csr(ncsr), slot(ns, -1), rows;
-    if (ncsr > 0) PCCHK(hipMemcpy(csr.data(), d_csr, ncsr * 4, hipMemcpyDeviceToHost));
+    if (ncsr > 0) QACHK(hipMemcpy(csr.data(), d_csr, ncsr * 4, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < nt; ++i) {
         if (tst[i] != TWXQA_SP_OK) continue;                     // (a list shorter than 3 is never walked)
         for (int64_t k = off[i]; k < off[i + 1]; ++k) slot[(size_t)csr[(size_t)k]] = 0;
@@ -479,71 +429,71 @@ extern "C" int twxpc_spatial_corrob(int device, int64_t nstn, int64_t ndays, con
     const size_t nslot = rows.size();
 
     // ---- 2. the row counts: neighbours from the pool as it is, targets under their flags -----------------------------
-    PCCHK(hipMalloc(&b_obs.p, ns * nd * 4));
+    QACHK(hipMalloc(&b_obs.p, ns * nd * 4));
     float *d_prcp = static_cast<float *>(b_obs.p);
-    PCCHK(hipMemcpy(d_prcp, prcp, ns * nd * 4, hipMemcpyHostToDevice));
-    PCCHK(hipMalloc(&b_flag.p, nt * nd));
+    QACHK(hipMemcpy(d_prcp, prcp, ns * nd * 4, hipMemcpyHostToDevice));
+    QACHK(hipMalloc(&b_flag.p, nt * nd));
     uint8_t *d_f = static_cast<uint8_t *>(b_flag.p);
-    PCCHK(hipMemcpy(d_f, flags, nt * nd, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_f, flags, nt * nd, hipMemcpyHostToDevice));
     const size_t ny = (size_t)cal.nyears;
-    PCCHK(hipMalloc(&b_cal.p, ny * 8 + nd * 4));                  // years (int2), row, mday (uint16)
+    QACHK(hipMalloc(&b_cal.p, ny * 8 + nd * 4));                  // years (int2), row, mday (uint16)
     int2 *d_yr = static_cast<int2 *>(b_cal.p);
     uint16_t *d_row = (uint16_t *)(d_yr + ny), *d_mday = d_row + nd;
-    PCCHK(hipMemcpy(d_yr, cal.yr.data(), ny * 8, hipMemcpyHostToDevice));
-    PCCHK(hipMemcpy(d_row, cal.row.data(), nd * 2, hipMemcpyHostToDevice));
-    PCCHK(hipMemcpy(d_mday, cal.mday.data(), nd * 2, hipMemcpyHostToDevice));
-    PCCHK(hipMalloc(&b_slot.p, ns * 4));
-    PCCHK(hipMemcpy(b_slot.p, slot.data(), ns * 4, hipMemcpyHostToDevice));
-    PCCHK(hipMalloc(&b_rows.p, std::max<size_t>(4, nslot * 4)));
-    if (nslot > 0) PCCHK(hipMemcpy(b_rows.p, rows.data(), nslot * 4, hipMemcpyHostToDevice));
-    PCCHK(hipMalloc(&b_cnt.p, (nslot + nt) * PC_ROWS * 2));       // [nslot + nt][366]
+    QACHK(hipMemcpy(d_yr, cal.yr.data(), ny * 8, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_row, cal.row.data(), nd * 2, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_mday, cal.mday.data(), nd * 2, hipMemcpyHostToDevice));
+    QACHK(hipMalloc(&b_slot.p, ns * 4));
+    QACHK(hipMemcpy(b_slot.p, slot.data(), ns * 4, hipMemcpyHostToDevice));
+    QACHK(hipMalloc(&b_rows.p, std::max<size_t>(4, nslot * 4)));
+    if (nslot > 0) QACHK(hipMemcpy(b_rows.p, rows.data(), nslot * 4, hipMemcpyHostToDevice));
+    QACHK(hipMalloc(&b_cnt.p, (nslot + nt) * PC_ROWS * 2));       // [nslot + nt][366]
     uint16_t *d_cntp = static_cast<uint16_t *>(b_cnt.p), *d_cntt = d_cntp + nslot * PC_ROWS;
-    PCCHK(tm.start());
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_pc_rowcounts, dim3((unsigned)(nslot + nt)), dim3(256), 0, nullptr, ndays, (int)nslot,
                        (const int32_t *)b_rows.p, (const int32_t *)d_idx, (const uint16_t *)d_mday, (const float *)d_prcp,
                        (const uint8_t *)d_f, d_cntp);
-    PCCHK(hipGetLastError());
-    PCCHK(tm.stop(&ms[1]));
+    QACHK(hipGetLastError());
+    QACHK(tm.stop_set(&ms[1]));
 
     // ---- 3. the walk ---------------------------------------------------------------------------------------------------
-    PCCHK(hipMalloc(&b_state.p, nt * nd));
+    QACHK(hipMalloc(&b_state.p, nt * nd));
     uint8_t *d_state = static_cast<uint8_t *>(b_state.p);
-    PCCHK(hipMemset(d_state, PC_ST_NONE, nt * nd));
-    PCCHK(hipMalloc(&b_work.p, 3 * nt * nd * 4));                 // first-7 extreme, all-neighbour minimum and maximum
+    QACHK(hipMemset(d_state, PC_ST_NONE, nt * nd));
+    QACHK(hipMalloc(&b_work.p, 3 * nt * nd * 4));                 // first-7 extreme, all-neighbour minimum and maximum
     float *d_ext = static_cast<float *>(b_work.p), *d_lo = d_ext + nt * nd, *d_hi = d_lo + nt * nd;
     double *d_abs = nullptr, *d_pct = nullptr, *d_thr = nullptr;
     const int nout = (abs_dif ? 1 : 0) + (pctile ? 1 : 0) + (thres ? 1 : 0);
     if (nout) {
-        PCCHK(hipMalloc(&b_out.p, (size_t)nout * nt * nd * 8));
-        PCCHK(hipMemset(b_out.p, 0xff, (size_t)nout * nt * nd * 8));      // (all bits set: a NaN)
+        QACHK(hipMalloc(&b_out.p, (size_t)nout * nt * nd * 8));
+        QACHK(hipMemset(b_out.p, 0xff, (size_t)nout * nt * nd * 8));      // (all bits set: a NaN)
         double *p = static_cast<double *>(b_out.p);
         if (abs_dif) { d_abs = p; p += nt * nd; }
         if (pctile) { d_pct = p; p += nt * nd; }
         if (thres) d_thr = p;
     }
-    PCCHK(tm.start());
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_pc_walk, dim3((unsigned)(nt * (size_t)nblk)), dim3(64), 0, nullptr, ndays, nblk,
                        (const float *)d_prcp, (const uint8_t *)d_f, (const int32_t *)d_idx, (const int64_t *)d_off,
                        (const int32_t *)d_csr, (const int32_t *)b_slot.p, (const uint16_t *)d_cntp, (const uint16_t *)d_cntt,
                        (const uint16_t *)d_row, d_state, d_ext, d_lo, d_hi, d_abs, d_thr);
-    PCCHK(hipGetLastError());
-    PCCHK(tm.stop(&ms[2]));
+    QACHK(hipGetLastError());
+    QACHK(tm.stop_set(&ms[2]));
 
     // ---- 4. the rank, the threshold and the flag -----------------------------------------------------------------------
-    PCCHK(tm.start());
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_pc_rank, dim3((unsigned)(nt * PC_ROWS)), dim3(256), 0, nullptr, ndays, cal.nyears,
                        (const int2 *)d_yr, (const uint16_t *)d_row, (const float *)d_prcp, (const uint8_t *)d_f,
                        (const int32_t *)d_idx, d_state, (const float *)d_ext, (const float *)d_lo, (const float *)d_hi,
                        d_pct, d_thr);
-    PCCHK(hipGetLastError());
+    QACHK(hipGetLastError());
     hipLaunchKernelGGL(k_pc_apply, dim3((unsigned)((nt * nd + 255) / 256)), dim3(256), 0, nullptr, (int64_t)(nt * nd),
                        (const uint8_t *)d_state, d_f);
-    PCCHK(hipGetLastError());
-    PCCHK(tm.stop(&ms[3]));
-    PCCHK(hipMemcpy(flags, d_f, nt * nd, hipMemcpyDeviceToHost));
-    if (abs_dif) PCCHK(hipMemcpy(abs_dif, d_abs, nt * nd * 8, hipMemcpyDeviceToHost));
-    if (pctile) PCCHK(hipMemcpy(pctile, d_pct, nt * nd * 8, hipMemcpyDeviceToHost));
-    if (thres) PCCHK(hipMemcpy(thres, d_thr, nt * nd * 8, hipMemcpyDeviceToHost));
+    QACHK(hipGetLastError());
+    QACHK(tm.stop_set(&ms[3]));
+    QACHK(hipMemcpy(flags, d_f, nt * nd, hipMemcpyDeviceToHost));
+    if (abs_dif) QACHK(hipMemcpy(abs_dif, d_abs, nt * nd * 8, hipMemcpyDeviceToHost));
+    if (pctile) QACHK(hipMemcpy(pctile, d_pct, nt * nd * 8, hipMemcpyDeviceToHost));
+    if (thres) QACHK(hipMemcpy(thres, d_thr, nt * nd * 8, hipMemcpyDeviceToHost));
     if (kernel_ms) memcpy(kernel_ms, ms, sizeof ms);
     return 0;
 }
@@ -553,28 +503,28 @@ extern "C" int twxpc_pors_counts(int device, int64_t nstn, int64_t ndays, const 
 {
     if (errbuf && errlen > 0) errbuf[0] = 0;
     if (nstn < 1 || ndays < 1 || nstn > INT32_MAX || ndays > INT32_MAX - 256)
-        return pc_fail(errbuf, errlen, "twxpc_pors_counts: need nstn >= 1 and ndays >= 1");
-    if (!vals || !ymd || !counts) return pc_fail(errbuf, errlen, "twxpc_pors_counts: null buffer");
+        return qa_fail(errbuf, errlen, "twxpc_pors_counts: need nstn >= 1 and ndays >= 1");
+    if (!vals || !ymd || !counts) return qa_fail(errbuf, errlen, "twxpc_pors_counts: null buffer");
     PcCalendar cal;
     if (pc_calendar("twxpc_pors_counts", ndays, ymd, cal, errbuf, errlen) != 0) return -1;
     const size_t ns = (size_t)nstn, nd = (size_t)ndays;
-    PCCHK(hipSetDevice(device));
-    PcBuf b_obs, b_cal, b_cnt;
-    PcTimer tm;
-    PCCHK(tm.init());
-    PCCHK(hipMalloc(&b_obs.p, ns * nd * 4));
-    PCCHK(hipMemcpy(b_obs.p, vals, ns * nd * 4, hipMemcpyHostToDevice));
-    PCCHK(hipMalloc(&b_cal.p, nd * 2));
-    PCCHK(hipMemcpy(b_cal.p, cal.mday.data(), nd * 2, hipMemcpyHostToDevice));
-    PCCHK(hipMalloc(&b_cnt.p, ns * PC_ROWS * 2));
+    QACHK(hipSetDevice(device));
+    QaBuf b_obs, b_cal, b_cnt;
+    QaTimer tm;
+    QACHK(tm.init());
+    QACHK(hipMalloc(&b_obs.p, ns * nd * 4));
+    QACHK(hipMemcpy(b_obs.p, vals, ns * nd * 4, hipMemcpyHostToDevice));
+    QACHK(hipMalloc(&b_cal.p, nd * 2));
+    QACHK(hipMemcpy(b_cal.p, cal.mday.data(), nd * 2, hipMemcpyHostToDevice));
+    QACHK(hipMalloc(&b_cnt.p, ns * PC_ROWS * 2));
     float ms = 0.0f;
-    PCCHK(tm.start());
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_pc_rowcounts, dim3((unsigned)ns), dim3(256), 0, nullptr, ndays, (int)ns, (const int32_t *)nullptr,
                        (const int32_t *)nullptr, (const uint16_t *)b_cal.p, (const float *)b_obs.p, (const uint8_t *)nullptr,
                        static_cast<uint16_t *>(b_cnt.p));
-    PCCHK(hipGetLastError());
-    PCCHK(tm.stop(&ms));
-    PCCHK(hipMemcpy(counts, b_cnt.p, ns * PC_ROWS * 2, hipMemcpyDeviceToHost));
+    QACHK(hipGetLastError());
+    QACHK(tm.stop_set(&ms));
+    QACHK(hipMemcpy(counts, b_cnt.p, ns * PC_ROWS * 2, hipMemcpyDeviceToHost));
     if (kernel_ms) *kernel_ms = ms;
     return 0;
 }

@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "twx_qa.h"
+#include "twx_qa_common.h"
 
 #define PQ_OK 1                              // qa_prcp.py:37-57
 #define PQ_MISSING 2
@@ -430,46 +431,6 @@ __global__ __launch_bounds__(256) void k_pq_clim(int64_t ndays, int64_t nstn, co
 // ---------------------------------------------------------------------------------
 namespace {
 
-int pq_fail(char *errbuf, int errlen, const char *what, hipError_t e = hipSuccess)
-{
-    if (errbuf && errlen > 0) {
-        if (e != hipSuccess) snprintf(errbuf, (size_t)errlen, "%s: %s", what, hipGetErrorString(e));
-        else snprintf(errbuf, (size_t)errlen, "%s", what);
-    }
-    return -1;
-}
-
-struct PqBuf {
-    void *p = nullptr;
-    ~PqBuf() { if (p) (void)hipFree(p); }
-};
-
-struct PqTimer {                                                 // HIP-event time of a run of launches on the null stream
-    hipEvent_t a = nullptr, b = nullptr;
-    ~PqTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    hipError_t init() { hipError_t e = hipEventCreate(&a); return e != hipSuccess ? e : hipEventCreate(&b); }
-    hipError_t start() { return hipEventRecord(a, nullptr); }
-    hipError_t stop(float *ms)
-    {
-        hipError_t e = hipEventRecord(b, nullptr);
-        if (e == hipSuccess) e = hipEventSynchronize(b);
-        if (e == hipSuccess) e = hipEventElapsedTime(ms, a, b);
-        return e;
-    }
-};
-
-int64_t pq_days_from_civil(int64_t y, int mth, int day)           // days since 1970-01-01, proleptic Gregorian
-{
-    y -= mth <= 2;
-    const int64_t era = (y >= 0 ? y : y - 399) / 400;
-    const int64_t yoe = y - era * 400;
-    const int64_t doy = (153 * (mth + (mth > 2 ? -3 : 9)) + 2) / 5 + day - 1;
-    const int64_t doe = yoe * 365 + yoe / 4 - yoe / 100 + doy;
-    return era * 146097 + doe - 719468;
-}
-
-bool pq_leap(int y) { return (y % 4 == 0 && y % 100 != 0) || y % 400 == 0; }
-
 struct PqCalendar {
     int nyears = 0, ndistinct = 0;
     std::vector<int32_t> yr;        // [nyears][2]: Jan 1's series index, leap
@@ -488,24 +449,24 @@ int pq_calendar(const char *who, int64_t ndays, const int32_t *ymd, bool gap_cap
     const int y0 = a / 10000, m0 = (a / 100) % 100, d0 = a % 100;
     if (a < 10101 || m0 < 1 || m0 > 12 || d0 < 1 || d0 > 31) {
         snprintf(msg, sizeof msg, "%s: ymd[0] is not a date", who);
-        return pq_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     // the years the axis touches, before anything is sized by them
-    const int64_t zlast = pq_days_from_civil(y0, m0, d0) + ndays - 1;
+    const int64_t zlast = qa_days_from_civil(y0, m0, d0) + ndays - 1;
     int64_t ylast = y0 + (ndays - 1) / 366;
-    while (pq_days_from_civil(ylast + 1, 1, 1) <= zlast) ++ylast;
+    while (qa_days_from_civil(ylast + 1, 1, 1) <= zlast) ++ylast;
     const int64_t nyears = ylast - y0 + 1;
     if (nyears * 29 > TWXPQ_MAX_WINDOW_VALUES) {
         snprintf(msg, sizeof msg, "%s: the series touches %lld years; a row of the percentile table holds at most "
                  "TWXPQ_MAX_WINDOW_VALUES = %d values (29 per year, %d years)", who, (long long)nyears,
                  TWXPQ_MAX_WINDOW_VALUES, TWXPQ_MAX_WINDOW_VALUES / 29);
-        return pq_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (gap_cap && nyears * 31 > TWXQA_MAX_GAP_VALUES) {
         snprintf(msg, sizeof msg, "%s: the series touches %lld years; the gap check sorts at most TWXQA_MAX_GAP_VALUES = %d "
                  "values of a calendar month (31 per year, %d years)", who, (long long)nyears, TWXQA_MAX_GAP_VALUES,
                  TWXQA_MAX_GAP_VALUES / 31);
-        return pq_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     c.nyears = (int)nyears;
     c.row.resize((size_t)ndays);
@@ -518,13 +479,13 @@ int pq_calendar(const char *who, int64_t ndays, const int32_t *ymd, bool gap_cap
     static const int mlen[12] = {31, 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31};
     int y = y0, mth = m0, day = d0, k = 0;
     bool seen[12] = {false, false, false, false, false, false, false, false, false, false, false, false};
-    int64_t jan1 = pq_days_from_civil(y0, 1, 1) - pq_days_from_civil(y0, m0, d0);
-    c.yr.assign({(int32_t)jan1, pq_leap(y0) ? 1 : 0});
+    int64_t jan1 = qa_days_from_civil(y0, 1, 1) - qa_days_from_civil(y0, m0, d0);
+    c.yr.assign({(int32_t)jan1, qa_leap(y0) ? 1 : 0});
     for (int64_t i = 0; i < ndays; ++i) {
         if (ymd[i] != y * 10000 + mth * 100 + day) {
             snprintf(msg, sizeof msg, "%s: ymd[%lld] = %d: the days are not consecutive calendar days", who, (long long)i,
                      (int)ymd[i]);
-            return pq_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         c.row[(size_t)i] = (int32_t)(i - jan1);                  // yday - 1 of the day's own year: 0 .. 365
         c.month[(size_t)i] = (uint8_t)mth;
@@ -533,51 +494,41 @@ int pq_calendar(const char *who, int64_t ndays, const int32_t *ymd, bool gap_cap
         if (c.ylen[(size_t)k]++ == 0) c.ystart[(size_t)k] = (int32_t)i;
         const size_t seg = (size_t)k * 12 + (size_t)(mth - 1);
         if (c.mlen[seg]++ == 0) c.mstart[seg] = (int32_t)i;
-        if (++day > mlen[mth - 1] + ((mth == 2 && pq_leap(y)) ? 1 : 0)) {
+        if (++day > mlen[mth - 1] + ((mth == 2 && qa_leap(y)) ? 1 : 0)) {
             day = 1;
             if (++mth > 12) {
                 mth = 1;
                 ++y;
                 jan1 = i + 1;
-                if (i + 1 < ndays) { ++k; c.yr.push_back((int32_t)jan1); c.yr.push_back(pq_leap(y) ? 1 : 0); }
+                if (i + 1 < ndays) { ++k; c.yr.push_back((int32_t)jan1); c.yr.push_back(qa_leap(y) ? 1 : 0); }
             }
         }
     }
     for (int m = 0; m < 12; ++m) c.ndistinct += seen[m] ? 1 : 0;
     if ((int)(c.yr.size() / 2) != c.nyears) {
         snprintf(msg, sizeof msg, "%s: calendar count mismatch", who);
-        return pq_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     return 0;
 }
 
-}  // namespace
-
-#define PQCHK(call)                                                                     \
-    do {                                                                                \
-        hipError_t e_ = (call);                                                         \
-        if (e_ != hipSuccess) return pq_fail(errbuf, errlen, #call, e_);                \
-    } while (0)
-
-namespace {
-
 // the device copy of the calendar; k's pointers point into b.p
-int pq_upload_calendar(const PqCalendar &cal, int64_t ndays, PqBuf &b, PqCal &k, char *errbuf, int errlen)
+int pq_upload_calendar(const PqCalendar &cal, int64_t ndays, QaBuf &b, PqCal &k, char *errbuf, int errlen)
 {
     const size_t nd = (size_t)ndays, ny = (size_t)cal.nyears;
     // int32 tables first (yr, row, ystart, ylen, mstart, mlen), then the bytes (month, yidx)
     const size_t o_yr = 0, o_row = o_yr + ny * 8, o_ys = o_row + nd * 4, o_yl = o_ys + ny * 4, o_ms = o_yl + ny * 4,
                  o_ml = o_ms + ny * 48, o_mth = o_ml + ny * 48, o_yi = o_mth + nd;
-    PQCHK(hipMalloc(&b.p, o_yi + nd));
+    QACHK(hipMalloc(&b.p, o_yi + nd));
     char *dc = static_cast<char *>(b.p);
-    PQCHK(hipMemcpy(dc + o_yr, cal.yr.data(), ny * 8, hipMemcpyHostToDevice));
-    PQCHK(hipMemcpy(dc + o_row, cal.row.data(), nd * 4, hipMemcpyHostToDevice));
-    PQCHK(hipMemcpy(dc + o_ys, cal.ystart.data(), ny * 4, hipMemcpyHostToDevice));
-    PQCHK(hipMemcpy(dc + o_yl, cal.ylen.data(), ny * 4, hipMemcpyHostToDevice));
-    PQCHK(hipMemcpy(dc + o_ms, cal.mstart.data(), ny * 48, hipMemcpyHostToDevice));
-    PQCHK(hipMemcpy(dc + o_ml, cal.mlen.data(), ny * 48, hipMemcpyHostToDevice));
-    PQCHK(hipMemcpy(dc + o_mth, cal.month.data(), nd, hipMemcpyHostToDevice));
-    PQCHK(hipMemcpy(dc + o_yi, cal.yidx.data(), nd, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(dc + o_yr, cal.yr.data(), ny * 8, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(dc + o_row, cal.row.data(), nd * 4, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(dc + o_ys, cal.ystart.data(), ny * 4, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(dc + o_yl, cal.ylen.data(), ny * 4, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(dc + o_ms, cal.mstart.data(), ny * 48, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(dc + o_ml, cal.mlen.data(), ny * 48, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(dc + o_mth, cal.month.data(), nd, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(dc + o_yi, cal.yidx.data(), nd, hipMemcpyHostToDevice));
     k.month = (const uint8_t *)(dc + o_mth);
     k.yidx = (const uint8_t *)(dc + o_yi);
     k.row = (const int32_t *)(dc + o_row);
@@ -605,87 +556,87 @@ extern "C" int twxpq_non_spatial(int device, int64_t nstn, int64_t ndays, const 
 {
     if (errbuf && errlen > 0) errbuf[0] = 0;
     if (!pq_sizes_ok(nstn, ndays))
-        return pq_fail(errbuf, errlen, "twxpq_non_spatial: need nstn >= 1, ndays >= 1 and fewer than 2^31 work items in one call");
-    if (!prcp || !tavg || !ymd || !flag) return pq_fail(errbuf, errlen, "twxpq_non_spatial: null buffer");
+        return qa_fail(errbuf, errlen, "twxpq_non_spatial: need nstn >= 1, ndays >= 1 and fewer than 2^31 work items in one call");
+    if (!prcp || !tavg || !ymd || !flag) return qa_fail(errbuf, errlen, "twxpq_non_spatial: null buffer");
     PqCalendar cal;
     if (pq_calendar("twxpq_non_spatial", ndays, ymd, true, cal, errbuf, errlen) != 0) return -1;
     const size_t ns = (size_t)nstn, nd = (size_t)ndays;
-    PQCHK(hipSetDevice(device));
-    PqBuf b_obs, b_flag, b_cal, b_pct, b_idx, b_cnt, b_mark;
-    PqTimer tm;
-    PQCHK(tm.init());
-    PQCHK(hipMalloc(&b_obs.p, 2 * ns * nd * 4));                  // prcp, then tavg: [2][nstn][ndays]
+    QACHK(hipSetDevice(device));
+    QaBuf b_obs, b_flag, b_cal, b_pct, b_idx, b_cnt, b_mark;
+    QaTimer tm;
+    QACHK(tm.init());
+    QACHK(hipMalloc(&b_obs.p, 2 * ns * nd * 4));                  // prcp, then tavg: [2][nstn][ndays]
     float *d_prcp = static_cast<float *>(b_obs.p), *d_tavg = d_prcp + ns * nd;
-    PQCHK(hipMemcpy(d_prcp, prcp, ns * nd * 4, hipMemcpyHostToDevice));
-    PQCHK(hipMemcpy(d_tavg, tavg, ns * nd * 4, hipMemcpyHostToDevice));
-    PQCHK(hipMalloc(&b_flag.p, ns * nd));
+    QACHK(hipMemcpy(d_prcp, prcp, ns * nd * 4, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_tavg, tavg, ns * nd * 4, hipMemcpyHostToDevice));
+    QACHK(hipMalloc(&b_flag.p, ns * nd));
     uint8_t *d_f = static_cast<uint8_t *>(b_flag.p);
     PqCal k;
     if (pq_upload_calendar(cal, ndays, b_cal, k, errbuf, errlen) != 0) return -1;
     const size_t pct_bytes = ns * PQ_ROWS * PQ_COLS * 8;
-    PQCHK(hipMalloc(&b_pct.p, pct_bytes));                        // [nstn][366][5]
+    QACHK(hipMalloc(&b_pct.p, pct_bytes));                        // [nstn][366][5]
     double *d_pct = static_cast<double *>(b_pct.p);
 
     float ms[TWXPQ_NKERNELS];
     for (int i = 0; i < TWXPQ_NKERNELS; ++i) ms[i] = 0.0f;
     const unsigned g_day = (unsigned)((ns * nd + 255) / 256);
     // ---- missing (2) ---------------------------------------------------------------------------------------------------
-    PQCHK(tm.start());
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_pq_init, dim3(g_day), dim3(256), 0, nullptr, (int64_t)(ns * nd), (const float *)d_prcp, d_f);
-    PQCHK(hipGetLastError());
-    PQCHK(tm.stop(&ms[0]));
+    QACHK(hipGetLastError());
+    QACHK(tm.stop_set(&ms[0]));
     // ---- the duplicates (4, 6, 5), impossible values (8) -----------------------------------------------------------------
-    PQCHK(tm.start());
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_pq_dups, dim3((unsigned)ns), dim3(256), 0, nullptr, ndays, k, (const float *)d_prcp, d_f);
-    PQCHK(hipGetLastError());
-    PQCHK(tm.stop(&ms[1]));
+    QACHK(hipGetLastError());
+    QACHK(tm.stop_set(&ms[1]));
     // ---- optional: streaks (9) ---------------------------------------------------------------------------------------------
     if (streak) {
-        PQCHK(tm.start());
+        QACHK(tm.start());
         hipLaunchKernelGGL(k_pq_streak, dim3((unsigned)ns), dim3(64), 0, nullptr, ndays, (const float *)d_prcp, d_f);
-        PQCHK(hipGetLastError());
-        PQCHK(tm.stop(&ms[2]));
+        QACHK(hipGetLastError());
+        QACHK(tm.stop_set(&ms[2]));
     }
     // ---- optional: frequent values (19), against the table of the series as it stands here ---------------------------------
     if (frequent) {
-        PQCHK(hipMalloc(&b_idx.p, ns * nd * 4));
-        PQCHK(hipMalloc(&b_cnt.p, ns * 4));
-        PQCHK(hipMalloc(&b_mark.p, ns * nd));
-        PQCHK(hipMemset(b_mark.p, 0, ns * nd));
-        PQCHK(tm.start());
+        QACHK(hipMalloc(&b_idx.p, ns * nd * 4));
+        QACHK(hipMalloc(&b_cnt.p, ns * 4));
+        QACHK(hipMalloc(&b_mark.p, ns * nd));
+        QACHK(hipMemset(b_mark.p, 0, ns * nd));
+        QACHK(tm.start());
         hipLaunchKernelGGL(k_pq_pctiles, dim3((unsigned)(ns * PQ_ROWS)), dim3(256), 0, nullptr, ndays, cal.nyears, k.yr,
                            (const float *)d_prcp, (const uint8_t *)d_f, d_pct);
-        PQCHK(hipGetLastError());
+        QACHK(hipGetLastError());
         hipLaunchKernelGGL(k_pq_compact, dim3((unsigned)ns), dim3(256), 0, nullptr, ndays, (const float *)d_prcp,
                            (const uint8_t *)d_f, static_cast<int32_t *>(b_idx.p), static_cast<int32_t *>(b_cnt.p));
-        PQCHK(hipGetLastError());
+        QACHK(hipGetLastError());
         hipLaunchKernelGGL(k_pq_frequent, dim3(g_day), dim3(256), 0, nullptr, ndays, nstn, k.row, (const float *)d_prcp,
                            (const int32_t *)b_idx.p, (const int32_t *)b_cnt.p, (const double *)d_pct,
                            static_cast<uint8_t *>(b_mark.p));
-        PQCHK(hipGetLastError());
+        QACHK(hipGetLastError());
         hipLaunchKernelGGL(k_pq_apply, dim3(g_day), dim3(256), 0, nullptr, (int64_t)(ns * nd),
                            (const uint8_t *)b_mark.p, d_f);
-        PQCHK(hipGetLastError());
-        PQCHK(tm.stop(&ms[3]));
+        QACHK(hipGetLastError());
+        QACHK(tm.stop_set(&ms[3]));
     }
     // ---- gaps (10) ---------------------------------------------------------------------------------------------------------
-    PQCHK(tm.start());
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_pq_gap, dim3((unsigned)(ns * 12)), dim3(256), 0, nullptr, ndays, k, (const float *)d_prcp, d_f);
-    PQCHK(hipGetLastError());
-    PQCHK(tm.stop(&ms[4]));
+    QACHK(hipGetLastError());
+    QACHK(tm.stop_set(&ms[4]));
     // ---- the percentile table of what is left, then the outliers (15) ----------------------------------------------------------
-    PQCHK(tm.start());
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_pq_pctiles, dim3((unsigned)(ns * PQ_ROWS)), dim3(256), 0, nullptr, ndays, cal.nyears, k.yr,
                        (const float *)d_prcp, (const uint8_t *)d_f, d_pct);
-    PQCHK(hipGetLastError());
-    PQCHK(tm.stop(&ms[5]));
-    if (pctiles) PQCHK(hipMemcpy(pctiles, d_pct, pct_bytes, hipMemcpyDeviceToHost));
-    PQCHK(tm.start());
+    QACHK(hipGetLastError());
+    QACHK(tm.stop_set(&ms[5]));
+    if (pctiles) QACHK(hipMemcpy(pctiles, d_pct, pct_bytes, hipMemcpyDeviceToHost));
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_pq_clim, dim3(g_day), dim3(256), 0, nullptr, ndays, nstn, k.row, (const float *)d_prcp,
                        (const float *)d_tavg, (const double *)d_pct, d_f);
-    PQCHK(hipGetLastError());
-    PQCHK(tm.stop(&ms[6]));
-    PQCHK(hipMemcpy(flag, d_f, ns * nd, hipMemcpyDeviceToHost));
+    QACHK(hipGetLastError());
+    QACHK(tm.stop_set(&ms[6]));
+    QACHK(hipMemcpy(flag, d_f, ns * nd, hipMemcpyDeviceToHost));
     if (kernel_ms) memcpy(kernel_ms, ms, sizeof ms);
     return 0;
 }
@@ -695,32 +646,32 @@ extern "C" int twxpq_percentiles(int device, int64_t nstn, int64_t ndays, const 
 {
     if (errbuf && errlen > 0) errbuf[0] = 0;
     if (!pq_sizes_ok(nstn, ndays))
-        return pq_fail(errbuf, errlen, "twxpq_percentiles: need nstn >= 1, ndays >= 1 and fewer than 2^31 work items in one call");
-    if (!vals || !ymd || !pctiles) return pq_fail(errbuf, errlen, "twxpq_percentiles: null buffer");
+        return qa_fail(errbuf, errlen, "twxpq_percentiles: need nstn >= 1, ndays >= 1 and fewer than 2^31 work items in one call");
+    if (!vals || !ymd || !pctiles) return qa_fail(errbuf, errlen, "twxpq_percentiles: null buffer");
     PqCalendar cal;
     if (pq_calendar("twxpq_percentiles", ndays, ymd, false, cal, errbuf, errlen) != 0) return -1;
     const size_t ns = (size_t)nstn, nd = (size_t)ndays;
-    PQCHK(hipSetDevice(device));
-    PqBuf b_obs, b_flag, b_cal, b_pct;
-    PqTimer tm;
-    PQCHK(tm.init());
-    PQCHK(hipMalloc(&b_obs.p, ns * nd * 4));
-    PQCHK(hipMemcpy(b_obs.p, vals, ns * nd * 4, hipMemcpyHostToDevice));
-    PQCHK(hipMalloc(&b_flag.p, ns * nd));
+    QACHK(hipSetDevice(device));
+    QaBuf b_obs, b_flag, b_cal, b_pct;
+    QaTimer tm;
+    QACHK(tm.init());
+    QACHK(hipMalloc(&b_obs.p, ns * nd * 4));
+    QACHK(hipMemcpy(b_obs.p, vals, ns * nd * 4, hipMemcpyHostToDevice));
+    QACHK(hipMalloc(&b_flag.p, ns * nd));
     PqCal k;
     if (pq_upload_calendar(cal, ndays, b_cal, k, errbuf, errlen) != 0) return -1;
     const size_t pct_bytes = ns * PQ_ROWS * PQ_COLS * 8;
-    PQCHK(hipMalloc(&b_pct.p, pct_bytes));
+    QACHK(hipMalloc(&b_pct.p, pct_bytes));
     float ms = 0.0f;
-    PQCHK(tm.start());
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_pq_init, dim3((unsigned)((ns * nd + 255) / 256)), dim3(256), 0, nullptr, (int64_t)(ns * nd),
                        (const float *)b_obs.p, static_cast<uint8_t *>(b_flag.p));
-    PQCHK(hipGetLastError());
+    QACHK(hipGetLastError());
     hipLaunchKernelGGL(k_pq_pctiles, dim3((unsigned)(ns * PQ_ROWS)), dim3(256), 0, nullptr, ndays, cal.nyears, k.yr,
                        (const float *)b_obs.p, (const uint8_t *)b_flag.p, static_cast<double *>(b_pct.p));
-    PQCHK(hipGetLastError());
-    PQCHK(tm.stop(&ms));
-    PQCHK(hipMemcpy(pctiles, b_pct.p, pct_bytes, hipMemcpyDeviceToHost));
+    QACHK(hipGetLastError());
+    QACHK(tm.stop_set(&ms));
+    QACHK(hipMemcpy(pctiles, b_pct.p, pct_bytes, hipMemcpyDeviceToHost));
     if (kernel_ms) *kernel_ms = ms;
     return 0;
 }

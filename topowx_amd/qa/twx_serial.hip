@@ -1,8 +1,8 @@
 // twx_serial.hip -- libtwxqa.so: the serially-complete station database of step18 (create_serially_complete_db,
 // twx/infill/post_infill.py:106-149, with add_monthly_normals / TairAggregate.daily_to_mthly_norms) and step17's check of a
 // whole series (has_bad_infill, scripts/step17_find_bad_infill_stns.py:40-68), as include/twx_qa.h states them
-// (twxsc_serial_complete, twxsc_series_check).  Its own translation unit: the buffer list, the event timer and the block
-// sum it shares with twx_infillchk.hip are restated, nothing there is edited.
+// (twxsc_serial_complete, twxsc_series_check).  Its own translation unit: the block sum it shares with twx_infillchk.hip
+// is restated, nothing there is edited; the buffer list and the event timer are twx_qa_common.h's.
 //
 // A series is one station's ndays <= TWXSC_MAX_DAYS days, station-major.  One workgroup of 256 (4 wavefronts) per series.
 //
@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "twx_qa.h"
+#include "twx_qa_common.h"
 
 #define SC_NW 4                              // wavefronts of a workgroup
 #define SC_THREADS (64 * SC_NW)
@@ -332,47 +333,6 @@ __global__ __launch_bounds__(SC_THREADS) void k_sc_series(const float *__restric
 
 namespace {
 
-int sc_fail(char *errbuf, int errlen, const char *what, hipError_t e = hipSuccess)
-{
-    if (errbuf && errlen > 0) {
-        if (e != hipSuccess) snprintf(errbuf, (size_t)errlen, "%s: %s", what, hipGetErrorString(e));
-        else snprintf(errbuf, (size_t)errlen, "%s", what);
-    }
-    return -1;
-}
-
-struct ScBufs {                                                  // every device allocation of a call, freed together
-    std::vector<void *> p;
-    ~ScBufs() { for (void *x : p) if (x) (void)hipFree(x); }
-    hipError_t get(void **out, size_t bytes)
-    {
-        hipError_t e = hipMalloc(out, bytes ? bytes : 1);
-        if (e == hipSuccess) p.push_back(*out);
-        return e;
-    }
-};
-
-struct ScTimer {                                                 // HIP-event time of a run of launches on the null stream
-    hipEvent_t a = nullptr, b = nullptr;
-    ~ScTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    hipError_t init() { hipError_t e = hipEventCreate(&a); return e != hipSuccess ? e : hipEventCreate(&b); }
-    hipError_t start() { return hipEventRecord(a, nullptr); }
-    hipError_t stop(float *acc)
-    {
-        float ms = 0.0f;
-        hipError_t e = hipEventRecord(b, nullptr);
-        if (e == hipSuccess) e = hipEventSynchronize(b);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
-        *acc += ms;
-        return e;
-    }
-};
-
-float sc_since(std::chrono::steady_clock::time_point t)
-{
-    return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t).count();
-}
-
 // the series of one batch: as many as fit the budget, at least one
 int64_t sc_batch(int64_t workspace_bytes, int64_t ndays, int64_t bytes_a_day)
 {
@@ -381,15 +341,6 @@ int64_t sc_batch(int64_t workspace_bytes, int64_t ndays, int64_t bytes_a_day)
 }
 
 }  // namespace
-
-#define SCCHK(call)                                                                     \
-    do {                                                                                \
-        hipError_t e_ = (call);                                                         \
-        if (e_ != hipSuccess) return sc_fail(errbuf, errlen, #call, e_);                \
-    } while (0)
-#define SCALLOC(bufs, ptr, type, count) SCCHK((bufs).get((void **)&(ptr), (size_t)(count) * sizeof(type)))
-#define SCUP(dst, src, type, count) SCCHK(hipMemcpy((dst), (src), (size_t)(count) * sizeof(type), hipMemcpyHostToDevice))
-#define SCDOWN(dst, src, type, count) SCCHK(hipMemcpy((dst), (src), (size_t)(count) * sizeof(type), hipMemcpyDeviceToHost))
 
 extern "C" int twxsc_serial_complete(int device, int64_t nseries, int64_t ndays, const float *tair,
                                      const float *tair_infilled, const int8_t *flag, int32_t run_threshold, float fill,
@@ -403,26 +354,26 @@ extern "C" int twxsc_serial_complete(int device, int64_t nseries, int64_t ndays,
     if (errbuf && errlen > 0) errbuf[0] = 0;
     if (nseries < 1 || nseries > INT32_MAX / 2 || ndays < 1 || ndays > TWXSC_MAX_DAYS) {
         snprintf(msg, sizeof msg, "%s: need 1 <= nseries <= %d and 1 <= ndays <= %d", fn, INT32_MAX / 2, TWXSC_MAX_DAYS);
-        return sc_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if ((tair_infilled == nullptr) != (flag == nullptr)) {
         snprintf(msg, sizeof msg, "%s: tair_infilled and flag must be given together or both be null", fn);
-        return sc_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     const bool norms = group_first != nullptr;
     if (!tair || !max_run || !nmissing || !all_infill || (flag && (!serial || !flag_out)) ||
         (norms && (!group_ndays || !norm || !norm_nmths))) {
         snprintf(msg, sizeof msg, "%s: null buffer", fn);
-        return sc_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (!std::isfinite(fill)) {
         snprintf(msg, sizeof msg, "%s: fill must be finite", fn);
-        return sc_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (norms) {
         if (ngroups < SC_NMONTHS || ngroups > TWXSC_MAX_GROUPS || ngroups % SC_NMONTHS != 0) {
             snprintf(msg, sizeof msg, "%s: ngroups must be a multiple of 12 in 12 .. %d", fn, TWXSC_MAX_GROUPS);
-            return sc_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         int64_t end = 0;                                         // the first day after the groups so far
         for (int32_t g = 0; g < ngroups; ++g) {
@@ -430,11 +381,11 @@ extern "C" int twxsc_serial_complete(int device, int64_t nseries, int64_t ndays,
             if (nd == 0) continue;
             if (nd < 0 || d0 < 0 || d0 + nd > ndays) {
                 snprintf(msg, sizeof msg, "%s: group %d lies outside the day axis", fn, (int)g);
-                return sc_fail(errbuf, errlen, msg);
+                return qa_fail(errbuf, errlen, msg);
             }
             if (d0 < end) {
                 snprintf(msg, sizeof msg, "%s: group %d is not after the groups before it (ascending, disjoint)", fn, (int)g);
-                return sc_fail(errbuf, errlen, msg);
+                return qa_fail(errbuf, errlen, msg);
             }
             end = d0 + nd;
         }
@@ -445,64 +396,64 @@ extern "C" int twxsc_serial_complete(int device, int64_t nseries, int64_t ndays,
     const int64_t per = sc_batch(workspace_bytes, ndays, bytes_a_day);
     const size_t NBMAX = (size_t)(per < nseries ? per : nseries);
 
-    SCCHK(hipSetDevice(device));
-    ScBufs bufs;
+    QACHK(hipSetDevice(device));
+    QaPool bufs;
     int32_t *d_run, *d_miss, *d_nm = nullptr, *d_gf = nullptr, *d_gn = nullptr;
     uint8_t *d_all;
     double *d_norm = nullptr;
     float *w_tair, *w_tinf = nullptr, *w_serial = nullptr;
     int8_t *w_flag = nullptr, *w_fout = nullptr;
     const auto t_alloc = std::chrono::steady_clock::now();
-    SCALLOC(bufs, d_run, int32_t, NS); SCALLOC(bufs, d_miss, int32_t, NS); SCALLOC(bufs, d_all, uint8_t, NS);
+    QAALLOC(bufs, d_run, int32_t, NS); QAALLOC(bufs, d_miss, int32_t, NS); QAALLOC(bufs, d_all, uint8_t, NS);
     if (norms) {
-        SCALLOC(bufs, d_norm, double, NS * SC_NMONTHS); SCALLOC(bufs, d_nm, int32_t, NS * SC_NMONTHS);
-        SCALLOC(bufs, d_gf, int32_t, ngroups); SCALLOC(bufs, d_gn, int32_t, ngroups);
-        SCUP(d_gf, group_first, int32_t, ngroups);
-        SCUP(d_gn, group_ndays, int32_t, ngroups);
+        QAALLOC(bufs, d_norm, double, NS * SC_NMONTHS); QAALLOC(bufs, d_nm, int32_t, NS * SC_NMONTHS);
+        QAALLOC(bufs, d_gf, int32_t, ngroups); QAALLOC(bufs, d_gn, int32_t, ngroups);
+        QAUP(d_gf, group_first, int32_t, ngroups);
+        QAUP(d_gn, group_ndays, int32_t, ngroups);
     }
-    SCALLOC(bufs, w_tair, float, NBMAX * ND);
-    if (flag) { SCALLOC(bufs, w_tinf, float, NBMAX * ND); SCALLOC(bufs, w_flag, int8_t, NBMAX * ND); }
-    if (serial) SCALLOC(bufs, w_serial, float, NBMAX * ND);
-    if (flag_out) SCALLOC(bufs, w_fout, int8_t, NBMAX * ND);
-    ScTimer tm;
+    QAALLOC(bufs, w_tair, float, NBMAX * ND);
+    if (flag) { QAALLOC(bufs, w_tinf, float, NBMAX * ND); QAALLOC(bufs, w_flag, int8_t, NBMAX * ND); }
+    if (serial) QAALLOC(bufs, w_serial, float, NBMAX * ND);
+    if (flag_out) QAALLOC(bufs, w_fout, int8_t, NBMAX * ND);
+    QaTimer tm;
     float ms[TWXSC_NTIMES] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (kernel_ms) { SCCHK(tm.init()); ms[2] = sc_since(t_alloc); }
+    if (kernel_ms) { QACHK(tm.init()); ms[2] = qa_since(t_alloc); }
     int nbatches = 0, nlaunches = 0;
     for (int64_t first = 0; first < nseries; first += per) {     // runs of series that fit the budget
         const size_t NB = (size_t)(nseries - first < per ? nseries - first : per);
         const size_t at = (size_t)first * ND;
         const auto t_up = std::chrono::steady_clock::now();
-        SCUP(w_tair, tair + at, float, NB * ND);
-        if (flag) { SCUP(w_tinf, tair_infilled + at, float, NB * ND); SCUP(w_flag, flag + at, int8_t, NB * ND); }
+        QAUP(w_tair, tair + at, float, NB * ND);
+        if (flag) { QAUP(w_tinf, tair_infilled + at, float, NB * ND); QAUP(w_flag, flag + at, int8_t, NB * ND); }
         ++nbatches;
-        if (kernel_ms) { SCCHK(hipDeviceSynchronize()); ms[2] += sc_since(t_up); SCCHK(tm.start()); }
+        if (kernel_ms) { QACHK(hipDeviceSynchronize()); ms[2] += qa_since(t_up); QACHK(tm.start()); }
         hipLaunchKernelGGL(k_sc_select, dim3((unsigned)NB), dim3(SC_THREADS), 0, nullptr, (const float *)w_tair,
                            (const float *)w_tinf, (const int8_t *)w_flag, (int)ndays, (int)run_threshold, fill, w_serial,
                            w_fout, first, d_run, d_miss, d_all);
-        SCCHK(hipGetLastError());
+        QACHK(hipGetLastError());
         ++nlaunches;
-        if (kernel_ms) { SCCHK(tm.stop(&ms[0])); }
+        if (kernel_ms) { QACHK(tm.stop_add(&ms[0])); }
         if (norms) {
-            if (kernel_ms) SCCHK(tm.start());
+            if (kernel_ms) QACHK(tm.start());
             hipLaunchKernelGGL(k_sc_norms, dim3((unsigned)NB), dim3(SC_THREADS), 0, nullptr, (const float *)w_tair,
                                (const float *)w_tinf, (const uint8_t *)d_all, (int)ndays, fill, (int)ngroups,
                                (const int32_t *)d_gf, (const int32_t *)d_gn, (int)max_miss, first, d_norm, d_nm);
-            SCCHK(hipGetLastError());
+            QACHK(hipGetLastError());
             ++nlaunches;
-            if (kernel_ms) { SCCHK(tm.stop(&ms[1])); }
+            if (kernel_ms) { QACHK(tm.stop_add(&ms[1])); }
         }
         const auto t_down = std::chrono::steady_clock::now();    // the copies wait for the launches (null stream)
-        if (serial) SCDOWN(serial + at, w_serial, float, NB * ND);
-        if (flag_out) SCDOWN(flag_out + at, w_fout, int8_t, NB * ND);
-        if (!serial && !flag_out) SCCHK(hipDeviceSynchronize()); // the next batch overwrites the inputs
-        ms[3] += sc_since(t_down);
+        if (serial) QADOWN(serial + at, w_serial, float, NB * ND);
+        if (flag_out) QADOWN(flag_out + at, w_fout, int8_t, NB * ND);
+        if (!serial && !flag_out) QACHK(hipDeviceSynchronize()); // the next batch overwrites the inputs
+        ms[3] += qa_since(t_down);
     }
     const auto t_down = std::chrono::steady_clock::now();
-    SCDOWN(max_run, d_run, int32_t, NS);
-    SCDOWN(nmissing, d_miss, int32_t, NS);
-    SCDOWN(all_infill, d_all, uint8_t, NS);
-    if (norms) { SCDOWN(norm, d_norm, double, NS * SC_NMONTHS); SCDOWN(norm_nmths, d_nm, int32_t, NS * SC_NMONTHS); }
-    ms[3] += sc_since(t_down);
+    QADOWN(max_run, d_run, int32_t, NS);
+    QADOWN(nmissing, d_miss, int32_t, NS);
+    QADOWN(all_infill, d_all, uint8_t, NS);
+    if (norms) { QADOWN(norm, d_norm, double, NS * SC_NMONTHS); QADOWN(norm_nmths, d_nm, int32_t, NS * SC_NMONTHS); }
+    ms[3] += qa_since(t_down);
     if (counts) { counts[0] = nlaunches; counts[1] = nbatches; }
     if (kernel_ms) memcpy(kernel_ms, ms, sizeof ms);
     return 0;
@@ -519,54 +470,54 @@ extern "C" int twxsc_series_check(int device, int64_t nseries, int64_t ndays, co
     if (errbuf && errlen > 0) errbuf[0] = 0;
     if (nseries < 1 || nseries > INT32_MAX / 2 || ndays < 1 || ndays > TWXSC_MAX_DAYS) {
         snprintf(msg, sizeof msg, "%s: need 1 <= nseries <= %d and 1 <= ndays <= %d", fn, INT32_MAX / 2, TWXSC_MAX_DAYS);
-        return sc_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (!series || !nimpossible || !nmissing || !cpt_stat || !cpt_tau || !reasons || !status) {
         snprintf(msg, sizeof msg, "%s: null buffer", fn);
-        return sc_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (!std::isfinite(fill) || !std::isfinite(impossible_high) || !std::isfinite(impossible_low)) {
         snprintf(msg, sizeof msg, "%s: fill, impossible_high and impossible_low must be finite", fn);
-        return sc_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (workspace_bytes <= 0) workspace_bytes = TWXSC_WORKSPACE_BYTES;
     const size_t NS = (size_t)nseries, ND = (size_t)ndays;
     const int64_t per = sc_batch(workspace_bytes, ndays, 4);
     const size_t NBMAX = (size_t)(per < nseries ? per : nseries);
 
-    SCCHK(hipSetDevice(device));
-    ScBufs bufs;
+    QACHK(hipSetDevice(device));
+    QaPool bufs;
     ScChk d_out;
     float *w_series;
     const auto t_alloc = std::chrono::steady_clock::now();
-    SCALLOC(bufs, d_out.nimpossible, int32_t, NS); SCALLOC(bufs, d_out.nmissing, int32_t, NS);
-    SCALLOC(bufs, d_out.cpt_tau, int32_t, NS); SCALLOC(bufs, d_out.reasons, int32_t, NS);
-    SCALLOC(bufs, d_out.status, int32_t, NS); SCALLOC(bufs, d_out.cpt_stat, double, NS);
-    SCALLOC(bufs, w_series, float, NBMAX * ND);
-    ScTimer tm;
+    QAALLOC(bufs, d_out.nimpossible, int32_t, NS); QAALLOC(bufs, d_out.nmissing, int32_t, NS);
+    QAALLOC(bufs, d_out.cpt_tau, int32_t, NS); QAALLOC(bufs, d_out.reasons, int32_t, NS);
+    QAALLOC(bufs, d_out.status, int32_t, NS); QAALLOC(bufs, d_out.cpt_stat, double, NS);
+    QAALLOC(bufs, w_series, float, NBMAX * ND);
+    QaTimer tm;
     float ms[TWXSC_NTIMES] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (kernel_ms) { SCCHK(tm.init()); ms[2] = sc_since(t_alloc); }
+    if (kernel_ms) { QACHK(tm.init()); ms[2] = qa_since(t_alloc); }
     int nbatches = 0;
     for (int64_t first = 0; first < nseries; first += per) {
         const size_t NB = (size_t)(nseries - first < per ? nseries - first : per);
         const auto t_up = std::chrono::steady_clock::now();
-        SCUP(w_series, series + (size_t)first * ND, float, NB * ND);
+        QAUP(w_series, series + (size_t)first * ND, float, NB * ND);
         ++nbatches;
-        if (kernel_ms) { SCCHK(hipDeviceSynchronize()); ms[2] += sc_since(t_up); SCCHK(tm.start()); }
+        if (kernel_ms) { QACHK(hipDeviceSynchronize()); ms[2] += qa_since(t_up); QACHK(tm.start()); }
         hipLaunchKernelGGL(k_sc_series, dim3((unsigned)NB), dim3(SC_THREADS), 0, nullptr, (const float *)w_series, (int)ndays,
                            fill, pen, impossible_high, impossible_low, first, d_out);
-        SCCHK(hipGetLastError());
-        if (kernel_ms) SCCHK(tm.stop(&ms[0]));
-        else SCCHK(hipDeviceSynchronize());                      // the next batch overwrites the rows
+        QACHK(hipGetLastError());
+        if (kernel_ms) QACHK(tm.stop_add(&ms[0]));
+        else QACHK(hipDeviceSynchronize());                      // the next batch overwrites the rows
     }
     const auto t_down = std::chrono::steady_clock::now();
-    SCDOWN(nimpossible, d_out.nimpossible, int32_t, NS);
-    SCDOWN(nmissing, d_out.nmissing, int32_t, NS);
-    SCDOWN(cpt_tau, d_out.cpt_tau, int32_t, NS);
-    SCDOWN(reasons, d_out.reasons, int32_t, NS);
-    SCDOWN(status, d_out.status, int32_t, NS);
-    SCDOWN(cpt_stat, d_out.cpt_stat, double, NS);
-    ms[3] = sc_since(t_down);
+    QADOWN(nimpossible, d_out.nimpossible, int32_t, NS);
+    QADOWN(nmissing, d_out.nmissing, int32_t, NS);
+    QADOWN(cpt_tau, d_out.cpt_tau, int32_t, NS);
+    QADOWN(reasons, d_out.reasons, int32_t, NS);
+    QADOWN(status, d_out.status, int32_t, NS);
+    QADOWN(cpt_stat, d_out.cpt_stat, double, NS);
+    ms[3] = qa_since(t_down);
     if (counts) { counts[0] = nbatches; counts[1] = nbatches; }
     if (kernel_ms) memcpy(kernel_ms, ms, sizeof ms);
     return 0;

@@ -37,9 +37,8 @@
 #include <vector>
 
 #include "twx_qa.h"
+#include "twx_qa_common.h"
 
-#define SP_RADIAN 0.017453292519943295       // util_geo.py:21
-#define SP_EARTH_KM 6371.009                 // util_geo.py:22
 #define SP_NGH_CORR 0.8                      // qa_temp.py:67
 #define SP_RESID_CUTOFF 8.0                  // qa_temp.py:68
 #define SP_RESID_STD_CUTOFF 4.0              // qa_temp.py:69
@@ -91,7 +90,7 @@ __global__ __launch_bounds__(256) void k_qa_radius(int64_t nstn, const double *_
     const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (t >= ntarget) return;                                // wave-uniform: one target per wave
     const int32_t self = target_idx[t];
-    const double lat1rad = lat[self] * SP_RADIAN, lon1rad = lon[self] * SP_RADIAN;
+    const double lat1rad = lat[self] * QA_RADIAN, lon1rad = lon[self] * QA_RADIAN;
     const double cos1 = cos(lat1rad);
     int64_t pos = 0, room = 0;
     if (fill) {                                              // a target over the cap has an empty list (off[t+1] == off[t])
@@ -104,11 +103,7 @@ __global__ __launch_bounds__(256) void k_qa_radius(int64_t nstn, const double *_
         const int64_t j = j0 + lane;
         bool in = false;
         if (j < nstn && j != self) {
-            const double lat2rad = lat[j] * SP_RADIAN, lon2rad = lon[j] * SP_RADIAN;
-            const double s1 = sin((lat1rad - lat2rad) / 2.0), s2 = sin((lon1rad - lon2rad) / 2.0);
-            const double a = s1 * s1 + (cos1 * cos(lat2rad)) * (s2 * s2);
-            const double dist = SP_EARTH_KM * (2.0 * asin(sqrt(a)));
-            in = dist <= TWXQA_NGH_RADIUS_KM;
+            in = qa_dist_km(lat1rad, lon1rad, cos1, lat[j], lon[j]) <= TWXQA_NGH_RADIUS_KM;
         }
         const uint64_t b = __ballot(in);
         if (fill && in) {
@@ -277,37 +272,7 @@ __global__ __launch_bounds__(64) void k_spatial_regress(int64_t ndays, int nmont
 // ---------------------------------------------------------------------------------
 namespace {
 
-int sp_fail(char *errbuf, int errlen, const char *what, hipError_t e = hipSuccess)
-{
-    if (errbuf && errlen > 0) {
-        if (e != hipSuccess) snprintf(errbuf, (size_t)errlen, "%s: %s", what, hipGetErrorString(e));
-        else snprintf(errbuf, (size_t)errlen, "%s", what);
-    }
-    return -1;
-}
-
-struct SpBuf {
-    void *p = nullptr;
-    ~SpBuf() { if (p) (void)hipFree(p); }
-};
-
-struct SpEvents {
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~SpEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-};
-
-// days since 1970-01-01 of a proleptic Gregorian date, and back
-int64_t days_from_civil(int64_t y, int mth, int day)
-{
-    y -= mth <= 2;
-    const int64_t era = (y >= 0 ? y : y - 399) / 400;
-    const int64_t yoe = y - era * 400;
-    const int64_t doy = (153 * (mth + (mth > 2 ? -3 : 9)) + 2) / 5 + day - 1;
-    const int64_t doe = yoe * 365 + yoe / 4 - yoe / 100 + doy;
-    return era * 146097 + doe - 719468;
-}
-
-int32_t ymd_from_days(int64_t z)
+int32_t ymd_from_days(int64_t z)                                 // the inverse of qa_days_from_civil, as yyyymmdd
 {
     z += 719468;
     const int64_t era = (z >= 0 ? z : z - 146096) / 146097;
@@ -322,12 +287,6 @@ int32_t ymd_from_days(int64_t z)
 }
 
 }  // namespace
-
-#define SPCHK(call)                                                                     \
-    do {                                                                                \
-        hipError_t e_ = (call);                                                         \
-        if (e_ != hipSuccess) return sp_fail(errbuf, errlen, #call, e_);                \
-    } while (0)
 
 extern "C" int twxqa_spatial_nmonths(int64_t ndays, const int32_t *ymd)
 {
@@ -345,44 +304,44 @@ extern "C" int twxqa_spatial_regress(int device, int64_t nstn, int64_t ndays, co
 {
     if (errbuf && errlen > 0) errbuf[0] = 0;
     if (nstn < 1 || ndays < 1 || ntarget < 1 || nstn > INT32_MAX || ndays > INT32_MAX - 64 || ntarget > INT32_MAX)
-        return sp_fail(errbuf, errlen, "twxqa_spatial_regress: need nstn >= 1, ndays >= 1 and ntarget >= 1");
+        return qa_fail(errbuf, errlen, "twxqa_spatial_regress: need nstn >= 1, ndays >= 1 and ntarget >= 1");
     if (!lon || !lat || !tmin || !tmax || !ymd || !target_idx || !flag_tmin || !flag_tmax)
-        return sp_fail(errbuf, errlen, "twxqa_spatial_regress: null buffer");
+        return qa_fail(errbuf, errlen, "twxqa_spatial_regress: null buffer");
     char msg[192];
     for (int64_t i = 0; i < nstn; ++i) {
         if (!std::isfinite(lon[i]) || !std::isfinite(lat[i])) {
             snprintf(msg, sizeof msg, "twxqa_spatial_regress: non-finite longitude / latitude of station %lld", (long long)i);
-            return sp_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
     }
     for (int64_t i = 0; i < ntarget; ++i) {
         if (target_idx[i] < 0 || target_idx[i] >= nstn) {
             snprintf(msg, sizeof msg, "twxqa_spatial_regress: target index %d (entry %lld) outside [0, %lld)",
                      (int)target_idx[i], (long long)i, (long long)nstn);
-            return sp_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
     }
     // the day axis: a valid first date, then consecutive calendar days
     const int32_t ymd0 = ymd[0];
     const int y0 = ymd0 / 10000, m0 = (ymd0 / 100) % 100, dd0 = ymd0 % 100;
-    if (ymd0 < 10101 || m0 < 1 || m0 > 12 || dd0 < 1) return sp_fail(errbuf, errlen, "twxqa_spatial_regress: ymd[0] is not a date");
-    const int64_t z0 = days_from_civil(y0, m0, dd0);
+    if (ymd0 < 10101 || m0 < 1 || m0 > 12 || dd0 < 1) return qa_fail(errbuf, errlen, "twxqa_spatial_regress: ymd[0] is not a date");
+    const int64_t z0 = qa_days_from_civil(y0, m0, dd0);
     for (int64_t i = 0; i < ndays; ++i) {
         if (ymd_from_days(z0 + i) != ymd[i]) {
             snprintf(msg, sizeof msg, "twxqa_spatial_regress: ymd[%lld] = %d: the days are not consecutive calendar days",
                      (long long)i, (int)ymd[i]);
-            return sp_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
     }
     // one item per calendar month the series touches: window [ws, we) = month -+ 15 days, month [ms, me), clipped
     const int nmonths = twxqa_spatial_nmonths(ndays, ymd);
     if (nmonths < 1 || (int64_t)nmonths * 2 * ntarget > INT32_MAX)
-        return sp_fail(errbuf, errlen, "twxqa_spatial_regress: more than 2^31 - 1 items in one call");
+        return qa_fail(errbuf, errlen, "twxqa_spatial_regress: more than 2^31 - 1 items in one call");
     std::vector<int32_t> mon((size_t)nmonths * 4);
     for (int k = 0; k < nmonths; ++k) {
         const int mi = m0 - 1 + k, y = y0 + mi / 12, mth = mi % 12 + 1;
-        const int64_t a = days_from_civil(y, mth, 1) - z0;
-        const int64_t b = days_from_civil(mth == 12 ? y + 1 : y, mth == 12 ? 1 : mth + 1, 1) - z0;
+        const int64_t a = qa_days_from_civil(y, mth, 1) - z0;
+        const int64_t b = qa_days_from_civil(mth == 12 ? y + 1 : y, mth == 12 ? 1 : mth + 1, 1) - z0;
         mon[4 * k + 0] = (int32_t)std::max<int64_t>(0, a - SP_MTH_BUFFER);
         mon[4 * k + 1] = (int32_t)std::min<int64_t>(ndays, b + SP_MTH_BUFFER);
         mon[4 * k + 2] = (int32_t)std::max<int64_t>(0, a);
@@ -390,88 +349,85 @@ extern "C" int twxqa_spatial_regress(int device, int64_t nstn, int64_t ndays, co
     }
     const size_t nitems = (size_t)nmonths * 2 * (size_t)ntarget, nt = (size_t)ntarget, ns = (size_t)nstn, nd = (size_t)ndays;
 
-    SPCHK(hipSetDevice(device));
-    SpBuf b_geo, b_obs, b_tgt, b_csr, b_flag, b_est, b_item;
-    SPCHK(hipMalloc(&b_geo.p, ns * 16));
+    QACHK(hipSetDevice(device));
+    QaBuf b_geo, b_obs, b_tgt, b_csr, b_flag, b_est, b_item;
+    QACHK(hipMalloc(&b_geo.p, ns * 16));
     double *d_lon = static_cast<double *>(b_geo.p), *d_lat = d_lon + ns;
-    SPCHK(hipMemcpy(d_lon, lon, ns * 8, hipMemcpyHostToDevice));
-    SPCHK(hipMemcpy(d_lat, lat, ns * 8, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_lon, lon, ns * 8, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_lat, lat, ns * 8, hipMemcpyHostToDevice));
     // per target: csr offsets (int64, nt + 1), index, count, status; then the month table
     const size_t off_off = 0, off_idx = off_off + (nt + 1) * 8, off_cnt = off_idx + nt * 4, off_st = off_cnt + nt * 4,
                  off_mon = (off_st + nt * 4 + 15) / 16 * 16, tgt_total = off_mon + (size_t)nmonths * 16;
-    SPCHK(hipMalloc(&b_tgt.p, tgt_total));
+    QACHK(hipMalloc(&b_tgt.p, tgt_total));
     char *dt = static_cast<char *>(b_tgt.p);
     int64_t *d_off = (int64_t *)(dt + off_off);
     int32_t *d_idx = (int32_t *)(dt + off_idx), *d_cnt = (int32_t *)(dt + off_cnt), *d_st = (int32_t *)(dt + off_st);
-    SPCHK(hipMemcpy(d_idx, target_idx, nt * 4, hipMemcpyHostToDevice));
-    SPCHK(hipMemcpy(dt + off_mon, mon.data(), (size_t)nmonths * 16, hipMemcpyHostToDevice));
-    SpEvents ev;
-    for (hipEvent_t &x : ev.e) SPCHK(hipEventCreate(&x));
+    QACHK(hipMemcpy(d_idx, target_idx, nt * 4, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(dt + off_mon, mon.data(), (size_t)nmonths * 16, hipMemcpyHostToDevice));
+    QaTimer tm, tm_fill;                                     // two pairs: the count pass is read after the fill pass
+    QACHK(tm.init());
+    QACHK(tm_fill.init());
 
     // ---- the radius lists: count, scan on the host, fill ---------------------------------------------------------
     const dim3 rgrid((unsigned)((ntarget + 3) / 4));
-    SPCHK(hipEventRecord(ev.e[0], nullptr));
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_qa_radius, rgrid, dim3(256), 0, nullptr, nstn, (const double *)d_lon, (const double *)d_lat, ntarget,
                        (const int32_t *)d_idx, 0, d_cnt, (const int64_t *)nullptr, (int32_t *)nullptr);
-    SPCHK(hipGetLastError());
-    SPCHK(hipEventRecord(ev.e[1], nullptr));
+    QACHK(hipGetLastError());
+    QACHK(hipEventRecord(tm.b, nullptr));                    // not stop_set(): the copy of the counts below waits for it
     std::vector<int32_t> cnt(nt), tst(nt);
     std::vector<int64_t> off(nt + 1);
-    SPCHK(hipMemcpy(cnt.data(), d_cnt, nt * 4, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(cnt.data(), d_cnt, nt * 4, hipMemcpyDeviceToHost));
     off[0] = 0;
     for (size_t i = 0; i < nt; ++i) {                        // a list above the cap is not built: the target says so
         tst[i] = cnt[i] > TWXQA_MAX_RADIUS_NGH ? TWXQA_SP_NGH_CAP : TWXQA_SP_OK;
         off[i + 1] = off[i] + (tst[i] == TWXQA_SP_OK ? cnt[i] : 0);
     }
-    SPCHK(hipMemcpy(d_off, off.data(), (nt + 1) * 8, hipMemcpyHostToDevice));
-    SPCHK(hipMemcpy(d_st, tst.data(), nt * 4, hipMemcpyHostToDevice));
-    SPCHK(hipMalloc(&b_csr.p, std::max<size_t>(4, (size_t)off[nt] * 4)));
+    QACHK(hipMemcpy(d_off, off.data(), (nt + 1) * 8, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_st, tst.data(), nt * 4, hipMemcpyHostToDevice));
+    QACHK(hipMalloc(&b_csr.p, std::max<size_t>(4, (size_t)off[nt] * 4)));
     int32_t *d_csr = static_cast<int32_t *>(b_csr.p);
     float ms_fill = 0.0f;
     if (off[nt] > 0) {
-        SPCHK(hipEventRecord(ev.e[2], nullptr));
+        QACHK(tm_fill.start());
         hipLaunchKernelGGL(k_qa_radius, rgrid, dim3(256), 0, nullptr, nstn, (const double *)d_lon, (const double *)d_lat,
                            ntarget, (const int32_t *)d_idx, 1, d_cnt, (const int64_t *)d_off, d_csr);
-        SPCHK(hipGetLastError());
-        SPCHK(hipEventRecord(ev.e[3], nullptr));
-        SPCHK(hipEventSynchronize(ev.e[3]));
-        SPCHK(hipEventElapsedTime(&ms_fill, ev.e[2], ev.e[3]));
+        QACHK(hipGetLastError());
+        QACHK(tm_fill.stop_set(&ms_fill));
     }
     float ms_count = 0.0f;
-    SPCHK(hipEventElapsedTime(&ms_count, ev.e[0], ev.e[1]));
+    QACHK(hipEventElapsedTime(&ms_count, tm.a, tm.b));
 
     // ---- the items ----------------------------------------------------------------------------------------------
-    SPCHK(hipMalloc(&b_obs.p, 2 * ns * nd * 4));
+    QACHK(hipMalloc(&b_obs.p, 2 * ns * nd * 4));
     float *d_tmin = static_cast<float *>(b_obs.p), *d_tmax = d_tmin + ns * nd;
-    SPCHK(hipMemcpy(d_tmin, tmin, ns * nd * 4, hipMemcpyHostToDevice));
-    SPCHK(hipMemcpy(d_tmax, tmax, ns * nd * 4, hipMemcpyHostToDevice));
-    SPCHK(hipMalloc(&b_flag.p, 2 * nt * nd));
+    QACHK(hipMemcpy(d_tmin, tmin, ns * nd * 4, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_tmax, tmax, ns * nd * 4, hipMemcpyHostToDevice));
+    QACHK(hipMalloc(&b_flag.p, 2 * nt * nd));
     uint8_t *d_fmin = static_cast<uint8_t *>(b_flag.p), *d_fmax = d_fmin + nt * nd;
-    SPCHK(hipMemset(d_fmin, 0, 2 * nt * nd));
+    QACHK(hipMemset(d_fmin, 0, 2 * nt * nd));
     double *d_est = nullptr;
     if (est) {                                               // all-ones bytes are a NaN: days without an estimate stay so
-        SPCHK(hipMalloc(&b_est.p, nt * 2 * nd * 8));
+        QACHK(hipMalloc(&b_est.p, nt * 2 * nd * 8));
         d_est = static_cast<double *>(b_est.p);
-        SPCHK(hipMemset(d_est, 0xff, nt * 2 * nd * 8));
+        QACHK(hipMemset(d_est, 0xff, nt * 2 * nd * 8));
     }
-    SPCHK(hipMalloc(&b_item.p, nitems * 16));
+    QACHK(hipMalloc(&b_item.p, nitems * 16));
     double *d_r = static_cast<double *>(b_item.p);
     int32_t *d_nv = (int32_t *)(d_r + nitems), *d_ist = d_nv + nitems;
-    SPCHK(hipEventRecord(ev.e[0], nullptr));
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_spatial_regress, dim3((unsigned)nitems), dim3(64), 0, nullptr, ndays, nmonths, (const float *)d_tmin,
                        (const float *)d_tmax, (const int4 *)(dt + off_mon), (const int32_t *)d_idx, (const int32_t *)d_st,
                        (const int64_t *)d_off, (const int32_t *)d_csr, d_fmin, d_fmax, d_est, d_r, d_nv, d_ist);
-    SPCHK(hipGetLastError());
-    SPCHK(hipEventRecord(ev.e[1], nullptr));
-    SPCHK(hipEventSynchronize(ev.e[1]));
+    QACHK(hipGetLastError());
     float ms_items = 0.0f;
-    SPCHK(hipEventElapsedTime(&ms_items, ev.e[0], ev.e[1]));
+    QACHK(tm.stop_set(&ms_items));
     if (kernel_ms) { kernel_ms[0] = ms_count + ms_fill; kernel_ms[1] = ms_items; }
-    SPCHK(hipMemcpy(flag_tmin, d_fmin, nt * nd, hipMemcpyDeviceToHost));
-    SPCHK(hipMemcpy(flag_tmax, d_fmax, nt * nd, hipMemcpyDeviceToHost));
-    if (est) SPCHK(hipMemcpy(est, d_est, nt * 2 * nd * 8, hipMemcpyDeviceToHost));
-    if (item_r) SPCHK(hipMemcpy(item_r, d_r, nitems * 8, hipMemcpyDeviceToHost));
-    if (item_nvalid) SPCHK(hipMemcpy(item_nvalid, d_nv, nitems * 4, hipMemcpyDeviceToHost));
-    if (item_status) SPCHK(hipMemcpy(item_status, d_ist, nitems * 4, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(flag_tmin, d_fmin, nt * nd, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(flag_tmax, d_fmax, nt * nd, hipMemcpyDeviceToHost));
+    if (est) QACHK(hipMemcpy(est, d_est, nt * 2 * nd * 8, hipMemcpyDeviceToHost));
+    if (item_r) QACHK(hipMemcpy(item_r, d_r, nitems * 8, hipMemcpyDeviceToHost));
+    if (item_nvalid) QACHK(hipMemcpy(item_nvalid, d_nv, nitems * 4, hipMemcpyDeviceToHost));
+    if (item_status) QACHK(hipMemcpy(item_status, d_ist, nitems * 4, hipMemcpyDeviceToHost));
     return 0;
 }

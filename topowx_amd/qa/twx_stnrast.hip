@@ -2,8 +2,8 @@
 // twx/infill/post_infill.py:248-352 and :443-510, of scripts/step19_add_raster_predictors.py) and the front of step20
 // (find_dup_stns, post_infill.py:193-246, and the "no good station has a missing value" check of
 // scripts/step20_add_bad_stn_flag.py:102-112), as include/twx_qa.h states them (twxrv_sample, twxrv_nearest_data,
-// twxrv_dup_classes, twxrv_col_count).  Its own translation unit: the buffer list and the event timer it shares with
-// twx_serial.hip are restated, nothing there is edited.
+// twxrv_dup_classes, twxrv_col_count).  Its own translation unit; the buffer list and the event timer it shares with
+// the other units are twx_qa_common.h's.
 //
 // k_rv_sample: one thread per station, a gather of at most five cells.  mpl_toolkits.basemap.interp is restated with the
 // expressions of k_sample (topowx_amd/csrc/twx_sample.h); the raster is read north-up, so the row of interp's flipped copy
@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "twx_qa.h"
+#include "twx_qa_common.h"
 
 #define RV_THREADS 256
 #define RV_RADIAN 0.017453292519943295       // RADIAN_CONVERSION_FACTOR, twx/utils/util_geo.py:21
@@ -270,47 +271,6 @@ __global__ __launch_bounds__(RV_THREADS) void k_rv_colcount(const void *__restri
 
 namespace {
 
-int rv_fail(char *errbuf, int errlen, const char *what, hipError_t e = hipSuccess)
-{
-    if (errbuf && errlen > 0) {
-        if (e != hipSuccess) snprintf(errbuf, (size_t)errlen, "%s: %s", what, hipGetErrorString(e));
-        else snprintf(errbuf, (size_t)errlen, "%s", what);
-    }
-    return -1;
-}
-
-struct RvBufs {                                                  // every device allocation of a call, freed together
-    std::vector<void *> p;
-    ~RvBufs() { for (void *x : p) if (x) (void)hipFree(x); }
-    hipError_t get(void **out, size_t bytes)
-    {
-        hipError_t e = hipMalloc(out, bytes ? bytes : 1);
-        if (e == hipSuccess) p.push_back(*out);
-        return e;
-    }
-};
-
-struct RvTimer {                                                 // HIP-event time of a run of launches on the null stream
-    hipEvent_t a = nullptr, b = nullptr;
-    ~RvTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    hipError_t init() { hipError_t e = hipEventCreate(&a); return e != hipSuccess ? e : hipEventCreate(&b); }
-    hipError_t start() { return hipEventRecord(a, nullptr); }
-    hipError_t stop(float *acc)
-    {
-        float ms = 0.0f;
-        hipError_t e = hipEventRecord(b, nullptr);
-        if (e == hipSuccess) e = hipEventSynchronize(b);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
-        *acc += ms;
-        return e;
-    }
-};
-
-float rv_since(std::chrono::steady_clock::time_point t)
-{
-    return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t).count();
-}
-
 // the grid of a north-up geographic raster; a message if it is refused
 const char *rv_grid(int64_t rows, int64_t cols, const double *geo_t, int has_band, double band_ndata, RvGrid *g)
 {
@@ -340,15 +300,6 @@ const char *rv_grid(int64_t rows, int64_t cols, const double *geo_t, int has_ban
 
 }  // namespace
 
-#define RVCHK(call)                                                                     \
-    do {                                                                                \
-        hipError_t e_ = (call);                                                         \
-        if (e_ != hipSuccess) return rv_fail(errbuf, errlen, #call, e_);                \
-    } while (0)
-#define RVALLOC(bufs, ptr, type, count) RVCHK((bufs).get((void **)&(ptr), (size_t)(count) * sizeof(type)))
-#define RVUP(dst, src, type, count) RVCHK(hipMemcpy((dst), (src), (size_t)(count) * sizeof(type), hipMemcpyHostToDevice))
-#define RVDOWN(dst, src, type, count) RVCHK(hipMemcpy((dst), (src), (size_t)(count) * sizeof(type), hipMemcpyDeviceToHost))
-
 extern "C" int twxrv_sample(int device, int64_t rows, int64_t cols, int32_t dtype, const void *data, const double *geo_t,
                             int32_t has_band_ndata, double band_ndata, double ndata, int64_t nstn, const double *lon,
                             const double *lat, int32_t extract_method, int32_t revert_nn, int32_t force_data_value,
@@ -361,46 +312,46 @@ extern "C" int twxrv_sample(int device, int64_t rows, int64_t cols, int32_t dtyp
     RvGrid g;
     if (const char *why = rv_grid(rows, cols, geo_t, has_band_ndata, band_ndata, &g)) {
         snprintf(msg, sizeof msg, "%s: %s", fn, why);
-        return rv_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (dtype != TWXRV_F32 && dtype != TWXRV_F64) {
         snprintf(msg, sizeof msg, "%s: dtype must be TWXRV_F32 or TWXRV_F64", fn);
-        return rv_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (extract_method != 0 && extract_method != 1) {
         snprintf(msg, sizeof msg, "%s: extract_method must be 0 (nearest) or 1 (bilinear)", fn);
-        return rv_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (nstn < 1 || nstn > INT32_MAX / 2) {
         snprintf(msg, sizeof msg, "%s: need 1 <= nstn <= %d", fn, INT32_MAX / 2);
-        return rv_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (!data || !lon || !lat || !value || !status || !row || !col) {
         snprintf(msg, sizeof msg, "%s: null buffer", fn);
-        return rv_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     for (int64_t i = 0; i < nstn; ++i) {
         if (!std::isfinite(lon[i]) || !std::isfinite(lat[i])) {
             snprintf(msg, sizeof msg, "%s: station %lld has a non-finite coordinate", fn, (long long)i);
-            return rv_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
     }
     const size_t NC = (size_t)rows * (size_t)cols, NS = (size_t)nstn, esz = dtype == TWXRV_F32 ? 4 : 8;
 
-    RVCHK(hipSetDevice(device));
-    RvBufs bufs;
+    QACHK(hipSetDevice(device));
+    QaPool bufs;
     void *d_data;
     double *d_lon, *d_lat, *d_val;
     int32_t *d_st, *d_row, *d_col;
     float ms[TWXRV_NTIMES] = {0.0f, 0.0f, 0.0f};
     const auto t_up = std::chrono::steady_clock::now();
-    RVCHK(bufs.get(&d_data, NC * esz));
-    RVALLOC(bufs, d_lon, double, NS); RVALLOC(bufs, d_lat, double, NS); RVALLOC(bufs, d_val, double, NS);
-    RVALLOC(bufs, d_st, int32_t, NS); RVALLOC(bufs, d_row, int32_t, NS); RVALLOC(bufs, d_col, int32_t, NS);
-    RVCHK(hipMemcpy(d_data, data, NC * esz, hipMemcpyHostToDevice));
-    RVUP(d_lon, lon, double, NS); RVUP(d_lat, lat, double, NS);
-    RvTimer tm;
-    if (kernel_ms) { RVCHK(tm.init()); RVCHK(hipDeviceSynchronize()); ms[1] = rv_since(t_up); RVCHK(tm.start()); }
+    QACHK(bufs.get(&d_data, NC * esz));
+    QAALLOC(bufs, d_lon, double, NS); QAALLOC(bufs, d_lat, double, NS); QAALLOC(bufs, d_val, double, NS);
+    QAALLOC(bufs, d_st, int32_t, NS); QAALLOC(bufs, d_row, int32_t, NS); QAALLOC(bufs, d_col, int32_t, NS);
+    QACHK(hipMemcpy(d_data, data, NC * esz, hipMemcpyHostToDevice));
+    QAUP(d_lon, lon, double, NS); QAUP(d_lat, lat, double, NS);
+    QaTimer tm;
+    if (kernel_ms) { QACHK(tm.init()); QACHK(hipDeviceSynchronize()); ms[1] = qa_since(t_up); QACHK(tm.start()); }
     const dim3 grid((unsigned)((NS + RV_THREADS - 1) / RV_THREADS)), block(RV_THREADS);
     if (dtype == TWXRV_F32)
         hipLaunchKernelGGL(k_rv_sample<float>, grid, block, 0, nullptr, (const float *)d_data, g, nstn, (const double *)d_lon,
@@ -410,12 +361,12 @@ extern "C" int twxrv_sample(int device, int64_t rows, int64_t cols, int32_t dtyp
         hipLaunchKernelGGL(k_rv_sample<double>, grid, block, 0, nullptr, (const double *)d_data, g, nstn,
                            (const double *)d_lon, (const double *)d_lat, (int)extract_method, (int)revert_nn,
                            (int)force_data_value, ndata, d_val, d_st, d_row, d_col);
-    RVCHK(hipGetLastError());
-    if (kernel_ms) RVCHK(tm.stop(&ms[0]));
+    QACHK(hipGetLastError());
+    if (kernel_ms) QACHK(tm.stop_add(&ms[0]));
     const auto t_down = std::chrono::steady_clock::now();
-    RVDOWN(value, d_val, double, NS); RVDOWN(status, d_st, int32_t, NS);
-    RVDOWN(row, d_row, int32_t, NS); RVDOWN(col, d_col, int32_t, NS);
-    ms[2] = rv_since(t_down);
+    QADOWN(value, d_val, double, NS); QADOWN(status, d_st, int32_t, NS);
+    QADOWN(row, d_row, int32_t, NS); QADOWN(col, d_col, int32_t, NS);
+    ms[2] = qa_since(t_down);
     if (kernel_ms) memcpy(kernel_ms, ms, sizeof ms);
     return 0;
 }
@@ -431,56 +382,56 @@ extern "C" int twxrv_nearest_data(int device, int64_t rows, int64_t cols, int32_
     RvGrid g;
     if (const char *why = rv_grid(rows, cols, geo_t, 0, 0.0, &g)) {
         snprintf(msg, sizeof msg, "%s: %s", fn, why);
-        return rv_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (dtype != TWXRV_F32 && dtype != TWXRV_F64) {
         snprintf(msg, sizeof msg, "%s: dtype must be TWXRV_F32 or TWXRV_F64", fn);
-        return rv_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (npts < 1 || npts > INT32_MAX / 2) {
         snprintf(msg, sizeof msg, "%s: need 1 <= npts <= %d", fn, INT32_MAX / 2);
-        return rv_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (!data || !row || !col || !value || !dist || !ring || !winner || !runner_up || !status) {
         snprintf(msg, sizeof msg, "%s: null buffer", fn);
-        return rv_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     for (int64_t i = 0; i < npts; ++i) {
         if (row[i] < 0 || row[i] >= rows || col[i] < 0 || col[i] >= cols) {
             snprintf(msg, sizeof msg, "%s: point %lld starts outside the raster", fn, (long long)i);
-            return rv_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
     }
     const size_t NC = (size_t)rows * (size_t)cols, NP = (size_t)npts, esz = dtype == TWXRV_F32 ? 4 : 8;
     const int rmax = (int)(rows > cols ? rows : cols);
 
-    RVCHK(hipSetDevice(device));
-    RvBufs bufs;
+    QACHK(hipSetDevice(device));
+    QaPool bufs;
     void *d_data;
     double *d_val, *d_dist, *d_d2;
     int32_t *d_row, *d_col, *d_ring, *d_win, *d_st;
     float ms[TWXRV_NTIMES] = {0.0f, 0.0f, 0.0f};
     const auto t_up = std::chrono::steady_clock::now();
-    RVCHK(bufs.get(&d_data, NC * esz));
-    RVALLOC(bufs, d_val, double, NP); RVALLOC(bufs, d_dist, double, NP); RVALLOC(bufs, d_d2, double, NP);
-    RVALLOC(bufs, d_row, int32_t, NP); RVALLOC(bufs, d_col, int32_t, NP); RVALLOC(bufs, d_ring, int32_t, NP);
-    RVALLOC(bufs, d_win, int32_t, NP); RVALLOC(bufs, d_st, int32_t, NP);
-    RVCHK(hipMemcpy(d_data, data, NC * esz, hipMemcpyHostToDevice));
-    RVUP(d_row, row, int32_t, NP); RVUP(d_col, col, int32_t, NP);
-    RvTimer tm;
-    if (kernel_ms) { RVCHK(tm.init()); RVCHK(hipDeviceSynchronize()); ms[1] = rv_since(t_up); RVCHK(tm.start()); }
+    QACHK(bufs.get(&d_data, NC * esz));
+    QAALLOC(bufs, d_val, double, NP); QAALLOC(bufs, d_dist, double, NP); QAALLOC(bufs, d_d2, double, NP);
+    QAALLOC(bufs, d_row, int32_t, NP); QAALLOC(bufs, d_col, int32_t, NP); QAALLOC(bufs, d_ring, int32_t, NP);
+    QAALLOC(bufs, d_win, int32_t, NP); QAALLOC(bufs, d_st, int32_t, NP);
+    QACHK(hipMemcpy(d_data, data, NC * esz, hipMemcpyHostToDevice));
+    QAUP(d_row, row, int32_t, NP); QAUP(d_col, col, int32_t, NP);
+    QaTimer tm;
+    if (kernel_ms) { QACHK(tm.init()); QACHK(hipDeviceSynchronize()); ms[1] = qa_since(t_up); QACHK(tm.start()); }
     if (dtype == TWXRV_F32)
         hipLaunchKernelGGL(k_rv_ring<float>, dim3((unsigned)NP), dim3(64), 0, nullptr, (const float *)d_data, g, ndata, rmax,
                            (const int32_t *)d_row, (const int32_t *)d_col, d_val, d_dist, d_ring, d_win, d_d2, d_st);
     else
         hipLaunchKernelGGL(k_rv_ring<double>, dim3((unsigned)NP), dim3(64), 0, nullptr, (const double *)d_data, g, ndata, rmax,
                            (const int32_t *)d_row, (const int32_t *)d_col, d_val, d_dist, d_ring, d_win, d_d2, d_st);
-    RVCHK(hipGetLastError());
-    if (kernel_ms) RVCHK(tm.stop(&ms[0]));
+    QACHK(hipGetLastError());
+    if (kernel_ms) QACHK(tm.stop_add(&ms[0]));
     const auto t_down = std::chrono::steady_clock::now();
-    RVDOWN(value, d_val, double, NP); RVDOWN(dist, d_dist, double, NP); RVDOWN(runner_up, d_d2, double, NP);
-    RVDOWN(ring, d_ring, int32_t, NP); RVDOWN(winner, d_win, int32_t, NP); RVDOWN(status, d_st, int32_t, NP);
-    ms[2] = rv_since(t_down);
+    QADOWN(value, d_val, double, NP); QADOWN(dist, d_dist, double, NP); QADOWN(runner_up, d_d2, double, NP);
+    QADOWN(ring, d_ring, int32_t, NP); QADOWN(winner, d_win, int32_t, NP); QADOWN(status, d_st, int32_t, NP);
+    ms[2] = qa_since(t_down);
     if (kernel_ms) memcpy(kernel_ms, ms, sizeof ms);
     return 0;
 }
@@ -493,31 +444,31 @@ extern "C" int twxrv_dup_classes(int device, int64_t nstn, const double *lon, co
     if (errbuf && errlen > 0) errbuf[0] = 0;
     if (nstn < 1 || nstn > TWXRV_MAX_DUP_STNS) {
         snprintf(msg, sizeof msg, "%s: need 1 <= nstn <= %d", fn, TWXRV_MAX_DUP_STNS);
-        return rv_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (!lon || !lat || !cls || !size) {
         snprintf(msg, sizeof msg, "%s: null buffer", fn);
-        return rv_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     const size_t NS = (size_t)nstn;
-    RVCHK(hipSetDevice(device));
-    RvBufs bufs;
+    QACHK(hipSetDevice(device));
+    QaPool bufs;
     double *d_lon, *d_lat;
     int32_t *d_cls, *d_size;
     float ms[TWXRV_NTIMES] = {0.0f, 0.0f, 0.0f};
     const auto t_up = std::chrono::steady_clock::now();
-    RVALLOC(bufs, d_lon, double, NS); RVALLOC(bufs, d_lat, double, NS);
-    RVALLOC(bufs, d_cls, int32_t, NS); RVALLOC(bufs, d_size, int32_t, NS);
-    RVUP(d_lon, lon, double, NS); RVUP(d_lat, lat, double, NS);
-    RvTimer tm;
-    if (kernel_ms) { RVCHK(tm.init()); RVCHK(hipDeviceSynchronize()); ms[1] = rv_since(t_up); RVCHK(tm.start()); }
+    QAALLOC(bufs, d_lon, double, NS); QAALLOC(bufs, d_lat, double, NS);
+    QAALLOC(bufs, d_cls, int32_t, NS); QAALLOC(bufs, d_size, int32_t, NS);
+    QAUP(d_lon, lon, double, NS); QAUP(d_lat, lat, double, NS);
+    QaTimer tm;
+    if (kernel_ms) { QACHK(tm.init()); QACHK(hipDeviceSynchronize()); ms[1] = qa_since(t_up); QACHK(tm.start()); }
     hipLaunchKernelGGL(k_rv_dup, dim3((unsigned)((NS + RV_THREADS - 1) / RV_THREADS)), dim3(RV_THREADS), 0, nullptr, (int)nstn,
                        (const double *)d_lon, (const double *)d_lat, d_cls, d_size);
-    RVCHK(hipGetLastError());
-    if (kernel_ms) RVCHK(tm.stop(&ms[0]));
+    QACHK(hipGetLastError());
+    if (kernel_ms) QACHK(tm.stop_add(&ms[0]));
     const auto t_down = std::chrono::steady_clock::now();
-    RVDOWN(cls, d_cls, int32_t, NS); RVDOWN(size, d_size, int32_t, NS);
-    ms[2] = rv_since(t_down);
+    QADOWN(cls, d_cls, int32_t, NS); QADOWN(size, d_size, int32_t, NS);
+    ms[2] = qa_since(t_down);
     if (kernel_ms) memcpy(kernel_ms, ms, sizeof ms);
     return 0;
 }
@@ -533,30 +484,30 @@ extern "C" int twxrv_col_count(int device, int64_t ndays, int64_t nstn, int32_t 
     if (kernel_ms) memset(kernel_ms, 0, TWXRV_NTIMES * sizeof(float));
     if (ndays < 1 || ndays > TWXSC_MAX_DAYS || nstn < 1 || nstn > INT32_MAX / 2) {
         snprintf(msg, sizeof msg, "%s: need 1 <= ndays <= %d and 1 <= nstn <= %d", fn, TWXSC_MAX_DAYS, INT32_MAX / 2);
-        return rv_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (kind != TWXRV_COUNT_I8_SUM && kind != TWXRV_COUNT_F32_MISSING) {
         snprintf(msg, sizeof msg, "%s: kind must be TWXRV_COUNT_I8_SUM or TWXRV_COUNT_F32_MISSING", fn);
-        return rv_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (ncol < 0 || ncol > INT32_MAX / 2 || (!cols && ncol != nstn)) {
         snprintf(msg, sizeof msg, "%s: need 0 <= ncol <= %d, and ncol = nstn without a column list", fn, INT32_MAX / 2);
-        return rv_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (kind == TWXRV_COUNT_I8_SUM && fill == fill && !(fill >= -128.0f && fill <= 127.0f && fill == (float)(int)fill)) {
         snprintf(msg, sizeof msg, "%s: the fill of an int8 variable must be NaN (none) or an integer in -128 .. 127", fn);
-        return rv_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (ncol == 0) return 0;                                     // an empty list: nothing to count, no device work
     if (!data || !out) {
         snprintf(msg, sizeof msg, "%s: null buffer", fn);
-        return rv_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (cols) {
         for (int64_t i = 0; i < ncol; ++i) {
             if (cols[i] < 0 || cols[i] >= nstn) {
                 snprintf(msg, sizeof msg, "%s: column %lld of the list is outside 0 .. nstn - 1", fn, (long long)i);
-                return rv_fail(errbuf, errlen, msg);
+                return qa_fail(errbuf, errlen, msg);
             }
         }
     }
@@ -566,25 +517,25 @@ extern "C" int twxrv_col_count(int device, int64_t ndays, int64_t nstn, int32_t 
     if (per < 1) per = 1;
     if (per > ndays) per = ndays;
 
-    RVCHK(hipSetDevice(device));
-    RvBufs bufs;
+    QACHK(hipSetDevice(device));
+    QaPool bufs;
     void *w_data;
     int32_t *d_cols = nullptr, *d_out;
     float ms[TWXRV_NTIMES] = {0.0f, 0.0f, 0.0f};
     const auto t_alloc = std::chrono::steady_clock::now();
-    RVCHK(bufs.get(&w_data, (size_t)per * NST * esz));
-    RVALLOC(bufs, d_out, int32_t, NCOL);
-    RVCHK(hipMemset(d_out, 0, NCOL * sizeof(int32_t)));
-    if (cols) { RVALLOC(bufs, d_cols, int32_t, NCOL); RVUP(d_cols, cols, int32_t, NCOL); }
-    RvTimer tm;
-    if (kernel_ms) { RVCHK(tm.init()); RVCHK(hipDeviceSynchronize()); ms[1] = rv_since(t_alloc); }
+    QACHK(bufs.get(&w_data, (size_t)per * NST * esz));
+    QAALLOC(bufs, d_out, int32_t, NCOL);
+    QACHK(hipMemset(d_out, 0, NCOL * sizeof(int32_t)));
+    if (cols) { QAALLOC(bufs, d_cols, int32_t, NCOL); QAUP(d_cols, cols, int32_t, NCOL); }
+    QaTimer tm;
+    if (kernel_ms) { QACHK(tm.init()); QACHK(hipDeviceSynchronize()); ms[1] = qa_since(t_alloc); }
     int nbatches = 0;
     for (int64_t first = 0; first < ndays; first += per) {       // runs of days that fit the budget
         const int64_t nd = ndays - first < per ? ndays - first : per;
         const auto t_up = std::chrono::steady_clock::now();
-        RVCHK(hipMemcpy(w_data, (const char *)data + (size_t)first * NST * esz, (size_t)nd * NST * esz, hipMemcpyHostToDevice));
+        QACHK(hipMemcpy(w_data, (const char *)data + (size_t)first * NST * esz, (size_t)nd * NST * esz, hipMemcpyHostToDevice));
         ++nbatches;
-        if (kernel_ms) { RVCHK(hipDeviceSynchronize()); ms[1] += rv_since(t_up); RVCHK(tm.start()); }
+        if (kernel_ms) { QACHK(hipDeviceSynchronize()); ms[1] += qa_since(t_up); QACHK(tm.start()); }
         const dim3 grid((unsigned)((NCOL + RV_COLS_PER_GROUP - 1) / RV_COLS_PER_GROUP),
                         (unsigned)((nd + RV_DAYS_PER_GROUP - 1) / RV_DAYS_PER_GROUP));
         if (kind == TWXRV_COUNT_I8_SUM)
@@ -593,13 +544,13 @@ extern "C" int twxrv_col_count(int device, int64_t ndays, int64_t nstn, int32_t 
         else
             hipLaunchKernelGGL(k_rv_colcount<1>, grid, dim3(RV_THREADS), 0, nullptr, (const void *)w_data, (int)nd, nstn, fill,
                                ncol, (const int32_t *)d_cols, d_out);
-        RVCHK(hipGetLastError());
-        if (kernel_ms) RVCHK(tm.stop(&ms[0]));
-        else RVCHK(hipDeviceSynchronize());                      // the next batch overwrites the days
+        QACHK(hipGetLastError());
+        if (kernel_ms) QACHK(tm.stop_add(&ms[0]));
+        else QACHK(hipDeviceSynchronize());                      // the next batch overwrites the days
     }
     const auto t_down = std::chrono::steady_clock::now();
-    RVDOWN(out, d_out, int32_t, NCOL);
-    ms[2] = rv_since(t_down);
+    QADOWN(out, d_out, int32_t, NCOL);
+    ms[2] = qa_since(t_down);
     if (counts) { counts[0] = nbatches; counts[1] = nbatches; }
     if (kernel_ms) memcpy(kernel_ms, ms, sizeof ms);
     return 0;

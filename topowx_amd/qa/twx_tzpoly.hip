@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "twx_qa.h"
+#include "twx_qa_common.h"
 #include "twx_tzpoly_pred.h"
 
 namespace {
@@ -214,45 +215,9 @@ __global__ __launch_bounds__(TZ_BLOCK) void k_tz_forced(const int32_t *__restric
 // ---------------------------------------------------------------------------------
 namespace {
 
-int tz_fail(char *errbuf, int errlen, const char *what, hipError_t e = hipSuccess)
-{
-    if (errbuf && errlen > 0) {
-        if (e != hipSuccess) snprintf(errbuf, (size_t)errlen, "%s: %s", what, hipGetErrorString(e));
-        else snprintf(errbuf, (size_t)errlen, "%s", what);
-    }
-    return -1;
-}
-
-struct TzBuf {
-    void *p = nullptr;
-    ~TzBuf() { if (p) (void)hipFree(p); }
-};
-
-struct TzTimer {                                                 // HIP-event time of work on the null stream
-    hipEvent_t a = nullptr, b = nullptr;
-    ~TzTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    hipError_t init() { hipError_t e = hipEventCreate(&a); return e != hipSuccess ? e : hipEventCreate(&b); }
-    hipError_t start() { return hipEventRecord(a, nullptr); }
-    hipError_t stop(float *ms)
-    {
-        float one = 0.0f;
-        hipError_t e = hipEventRecord(b, nullptr);
-        if (e == hipSuccess) e = hipEventSynchronize(b);
-        if (e == hipSuccess) e = hipEventElapsedTime(&one, a, b);
-        *ms += one;
-        return e;
-    }
-};
-
 unsigned tz_grid(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 }  // namespace
-
-#define TZCHK(call)                                                                     \
-    do {                                                                                \
-        hipError_t e_ = (call);                                                         \
-        if (e_ != hipSuccess) return tz_fail(errbuf, errlen, #call, e_);                \
-    } while (0)
 
 extern "C" int twxtz_locate(int device, int64_t npt, const double *lon, const double *lat, int64_t npoly, const int64_t *edge_off,
                             const double *bbox, const double *edges, double max_force_deg, int32_t *poly, int32_t *status,
@@ -262,40 +227,40 @@ extern "C" int twxtz_locate(int device, int64_t npt, const double *lon, const do
     if (errbuf && errlen > 0) errbuf[0] = 0;
     char msg[320];
     if (!lon || !lat || !edge_off || !bbox || !poly || !status || !dist2 || !counts || (uncertain_cap > 0 && !uncertain))
-        return tz_fail(errbuf, errlen, "twxtz_locate: null buffer");
+        return qa_fail(errbuf, errlen, "twxtz_locate: null buffer");
     if (npt < 1 || npt > TWXTZ_MAX_POINTS || npoly < 1 || npoly > TWXTZ_MAX_POLY) {
         snprintf(msg, sizeof msg, "twxtz_locate: need 1 <= npt <= TWXTZ_MAX_POINTS = %d and 1 <= npoly <= TWXTZ_MAX_POLY = %d",
                  TWXTZ_MAX_POINTS, TWXTZ_MAX_POLY);
-        return tz_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (uncertain_cap < 0 || uncertain_cap > TWXTZ_MAX_UNCERTAIN) {
         snprintf(msg, sizeof msg, "twxtz_locate: need 0 <= uncertain_cap <= TWXTZ_MAX_UNCERTAIN = %lld", (long long)TWXTZ_MAX_UNCERTAIN);
-        return tz_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
-    if (!(max_force_deg >= 0.0)) return tz_fail(errbuf, errlen, "twxtz_locate: max_force_deg must be >= 0 (infinity: no limit)");
-    if (edge_off[0] != 0) return tz_fail(errbuf, errlen, "twxtz_locate: edge_off must start at 0");
+    if (!(max_force_deg >= 0.0)) return qa_fail(errbuf, errlen, "twxtz_locate: max_force_deg must be >= 0 (infinity: no limit)");
+    if (edge_off[0] != 0) return qa_fail(errbuf, errlen, "twxtz_locate: edge_off must start at 0");
     for (int64_t p = 0; p < npoly; ++p) {
         if (edge_off[p + 1] < edge_off[p]) {
             snprintf(msg, sizeof msg, "twxtz_locate: edge_off descends at polygon %lld", (long long)p);
-            return tz_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
         const double *bb = bbox + 4 * p;
         if (!(std::isfinite(bb[0]) && std::isfinite(bb[1]) && std::isfinite(bb[2]) && std::isfinite(bb[3]) && bb[0] <= bb[2] &&
               bb[1] <= bb[3])) {
             snprintf(msg, sizeof msg, "twxtz_locate: the bbox of polygon %lld is not finite or not ordered", (long long)p);
-            return tz_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
     }
     const int64_t nedge = edge_off[npoly];
     if (nedge < 1 || nedge > TWXTZ_MAX_EDGES || !edges) {
         snprintf(msg, sizeof msg, "twxtz_locate: need 1 <= edges <= TWXTZ_MAX_EDGES = %lld", (long long)TWXTZ_MAX_EDGES);
-        return tz_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     for (int64_t e = 0; e < nedge; ++e) {
         const double *g = edges + 4 * e;
         if (!(std::isfinite(g[0]) && std::isfinite(g[1]) && std::isfinite(g[2]) && std::isfinite(g[3])) || (g[0] == g[2] && g[1] == g[3])) {
             snprintf(msg, sizeof msg, "twxtz_locate: edge %lld is not finite or has no length", (long long)e);
-            return tz_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
     }
     const double max_force2 = std::isinf(max_force_deg) ? INFINITY : max_force_deg * max_force_deg;
@@ -303,112 +268,112 @@ extern "C" int twxtz_locate(int device, int64_t npt, const double *lon, const do
     float ms[TWXTZ_NPHASES];
     for (int i = 0; i < TWXTZ_NPHASES; ++i) ms[i] = 0.0f;
     for (int i = 0; i < TWXTZ_C_N; ++i) counts[i] = 0;
-    TZCHK(hipSetDevice(device));
-    TzBuf b_lon, b_lat, b_off, b_bbox, b_edges, b_np, b_ni, b_poff, b_ioff, b_ppoly, b_ipair, b_ichunk, b_ipt, b_word, b_poly,
+    QACHK(hipSetDevice(device));
+    QaBuf b_lon, b_lat, b_off, b_bbox, b_edges, b_np, b_ni, b_poff, b_ioff, b_ppoly, b_ipair, b_ichunk, b_ipt, b_word, b_poly,
         b_status, b_d2, b_unc, b_nunc, b_pend;
-    TzTimer tm;
-    TZCHK(tm.init());
+    QaTimer tm;
+    QACHK(tm.init());
     const size_t n = (size_t)npt;
-    TZCHK(hipMalloc(&b_lon.p, n * 8));
-    TZCHK(hipMalloc(&b_lat.p, n * 8));
-    TZCHK(hipMalloc(&b_off.p, ((size_t)npoly + 1) * 8));
-    TZCHK(hipMalloc(&b_bbox.p, (size_t)npoly * 32));
-    TZCHK(hipMalloc(&b_edges.p, (size_t)nedge * 32));
-    TZCHK(hipMalloc(&b_np.p, n * 8));
-    TZCHK(hipMalloc(&b_ni.p, n * 8));
-    TZCHK(hipMalloc(&b_poff.p, (n + 1) * 8));
-    TZCHK(hipMalloc(&b_ioff.p, (n + 1) * 8));
-    TZCHK(hipMalloc(&b_poly.p, n * 4));
-    TZCHK(hipMalloc(&b_status.p, n * 4));
-    TZCHK(hipMalloc(&b_d2.p, n * 8));
-    TZCHK(hipMalloc(&b_unc.p, (size_t)std::max<int64_t>(uncertain_cap, 1) * 8));
-    TZCHK(hipMalloc(&b_nunc.p, 8));
-    TZCHK(hipMemset(b_nunc.p, 0, 8));
+    QACHK(hipMalloc(&b_lon.p, n * 8));
+    QACHK(hipMalloc(&b_lat.p, n * 8));
+    QACHK(hipMalloc(&b_off.p, ((size_t)npoly + 1) * 8));
+    QACHK(hipMalloc(&b_bbox.p, (size_t)npoly * 32));
+    QACHK(hipMalloc(&b_edges.p, (size_t)nedge * 32));
+    QACHK(hipMalloc(&b_np.p, n * 8));
+    QACHK(hipMalloc(&b_ni.p, n * 8));
+    QACHK(hipMalloc(&b_poff.p, (n + 1) * 8));
+    QACHK(hipMalloc(&b_ioff.p, (n + 1) * 8));
+    QACHK(hipMalloc(&b_poly.p, n * 4));
+    QACHK(hipMalloc(&b_status.p, n * 4));
+    QACHK(hipMalloc(&b_d2.p, n * 8));
+    QACHK(hipMalloc(&b_unc.p, (size_t)std::max<int64_t>(uncertain_cap, 1) * 8));
+    QACHK(hipMalloc(&b_nunc.p, 8));
+    QACHK(hipMemset(b_nunc.p, 0, 8));
     // ---- upload
-    TZCHK(tm.start());
-    TZCHK(hipMemcpy(b_lon.p, lon, n * 8, hipMemcpyHostToDevice));
-    TZCHK(hipMemcpy(b_lat.p, lat, n * 8, hipMemcpyHostToDevice));
-    TZCHK(hipMemcpy(b_off.p, edge_off, ((size_t)npoly + 1) * 8, hipMemcpyHostToDevice));
-    TZCHK(hipMemcpy(b_bbox.p, bbox, (size_t)npoly * 32, hipMemcpyHostToDevice));
-    TZCHK(hipMemcpy(b_edges.p, edges, (size_t)nedge * 32, hipMemcpyHostToDevice));
-    TZCHK(tm.stop(&ms[TWXTZ_T_UPLOAD]));
+    QACHK(tm.start());
+    QACHK(hipMemcpy(b_lon.p, lon, n * 8, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(b_lat.p, lat, n * 8, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(b_off.p, edge_off, ((size_t)npoly + 1) * 8, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(b_bbox.p, bbox, (size_t)npoly * 32, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(b_edges.p, edges, (size_t)nedge * 32, hipMemcpyHostToDevice));
+    QACHK(tm.stop_add(&ms[TWXTZ_T_UPLOAD]));
     const double *d_lon = static_cast<const double *>(b_lon.p), *d_lat = static_cast<const double *>(b_lat.p);
     const int64_t *d_off = static_cast<const int64_t *>(b_off.p);
     const double *d_bbox = static_cast<const double *>(b_bbox.p);
     const double4 *d_edges = static_cast<const double4 *>(b_edges.p);
     // ---- candidates: count, scan (host), scatter
     std::vector<int64_t> np(n), ni(n), poff(n + 1, 0), ioff(n + 1, 0);
-    TZCHK(tm.start());
+    QACHK(tm.start());
     hipLaunchKernelGGL(k_tz_count, dim3(tz_grid(npt, TZ_BLOCK)), dim3(TZ_BLOCK), 0, nullptr, npt, d_lon, d_lat, (int32_t)npoly, d_off,
                        d_bbox, static_cast<int64_t *>(b_np.p), static_cast<int64_t *>(b_ni.p));
-    TZCHK(hipGetLastError());
-    TZCHK(hipMemcpy(np.data(), b_np.p, n * 8, hipMemcpyDeviceToHost));
-    TZCHK(hipMemcpy(ni.data(), b_ni.p, n * 8, hipMemcpyDeviceToHost));
+    QACHK(hipGetLastError());
+    QACHK(hipMemcpy(np.data(), b_np.p, n * 8, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(ni.data(), b_ni.p, n * 8, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n; ++i) poff[i + 1] = poff[i] + np[i], ioff[i + 1] = ioff[i] + ni[i];
     const int64_t npair = poff[n], nitem = ioff[n];
     if (nitem > TWXTZ_MAX_ITEMS) {
         snprintf(msg, sizeof msg, "twxtz_locate: %lld work items, more than TWXTZ_MAX_ITEMS = %lld: pass the points in parts",
                  (long long)nitem, (long long)TWXTZ_MAX_ITEMS);
-        return tz_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
-    TZCHK(hipMemcpy(b_poff.p, poff.data(), (n + 1) * 8, hipMemcpyHostToDevice));
-    TZCHK(hipMemcpy(b_ioff.p, ioff.data(), (n + 1) * 8, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(b_poff.p, poff.data(), (n + 1) * 8, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(b_ioff.p, ioff.data(), (n + 1) * 8, hipMemcpyHostToDevice));
     if (npair > 0) {
-        TZCHK(hipMalloc(&b_ppoly.p, (size_t)npair * 4));
-        TZCHK(hipMalloc(&b_word.p, (size_t)npair * 4));
-        TZCHK(hipMalloc(&b_ipair.p, (size_t)nitem * 8));
-        TZCHK(hipMalloc(&b_ichunk.p, (size_t)nitem * 4));
-        TZCHK(hipMalloc(&b_ipt.p, (size_t)nitem * 4));
-        TZCHK(hipMemset(b_word.p, 0, (size_t)npair * 4));
+        QACHK(hipMalloc(&b_ppoly.p, (size_t)npair * 4));
+        QACHK(hipMalloc(&b_word.p, (size_t)npair * 4));
+        QACHK(hipMalloc(&b_ipair.p, (size_t)nitem * 8));
+        QACHK(hipMalloc(&b_ichunk.p, (size_t)nitem * 4));
+        QACHK(hipMalloc(&b_ipt.p, (size_t)nitem * 4));
+        QACHK(hipMemset(b_word.p, 0, (size_t)npair * 4));
         hipLaunchKernelGGL(k_tz_scatter, dim3(tz_grid(npt, TZ_BLOCK)), dim3(TZ_BLOCK), 0, nullptr, npt, d_lon, d_lat, (int32_t)npoly,
                            d_off, d_bbox, static_cast<const int64_t *>(b_poff.p), static_cast<const int64_t *>(b_ioff.p),
                            static_cast<int32_t *>(b_ppoly.p), static_cast<int64_t *>(b_ipair.p), static_cast<int32_t *>(b_ichunk.p),
                            static_cast<int32_t *>(b_ipt.p));
-        TZCHK(hipGetLastError());
+        QACHK(hipGetLastError());
     }
-    TZCHK(tm.stop(&ms[TWXTZ_T_CANDIDATES]));
+    QACHK(tm.stop_add(&ms[TWXTZ_T_CANDIDATES]));
     // ---- containment and the pick
-    TZCHK(tm.start());
+    QACHK(tm.start());
     if (nitem > 0) {
         hipLaunchKernelGGL(k_tz_contain, dim3(tz_grid(nitem, TZ_BLOCK / 64)), dim3(TZ_BLOCK), 0, nullptr, nitem, d_lon, d_lat, d_off,
                            d_edges, static_cast<const int32_t *>(b_ppoly.p), static_cast<const int64_t *>(b_ipair.p),
                            static_cast<const int32_t *>(b_ichunk.p), static_cast<const int32_t *>(b_ipt.p),
                            static_cast<uint32_t *>(b_word.p));
-        TZCHK(hipGetLastError());
+        QACHK(hipGetLastError());
     }
     hipLaunchKernelGGL(k_tz_pick, dim3(tz_grid(npt, TZ_BLOCK)), dim3(TZ_BLOCK), 0, nullptr, npt, d_lon, d_lat,
                        static_cast<const int64_t *>(b_poff.p), static_cast<const int32_t *>(b_ppoly.p),
                        static_cast<const uint32_t *>(b_word.p), static_cast<int32_t *>(b_poly.p), static_cast<int32_t *>(b_status.p),
                        static_cast<double *>(b_d2.p), static_cast<int32_t *>(b_unc.p), uncertain_cap,
                        static_cast<unsigned long long *>(b_nunc.p));
-    TZCHK(hipGetLastError());
-    TZCHK(hipMemcpy(status, b_status.p, n * 4, hipMemcpyDeviceToHost));
-    TZCHK(tm.stop(&ms[TWXTZ_T_CONTAIN]));
+    QACHK(hipGetLastError());
+    QACHK(hipMemcpy(status, b_status.p, n * 4, hipMemcpyDeviceToHost));
+    QACHK(tm.stop_add(&ms[TWXTZ_T_CONTAIN]));
     // ---- the forced search of the points nothing contains
     std::vector<int32_t> pending;
     for (size_t i = 0; i < n; ++i)
         if (status[i] == TWXTZ_PENDING) pending.push_back((int32_t)i);
-    TZCHK(tm.start());
+    QACHK(tm.start());
     if (!pending.empty()) {
-        TZCHK(hipMalloc(&b_pend.p, pending.size() * 4));
-        TZCHK(hipMemcpy(b_pend.p, pending.data(), pending.size() * 4, hipMemcpyHostToDevice));
+        QACHK(hipMalloc(&b_pend.p, pending.size() * 4));
+        QACHK(hipMemcpy(b_pend.p, pending.data(), pending.size() * 4, hipMemcpyHostToDevice));
         hipLaunchKernelGGL(k_tz_forced, dim3((unsigned)pending.size()), dim3(TZ_BLOCK), 0, nullptr,
                            static_cast<const int32_t *>(b_pend.p), d_lon, d_lat, (int32_t)npoly, d_off, d_edges, max_force2,
                            static_cast<int32_t *>(b_poly.p), static_cast<int32_t *>(b_status.p), static_cast<double *>(b_d2.p),
                            static_cast<int32_t *>(b_unc.p), uncertain_cap, static_cast<unsigned long long *>(b_nunc.p));
-        TZCHK(hipGetLastError());
+        QACHK(hipGetLastError());
     }
-    TZCHK(tm.stop(&ms[TWXTZ_T_FORCED]));
+    QACHK(tm.stop_add(&ms[TWXTZ_T_FORCED]));
     // ---- download
     unsigned long long nunc = 0;
-    TZCHK(tm.start());
-    TZCHK(hipMemcpy(poly, b_poly.p, n * 4, hipMemcpyDeviceToHost));
-    TZCHK(hipMemcpy(status, b_status.p, n * 4, hipMemcpyDeviceToHost));
-    TZCHK(hipMemcpy(dist2, b_d2.p, n * 8, hipMemcpyDeviceToHost));
-    TZCHK(hipMemcpy(&nunc, b_nunc.p, 8, hipMemcpyDeviceToHost));
+    QACHK(tm.start());
+    QACHK(hipMemcpy(poly, b_poly.p, n * 4, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(status, b_status.p, n * 4, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(dist2, b_d2.p, n * 8, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(&nunc, b_nunc.p, 8, hipMemcpyDeviceToHost));
     const int64_t nkeep = std::min<int64_t>((int64_t)nunc, uncertain_cap);
-    if (nkeep > 0) TZCHK(hipMemcpy(uncertain, b_unc.p, (size_t)nkeep * 8, hipMemcpyDeviceToHost));
-    TZCHK(tm.stop(&ms[TWXTZ_T_DOWNLOAD]));
+    if (nkeep > 0) QACHK(hipMemcpy(uncertain, b_unc.p, (size_t)nkeep * 8, hipMemcpyDeviceToHost));
+    QACHK(tm.stop_add(&ms[TWXTZ_T_DOWNLOAD]));
     if (nkeep > 0) {                                              // the order of arrival is not kept: (point, polygon) ascending
         std::vector<std::pair<int32_t, int32_t>> v((size_t)nkeep);
         for (int64_t k = 0; k < nkeep; ++k) v[(size_t)k] = {uncertain[2 * k], uncertain[2 * k + 1]};

@@ -2,8 +2,8 @@
 // scripts/step15_mpi_xval_infill.py): which observations of a station are hidden from its own infill (twxxv_holdout,
 // XvalInfill.__init__:73-86 in closed form) and how the infilled series compares with them (twxxv_score, run_xval:153-154
 // with the writer's np.ma arithmetic, step15:127-134).  The chain between them is the library's own: twxxv_infill_matrix
-// (twx_infillmat.hip), twxem_mean_variance, twxpp_ppca_fit, twxck_infill_check.  Its own translation unit: the helpers it
-// shares with the other units of the library (the buffer list, the event timer) are restated, nothing there is edited.
+// (twx_infillmat.hip), twxem_mean_variance, twxpp_ppca_fit, twxck_infill_check.  Its own translation unit; the helpers it
+// shares with the other units of the library (the buffer list, the event timer) are twx_qa_common.h's.
 //
 // k_xv_holdout: one wavefront per row, walked from the last day backwards in chunks of 64.  The reference keeps the last
 // nkeep finite days (np.nonzero(fin)[0][-nkeep:]) and hides every other finite day: day d is held iff it is finite and at
@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "twx_qa.h"
+#include "twx_qa_common.h"
 
 #define XV_NAN_BITS 0x7fc00000u                                 // the float32 quiet NaN numpy writes for np.nan
 
@@ -117,50 +118,6 @@ __global__ __launch_bounds__(256) void k_xv_score(int64_t ndays, const double *_
 // ---------------------------------------------------------------------------------
 // host entries
 // ---------------------------------------------------------------------------------
-namespace {
-
-int xv_fail(char *errbuf, int errlen, const char *what, hipError_t e = hipSuccess)
-{
-    if (errbuf && errlen > 0) {
-        if (e != hipSuccess) snprintf(errbuf, (size_t)errlen, "%s: %s", what, hipGetErrorString(e));
-        else snprintf(errbuf, (size_t)errlen, "%s", what);
-    }
-    return -1;
-}
-
-struct XvBufs {                                                  // every device allocation of a call, freed together
-    std::vector<void *> p;
-    ~XvBufs() { for (void *x : p) if (x) (void)hipFree(x); }
-    hipError_t get(void **out, size_t bytes)
-    {
-        hipError_t e = hipMalloc(out, bytes ? bytes : 1);
-        if (e == hipSuccess) p.push_back(*out);
-        return e;
-    }
-};
-
-struct XvTimer {                                                 // HIP-event time of a launch on the null stream
-    hipEvent_t a = nullptr, b = nullptr;
-    ~XvTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    hipError_t init() { hipError_t e = hipEventCreate(&a); return e != hipSuccess ? e : hipEventCreate(&b); }
-    hipError_t start() { return hipEventRecord(a, nullptr); }
-    hipError_t stop(float *ms)
-    {
-        hipError_t e = hipEventRecord(b, nullptr);
-        if (e == hipSuccess) e = hipEventSynchronize(b);
-        if (e == hipSuccess) e = hipEventElapsedTime(ms, a, b);
-        return e;
-    }
-};
-
-}  // namespace
-
-#define XVCHK(call)                                                                     \
-    do {                                                                                \
-        hipError_t e_ = (call);                                                         \
-        if (e_ != hipSuccess) return xv_fail(errbuf, errlen, #call, e_);                \
-    } while (0)
-#define XVALLOC(ptr, type, count) XVCHK(bufs.get((void **)&(ptr), (size_t)(count) * sizeof(type)))
 
 extern "C" int twxxv_holdout(int device, int64_t nstn, int64_t ndays, const float *obs, int64_t ntarget,
                              const int32_t *target_idx, int32_t nkeep, uint8_t *held, float *train_obs, int32_t *nheld,
@@ -171,37 +128,37 @@ extern "C" int twxxv_holdout(int device, int64_t nstn, int64_t ndays, const floa
     if (errbuf && errlen > 0) errbuf[0] = 0;
     if (nstn < 1 || ndays < 1 || ntarget < 1 || nstn > INT32_MAX || ndays > INT32_MAX || ntarget > INT32_MAX || nkeep < 0) {
         snprintf(msg, sizeof msg, "%s: need nstn, ndays, ntarget >= 1 and nkeep >= 0", fn);
-        return xv_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (!obs || !target_idx || !held || !train_obs || !nheld || !nfinite) {
         snprintf(msg, sizeof msg, "%s: null buffer", fn);
-        return xv_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     for (int64_t t = 0; t < ntarget; ++t)
         if (target_idx[t] < 0 || target_idx[t] >= nstn) {
             snprintf(msg, sizeof msg, "%s: target index %d outside [0, %lld)", fn, (int)target_idx[t], (long long)nstn);
-            return xv_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
-    XVCHK(hipSetDevice(device));
-    XvBufs bufs;
+    QACHK(hipSetDevice(device));
+    QaPool bufs;
     const size_t NT = (size_t)ntarget, ND = (size_t)ndays;
     uint32_t *d_rows, *d_train;
     uint8_t *d_held;
     int32_t *d_nheld, *d_nfin;
-    XVALLOC(d_rows, uint32_t, NT * ND); XVALLOC(d_train, uint32_t, NT * ND); XVALLOC(d_held, uint8_t, NT * ND);
-    XVALLOC(d_nheld, int32_t, NT); XVALLOC(d_nfin, int32_t, NT);
+    QAALLOC(bufs, d_rows, uint32_t, NT * ND); QAALLOC(bufs, d_train, uint32_t, NT * ND); QAALLOC(bufs, d_held, uint8_t, NT * ND);
+    QAALLOC(bufs, d_nheld, int32_t, NT); QAALLOC(bufs, d_nfin, int32_t, NT);
     for (size_t t = 0; t < NT; ++t)                               // only the targets' rows go up
-        XVCHK(hipMemcpy(d_rows + t * ND, obs + (size_t)target_idx[t] * ND, ND * 4, hipMemcpyHostToDevice));
-    XvTimer tm;
-    if (kernel_ms) { XVCHK(tm.init()); XVCHK(tm.start()); }
+        QACHK(hipMemcpy(d_rows + t * ND, obs + (size_t)target_idx[t] * ND, ND * 4, hipMemcpyHostToDevice));
+    QaTimer tm;
+    if (kernel_ms) { QACHK(tm.init()); QACHK(tm.start()); }
     hipLaunchKernelGGL(k_xv_holdout, dim3((unsigned)ntarget), dim3(64), 0, nullptr, ndays, nkeep,
                        (const uint32_t *)d_rows, d_held, d_train, d_nheld, d_nfin);
-    XVCHK(hipGetLastError());
-    if (kernel_ms) XVCHK(tm.stop(kernel_ms));
-    XVCHK(hipMemcpy(held, d_held, NT * ND, hipMemcpyDeviceToHost));
-    XVCHK(hipMemcpy(train_obs, d_train, NT * ND * 4, hipMemcpyDeviceToHost));
-    XVCHK(hipMemcpy(nheld, d_nheld, NT * 4, hipMemcpyDeviceToHost));
-    XVCHK(hipMemcpy(nfinite, d_nfin, NT * 4, hipMemcpyDeviceToHost));
+    QACHK(hipGetLastError());
+    if (kernel_ms) QACHK(tm.stop_set(kernel_ms));
+    QACHK(hipMemcpy(held, d_held, NT * ND, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(train_obs, d_train, NT * ND * 4, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(nheld, d_nheld, NT * 4, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(nfinite, d_nfin, NT * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -214,44 +171,44 @@ extern "C" int twxxv_score(int device, int64_t nseries, int64_t ndays, const dou
     if (errbuf && errlen > 0) errbuf[0] = 0;
     if (nseries < 1 || ndays < 1 || nseries > INT32_MAX || ndays > INT32_MAX) {
         snprintf(msg, sizeof msg, "%s: need nseries, ndays >= 1", fn);
-        return xv_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     if (!infill || !obs || !held || !group || !n || !bias || !mae || !obs_out || !infill_out) {
         snprintf(msg, sizeof msg, "%s: null buffer", fn);
-        return xv_fail(errbuf, errlen, msg);
+        return qa_fail(errbuf, errlen, msg);
     }
     for (int64_t d = 0; d < ndays; ++d)
         if (group[d] < -1 || group[d] >= TWXXV_NGROUPS) {
             snprintf(msg, sizeof msg, "%s: group[%lld] = %d outside -1 .. %d", fn, (long long)d, (int)group[d],
                      TWXXV_NGROUPS - 1);
-            return xv_fail(errbuf, errlen, msg);
+            return qa_fail(errbuf, errlen, msg);
         }
-    XVCHK(hipSetDevice(device));
-    XvBufs bufs;
+    QACHK(hipSetDevice(device));
+    QaPool bufs;
     const size_t NS = (size_t)nseries, ND = (size_t)ndays, NO = NS * (TWXXV_NGROUPS + 1);
     double *d_infill, *d_bias, *d_mae;
     float *d_obs, *d_oo, *d_io;
     uint8_t *d_held;
     int8_t *d_group;
     int32_t *d_n;
-    XVALLOC(d_infill, double, NS * ND); XVALLOC(d_obs, float, NS * ND); XVALLOC(d_held, uint8_t, NS * ND);
-    XVALLOC(d_group, int8_t, ND); XVALLOC(d_n, int32_t, NO); XVALLOC(d_bias, double, NO); XVALLOC(d_mae, double, NO);
-    XVALLOC(d_oo, float, NS * ND); XVALLOC(d_io, float, NS * ND);
-    XVCHK(hipMemcpy(d_infill, infill, NS * ND * 8, hipMemcpyHostToDevice));
-    XVCHK(hipMemcpy(d_obs, obs, NS * ND * 4, hipMemcpyHostToDevice));
-    XVCHK(hipMemcpy(d_held, held, NS * ND, hipMemcpyHostToDevice));
-    XVCHK(hipMemcpy(d_group, group, ND, hipMemcpyHostToDevice));
-    XvTimer tm;
-    if (kernel_ms) { XVCHK(tm.init()); XVCHK(tm.start()); }
+    QAALLOC(bufs, d_infill, double, NS * ND); QAALLOC(bufs, d_obs, float, NS * ND); QAALLOC(bufs, d_held, uint8_t, NS * ND);
+    QAALLOC(bufs, d_group, int8_t, ND); QAALLOC(bufs, d_n, int32_t, NO); QAALLOC(bufs, d_bias, double, NO); QAALLOC(bufs, d_mae, double, NO);
+    QAALLOC(bufs, d_oo, float, NS * ND); QAALLOC(bufs, d_io, float, NS * ND);
+    QACHK(hipMemcpy(d_infill, infill, NS * ND * 8, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_obs, obs, NS * ND * 4, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_held, held, NS * ND, hipMemcpyHostToDevice));
+    QACHK(hipMemcpy(d_group, group, ND, hipMemcpyHostToDevice));
+    QaTimer tm;
+    if (kernel_ms) { QACHK(tm.init()); QACHK(tm.start()); }
     hipLaunchKernelGGL(k_xv_score, dim3((unsigned)nseries), dim3(256), 0, nullptr, ndays, (const double *)d_infill,
                        (const float *)d_obs, (const uint8_t *)d_held, (const int8_t *)d_group, d_n, d_bias, d_mae, d_oo,
                        d_io);
-    XVCHK(hipGetLastError());
-    if (kernel_ms) XVCHK(tm.stop(kernel_ms));
-    XVCHK(hipMemcpy(n, d_n, NO * 4, hipMemcpyDeviceToHost));
-    XVCHK(hipMemcpy(bias, d_bias, NO * 8, hipMemcpyDeviceToHost));
-    XVCHK(hipMemcpy(mae, d_mae, NO * 8, hipMemcpyDeviceToHost));
-    XVCHK(hipMemcpy(obs_out, d_oo, NS * ND * 4, hipMemcpyDeviceToHost));
-    XVCHK(hipMemcpy(infill_out, d_io, NS * ND * 4, hipMemcpyDeviceToHost));
+    QACHK(hipGetLastError());
+    if (kernel_ms) QACHK(tm.stop_set(kernel_ms));
+    QACHK(hipMemcpy(n, d_n, NO * 4, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(bias, d_bias, NO * 8, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(mae, d_mae, NO * 8, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(obs_out, d_oo, NS * ND * 4, hipMemcpyDeviceToHost));
+    QACHK(hipMemcpy(infill_out, d_io, NS * ND * 4, hipMemcpyDeviceToHost));
     return 0;
 }
