@@ -163,7 +163,7 @@ def test_header_binding_and_build_naming():
     statuses = [int(v) for v in re.findall(r"#define TWX(?:EM|PP|CK)_[A-Z_]+ (\d+) +/\*", h)]
     assert len({_qalib.CK_NOT_FITTED, _qalib.CK_FEW_ROWS, _qalib.CK_ROW_CAP} & {20, 21, 22, 23, 24, 25}) == 0 and statuses
     build = open(os.path.join(ROOT, "build.sh")).read()
-    assert "topowx_amd/qa/twx_infillchk.[h]ip" in build and os.path.exists(os.path.join(ROOT, "topowx_amd", "qa", "twx_infillchk.hip"))
+    assert "topowx_amd/qa/twx_infillchk.hip" in build and os.path.exists(os.path.join(ROOT, "topowx_amd", "qa", "twx_infillchk.hip"))
     from topowx_amd.infill import infill_daily as facade
     import inspect
     sig = inspect.signature(facade)

@@ -81,7 +81,12 @@ def test_header_and_binding():
     assert sorted(infill.EM_STATUS) == [0, 4, 20, 21, 22, 23] and sorted(infill.ITEM_STATUS) == [0, 4, 7, 18, 19]
     assert infill.InfillEstimates.EM_STATUS is infill.EM_STATUS
     build = open(os.path.join(ROOT, "build.sh")).read()
-    assert "topowx_amd/qa/twx_emnorm.hip" in build and build.count(".hip") == 7      # libtwxqa's sixth unit
+    assert "topowx_amd/qa/twx_emnorm.hip" in build
+    # every unit of topowx_amd/qa is named in the build script exactly once, and nothing that is not there
+    named = re.findall(r"topowx_amd/qa/(twx_\w+\.hip)", build)
+    on_disk = [f for f in os.listdir(os.path.join(ROOT, "topowx_amd", "qa")) if re.fullmatch(r"twx_\w+\.hip", f)]
+    assert sorted(named) == sorted(on_disk) and len(set(named)) == len(named)
+    assert build.count("topowx_amd/csrc/twx_hip.hip") == 1
     for name in ("assemble_columns", "nnr_components", "estimate_mean_variance", "infill_mean_variance", "InfillEstimates"):
         assert name in infill.__all__ and hasattr(infill, name)
 

@@ -299,7 +299,7 @@ def test_unit_is_declared_bound_and_built():
     assert int(re.search(r"#define TWXGH_NKERNELS (\d+)", h).group(1)) == len(_qalib.GH_KERNELS)
     assert int(re.search(r"#define TWXGH_FB_WORDS (\d+)", h).group(1)) == _qalib.GH_FB_WORDS
     assert int(re.search(r"#define TWXGH_MAX_BYTES \(\(int64_t\)(\d+)\)", h).group(1)) == _qalib.GH_MAX_BYTES
-    assert "topowx_amd/qa/twx_ghcn.[h]ip" in open(os.path.join(ROOT, "build.sh")).read()
+    assert "topowx_amd/qa/twx_ghcn.hip" in open(os.path.join(ROOT, "build.sh")).read()
     res = os.path.join(ROOT, "topowx_amd", "libtwxqa.resources.txt")
     if not os.path.exists(_qalib.LIB_PATH) or not os.path.exists(res):
         pytest.skip("no build in this checkout (run ./build.sh)")

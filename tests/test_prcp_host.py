@@ -133,7 +133,7 @@ def test_header_binding_and_build_script_agree():
         assert m and int(m.group(1)) == val, macro
     assert _qalib.PQ_MAX_WINDOW_VALUES // 29 == 141 and _qalib.PQ_MAX_WINDOW_VALUES & (_qalib.PQ_MAX_WINDOW_VALUES - 1) == 0
     b = open(os.path.join(ROOT, "build.sh")).read()
-    assert "topowx_amd/qa/twx_prcpqa.[h]ip" in b and os.path.exists(os.path.join(ROOT, "topowx_amd", "qa", "twx_prcpqa.hip"))
+    assert "topowx_amd/qa/twx_prcpqa.hip" in b and os.path.exists(os.path.join(ROOT, "topowx_amd", "qa", "twx_prcpqa.hip"))
     src = open(os.path.join(ROOT, "topowx_amd", "qa", "twx_prcpqa.hip")).read()
     assert sorted(set(re.findall(r'extern "C" int (twxpq_\w+)\(', src))) == sorted(_qalib.PQ_EXPORTS)
     assert sorted(set(re.findall(r"\b(k_pq_\w+)\(", src))) == sorted(NEW_KERNELS)

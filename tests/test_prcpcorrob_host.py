@@ -131,7 +131,7 @@ def test_header_binding_and_build_script_agree():
     assert (_qalib.SP_OK, _qalib.SP_FEW_NGHS, _qalib.SP_NGH_CAP) == (RC.SP_OK, RC.SP_FEW_NGHS, RC.SP_NGH_CAP)
     assert _qalib.MAX_RADIUS_NGH == RC.MAX_RADIUS_NGH
     b = open(os.path.join(ROOT, "build.sh")).read()
-    assert "topowx_amd/qa/twx_prcpcorrob.[h]ip" in b
+    assert "topowx_amd/qa/twx_prcpcorrob.hip" in b
     src = open(os.path.join(ROOT, "topowx_amd", "qa", "twx_prcpcorrob.hip")).read()
     assert sorted(set(re.findall(r'extern "C" int (twxpc_\w+)\(', src))) == sorted(_qalib.PC_EXPORTS)
     assert sorted(set(re.findall(r"__global__[^\n]*\bvoid (k_\w+)\(", src))) == sorted(NEW_KERNELS)
@@ -222,8 +222,7 @@ def test_argument_checks_come_before_any_device_work():
     with pytest.raises(_qalib.QaError, match="%d years" % years):
         _qalib.prcp_pors_counts(series, long_days[YMD])
     # a target index out of range, past the binding's own check
-    fn = _qalib._pq_fn("twxpc_spatial_corrob", [ctypes.c_int, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 4 +
-                       [ctypes.c_int64] + [ctypes.c_void_p] * 7 + [ctypes.c_char_p, ctypes.c_int])
+    fn = _qalib.load().twxpc_spatial_corrob
     buf = ctypes.create_string_buffer(512)
     tgt = np.array([0, n], np.int32)
     fl = np.ones((2, nd), np.uint8)

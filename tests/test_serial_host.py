@@ -130,7 +130,7 @@ def test_header_binding_and_build():
                                                                           _qalib.SC_RUN_THRESHOLD, _qalib.SC_MAX_MISS)
     assert np.float32(_qalib.SC_FILL_F4) == RS.FILL_F4 == ncio.FILL_F4
     build = open(os.path.join(ROOT, "build.sh")).read()
-    assert "topowx_amd/qa/twx_serial.[h]ip" in build and os.path.exists(os.path.join(ROOT, "topowx_amd", "qa", "twx_serial.hip"))
+    assert "topowx_amd/qa/twx_serial.hip" in build and os.path.exists(os.path.join(ROOT, "topowx_amd", "qa", "twx_serial.hip"))
     assert SERIAL_DB_VARIABLES["tmax"][0][:3] == ("tmax", "f4", float(ncio.FILL_F4)) and SERIAL_DB_VARIABLES["tmin"][1][:3] == ("flag_infilled", "i1", -127)
     import topowx_amd.infill as infill
     for name in ("write_infill_db", "get_bad_infill_stnids", "suspect_infill_stnids", "find_bad_infill_stns", "write_bad_stns_csv",

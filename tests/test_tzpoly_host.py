@@ -219,7 +219,12 @@ def test_unit_is_declared_bound_and_built():
     assert (RT.INSIDE, RT.FORCED, RT.NONE, RT.BAD_POINT) == (_qalib.TZ_INSIDE, _qalib.TZ_FORCED, _qalib.TZ_NONE, _qalib.TZ_BAD_POINT)
     assert TC.CHUNK == _qalib.TZ_CHUNK_EDGES
     build = open(os.path.join(ROOT, "build.sh")).read()
-    assert "topowx_amd/qa/twx_tzpoly.[h]ip" in build and build.count(".hip") == 7
+    assert "topowx_amd/qa/twx_tzpoly.hip" in build
+    # every unit of topowx_amd/qa is named in the build script exactly once, and nothing that is not there
+    named = re.findall(r"topowx_amd/qa/(twx_\w+\.hip)", build)
+    on_disk = [f for f in os.listdir(os.path.join(ROOT, "topowx_amd", "qa")) if re.fullmatch(r"twx_\w+\.hip", f)]
+    assert sorted(named) == sorted(on_disk) and len(set(named)) == len(named)
+    assert build.count("topowx_amd/csrc/twx_hip.hip") == 1
     pred = open(os.path.join(ROOT, "topowx_amd", "qa", "twx_tzpoly_pred.h")).read()
     assert "__host__ __device__" in pred and "hip_runtime" not in pred
     assert "Shewchuk" in open(os.path.join(ROOT, "PAPERS.md")).read()

@@ -36,29 +36,111 @@ class QaError(RuntimeError):
     pass
 
 
+class TwxmoStreams(C.Structure):
+    """twxmo_streams (include/twx_qa.h)."""
+    _fields_ = [("data", C.c_void_p), ("offset", C.POINTER(C.c_int64)), ("nstreams", C.c_int64), ("slot_bytes", C.c_int64),
+                ("nchunk", C.c_int32), ("chunk_y", C.c_int32), ("chunk_x", C.c_int32), ("reserved", C.c_int32)]
+
+
+# Every export of include/twx_qa.h: name -> (restype, argtypes).  ``load`` applies the table once;
+# tests/test_qalib_prototypes.py compares it with the header's prototypes.
+_ERR = [C.c_char_p, C.c_int]          # errbuf, errlen
+_PROTOTYPES = {
+    "twxqa_outlier_wls": (C.c_int, [C.c_int, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_int32] +
+                          [C.c_void_p] * 6 + _ERR),
+    "twxqa_spatial_nmonths": (C.c_int, [C.c_int64, C.c_void_p]),
+    "twxqa_spatial_regress": (C.c_int, [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64] +
+                              [C.c_void_p] * 8 + _ERR),
+    "twxqa_doy_norms": (C.c_int, [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 4 + _ERR),
+    "twxqa_spatial_only": (C.c_int, [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64] + [C.c_void_p] * 6 + _ERR),
+    "twxqa_non_spatial": (C.c_int, [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 7 + _ERR),
+    "twxif_infill_matrix": (C.c_int, [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_int32] +
+                            [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 8 + _ERR),
+    "twxem_mean_variance": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64] +
+                            [C.c_void_p] * 5 + [C.c_int64] + [C.c_void_p] * 4 +
+                            [C.c_double, C.c_int32, C.c_int32, C.c_int64] + [C.c_void_p] * 9 + _ERR),
+    "twxpp_ppca_fit": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64] +
+                       [C.c_void_p] * 6 + [C.c_int64] + [C.c_void_p] * 7 + [C.c_double, C.c_int32, C.c_int32, C.c_int64] +
+                       [C.c_void_p] * 9 + _ERR),
+    "twxck_infill_check": (C.c_int, [C.c_int, C.c_int64] + [C.c_void_p] * 4 + [C.c_double] * 4 + [C.c_int64] +
+                           [C.c_void_p] * 10 + _ERR),
+    "twxxv_holdout": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32] +
+                      [C.c_void_p] * 5 + _ERR),
+    "twxxv_infill_matrix": (C.c_int, [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 5 +
+                            [C.c_int64, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 4 +
+                            [C.c_int64] + [C.c_void_p] * 8 + _ERR),
+    "twxxv_score": (C.c_int, [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 10 + _ERR),
+    "twxsc_serial_complete": (C.c_int, [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 3 + [C.c_int32, C.c_float, C.c_int32] +
+                              [C.c_void_p] * 2 + [C.c_int32, C.c_int64] + [C.c_void_p] * 9 + _ERR),
+    "twxsc_series_check": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_float] + [C.c_double] * 3 + [C.c_int64] +
+                           [C.c_void_p] * 8 + _ERR),
+    "twxnr_components": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                   C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 11 + [C.c_int64] +
+                         [C.c_void_p] * 2 + _ERR),
+    "twxhm_obs_cnt": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int64] * 3 +
+                      [C.c_void_p] * 3 + _ERR),
+    "twxhm_monthly_means": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                      C.c_int32, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_void_p] * 2 + _ERR),
+    "twxhm_tobs_shift": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                   C.c_void_p] + [C.c_void_p] * 2 + _ERR),
+    "twxhm_homog_daily": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int32] + [C.c_void_p] * 10 +
+                          [C.c_int64] + [C.c_void_p] * 4 + [C.c_void_p] * 2 + _ERR),
+    "twxrv_sample": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_double,
+                               C.c_double, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] +
+                     [C.c_void_p] * 5 + _ERR),
+    "twxrv_nearest_data": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_double,
+                                     C.c_int64] + [C.c_void_p] * 9 + _ERR),
+    "twxrv_dup_classes": (C.c_int, [C.c_int, C.c_int64] + [C.c_void_p] * 5 + _ERR),
+    "twxrv_col_count": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_float, C.c_int64, C.c_void_p,
+                                  C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p] + _ERR),
+    "twxpq_non_spatial": (C.c_int, [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 3 + [C.c_int32, C.c_int32] +
+                          [C.c_void_p] * 3 + _ERR),
+    "twxpq_percentiles": (C.c_int, [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 4 + _ERR),
+    "twxpc_spatial_corrob": (C.c_int, [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64] +
+                             [C.c_void_p] * 7 + _ERR),
+    "twxpc_pors_counts": (C.c_int, [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 4 + _ERR),
+    "twxgh_parse_dly": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                  C.c_int32, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p] + _ERR),
+    "twxgh_parse_tobs": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_char_p,
+                                   C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                   C.c_void_p, C.c_void_p] + _ERR),
+    "twxgh_host_alloc": (C.c_void_p, [C.c_int64]),
+    "twxgh_host_free": (None, [C.c_void_p]),
+    "twxns_subset": (C.c_int, [C.c_int, C.c_int, C.c_void_p] + [C.c_int64] * 4 + [C.c_float, C.c_float] + [C.c_void_p] * 4 +
+                     [C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int] +
+                     [C.c_void_p] * 3 + _ERR),
+    "twxtz_locate": (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p] +
+                     _ERR),
+    "twxmo_sizes": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p] + _ERR),
+    "twxmo_create": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p] + _ERR),
+    "twxmo_destroy": (None, [C.c_void_p]),
+    "twxmo_last_error": (C.c_char_p, [C.c_void_p]),
+    "twxmo_clear": (C.c_int, [C.c_void_p, C.c_int64]),
+    "twxmo_place": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "twxmo_staging": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "twxmo_monthly": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "twxmo_deflate": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.POINTER(TwxmoStreams)]),
+    "twxmo_download": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
+    "twxmo_timing": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
+
 def load():
-    """Load libtwxqa.so; raises if it has not been built (no fallback)."""
+    """Load libtwxqa.so and give every export its prototype; raises if the library has not been built or lacks an export
+    (no fallback).  An entry that reports a missing build before it looks at its arguments calls this first; the others
+    check their arguments first and load in ``_call``."""
     global _LIB
     if _LIB is None:
         if not os.path.exists(LIB_PATH):
             raise QaError("%s not found: build it with ./build.sh (hipcc --offload-arch=gfx950); "
                           "there is no CPU fallback" % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        L.twxqa_outlier_wls.restype = C.c_int
-        L.twxqa_outlier_wls.argtypes = [C.c_int, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_int32] + \
-            [C.c_void_p] * 6 + [C.c_char_p, C.c_int]
-        L.twxqa_spatial_nmonths.restype = C.c_int
-        L.twxqa_spatial_nmonths.argtypes = [C.c_int64, C.c_void_p]
-        L.twxqa_spatial_regress.restype = C.c_int
-        L.twxqa_spatial_regress.argtypes = [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64] + \
-            [C.c_void_p] * 8 + [C.c_char_p, C.c_int]
-        L.twxqa_doy_norms.restype = C.c_int
-        L.twxqa_doy_norms.argtypes = [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 4 + [C.c_char_p, C.c_int]
-        L.twxqa_spatial_only.restype = C.c_int
-        L.twxqa_spatial_only.argtypes = [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64] + \
-            [C.c_void_p] * 6 + [C.c_char_p, C.c_int]
-        L.twxqa_non_spatial.restype = C.c_int
-        L.twxqa_non_spatial.argtypes = [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 7 + [C.c_char_p, C.c_int]
+        for name, (restype, argtypes) in _PROTOTYPES.items():
+            if not hasattr(L, name):
+                raise QaError("%s has no %s: it is older than this binding, run ./build.sh" % (LIB_PATH, name))
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _LIB = L
     return _LIB
 
@@ -67,13 +149,40 @@ def _c(a, dt):
     return np.ascontiguousarray(a, dt)
 
 
+def _call(name, args, ntimes, counts=None, ok=(0,)):
+    """Call the entry ``name`` with ``args`` and the tail the timed entries end in -- ``counts`` (a numpy array, if the entry
+    has one), kernel_ms [ntimes], errbuf, errlen.  Returns the times; a return value outside ``ok`` raises ``QaError``."""
+    ms = (C.c_float * ntimes)()
+    buf = C.create_string_buffer(512)
+    tail = (C.addressof(ms), buf, 512)
+    if counts is not None:
+        tail = (counts.ctypes.data,) + tail
+    if getattr(load(), name)(*(tuple(args) + tail)) not in ok:
+        raise QaError("%s failed: %s" % (name, buf.value.decode(errors="replace")))
+    return [float(v) for v in ms]
+
+
+def _ms_keys(kernels, host=()):
+    return tuple(k + "_kernel_ms" for k in kernels) + tuple(h + "_ms" for h in host)
+
+
+def _put_times(timing, keys, ms, add=False, **ints):
+    """Put the times ``ms`` into ``timing`` (a dict, or None: nothing happens) under ``keys`` (None skips a slot), then the
+    integer counters ``ints``.  ``add`` False assigns: the dict describes the last call; True accumulates over calls."""
+    if timing is None:
+        return
+    for key, v in list(zip(keys, ms)) + list(ints.items()):
+        if key is not None:
+            timing[key] = timing.get(key, 0) + v if add else v
+
+
 def outlier_wls(lon, lat, elev, lst13, norm13, pt, idx, wgt, knn_status, device=0, timing=None):
     """``twxqa_outlier_wls``: leave-one-out WLS errors of ``XvalOutlier.run_xval_stn`` (optimize.py:113-153).
 
     lon, lat, elev [nstn], lst13 / norm13 [13, nstn]: the pool (row 12 = annual means); pt [npts, 29]: the left-out
     stations; idx / wgt [npts, k] and knn_status [npts]: their neighbours as ``_lib.Context.knn`` returns them.
     Returns (err [npts, 13], status [npts, 13]); ``timing`` (a dict) receives the kernel's device time as ``kernel_ms``."""
-    L = load()
+    load()
     lon, lat, elev = (_c(a, np.float64) for a in (lon, lat, elev))
     nstn = lon.size
     lst13, norm13 = _c(lst13, np.float64), _c(norm13, np.float64)
@@ -90,15 +199,10 @@ def outlier_wls(lon, lat, elev, lst13, norm13, pt, idx, wgt, knn_status, device=
     k = idx.shape[1]
     err = np.empty((npts, NTARGET))
     status = np.empty((npts, NTARGET), np.int32)
-    ms = C.c_float(0.0)
-    buf = C.create_string_buffer(512)
-    rc = L.twxqa_outlier_wls(int(device), nstn, lon.ctypes.data, lat.ctypes.data, elev.ctypes.data, lst13.ctypes.data,
-                             norm13.ctypes.data, npts, pt.ctypes.data, k, idx.ctypes.data, wgt.ctypes.data,
-                             knn_status.ctypes.data, err.ctypes.data, status.ctypes.data, C.addressof(ms), buf, 512)
-    if rc != 0:
-        raise QaError("twxqa_outlier_wls failed: %s" % buf.value.decode(errors="replace"))
-    if timing is not None:
-        timing["kernel_ms"] = float(ms.value)
+    ms = _call("twxqa_outlier_wls", (int(device), nstn, lon.ctypes.data, lat.ctypes.data, elev.ctypes.data, lst13.ctypes.data,
+                                     norm13.ctypes.data, npts, pt.ctypes.data, k, idx.ctypes.data, wgt.ctypes.data,
+                                     knn_status.ctypes.data, err.ctypes.data, status.ctypes.data), 1)
+    _put_times(timing, ("kernel_ms",), ms)
     return err, status
 
 
@@ -111,6 +215,19 @@ def spatial_nmonths(ymd):
     return int(n)
 
 
+def _sp_inputs(lon, lat, tmin, tmax, ymd, target_idx):
+    """The inputs of ``spatial_regress`` and ``spatial_only``, converted and checked."""
+    lon, lat = _c(lon, np.float64), _c(lat, np.float64)
+    tmin, tmax = _c(tmin, np.float32), _c(tmax, np.float32)
+    ymd, target_idx = _c(ymd, np.int32), _c(target_idx, np.int32)
+    nstn, ndays = lon.size, ymd.size
+    if lon.ndim != 1 or lat.shape != lon.shape or tmin.shape != (nstn, ndays) or tmax.shape != (nstn, ndays):
+        raise ValueError("lon / lat must be [nstn] and tmin / tmax [nstn, ndays]")
+    if target_idx.ndim != 1:
+        raise ValueError("target_idx must be [ntarget]")
+    return lon, lat, tmin, tmax, ymd, target_idx
+
+
 def spatial_regress(lon, lat, tmin, tmax, ymd, target_idx, device=0, details=False, timing=None):
     """``twxqa_spatial_regress``: step08's spatial regression check (qa_temp.py:688-738, 858-1015).
 
@@ -118,16 +235,9 @@ def spatial_regress(lon, lat, tmin, tmax, ymd, target_idx, device=0, details=Fal
     target_idx [ntarget].  Returns (flag_tmin, flag_tmax), each uint8 [ntarget, ndays] (1 = flagged); with ``details``
     also a dict of est [ntarget, 2, ndays] and r / nvalid / status [ntarget, 2, nmonths].  ``timing`` (a dict) receives
     ``radius_kernel_ms`` and ``regress_kernel_ms``."""
-    L = load()
-    lon, lat = _c(lon, np.float64), _c(lat, np.float64)
-    tmin, tmax = _c(tmin, np.float32), _c(tmax, np.float32)
-    ymd, target_idx = _c(ymd, np.int32), _c(target_idx, np.int32)
+    load()
+    lon, lat, tmin, tmax, ymd, target_idx = _sp_inputs(lon, lat, tmin, tmax, ymd, target_idx)
     nstn, ndays, nt = lon.size, ymd.size, target_idx.size
-    if lon.ndim != 1 or lat.shape != lon.shape or tmin.shape != (nstn, ndays) or tmax.shape != (nstn, ndays):
-        raise ValueError("lon / lat must be [nstn] and tmin / tmax [nstn, ndays]")
-    if target_idx.ndim != 1:
-        raise ValueError("target_idx must be [ntarget]")
-    buf = C.create_string_buffer(512)
     fmin, fmax = np.zeros((nt, ndays), np.uint8), np.zeros((nt, ndays), np.uint8)
     det, ptr = {}, [None, None, None, None]
     if details:
@@ -135,14 +245,10 @@ def spatial_regress(lon, lat, tmin, tmax, ymd, target_idx, device=0, details=Fal
         det = dict(est=np.empty((nt, 2, ndays)), r=np.empty((nt, 2, nm)), nvalid=np.empty((nt, 2, nm), np.int32),
                    status=np.empty((nt, 2, nm), np.int32))
         ptr = [det[k].ctypes.data for k in ("est", "r", "nvalid", "status")]
-    ms = (C.c_float * 2)(0.0, 0.0)
-    rc = L.twxqa_spatial_regress(int(device), nstn, ndays, lon.ctypes.data, lat.ctypes.data, tmin.ctypes.data,
-                                 tmax.ctypes.data, ymd.ctypes.data, nt, target_idx.ctypes.data, fmin.ctypes.data,
-                                 fmax.ctypes.data, ptr[0], ptr[1], ptr[2], ptr[3], C.addressof(ms), buf, 512)
-    if rc != 0:
-        raise QaError("twxqa_spatial_regress failed: %s" % buf.value.decode(errors="replace"))
-    if timing is not None:
-        timing["radius_kernel_ms"], timing["regress_kernel_ms"] = float(ms[0]), float(ms[1])
+    ms = _call("twxqa_spatial_regress", (int(device), nstn, ndays, lon.ctypes.data, lat.ctypes.data, tmin.ctypes.data,
+                                         tmax.ctypes.data, ymd.ctypes.data, nt, target_idx.ctypes.data, fmin.ctypes.data,
+                                         fmax.ctypes.data, ptr[0], ptr[1], ptr[2], ptr[3]), 2)
+    _put_times(timing, ("radius_kernel_ms", "regress_kernel_ms"), ms)
     return (fmin, fmax, det) if details else (fmin, fmax)
 
 
@@ -150,19 +256,14 @@ def doy_norms(series, ymd, device=0, timing=None):
     """``twxqa_doy_norms``: the two day-of-year tables of biweight means of each series (qa_temp.py:1111-1130, 1171-1184,
     1215-1228).  series [nseries, ndays] float32 (NaN = missing), ymd [ndays] consecutive days.  Returns norms
     [nseries, 731]: rows 0..364 the 365-row table, rows 365..730 the 366-row table.  ``timing`` receives ``kernel_ms``."""
-    L = load()
+    load()
     series, ymd = _c(series, np.float32), _c(ymd, np.int32)
     if series.ndim != 2 or ymd.ndim != 1 or series.shape[1] != ymd.size:
         raise ValueError("series must be [nseries, ndays] and ymd [ndays]")
     out = np.empty((series.shape[0], NORM_ROWS))
-    ms = C.c_float(0.0)
-    buf = C.create_string_buffer(512)
-    rc = L.twxqa_doy_norms(int(device), series.shape[0], ymd.size, series.ctypes.data, ymd.ctypes.data, out.ctypes.data,
-                           C.addressof(ms), buf, 512)
-    if rc != 0:
-        raise QaError("twxqa_doy_norms failed: %s" % buf.value.decode(errors="replace"))
-    if timing is not None:
-        timing["kernel_ms"] = float(ms.value)
+    ms = _call("twxqa_doy_norms", (int(device), series.shape[0], ymd.size, series.ctypes.data, ymd.ctypes.data,
+                                   out.ctypes.data), 1)
+    _put_times(timing, ("kernel_ms",), ms)
     return out
 
 
@@ -172,27 +273,15 @@ def spatial_only(lon, lat, tmin, tmax, ymd, target_idx, device=0, timing=None):
     uint8 [ntarget, ndays] in the reference's numbering (1, 2, 16, 17, 18), norms [ntarget, 2, 731] (the target tables)
     and status [ntarget] (SP_OK / SP_FEW_NGHS / SP_NGH_CAP).  ``timing`` receives ``<kernel>_kernel_ms`` for the names in
     ``SPATIAL_ONLY_KERNELS``."""
-    L = load()
-    lon, lat = _c(lon, np.float64), _c(lat, np.float64)
-    tmin, tmax = _c(tmin, np.float32), _c(tmax, np.float32)
-    ymd, target_idx = _c(ymd, np.int32), _c(target_idx, np.int32)
+    load()
+    lon, lat, tmin, tmax, ymd, target_idx = _sp_inputs(lon, lat, tmin, tmax, ymd, target_idx)
     nstn, ndays, nt = lon.size, ymd.size, target_idx.size
-    if lon.ndim != 1 or lat.shape != lon.shape or tmin.shape != (nstn, ndays) or tmax.shape != (nstn, ndays):
-        raise ValueError("lon / lat must be [nstn] and tmin / tmax [nstn, ndays]")
-    if target_idx.ndim != 1:
-        raise ValueError("target_idx must be [ntarget]")
-    buf = C.create_string_buffer(512)
     fmin, fmax = np.zeros((nt, ndays), np.uint8), np.zeros((nt, ndays), np.uint8)
     norms, status = np.empty((nt, 2, NORM_ROWS)), np.empty(nt, np.int32)
-    ms = (C.c_float * 6)()
-    rc = L.twxqa_spatial_only(int(device), nstn, ndays, lon.ctypes.data, lat.ctypes.data, tmin.ctypes.data,
-                              tmax.ctypes.data, ymd.ctypes.data, nt, target_idx.ctypes.data, fmin.ctypes.data,
-                              fmax.ctypes.data, norms.ctypes.data, status.ctypes.data, C.addressof(ms), buf, 512)
-    if rc != 0:
-        raise QaError("twxqa_spatial_only failed: %s" % buf.value.decode(errors="replace"))
-    if timing is not None:
-        for k, name in enumerate(SPATIAL_ONLY_KERNELS):
-            timing[name + "_kernel_ms"] = float(ms[k])
+    ms = _call("twxqa_spatial_only", (int(device), nstn, ndays, lon.ctypes.data, lat.ctypes.data, tmin.ctypes.data,
+                                      tmax.ctypes.data, ymd.ctypes.data, nt, target_idx.ctypes.data, fmin.ctypes.data,
+                                      fmax.ctypes.data, norms.ctypes.data, status.ctypes.data), len(SPATIAL_ONLY_KERNELS))
+    _put_times(timing, _ms_keys(SPATIAL_ONLY_KERNELS), ms)
     return fmin, fmax, norms, status
 
 
@@ -202,23 +291,17 @@ def non_spatial(tmin, tmax, ymd, device=0, details=False, timing=None):
     each uint8 [nstn, ndays] in the reference's numbering (1 .. 13, 15, 18); with ``details`` also norms
     [nstn, 2, 731, 2]: mean and standard deviation of the day-of-year rows as the outlier check used them.  ``timing``
     receives ``<kernel>_kernel_ms`` for the names in ``NON_SPATIAL_KERNELS``."""
-    L = load()
+    load()
     tmin, tmax, ymd = _c(tmin, np.float32), _c(tmax, np.float32), _c(ymd, np.int32)
     if tmin.ndim != 2 or tmax.shape != tmin.shape or ymd.ndim != 1 or tmin.shape[1] != ymd.size:
         raise ValueError("tmin / tmax must be [nstn, ndays] and ymd [ndays]")
     nstn, ndays = tmin.shape
-    buf = C.create_string_buffer(512)
     fmin, fmax = np.zeros((nstn, ndays), np.uint8), np.zeros((nstn, ndays), np.uint8)
     norms = np.empty((nstn, 2, NORM_ROWS, 2)) if details else None
-    ms = (C.c_float * len(NON_SPATIAL_KERNELS))()
-    rc = L.twxqa_non_spatial(int(device), nstn, ndays, tmin.ctypes.data, tmax.ctypes.data, ymd.ctypes.data,
-                             fmin.ctypes.data, fmax.ctypes.data, norms.ctypes.data if details else None, C.addressof(ms),
-                             buf, 512)
-    if rc != 0:
-        raise QaError("twxqa_non_spatial failed: %s" % buf.value.decode(errors="replace"))
-    if timing is not None:
-        for k, name in enumerate(NON_SPATIAL_KERNELS):
-            timing[name + "_kernel_ms"] = float(ms[k])
+    ms = _call("twxqa_non_spatial", (int(device), nstn, ndays, tmin.ctypes.data, tmax.ctypes.data, ymd.ctypes.data,
+                                     fmin.ctypes.data, fmax.ctypes.data, norms.ctypes.data if details else None),
+               len(NON_SPATIAL_KERNELS))
+    _put_times(timing, _ms_keys(NON_SPATIAL_KERNELS), ms)
     return (fmin, fmax, norms) if details else (fmin, fmax)
 
 
@@ -245,20 +328,9 @@ def infill_matrix(lon, lat, obs, ymd, eligible, target_idx, group, nthres_all, n
 
     ``exclude_idx`` [ntarget] (-1 or a pool row that is never a neighbour of that target) picks ``twxxv_infill_matrix``, the
     same driver and kernels with that one comparison more (step15)."""
-    L = load()
+    load()
     if exclude_idx is not None:
-        if not hasattr(L.twxxv_infill_matrix, "_twx_ready"):
-            L.twxxv_infill_matrix.restype = C.c_int
-            L.twxxv_infill_matrix.argtypes = [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + \
-                [C.c_int64, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 4 + \
-                [C.c_int64] + [C.c_void_p] * 8 + [C.c_char_p, C.c_int]
-            L.twxxv_infill_matrix._twx_ready = True
         exclude_idx = _c(exclude_idx, np.int32)
-    if not hasattr(L.twxif_infill_matrix, "_twx_ready"):
-        L.twxif_infill_matrix.restype = C.c_int
-        L.twxif_infill_matrix.argtypes = [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_int32] + \
-            [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 8 + [C.c_char_p, C.c_int]
-        L.twxif_infill_matrix._twx_ready = True
     lon, lat, obs = _c(lon, np.float64), _c(lat, np.float64), _c(obs, np.float32)
     ymd, target_idx = _c(ymd, np.int32), _c(target_idx, np.int32)
     eligible, group = _c(eligible, np.uint8), _c(group, np.int8)
@@ -279,31 +351,24 @@ def infill_matrix(lon, lat, obs, ymd, eligible, target_idx, group, nthres_all, n
                off=np.zeros(ni + 1, np.int64))
     col = dict(idx=np.empty(cap, np.int32), ioa=np.empty(cap), dist=np.empty(cap), nlap=np.empty(cap, np.int32),
                nlap_stn=np.empty(cap, np.int32), keep=np.empty(cap, np.uint8))
-    rounds = C.c_int32(0)
-    ms = (C.c_float * (len(INFILL_MATRIX_KERNELS) + len(INFILL_MATRIX_HOST_TIMES)))()
-    buf = C.create_string_buffer(512)
+    rounds = np.zeros(1, np.int32)
     head = (int(device), nstn, ndays, lon.ctypes.data, lat.ctypes.data, obs.ctypes.data, ymd.ctypes.data,
             eligible.ctypes.data, nt, target_idx.ctypes.data)
-    tail = (ng, group.ctypes.data, nthres_all.ctypes.data, nthres_target_por.ctypes.data, int(min_daily_nnghs),
+    rest = (ng, group.ctypes.data, nthres_all.ctypes.data, nthres_target_por.ctypes.data, int(min_daily_nnghs),
             out["status"].ctypes.data, out["nnghs"].ctypes.data, out["max_dist"].ctypes.data, out["off"].ctypes.data, cap,
             col["idx"].ctypes.data, col["ioa"].ctypes.data, col["dist"].ctypes.data, col["nlap"].ctypes.data,
-            col["nlap_stn"].ctypes.data, col["keep"].ctypes.data, C.addressof(rounds), C.addressof(ms), buf, 512)
+            col["nlap_stn"].ctypes.data, col["keep"].ctypes.data)
+    ntimes = len(INFILL_MATRIX_KERNELS) + len(INFILL_MATRIX_HOST_TIMES)
     if exclude_idx is None:
-        name, rc = "twxif_infill_matrix", L.twxif_infill_matrix(*(head + tail))
+        ms = _call("twxif_infill_matrix", head + rest, ntimes, rounds)
     else:
-        name, rc = "twxxv_infill_matrix", L.twxxv_infill_matrix(*(head + (exclude_idx.ctypes.data,) + tail))
-    if rc != 0:
-        raise QaError("%s failed: %s" % (name, buf.value.decode(errors="replace")))
+        ms = _call("twxxv_infill_matrix", head + (exclude_idx.ctypes.data,) + rest, ntimes, rounds)
     total = int(out["off"][-1])
     for k, a in col.items():
         out[k] = a[:total].copy()
-    out["rounds"] = int(rounds.value)
-    if timing is not None:
-        for k, name in enumerate(INFILL_MATRIX_KERNELS):
-            timing[name + "_kernel_ms"] = float(ms[k])
-        for k, name in enumerate(INFILL_MATRIX_HOST_TIMES):          # allocations + copies in, copies out
-            timing[name + "_ms"] = float(ms[len(INFILL_MATRIX_KERNELS) + k])
-        timing["rounds"] = out["rounds"]
+    out["rounds"] = int(rounds[0])
+    # the host times: allocations + copies in, copies out
+    _put_times(timing, _ms_keys(INFILL_MATRIX_KERNELS, INFILL_MATRIX_HOST_TIMES), ms, rounds=out["rounds"])
     return out
 
 
@@ -314,6 +379,21 @@ EM_MAX_COLS = 31          # TWXEM_MAX_COLS
 EM_MAX_ROWS = 8192        # TWXEM_MAX_ROWS
 EM_KERNELS = ("em_prep", "em_iter")                     # TWXEM_NKERNELS
 EM_HOST_TIMES = ("em_upload", "em_download")            # the rest of TWXEM_NTIMES: host-clock milliseconds
+
+
+def _pack_sets(sets, ng, nrows):
+    """(set_group, set_ncol, set_vals) of ``twxem_mean_variance`` / ``twxpp_ppca_fit`` for ``sets``, a sequence of (group,
+    values [days of the group, ncol]); ``nrows`` [ng]: the days of every group."""
+    sets = list(sets)
+    set_group, set_ncol = np.zeros(len(sets), np.int32), np.zeros(len(sets), np.int32)
+    vals = []
+    for s, (g, v) in enumerate(sets):
+        v = np.asarray(v, np.float64)
+        if v.ndim != 2 or not 0 <= int(g) < ng or v.shape[0] != nrows[int(g)]:
+            raise ValueError("extra-column set %d must be [days of its group, ncol]" % s)
+        set_group[s], set_ncol[s] = int(g), v.shape[1]
+        vals.append(np.ascontiguousarray(v.T).ravel())              # column after column
+    return set_group, set_ncol, np.concatenate(vals) if vals else np.zeros(0)
 
 
 def em_mean_variance(obs, group, item_target, item_group, col_off, col_idx, sets=(), item_set=None, matrix_status=None,
@@ -329,13 +409,7 @@ def em_mean_variance(obs, group, item_target, item_group, col_off, col_idx, sets
     ``rounds`` and ``batches``, and with ``full`` mu [nitem, 31] and sigma [nitem, 31, 31].  ``timing`` receives
     ``em_prep_kernel_ms`` / ``em_iter_kernel_ms``, the host-clock ``em_upload_ms`` / ``em_download_ms``, ``em_rounds`` and
     ``em_batches``."""
-    L = load()
-    if not hasattr(L.twxem_mean_variance, "_twx_ready"):
-        L.twxem_mean_variance.restype = C.c_int
-        L.twxem_mean_variance.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64] + \
-            [C.c_void_p] * 5 + [C.c_int64] + [C.c_void_p] * 4 + [C.c_double, C.c_int32, C.c_int32, C.c_int64] + \
-            [C.c_void_p] * 9 + [C.c_char_p, C.c_int]
-        L.twxem_mean_variance._twx_ready = True
+    load()
     obs, group = _c(obs, np.float32), _c(group, np.int8)
     item_target, item_group = _c(item_target, np.int32), _c(item_group, np.int32)
     col_off, col_idx = _c(col_off, np.int64), _c(col_idx, np.int32)
@@ -348,16 +422,7 @@ def em_mean_variance(obs, group, item_target, item_group, col_off, col_idx, sets
     ng = int(group.max()) + 1 if group.size and group.max() >= 0 else 1
     ng = max(ng, int(item_group.max()) + 1 if ni else 1)
     nrows = np.bincount(group[group >= 0].astype(np.int64), minlength=ng)
-    sets = list(sets)
-    set_group, set_ncol = np.zeros(len(sets), np.int32), np.zeros(len(sets), np.int32)
-    vals = []
-    for s, (g, v) in enumerate(sets):
-        v = np.asarray(v, np.float64)
-        if v.ndim != 2 or not 0 <= int(g) < ng or v.shape[0] != nrows[int(g)]:
-            raise ValueError("extra-column set %d must be [days of its group, ncol]" % s)
-        set_group[s], set_ncol[s] = int(g), v.shape[1]
-        vals.append(np.ascontiguousarray(v.T).ravel())              # column after column
-    set_vals = np.concatenate(vals) if vals else np.zeros(0)
+    set_group, set_ncol, set_vals = _pack_sets(sets, ng, nrows)
     item_set = np.full(ni, -1, np.int32) if item_set is None else _c(item_set, np.int32)
     if item_set.shape != (ni,):
         raise ValueError("item_set must be [nitem]")
@@ -369,27 +434,19 @@ def em_mean_variance(obs, group, item_target, item_group, col_off, col_idx, sets
                status=np.empty(ni, np.int32))
     if full:
         out["mu"], out["sigma"] = np.empty((ni, EM_MAX_COLS)), np.empty((ni, EM_MAX_COLS, EM_MAX_COLS))
-    counts = (C.c_int32 * 2)()
-    ms = (C.c_float * (len(EM_KERNELS) + len(EM_HOST_TIMES)))()
-    buf = C.create_string_buffer(512)
-    rc = L.twxem_mean_variance(int(device), obs.shape[0], obs.shape[1], obs.ctypes.data, ng, group.ctypes.data, ni,
-                               item_target.ctypes.data, item_group.ctypes.data,
-                               matrix_status.ctypes.data if matrix_status is not None else None, col_off.ctypes.data,
-                               col_idx.ctypes.data, len(sets), set_group.ctypes.data, set_ncol.ctypes.data,
-                               set_vals.ctypes.data, item_set.ctypes.data, float(criterion), int(maxits),
-                               int(iters_per_launch), int(workspace_bytes), out["mean"].ctypes.data,
-                               out["variance"].ctypes.data, out["iters"].ctypes.data, out["delta"].ctypes.data,
-                               out["status"].ctypes.data, out["mu"].ctypes.data if full else None,
-                               out["sigma"].ctypes.data if full else None, C.addressof(counts), C.addressof(ms), buf, 512)
-    if rc != 0:
-        raise QaError("twxem_mean_variance failed: %s" % buf.value.decode(errors="replace"))
+    counts = np.zeros(2, np.int32)
+    ms = _call("twxem_mean_variance",
+               (int(device), obs.shape[0], obs.shape[1], obs.ctypes.data, ng, group.ctypes.data, ni,
+                item_target.ctypes.data, item_group.ctypes.data,
+                matrix_status.ctypes.data if matrix_status is not None else None, col_off.ctypes.data,
+                col_idx.ctypes.data, set_group.size, set_group.ctypes.data, set_ncol.ctypes.data,
+                set_vals.ctypes.data, item_set.ctypes.data, float(criterion), int(maxits),
+                int(iters_per_launch), int(workspace_bytes), out["mean"].ctypes.data,
+                out["variance"].ctypes.data, out["iters"].ctypes.data, out["delta"].ctypes.data,
+                out["status"].ctypes.data, out["mu"].ctypes.data if full else None,
+                out["sigma"].ctypes.data if full else None), len(EM_KERNELS) + len(EM_HOST_TIMES), counts)
     out["rounds"], out["batches"] = int(counts[0]), int(counts[1])
-    if timing is not None:
-        for k, name in enumerate(EM_KERNELS):
-            timing[name + "_kernel_ms"] = float(ms[k])
-        for k, name in enumerate(EM_HOST_TIMES):
-            timing[name + "_ms"] = float(ms[len(EM_KERNELS) + k])
-        timing["em_rounds"], timing["em_batches"] = out["rounds"], out["batches"]
+    _put_times(timing, _ms_keys(EM_KERNELS, EM_HOST_TIMES), ms, em_rounds=out["rounds"], em_batches=out["batches"])
     return out
 
 
@@ -428,25 +485,16 @@ def ppca_pack(obs, group, item_target, item_group, item_npcs, col_off, col_idx, 
     if item_group.min() < 0:
         raise ValueError("item_group must be >= 0")
     nrows = np.bincount(group[group >= 0].astype(np.int64), minlength=ng)
-    sets = list(sets)
-    set_group, set_ncol = np.zeros(len(sets), np.int32), np.zeros(len(sets), np.int32)
-    vals = []
-    for s, (g, v) in enumerate(sets):
-        v = np.asarray(v, np.float64)
-        if v.ndim != 2 or not 0 <= int(g) < ng or v.shape[0] != nrows[int(g)]:
-            raise ValueError("extra-column set %d must be [days of its group, ncol]" % s)
-        set_group[s], set_ncol[s] = int(g), v.shape[1]
-        vals.append(np.ascontiguousarray(v.T).ravel())              # column after column
-    set_vals = np.concatenate(vals) if vals else np.zeros(0)
+    set_group, set_ncol, set_vals = _pack_sets(sets, ng, nrows)
     item_set = np.full(ni, -1, np.int32) if item_set is None else _c(item_set, np.int32)
-    if item_set.shape != (ni,) or (ni and (item_set.min() < -1 or item_set.max() >= len(sets))):
+    if item_set.shape != (ni,) or (ni and (item_set.min() < -1 or item_set.max() >= set_group.size)):
         raise ValueError("item_set must be [nitem] of -1 or a set index")
     if matrix_status is None:
         matrix_status = np.zeros(ni, np.int32)
     matrix_status = _c(matrix_status, np.int32)
     if matrix_status.shape != (ni,):
         raise ValueError("matrix_status must be [nitem]")
-    ncols = (1 + np.diff(col_off) + np.where(item_set >= 0, set_ncol[np.maximum(item_set, 0)] if len(sets) else 0, 0)
+    ncols = (1 + np.diff(col_off) + np.where(item_set >= 0, set_ncol[np.maximum(item_set, 0)] if set_group.size else 0, 0)
              ).astype(np.int64)
     norms, stds = _c(norms, np.float64), _c(stds, np.float64)
     if norms.shape != (int(ncols.sum()),) or stds.shape != norms.shape:
@@ -475,13 +523,7 @@ def ppca_fit(obs, group, item_target, item_group, item_npcs, col_off, col_idx, n
     (flat) with ``fit_off`` [nitem + 1], r2cum [nitem, 32], iters, rel, status [nitem], ``rounds``, ``batches``, and with
     ``full`` C [nitem, 64, 32] and M [nitem, 64].  ``timing`` receives ``pp_prep_kernel_ms`` / ``pp_iter_kernel_ms``, the
     host-clock ``pp_upload_ms`` / ``pp_download_ms`` (accumulated over calls when present), ``pp_rounds``, ``pp_batches``."""
-    L = load()
-    if not hasattr(L.twxpp_ppca_fit, "_twx_ready"):
-        L.twxpp_ppca_fit.restype = C.c_int
-        L.twxpp_ppca_fit.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64] + \
-            [C.c_void_p] * 6 + [C.c_int64] + [C.c_void_p] * 7 + [C.c_double, C.c_int32, C.c_int32, C.c_int64] + \
-            [C.c_void_p] * 9 + [C.c_char_p, C.c_int]
-        L.twxpp_ppca_fit._twx_ready = True
+    load()
     p = ppca_pack(obs, group, item_target, item_group, item_npcs, col_off, col_idx, norms, stds, c0, sets, item_set,
                   matrix_status)
     ni = p["item_target"].size
@@ -489,29 +531,21 @@ def ppca_fit(obs, group, item_target, item_group, item_npcs, col_off, col_idx, n
                iters=np.empty(ni, np.int32), rel=np.empty(ni), status=np.empty(ni, np.int32))
     if full:
         out["C"], out["M"] = np.empty((ni, PP_MAX_COLS, PP_MAX_PCS)), np.empty((ni, PP_MAX_COLS))
-    counts = (C.c_int32 * 2)()
-    ms = (C.c_float * (len(PP_KERNELS) + len(PP_HOST_TIMES)))()
-    buf = C.create_string_buffer(512)
-    rc = L.twxpp_ppca_fit(int(device), p["obs"].shape[0], p["obs"].shape[1], p["obs"].ctypes.data, p["ng"],
-                          p["group"].ctypes.data, ni, p["item_target"].ctypes.data, p["item_group"].ctypes.data,
-                          p["matrix_status"].ctypes.data, p["item_npcs"].ctypes.data, p["col_off"].ctypes.data,
-                          p["col_idx"].ctypes.data, p["set_group"].size, p["set_group"].ctypes.data,
-                          p["set_ncol"].ctypes.data, p["set_vals"].ctypes.data, p["item_set"].ctypes.data,
-                          p["norms"].ctypes.data, p["stds"].ctypes.data, p["c0"].ctypes.data, float(threshold), int(maxits),
-                          int(iters_per_launch), int(workspace_bytes), out["fit"].ctypes.data, out["r2cum"].ctypes.data,
-                          out["iters"].ctypes.data, out["rel"].ctypes.data, out["status"].ctypes.data,
-                          out["C"].ctypes.data if full else None, out["M"].ctypes.data if full else None,
-                          C.addressof(counts), C.addressof(ms), buf, 512)
-    if rc != 0:
-        raise QaError("twxpp_ppca_fit failed: %s" % buf.value.decode(errors="replace"))
+    counts = np.zeros(2, np.int32)
+    ms = _call("twxpp_ppca_fit",
+               (int(device), p["obs"].shape[0], p["obs"].shape[1], p["obs"].ctypes.data, p["ng"],
+                p["group"].ctypes.data, ni, p["item_target"].ctypes.data, p["item_group"].ctypes.data,
+                p["matrix_status"].ctypes.data, p["item_npcs"].ctypes.data, p["col_off"].ctypes.data,
+                p["col_idx"].ctypes.data, p["set_group"].size, p["set_group"].ctypes.data,
+                p["set_ncol"].ctypes.data, p["set_vals"].ctypes.data, p["item_set"].ctypes.data,
+                p["norms"].ctypes.data, p["stds"].ctypes.data, p["c0"].ctypes.data, float(threshold), int(maxits),
+                int(iters_per_launch), int(workspace_bytes), out["fit"].ctypes.data, out["r2cum"].ctypes.data,
+                out["iters"].ctypes.data, out["rel"].ctypes.data, out["status"].ctypes.data,
+                out["C"].ctypes.data if full else None, out["M"].ctypes.data if full else None),
+               len(PP_KERNELS) + len(PP_HOST_TIMES), counts)
     out["rounds"], out["batches"] = int(counts[0]), int(counts[1])
-    if timing is not None:
-        for k, name in enumerate(PP_KERNELS + PP_HOST_TIMES):
-            key = name + ("_kernel_ms" if k < len(PP_KERNELS) else "_ms")
-            timing[key] = timing.get(key, 0.0) + float(ms[k])
-        timing["pp_rounds"] = timing.get("pp_rounds", 0) + out["rounds"]
-        timing["pp_batches"] = timing.get("pp_batches", 0) + out["batches"]
-        timing["pp_calls"] = timing.get("pp_calls", 0) + 1
+    _put_times(timing, _ms_keys(PP_KERNELS, PP_HOST_TIMES), ms, add=True, pp_rounds=out["rounds"],
+               pp_batches=out["batches"], pp_calls=1)
     return out
 
 
@@ -552,12 +586,7 @@ def infill_check(off, fit, obs, pen=None, sig=CK_SIG, mae_max=CK_MAE_MAX, r2_min
     Returns a dict of nobs, mae, r2, nimpossible, cpt_stat, cpt_tau, reasons (``CK_*`` bits), status and pen [nitem], and
     ``batches``.  ``timing`` receives ``ck_check_kernel_ms``, the host-clock ``ck_upload_ms`` / ``ck_download_ms``
     (accumulated over calls when present), ``ck_batches`` and ``ck_calls``."""
-    L = load()
-    if not hasattr(L.twxck_infill_check, "_twx_ready"):
-        L.twxck_infill_check.restype = C.c_int
-        L.twxck_infill_check.argtypes = [C.c_int, C.c_int64] + [C.c_void_p] * 4 + [C.c_double] * 4 + [C.c_int64] + \
-            [C.c_void_p] * 10 + [C.c_char_p, C.c_int]
-        L.twxck_infill_check._twx_ready = True
+    load()
     off, fit, obs = _c(off, np.int64), _c(fit, np.float64), _c(obs, np.float64)
     if off.ndim != 1 or off.size < 2 or fit.ndim != 1 or obs.shape != fit.shape:
         raise ValueError("off must be [nitem + 1 >= 2] and fit / obs flat arrays of one length")
@@ -571,24 +600,15 @@ def infill_check(off, fit, obs, pen=None, sig=CK_SIG, mae_max=CK_MAE_MAX, r2_min
     out = dict(nobs=np.empty(ni, np.int32), mae=np.empty(ni), r2=np.empty(ni), nimpossible=np.empty(ni, np.int32),
                cpt_stat=np.empty(ni), cpt_tau=np.empty(ni, np.int32), reasons=np.empty(ni, np.int32),
                status=np.empty(ni, np.int32))
-    counts = (C.c_int32 * 2)()
-    ms = (C.c_float * (len(CK_KERNELS) + len(CK_HOST_TIMES)))()
-    buf = C.create_string_buffer(512)
-    rc = L.twxck_infill_check(int(device), ni, off.ctypes.data, fit.ctypes.data, obs.ctypes.data, pen.ctypes.data,
-                              float(mae_max), float(r2_min), float(impossible_high), float(impossible_low),
-                              int(workspace_bytes), out["nobs"].ctypes.data, out["mae"].ctypes.data, out["r2"].ctypes.data,
-                              out["nimpossible"].ctypes.data, out["cpt_stat"].ctypes.data, out["cpt_tau"].ctypes.data,
-                              out["reasons"].ctypes.data, out["status"].ctypes.data, C.addressof(counts), C.addressof(ms),
-                              buf, 512)
-    if rc != 0:
-        raise QaError("twxck_infill_check failed: %s" % buf.value.decode(errors="replace"))
+    counts = np.zeros(2, np.int32)
+    ms = _call("twxck_infill_check",
+               (int(device), ni, off.ctypes.data, fit.ctypes.data, obs.ctypes.data, pen.ctypes.data,
+                float(mae_max), float(r2_min), float(impossible_high), float(impossible_low),
+                int(workspace_bytes), out["nobs"].ctypes.data, out["mae"].ctypes.data, out["r2"].ctypes.data,
+                out["nimpossible"].ctypes.data, out["cpt_stat"].ctypes.data, out["cpt_tau"].ctypes.data,
+                out["reasons"].ctypes.data, out["status"].ctypes.data), len(CK_KERNELS) + len(CK_HOST_TIMES), counts)
     out["pen"], out["batches"] = pen, int(counts[1])
-    if timing is not None:
-        for k, name in enumerate(CK_KERNELS + CK_HOST_TIMES):
-            key = name + ("_kernel_ms" if k < len(CK_KERNELS) else "_ms")
-            timing[key] = timing.get(key, 0.0) + float(ms[k])
-        timing["ck_batches"] = timing.get("ck_batches", 0) + out["batches"]
-        timing["ck_calls"] = timing.get("ck_calls", 0) + 1
+    _put_times(timing, _ms_keys(CK_KERNELS, CK_HOST_TIMES), ms, add=True, ck_batches=out["batches"], ck_calls=1)
     return out
 
 
@@ -608,12 +628,7 @@ def holdout(obs, target_idx, nkeep, device=0, timing=None):
     ``target_idx`` of obs [nstn, ndays] float32 (station-major).  A finite day is held iff ``nkeep > 0`` and at least
     ``nkeep`` finite days of the row lie after it.  Returns a dict of ``held`` [ntarget, ndays] bool, ``train_obs``
     [ntarget, ndays] float32 (held days NaN, the rest bit for bit), ``nheld`` and ``nfinite`` [ntarget]."""
-    L = load()
-    if not hasattr(L.twxxv_holdout, "_twx_ready"):
-        L.twxxv_holdout.restype = C.c_int
-        L.twxxv_holdout.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32] + \
-            [C.c_void_p] * 5 + [C.c_char_p, C.c_int]
-        L.twxxv_holdout._twx_ready = True
+    load()
     obs, target_idx = _c(obs, np.float32), _c(target_idx, np.int32)
     if obs.ndim != 2 or target_idx.ndim != 1:
         raise ValueError("obs must be [nstn, ndays] and target_idx [ntarget]")
@@ -623,14 +638,9 @@ def holdout(obs, target_idx, nkeep, device=0, timing=None):
     nt = target_idx.size
     held, train = np.zeros((nt, ndays), np.uint8), np.empty((nt, ndays), np.float32)
     nheld, nfin = np.zeros(nt, np.int32), np.zeros(nt, np.int32)
-    ms = C.c_float(0.0)
-    buf = C.create_string_buffer(512)
-    rc = L.twxxv_holdout(int(device), nstn, ndays, obs.ctypes.data, nt, target_idx.ctypes.data, int(nkeep),
-                         held.ctypes.data, train.ctypes.data, nheld.ctypes.data, nfin.ctypes.data, C.addressof(ms), buf, 512)
-    if rc != 0:
-        raise QaError("twxxv_holdout failed: %s" % buf.value.decode(errors="replace"))
-    if timing is not None:
-        timing["xv_holdout_kernel_ms"] = float(ms.value)
+    ms = _call("twxxv_holdout", (int(device), nstn, ndays, obs.ctypes.data, nt, target_idx.ctypes.data, int(nkeep),
+                                 held.ctypes.data, train.ctypes.data, nheld.ctypes.data, nfin.ctypes.data), 1)
+    _put_times(timing, ("xv_holdout_kernel_ms",), ms)
     return dict(held=held.view(np.bool_), train_obs=train, nheld=nheld, nfinite=nfin)
 
 
@@ -639,11 +649,7 @@ def xval_score(infill, obs, held, group, device=0, timing=None):
     writer's arithmetic, step15:127-134).  infill [ns, ndays] float64; obs [ns, ndays] float32; held [ns, ndays] bool; group
     [ndays] int8, -1 or 0 .. 11.  Returns a dict of ``n``, ``bias``, ``mae`` [ns] over the whole series, ``group_n``,
     ``group_bias``, ``group_mae`` [ns, 12], and ``obs_out`` / ``infill_out`` [ns, ndays] float32 (NaN off the scored days)."""
-    L = load()
-    if not hasattr(L.twxxv_score, "_twx_ready"):
-        L.twxxv_score.restype = C.c_int
-        L.twxxv_score.argtypes = [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 10 + [C.c_char_p, C.c_int]
-        L.twxxv_score._twx_ready = True
+    load()
     infill, obs = _c(infill, np.float64), _c(obs, np.float32)
     held, group = _c(np.asarray(held) != 0, np.uint8), _c(group, np.int8)
     if infill.ndim != 2 or obs.shape != infill.shape or held.shape != infill.shape or group.shape != infill.shape[1:]:
@@ -652,15 +658,10 @@ def xval_score(infill, obs, held, group, device=0, timing=None):
     n = np.zeros((ns, XV_NSCORES), np.int32)
     bias, mae = np.empty((ns, XV_NSCORES)), np.empty((ns, XV_NSCORES))
     oo, io = np.empty((ns, ndays), np.float32), np.empty((ns, ndays), np.float32)
-    ms = C.c_float(0.0)
-    buf = C.create_string_buffer(512)
-    rc = L.twxxv_score(int(device), ns, ndays, infill.ctypes.data, obs.ctypes.data, held.ctypes.data, group.ctypes.data,
-                       n.ctypes.data, bias.ctypes.data, mae.ctypes.data, oo.ctypes.data, io.ctypes.data, C.addressof(ms),
-                       buf, 512)
-    if rc != 0:
-        raise QaError("twxxv_score failed: %s" % buf.value.decode(errors="replace"))
-    if timing is not None:
-        timing["xv_score_kernel_ms"] = float(ms.value)
+    ms = _call("twxxv_score", (int(device), ns, ndays, infill.ctypes.data, obs.ctypes.data, held.ctypes.data,
+                               group.ctypes.data, n.ctypes.data, bias.ctypes.data, mae.ctypes.data, oo.ctypes.data,
+                               io.ctypes.data), 1)
+    _put_times(timing, ("xv_score_kernel_ms",), ms)
     return dict(n=n[:, XV_NGROUPS].copy(), bias=bias[:, XV_NGROUPS].copy(), mae=mae[:, XV_NGROUPS].copy(),
                 group_n=n[:, :XV_NGROUPS].copy(), group_bias=bias[:, :XV_NGROUPS].copy(),
                 group_mae=mae[:, :XV_NGROUPS].copy(), obs_out=oo, infill_out=io)
@@ -726,12 +727,7 @@ def serial_complete(tair, tair_infilled=None, flag=None, run_threshold=SC_RUN_TH
     groups ``norm`` [nseries, 12] float64 and ``norm_nmths`` int32.  ``timing`` receives ``sc_select_kernel_ms`` /
     ``sc_norms_kernel_ms``, the host-clock ``sc_upload_ms`` / ``sc_download_ms`` (accumulated over calls), ``sc_batches``
     and ``sc_calls``."""
-    L = load()
-    if not hasattr(L.twxsc_serial_complete, "_twx_ready"):
-        L.twxsc_serial_complete.restype = C.c_int
-        L.twxsc_serial_complete.argtypes = [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 3 + [C.c_int32, C.c_float, C.c_int32] + \
-            [C.c_void_p] * 2 + [C.c_int32, C.c_int64] + [C.c_void_p] * 9 + [C.c_char_p, C.c_int]
-        L.twxsc_serial_complete._twx_ready = True
+    load()
     tair = _c(tair, np.float32)
     if tair.ndim != 2:
         raise ValueError("tair must be [nseries, ndays]")
@@ -757,27 +753,19 @@ def serial_complete(tair, tair_infilled=None, flag=None, run_threshold=SC_RUN_TH
         out["serial"], out["flag_infilled"] = np.empty((ns, nd), np.float32), np.empty((ns, nd), np.int8)
     if norms:
         out["norm"], out["norm_nmths"] = np.empty((ns, 12)), np.empty((ns, 12), np.int32)
-    counts = (C.c_int32 * 2)()
-    ms = (C.c_float * (len(SC_KERNELS) + len(SC_HOST_TIMES)))()
-    buf = C.create_string_buffer(512)
-    rc = L.twxsc_serial_complete(int(device), ns, nd, tair.ctypes.data, tair_infilled.ctypes.data if full else None,
-                                 flag.ctypes.data if full else None, int(run_threshold), float(fill), ng,
-                                 group_first.ctypes.data if norms else None, group_ndays.ctypes.data if norms else None,
-                                 -1 if max_miss is None else int(max_miss), int(workspace_bytes),
-                                 out["serial"].ctypes.data if full else None, out["flag_infilled"].ctypes.data if full else None,
-                                 out["max_run"].ctypes.data, out["nmissing"].ctypes.data, out["all_infill"].ctypes.data,
-                                 out["norm"].ctypes.data if norms else None, out["norm_nmths"].ctypes.data if norms else None,
-                                 C.addressof(counts), C.addressof(ms), buf, 512)
-    if rc != 0:
-        raise QaError("twxsc_serial_complete failed: %s" % buf.value.decode(errors="replace"))
+    counts = np.zeros(2, np.int32)
+    ms = _call("twxsc_serial_complete",
+               (int(device), ns, nd, tair.ctypes.data, tair_infilled.ctypes.data if full else None,
+                flag.ctypes.data if full else None, int(run_threshold), float(fill), ng,
+                group_first.ctypes.data if norms else None, group_ndays.ctypes.data if norms else None,
+                -1 if max_miss is None else int(max_miss), int(workspace_bytes),
+                out["serial"].ctypes.data if full else None, out["flag_infilled"].ctypes.data if full else None,
+                out["max_run"].ctypes.data, out["nmissing"].ctypes.data, out["all_infill"].ctypes.data,
+                out["norm"].ctypes.data if norms else None, out["norm_nmths"].ctypes.data if norms else None),
+               len(SC_KERNELS) + len(SC_HOST_TIMES), counts)
     out["all_infill"] = out["all_infill"].view(np.bool_)
     out["batches"] = int(counts[1])
-    if timing is not None:
-        for k, name in enumerate(SC_KERNELS + SC_HOST_TIMES):
-            key = name + ("_kernel_ms" if k < len(SC_KERNELS) else "_ms")
-            timing[key] = timing.get(key, 0.0) + float(ms[k])
-        timing["sc_batches"] = timing.get("sc_batches", 0) + out["batches"]
-        timing["sc_calls"] = timing.get("sc_calls", 0) + 1
+    _put_times(timing, _ms_keys(SC_KERNELS, SC_HOST_TIMES), ms, add=True, sc_batches=out["batches"], sc_calls=1)
     return out
 
 
@@ -789,12 +777,7 @@ def series_check(series, pen=None, sig=CK_SIG, fill=SC_FILL_F4, impossible_high=
     point).  Returns a dict of nimpossible, nmissing, cpt_stat, cpt_tau, reasons (``CK_*`` bits), status [nseries], ``pen``
     and ``batches``.  ``timing`` receives ``sc_series_kernel_ms``, the host-clock ``sc_series_upload_ms`` /
     ``sc_series_download_ms`` (accumulated over calls), ``sc_series_batches`` and ``sc_series_calls``."""
-    L = load()
-    if not hasattr(L.twxsc_series_check, "_twx_ready"):
-        L.twxsc_series_check.restype = C.c_int
-        L.twxsc_series_check.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_float] + [C.c_double] * 3 + [C.c_int64] + \
-            [C.c_void_p] * 8 + [C.c_char_p, C.c_int]
-        L.twxsc_series_check._twx_ready = True
+    load()
     series = _c(series, np.float32)
     if series.ndim != 2:
         raise ValueError("series must be [nseries, ndays]")
@@ -802,23 +785,14 @@ def series_check(series, pen=None, sig=CK_SIG, fill=SC_FILL_F4, impossible_high=
     pen = cpt_penalty(nd, sig) if pen is None else float(pen)
     out = dict(nimpossible=np.empty(ns, np.int32), nmissing=np.empty(ns, np.int32), cpt_stat=np.empty(ns),
                cpt_tau=np.empty(ns, np.int32), reasons=np.empty(ns, np.int32), status=np.empty(ns, np.int32))
-    counts = (C.c_int32 * 2)()
-    ms = (C.c_float * len(SC_CHECK_TIMES))()
-    buf = C.create_string_buffer(512)
-    rc = L.twxsc_series_check(int(device), ns, nd, series.ctypes.data, float(fill), pen, float(impossible_high),
-                              float(impossible_low), int(workspace_bytes), out["nimpossible"].ctypes.data,
-                              out["nmissing"].ctypes.data, out["cpt_stat"].ctypes.data, out["cpt_tau"].ctypes.data,
-                              out["reasons"].ctypes.data, out["status"].ctypes.data, C.addressof(counts), C.addressof(ms),
-                              buf, 512)
-    if rc != 0:
-        raise QaError("twxsc_series_check failed: %s" % buf.value.decode(errors="replace"))
+    counts = np.zeros(2, np.int32)
+    ms = _call("twxsc_series_check",
+               (int(device), ns, nd, series.ctypes.data, float(fill), pen, float(impossible_high),
+                float(impossible_low), int(workspace_bytes), out["nimpossible"].ctypes.data,
+                out["nmissing"].ctypes.data, out["cpt_stat"].ctypes.data, out["cpt_tau"].ctypes.data,
+                out["reasons"].ctypes.data, out["status"].ctypes.data), len(SC_CHECK_TIMES), counts)
     out["pen"], out["batches"] = pen, int(counts[1])
-    if timing is not None:
-        for k, key in enumerate(SC_CHECK_TIMES):
-            if key:
-                timing[key] = timing.get(key, 0.0) + float(ms[k])
-        timing["sc_series_batches"] = timing.get("sc_series_batches", 0) + out["batches"]
-        timing["sc_series_calls"] = timing.get("sc_series_calls", 0) + 1
+    _put_times(timing, SC_CHECK_TIMES, ms, add=True, sc_series_batches=out["batches"], sc_series_calls=1)
     return out
 
 
@@ -887,13 +861,7 @@ def nnr_components_batched(cols, set_off, set_col, group, max_var=(0.99,), ngrou
     group [ndays] int8, -1 or 0 .. G - 1; ``max_var``: the cuts, each in (0, 1).  Returns an ``NrComponents``.  ``timing``
     receives ``nr_gram_kernel_ms`` / ``nr_eig_kernel_ms`` / ``nr_scores_kernel_ms`` and the host-clock ``nr_upload_ms`` /
     ``nr_download_ms``."""
-    L = load()
-    if not hasattr(L.twxnr_components, "_twx_ready"):
-        L.twxnr_components.restype = C.c_int
-        L.twxnr_components.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
-                                       C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 11 + [C.c_int64] + \
-            [C.c_void_p] * 2 + [C.c_char_p, C.c_int]
-        L.twxnr_components._twx_ready = True
+    load()
     cols, group = _c(cols, np.float32), _c(group, np.int8)
     set_off, set_col = _c(set_off, np.int64), _c(set_col, np.int32)
     max_var = _c(np.atleast_1d(np.asarray(max_var, np.float64)), np.float64)
@@ -915,22 +883,15 @@ def nnr_components_batched(cols, set_off, set_col, group, max_var=(0.99,), ngrou
                sweeps=np.empty((nset, max(ng, 0)), np.int32), ncomp=np.empty((nset, max(ng, 0), nthr), np.int32),
                mean=np.empty(ntot), sd=np.empty(ntot), var_explain=np.empty(ntot), eigval=np.empty(ntot),
                loadings=np.empty(sq), score_off=np.zeros(ni + 1, np.int64), scores=np.empty(cap))
-    ms = (C.c_float * (len(NR_KERNELS) + len(NR_HOST_TIMES)))()
-    buf = C.create_string_buffer(512)
-    rc = L.twxnr_components(int(device), cols.shape[1], cols.shape[0], cols.ctypes.data, nset, set_off.ctypes.data,
-                            set_col.ctypes.data, ng, group.ctypes.data, nthr, max_var.ctypes.data,
-                            out["status"].ctypes.data, out["bad_col"].ctypes.data, out["ncomp"].ctypes.data,
-                            out["sweeps"].ctypes.data, out["mean"].ctypes.data, out["sd"].ctypes.data,
-                            out["var_explain"].ctypes.data, out["eigval"].ctypes.data, out["loadings"].ctypes.data,
-                            out["score_off"].ctypes.data, cap, out["scores"].ctypes.data, C.addressof(ms), buf, 512)
-    if rc != 0:
-        raise QaError("twxnr_components failed: %s" % buf.value.decode(errors="replace"))
+    ms = _call("twxnr_components",
+               (int(device), cols.shape[1], cols.shape[0], cols.ctypes.data, nset, set_off.ctypes.data,
+                set_col.ctypes.data, ng, group.ctypes.data, nthr, max_var.ctypes.data,
+                out["status"].ctypes.data, out["bad_col"].ctypes.data, out["ncomp"].ctypes.data,
+                out["sweeps"].ctypes.data, out["mean"].ctypes.data, out["sd"].ctypes.data,
+                out["var_explain"].ctypes.data, out["eigval"].ctypes.data, out["loadings"].ctypes.data,
+                out["score_off"].ctypes.data, cap, out["scores"].ctypes.data), len(NR_KERNELS) + len(NR_HOST_TIMES))
     out["scores"] = out["scores"][:int(out["score_off"][-1])]
-    if timing is not None:
-        for k, name in enumerate(NR_KERNELS + NR_HOST_TIMES):
-            key = name + ("_kernel_ms" if k < len(NR_KERNELS) else "_ms")
-            timing[key] = timing.get(key, 0.0) + float(ms[k])
-        timing["nr_calls"] = timing.get("nr_calls", 0) + 1
+    _put_times(timing, _ms_keys(NR_KERNELS, NR_HOST_TIMES), ms, add=True, nr_calls=1)
     return NrComponents(set_off, nrows, max_var, out)
 
 
@@ -941,7 +902,6 @@ HM_MAX_MONTHS = 16384     # TWXHM_MAX_MONTHS
 HM_MAX_MISS = 9           # TWXHM_DEFAULT_MAX_MISS
 HM_PHA_MISSING = -9999    # TWXHM_PHA_MISSING
 HM_KERNELS = ("hm_cnt", "hm_means", "hm_tobs", "hm_delta", "hm_apply")
-_HM_TAIL = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]       # counts, kernel_ms, errbuf, errlen
 
 
 def month_groups(year, month):
@@ -981,21 +941,12 @@ def _hm_months(ndays, mth_first, mth_ndays):
     return mth_first, mth_ndays
 
 
-def _hm_call(fn, name, args, timing, kernels):
-    counts = (C.c_int32 * 2)()
-    ms = (C.c_float * 4)()
-    buf = C.create_string_buffer(512)
-    rc = fn(*(list(args) + [C.addressof(counts), C.addressof(ms), buf, 512]))
-    if rc != 0:
-        raise QaError("%s failed: %s" % (name, buf.value.decode(errors="replace")))
-    if timing is not None:
-        for k, kn in enumerate(kernels):
-            key = kn + "_kernel_ms"
-            timing[key] = timing.get(key, 0.0) + float(ms[k])
-        for k, key in ((2, "hm_upload_ms"), (3, "hm_download_ms")):
-            timing[key] = timing.get(key, 0.0) + float(ms[k])
-        timing["hm_batches"] = timing.get("hm_batches", 0) + int(counts[1])
-        timing["hm_calls"] = timing.get("hm_calls", 0) + 1
+def _hm_call(name, args, timing, kernels):
+    """A ``twxhm_*`` entry: its one or two kernels' times, then upload and download; returns the number of batches."""
+    counts = np.zeros(2, np.int32)
+    ms = _call(name, args, 4, counts)
+    keys = _ms_keys(kernels) + (None,) * (2 - len(kernels)) + ("hm_upload_ms", "hm_download_ms")
+    _put_times(timing, keys, ms, add=True, hm_batches=int(counts[1]), hm_calls=1)
     return int(counts[1])
 
 
@@ -1012,15 +963,9 @@ def obs_cnt(obs, day_month, first_day, last_day, workspace_bytes=0, device=0, ti
     first_day, last_day = int(first_day), int(last_day)
     if not 0 <= first_day <= last_day < nd:
         raise ValueError("need 0 <= first_day <= last_day < ndays")
-    L = load()
-    if not hasattr(L.twxhm_obs_cnt, "_twx_ready"):
-        L.twxhm_obs_cnt.restype = C.c_int
-        L.twxhm_obs_cnt.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int64] * 3 + \
-            [C.c_void_p] + _HM_TAIL
-        L.twxhm_obs_cnt._twx_ready = True
     cnt = np.empty((ns, 12), np.int32)
-    _hm_call(L.twxhm_obs_cnt, "twxhm_obs_cnt", (int(device), ns, nd, obs.ctypes.data, day_month.ctypes.data, first_day,
-                                                last_day, int(workspace_bytes), cnt.ctypes.data), timing, HM_KERNELS[0:1])
+    _hm_call("twxhm_obs_cnt", (int(device), ns, nd, obs.ctypes.data, day_month.ctypes.data, first_day, last_day,
+                               int(workspace_bytes), cnt.ctypes.data), timing, HM_KERNELS[0:1])
     return cnt
 
 
@@ -1031,14 +976,8 @@ def monthly_means(obs, mth_first, mth_ndays, max_miss=HM_MAX_MISS, workspace_byt
     ns, nd = obs.shape
     mth_first, mth_ndays = _hm_months(nd, mth_first, mth_ndays)
     nm = mth_first.size
-    L = load()
-    if not hasattr(L.twxhm_monthly_means, "_twx_ready"):
-        L.twxhm_monthly_means.restype = C.c_int
-        L.twxhm_monthly_means.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
-                                          C.c_int32, C.c_int64, C.c_void_p, C.c_void_p] + _HM_TAIL
-        L.twxhm_monthly_means._twx_ready = True
     mean, miss = np.empty((ns, nm), np.float32), np.empty((ns, nm), np.int16)
-    _hm_call(L.twxhm_monthly_means, "twxhm_monthly_means",
+    _hm_call("twxhm_monthly_means",
              (int(device), ns, nd, obs.ctypes.data, nm, mth_first.ctypes.data, mth_ndays.ctypes.data,
               -1 if max_miss is None else int(max_miss), int(workspace_bytes), mean.ctypes.data, miss.ctypes.data),
              timing, HM_KERNELS[1:2])
@@ -1050,16 +989,9 @@ def tobs_shift(tmax, tobs, workspace_bytes=0, device=0, timing=None):
     tmax = _hm_rows("tmax", tmax)
     tobs = _hm_rows("tobs", tobs, tmax.shape)
     ns, nd = tmax.shape
-    L = load()
-    if not hasattr(L.twxhm_tobs_shift, "_twx_ready"):
-        L.twxhm_tobs_shift.restype = C.c_int
-        L.twxhm_tobs_shift.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                       C.c_void_p] + _HM_TAIL
-        L.twxhm_tobs_shift._twx_ready = True
     out, nshift = np.empty((ns, nd), np.float32), np.empty(ns, np.int32)
-    _hm_call(L.twxhm_tobs_shift, "twxhm_tobs_shift", (int(device), ns, nd, tmax.ctypes.data, tobs.ctypes.data,
-                                                      int(workspace_bytes), out.ctypes.data, nshift.ctypes.data),
-             timing, HM_KERNELS[2:3])
+    _hm_call("twxhm_tobs_shift", (int(device), ns, nd, tmax.ctypes.data, tobs.ctypes.data, int(workspace_bytes),
+                                  out.ctypes.data, nshift.ctypes.data), timing, HM_KERNELS[2:3])
     return out, nshift
 
 
@@ -1093,16 +1025,10 @@ def homog_daily(obs, mth_mean, mth_miss, pha, mth_ymd, mth_first, mth_ndays, adj
         inner[adj_off[:-1][adj_off[:-1] < na]] = False           # the first entry of a station has no predecessor
         if (inner[1:] & (np.diff(adj_ymd_start) < 0)).any():
             raise ValueError("a station's adjustments must be sorted by adj_ymd_start")
-    L = load()
-    if not hasattr(L.twxhm_homog_daily, "_twx_ready"):
-        L.twxhm_homog_daily.restype = C.c_int
-        L.twxhm_homog_daily.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int32] + [C.c_void_p] * 10 + \
-            [C.c_int64] + [C.c_void_p] * 4 + _HM_TAIL
-        L.twxhm_homog_daily._twx_ready = True
     out = dict(delta=np.empty((ns, nm)), out=np.empty((ns, nd), np.float32), status=np.empty(ns, np.int32),
                nchanged=np.empty(ns, np.int32))
     out["batches"] = _hm_call(
-        L.twxhm_homog_daily, "twxhm_homog_daily",
+        "twxhm_homog_daily",
         (int(device), ns, nd, obs.ctypes.data, nm, mth_mean.ctypes.data, mth_miss.ctypes.data, pha.ctypes.data,
          mth_ymd.ctypes.data, mth_first.ctypes.data, mth_ndays.ctypes.data, adj_off.ctypes.data,
          adj_ymd_start.ctypes.data if na else None, adj_ymd_end.ctypes.data if na else None, adj.ctypes.data if na else None,
@@ -1150,16 +1076,11 @@ def _rv_raster(data, geo_t):
     return a, (RV_F32 if a.dtype == np.float32 else RV_F64), geo_t
 
 
-def _rv_call(fn, name, args, timing, kernel, tail=()):
-    ms = (C.c_float * RV_NTIMES)()
-    buf = C.create_string_buffer(512)
-    rc = fn(*(list(args) + list(tail) + [C.addressof(ms), buf, 512]))
-    if rc != 0:
-        raise QaError("%s failed: %s" % (name, buf.value.decode(errors="replace")))
-    if timing is not None:
-        for key, v in ((kernel + "_kernel_ms", ms[0]), ("rv_upload_ms", ms[1]), ("rv_download_ms", ms[2])):
-            timing[key] = timing.get(key, 0.0) + float(v)
-        timing["rv_calls"] = timing.get("rv_calls", 0) + 1
+def _rv_call(name, args, timing, kernel, counts=None):
+    """A ``twxrv_*`` entry: its kernel's time, then upload and download; ``counts`` [2] int32 where the entry has batches."""
+    ms = _call(name, args, RV_NTIMES, counts)
+    batches = {} if counts is None else {"rv_batches": int(counts[1])}
+    _put_times(timing, (kernel + "_kernel_ms", "rv_upload_ms", "rv_download_ms"), ms, add=True, rv_calls=1, **batches)
 
 
 def raster_sample(data, geo_t, ndata, lon, lat, band_ndata=None, extract_method=1, revert_nn=False, force_data_value=False,
@@ -1177,15 +1098,8 @@ def raster_sample(data, geo_t, ndata, lon, lat, band_ndata=None, extract_method=
     if extract_method not in (0, 1):
         raise ValueError("extract_method must be 0 (nearest) or 1 (bilinear); 3 (cubic spline) is not supported")
     n = lon.size
-    L = load()
-    if not hasattr(L.twxrv_sample, "_twx_ready"):
-        L.twxrv_sample.restype = C.c_int
-        L.twxrv_sample.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_double,
-                                   C.c_double, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + \
-            [C.c_void_p] * 5 + [C.c_char_p, C.c_int]
-        L.twxrv_sample._twx_ready = True
     out = dict(value=np.empty(n), status=np.empty(n, np.int32), row=np.empty(n, np.int32), col=np.empty(n, np.int32))
-    _rv_call(L.twxrv_sample, "twxrv_sample",
+    _rv_call("twxrv_sample",
              (int(device), a.shape[0], a.shape[1], code, a.ctypes.data, geo_t.ctypes.data, 0 if band_ndata is None else 1,
               0.0 if band_ndata is None else float(band_ndata), float(ndata), n, lon.ctypes.data, lat.ctypes.data,
               int(extract_method), 1 if revert_nn else 0, 1 if force_data_value else 0, out["value"].ctypes.data,
@@ -1238,15 +1152,9 @@ def raster_nearest_data(data, geo_t, ndata, row, col, device=0, timing=None):
     if row.min() < 0 or row.max() >= a.shape[0] or col.min() < 0 or col.max() >= a.shape[1]:
         raise ValueError("a start lies outside the raster")
     n = row.size
-    L = load()
-    if not hasattr(L.twxrv_nearest_data, "_twx_ready"):
-        L.twxrv_nearest_data.restype = C.c_int
-        L.twxrv_nearest_data.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_double,
-                                         C.c_int64] + [C.c_void_p] * 9 + [C.c_char_p, C.c_int]
-        L.twxrv_nearest_data._twx_ready = True
     out = dict(value=np.empty(n), dist=np.empty(n), runner_up=np.empty(n), ring=np.empty(n, np.int32),
                winner=np.empty(n, np.int32), status=np.empty(n, np.int32))
-    _rv_call(L.twxrv_nearest_data, "twxrv_nearest_data",
+    _rv_call("twxrv_nearest_data",
              (int(device), a.shape[0], a.shape[1], code, a.ctypes.data, geo_t.ctypes.data, float(ndata), n, row.ctypes.data,
               col.ctypes.data, out["value"].ctypes.data, out["dist"].ctypes.data, out["ring"].ctypes.data,
               out["winner"].ctypes.data, out["runner_up"].ctypes.data, out["status"].ctypes.data), timing, RV_KERNELS[1])
@@ -1267,14 +1175,9 @@ def dup_classes(lon, lat, device=0, timing=None):
     if lon.ndim != 1 or lon.size < 1 or lat.shape != lon.shape:
         raise ValueError("lon / lat must be [nstn >= 1]")
     n = lon.size
-    L = load()
-    if not hasattr(L.twxrv_dup_classes, "_twx_ready"):
-        L.twxrv_dup_classes.restype = C.c_int
-        L.twxrv_dup_classes.argtypes = [C.c_int, C.c_int64] + [C.c_void_p] * 5 + [C.c_char_p, C.c_int]
-        L.twxrv_dup_classes._twx_ready = True
     cls, size = np.empty(n, np.int32), np.empty(n, np.int32)
-    _rv_call(L.twxrv_dup_classes, "twxrv_dup_classes", (int(device), n, lon.ctypes.data, lat.ctypes.data, cls.ctypes.data,
-                                                        size.ctypes.data), timing, RV_KERNELS[2])
+    _rv_call("twxrv_dup_classes", (int(device), n, lon.ctypes.data, lat.ctypes.data, cls.ctypes.data, size.ctypes.data),
+             timing, RV_KERNELS[2])
     return cls, size
 
 
@@ -1305,19 +1208,10 @@ def col_count(data, cols=None, fill=None, workspace_bytes=0, device=0, timing=No
         if cols.size == 0:
             return np.zeros(0, np.int32)
     ncol = ns if cols is None else cols.size
-    L = load()
-    if not hasattr(L.twxrv_col_count, "_twx_ready"):
-        L.twxrv_col_count.restype = C.c_int
-        L.twxrv_col_count.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_float, C.c_int64, C.c_void_p,
-                                      C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
-        L.twxrv_col_count._twx_ready = True
     out = np.empty(ncol, np.int32)
-    counts = (C.c_int32 * 2)()
-    _rv_call(L.twxrv_col_count, "twxrv_col_count",
+    _rv_call("twxrv_col_count",
              (int(device), nd, ns, kind, data.ctypes.data, float(fill), ncol, None if cols is None else cols.ctypes.data,
-              int(workspace_bytes), out.ctypes.data), timing, RV_KERNELS[3], tail=(C.addressof(counts),))
-    if timing is not None:
-        timing["rv_batches"] = timing.get("rv_batches", 0) + int(counts[1])
+              int(workspace_bytes), out.ctypes.data), timing, RV_KERNELS[3], np.zeros(2, np.int32))
     return out
 
 
@@ -1328,12 +1222,6 @@ PQ_PCTILE_COLS = 5                    # TWXPQ_PCTILE_COLS: 30th, 50th, 70th, 90t
 PQ_MIN_PERCENTILE_VALUES = 20         # TWXPQ_MIN_PERCENTILE_VALUES
 PQ_MAX_WINDOW_VALUES = 4096           # TWXPQ_MAX_WINDOW_VALUES: 29 values per year of the series
 PQ_KERNELS = ("pq_init", "pq_dups", "pq_streak", "pq_frequent", "pq_gap", "pq_pctiles", "pq_clim")     # TWXPQ_NKERNELS
-
-
-def _pq_fn(name, argtypes):
-    fn = getattr(load(), name)
-    fn.restype, fn.argtypes = C.c_int, argtypes
-    return fn
 
 
 def _pq_series(name, a, ymd):
@@ -1353,20 +1241,13 @@ def prcp_non_spatial(prcp, tavg, ymd, streak=False, frequent=False, device=0, de
     prcp, tavg = _pq_series("prcp", prcp, ymd), _pq_series("tavg", tavg, ymd)
     if tavg.shape != prcp.shape:
         raise ValueError("prcp and tavg must have one shape")
-    fn = _pq_fn("twxpq_non_spatial", [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 3 + [C.c_int32, C.c_int32] +
-                [C.c_void_p] * 3 + [C.c_char_p, C.c_int])
     nstn, ndays = prcp.shape
-    buf = C.create_string_buffer(512)
     flag = np.zeros((nstn, ndays), np.uint8)
     pct = np.empty((nstn, PQ_PCTILE_ROWS, PQ_PCTILE_COLS)) if details else None
-    ms = (C.c_float * len(PQ_KERNELS))()
-    rc = fn(int(device), nstn, ndays, prcp.ctypes.data, tavg.ctypes.data, ymd.ctypes.data, int(bool(streak)),
-            int(bool(frequent)), flag.ctypes.data, pct.ctypes.data if details else None, C.addressof(ms), buf, 512)
-    if rc != 0:
-        raise QaError("twxpq_non_spatial failed: %s" % buf.value.decode(errors="replace"))
-    if timing is not None:
-        for k, name in enumerate(PQ_KERNELS):
-            timing[name + "_kernel_ms"] = float(ms[k])
+    ms = _call("twxpq_non_spatial", (int(device), nstn, ndays, prcp.ctypes.data, tavg.ctypes.data, ymd.ctypes.data,
+                                     int(bool(streak)), int(bool(frequent)), flag.ctypes.data,
+                                     pct.ctypes.data if details else None), len(PQ_KERNELS))
+    _put_times(timing, _ms_keys(PQ_KERNELS), ms)
     return (flag, pct) if details else flag
 
 
@@ -1375,16 +1256,10 @@ def prcp_percentiles(vals, ymd, device=0, timing=None):
     [nstn, ndays] float32 (NaN = missing).  Returns [nstn, 366, 5] float64; a row with fewer than 20 values > 0 is NaN."""
     ymd = _c(ymd, np.int32)
     vals = _pq_series("vals", vals, ymd)
-    fn = _pq_fn("twxpq_percentiles", [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 4 + [C.c_char_p, C.c_int])
-    buf = C.create_string_buffer(512)
     pct = np.empty((vals.shape[0], PQ_PCTILE_ROWS, PQ_PCTILE_COLS))
-    ms = C.c_float(0.0)
-    rc = fn(int(device), vals.shape[0], vals.shape[1], vals.ctypes.data, ymd.ctypes.data, pct.ctypes.data,
-            C.addressof(ms), buf, 512)
-    if rc != 0:
-        raise QaError("twxpq_percentiles failed: %s" % buf.value.decode(errors="replace"))
-    if timing is not None:
-        timing["pq_pctiles_kernel_ms"] = float(ms.value)
+    ms = _call("twxpq_percentiles", (int(device), vals.shape[0], vals.shape[1], vals.ctypes.data, ymd.ctypes.data,
+                                     pct.ctypes.data), 1)
+    _put_times(timing, ("pq_pctiles_kernel_ms",), ms)
     return pct
 
 
@@ -1416,20 +1291,13 @@ def prcp_spatial_corrob(lon, lat, prcp, ymd, target_idx, flags, device=0, detail
     fl = np.array(flags, np.uint8, order="C")                    # a copy: the input is not modified
     if fl.shape != (tgt.size, ndays):
         raise ValueError("flags must be [ntarget, ndays]")
-    fn = _pq_fn("twxpc_spatial_corrob", [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64] +
-                [C.c_void_p] * 7 + [C.c_char_p, C.c_int])
-    buf = C.create_string_buffer(512)
     status = np.zeros(tgt.size, np.int32)
     det = [np.empty((tgt.size, ndays)) for _ in range(3)] if details else [None] * 3
-    ms = (C.c_float * len(PC_KERNELS))()
-    rc = fn(int(device), nstn, ndays, lon.ctypes.data, lat.ctypes.data, prcp.ctypes.data, ymd.ctypes.data, tgt.size,
-            tgt.ctypes.data, fl.ctypes.data, status.ctypes.data, *[d.ctypes.data if details else None for d in det],
-            C.addressof(ms), buf, 512)
-    if rc != 0:
-        raise QaError("twxpc_spatial_corrob failed: %s" % buf.value.decode(errors="replace"))
-    if timing is not None:
-        for k, name in enumerate(PC_KERNELS):
-            timing[name + "_kernel_ms"] = float(ms[k])
+    ms = _call("twxpc_spatial_corrob",
+               (int(device), nstn, ndays, lon.ctypes.data, lat.ctypes.data, prcp.ctypes.data, ymd.ctypes.data, tgt.size,
+                tgt.ctypes.data, fl.ctypes.data, status.ctypes.data, *[d.ctypes.data if details else None for d in det]),
+               len(PC_KERNELS))
+    _put_times(timing, _ms_keys(PC_KERNELS), ms)
     return (fl, status) + tuple(det) if details else (fl, status)
 
 
@@ -1438,16 +1306,10 @@ def prcp_pors_counts(vals, ymd, device=0, timing=None):
     float32 (NaN = missing).  Returns [nstn, 366] uint16."""
     ymd = _c(ymd, np.int32)
     vals = _pq_series("vals", vals, ymd)
-    fn = _pq_fn("twxpc_pors_counts", [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 4 + [C.c_char_p, C.c_int])
-    buf = C.create_string_buffer(512)
     cnt = np.empty((vals.shape[0], PQ_PCTILE_ROWS), np.uint16)
-    ms = C.c_float(0.0)
-    rc = fn(int(device), vals.shape[0], vals.shape[1], vals.ctypes.data, ymd.ctypes.data, cnt.ctypes.data,
-            C.addressof(ms), buf, 512)
-    if rc != 0:
-        raise QaError("twxpc_pors_counts failed: %s" % buf.value.decode(errors="replace"))
-    if timing is not None:
-        timing["pc_rowcounts_kernel_ms"] = float(ms.value)
+    ms = _call("twxpc_pors_counts", (int(device), vals.shape[0], vals.shape[1], vals.ctypes.data, ymd.ctypes.data,
+                                     cnt.ctypes.data), 1)
+    _put_times(timing, ("pc_rowcounts_kernel_ms",), ms)
     return cnt
 
 
@@ -1475,12 +1337,6 @@ def _gh_buffer(buf, file_off):
     return a, int(off[-1]), off
 
 
-def _gh_timing(timing, ms):
-    if timing is not None:
-        for k, name in enumerate(GH_KERNELS):
-            timing[name + "_kernel_ms"] = timing.get(name + "_kernel_ms", 0.0) + float(ms[k])
-
-
 def ghcn_parse_dly(buf, file_off, file_col, nrows, min_ymd, max_ymd, ndays, fallback_cap=4096, device=0, timing=None):
     """``twxgh_parse_dly``: ``InsertGhcn.parse_stn_obs`` (create_db_all_stations.py:1042-1103) of the .dly files laid end to
     end in ``buf`` (any object with the buffer protocol) at ``file_off`` [nfiles + 1]; file f fills row ``file_col[f]``.
@@ -1495,9 +1351,6 @@ def ghcn_parse_dly(buf, file_off, file_col, nrows, min_ymd, max_ymd, ndays, fall
         raise ValueError("file_col must be [nfiles] distinct rows in 0 .. nrows - 1")
     if ndays < 1:
         raise ValueError("ndays must be the number of days from min_ymd to max_ymd")
-    fn = _pq_fn("twxgh_parse_dly", [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
-                                    C.c_int32, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p,
-                                                                                C.c_char_p, C.c_int])
     cap = int(fallback_cap)
     while True:
         val = np.empty((3, nrows, ndays), np.float32)
@@ -1505,14 +1358,11 @@ def ghcn_parse_dly(buf, file_off, file_col, nrows, min_ymd, max_ymd, ndays, fall
         bad = np.empty(nfiles, np.uint32)
         fb = np.zeros((max(cap, 1), GH_FB_WORDS), np.uint32)
         counts = np.zeros(3, np.int64)
-        ms = (C.c_float * len(GH_KERNELS))()
-        buf512 = C.create_string_buffer(512)
-        rc = fn(int(device), a.ctypes.data if nbytes else None, nbytes, nfiles, off.ctypes.data, col.ctypes.data, nrows,
-                int(min_ymd), int(max_ymd), ndays, val.ctypes.data, qf.ctypes.data, bad.ctypes.data, fb.ctypes.data, cap,
-                counts.ctypes.data, C.addressof(ms), buf512, 512)
-        if rc != 0:
-            raise QaError("twxgh_parse_dly failed: %s" % buf512.value.decode(errors="replace"))
-        _gh_timing(timing, ms)
+        ms = _call("twxgh_parse_dly",
+                   (int(device), a.ctypes.data if nbytes else None, nbytes, nfiles, off.ctypes.data, col.ctypes.data, nrows,
+                    int(min_ymd), int(max_ymd), ndays, val.ctypes.data, qf.ctypes.data, bad.ctypes.data, fb.ctypes.data, cap),
+                   len(GH_KERNELS), counts)
+        _put_times(timing, _ms_keys(GH_KERNELS), ms, add=True)
         if counts[2] <= cap:
             return val, qf, bad, fb[:int(counts[2])].copy(), counts
         cap = int(counts[2])
@@ -1536,22 +1386,16 @@ def ghcn_parse_tobs(buf, file_off, ids11, element, min_ymd, max_ymd, win0, tobs,
     table = np.zeros((ids.size, 11), np.uint8)
     for k, s in enumerate(ids):
         table[k, :len(s)] = np.frombuffer(s, np.uint8)
-    fn = _pq_fn("twxgh_parse_tobs", [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_char_p,
-                                     C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
-                                     C.c_void_p, C.c_void_p, C.c_char_p, C.c_int])
     cap = int(bad_cap)
     keep = tobs.copy()
     while True:
         bad = np.zeros((max(cap, 1), 2), np.uint32)
         counts = np.zeros(5, np.int64)
-        ms = (C.c_float * len(GH_KERNELS))()
-        buf512 = C.create_string_buffer(512)
-        rc = fn(int(device), a.ctypes.data if nbytes else None, nbytes, off.size - 1, off.ctypes.data, ids.size,
-                table.ctypes.data, elem, int(min_ymd), int(max_ymd), int(win0), tobs.shape[1], tobs.ctypes.data,
-                bad.ctypes.data, cap, counts.ctypes.data, C.addressof(ms), buf512, 512)
-        if rc != 0:
-            raise QaError("twxgh_parse_tobs failed: %s" % buf512.value.decode(errors="replace"))
-        _gh_timing(timing, ms)
+        ms = _call("twxgh_parse_tobs",
+                   (int(device), a.ctypes.data if nbytes else None, nbytes, off.size - 1, off.ctypes.data, ids.size,
+                    table.ctypes.data, elem, int(min_ymd), int(max_ymd), int(win0), tobs.shape[1], tobs.ctypes.data,
+                    bad.ctypes.data, cap), len(GH_KERNELS), counts)
+        _put_times(timing, _ms_keys(GH_KERNELS), ms, add=True)
         if counts[3] <= cap:
             return bad[:int(counts[3])].copy(), counts
         cap = int(counts[3])
@@ -1564,8 +1408,6 @@ class PinnedBuffer(object):
 
     def __init__(self, nbytes):
         lib = load()
-        lib.twxgh_host_alloc.restype, lib.twxgh_host_alloc.argtypes = C.c_void_p, [C.c_int64]
-        lib.twxgh_host_free.restype, lib.twxgh_host_free.argtypes = None, [C.c_void_p]
         self._lib, self.nbytes = lib, int(nbytes)
         self._p = lib.twxgh_host_alloc(self.nbytes)
         if not self._p:
@@ -1665,19 +1507,11 @@ def ns_subset(raw, scale, offset, marks, rec_slot, rec_day, ndays, lat_idx, lon_
     outs = [np.empty(s, np.float32) for s in shapes] or [np.empty(1, np.float32)]
     ptrs = (C.c_void_p * len(outs))(*[o.ctypes.data for o in outs])
     counts = np.zeros((max(nprod, 1), 3), np.int64)
-    ms = (C.c_float * len(NS_KERNELS))()
-    fn = _pq_fn("twxns_subset", [C.c_int, C.c_int, C.c_void_p] + [C.c_int64] * 4 + [C.c_float, C.c_float] + [C.c_void_p] * 4 +
-                [C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int] + [C.c_void_p] * 3 +
-                [C.c_char_p, C.c_int])
-    buf512 = C.create_string_buffer(512)
-    rc = fn(int(device), int(dtype), raw.ctypes.data, nrec, nl, ny, nx, float(np.float32(scale)), float(np.float32(offset)),
-            mk.ctypes.data, has.ctypes.data, slot.ctypes.data, day.ctypes.data, ndays, lat.size, lat.ctypes.data, lon.size,
-            lon.ctypes.data, nprod, pd.ctypes.data, int(layout), C.addressof(ptrs), counts.ctypes.data, C.addressof(ms), buf512, 512)
-    if rc != 0:
-        raise QaError("twxns_subset failed: %s" % buf512.value.decode(errors="replace"))
-    if timing is not None:
-        for k, name in enumerate(NS_KERNELS):
-            timing[name + "_ms"] = timing.get(name + "_ms", 0.0) + float(ms[k])
+    ms = _call("twxns_subset",
+               (int(device), int(dtype), raw.ctypes.data, nrec, nl, ny, nx, float(np.float32(scale)), float(np.float32(offset)),
+                mk.ctypes.data, has.ctypes.data, slot.ctypes.data, day.ctypes.data, ndays, lat.size, lat.ctypes.data, lon.size,
+                lon.ctypes.data, nprod, pd.ctypes.data, int(layout), C.addressof(ptrs)), len(NS_KERNELS), counts)
+    _put_times(timing, _ms_keys((), NS_KERNELS), ms, add=True)
     return outs, counts[:nprod]
 
 
@@ -1707,26 +1541,17 @@ def tz_locate(lon, lat, edge_off, bbox, edges, max_force_deg=1.0, uncertain_cap=
             (off.size and int(off[-1]) != ed.shape[0]):
         raise ValueError("need edge_off [npoly + 1] ending at nedge, bbox [npoly, 4] and edges [nedge, 4]")
     mf = float("inf") if max_force_deg is None else float(max_force_deg)
-    fn = _pq_fn("twxtz_locate", [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                 C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
-                                 C.c_char_p, C.c_int])
     npt, cap = lon.size, int(uncertain_cap)
     while True:
         poly, status, d2 = np.empty(npt, np.int32), np.empty(npt, np.int32), np.empty(npt, np.float64)
         unc = np.zeros((max(cap, 1), 2), np.int32)
         counts = np.zeros(4, np.int64)
-        ms = (C.c_float * len(TZ_PHASES))()
-        buf512 = C.create_string_buffer(512)
-        rc = fn(int(device), npt, lon.ctypes.data, lat.ctypes.data, off.size - 1, off.ctypes.data, bb.ctypes.data,
-                ed.ctypes.data if ed.size else None, mf, poly.ctypes.data, status.ctypes.data, d2.ctypes.data, unc.ctypes.data,
-                cap, counts.ctypes.data, C.addressof(ms), buf512, 512)
-        if rc not in (0, TZ_OVERFLOW):
-            raise QaError("twxtz_locate failed: %s" % buf512.value.decode(errors="replace"))
-        if timing is not None:
-            for k, name in enumerate(TZ_PHASES):
-                timing[name + "_ms"] = timing.get(name + "_ms", 0.0) + float(ms[k])
-            timing["tz_calls"] = timing.get("tz_calls", 0) + 1
-        if rc == 0:
+        ms = _call("twxtz_locate",
+                   (int(device), npt, lon.ctypes.data, lat.ctypes.data, off.size - 1, off.ctypes.data, bb.ctypes.data,
+                    ed.ctypes.data if ed.size else None, mf, poly.ctypes.data, status.ctypes.data, d2.ctypes.data,
+                    unc.ctypes.data, cap), len(TZ_PHASES), counts, ok=(0, TZ_OVERFLOW))
+        _put_times(timing, _ms_keys((), TZ_PHASES), ms, add=True, tz_calls=1)
+        if counts[TZ_C_UNCERTAIN] <= cap:                          # otherwise the entry returned TZ_OVERFLOW: the list was too small
             return poly, status, d2, unc[:int(counts[TZ_C_UNCERTAIN])].copy(), counts
         cap = int(counts[TZ_C_UNCERTAIN])
 
@@ -1740,19 +1565,12 @@ MO_SIZES = ("Yp", "Xp", "nchunk", "nseg", "slot_bytes", "device_bytes", "pinned_
 MO_FILL_I2 = np.int16(-32767)
 
 
-class TwxmoStreams(C.Structure):
-    """twxmo_streams (include/twx_qa.h)."""
-    _fields_ = [("data", C.c_void_p), ("offset", C.POINTER(C.c_int64)), ("nstreams", C.c_int64), ("slot_bytes", C.c_int64),
-                ("nchunk", C.c_int32), ("chunk_y", C.c_int32), ("chunk_x", C.c_int32), ("reserved", C.c_int32)]
-
-
 def mosaic_sizes(max_days, Y, X, chunk_y, chunk_x):
     """``twxmo_sizes``: dict of ``MO_SIZES`` for an object with these arguments (no device needed); ValueError when the library
     refuses them."""
-    fn = _pq_fn("twxmo_sizes", [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_char_p, C.c_int])
     sz = np.zeros(len(MO_SIZES), np.int64)
     buf = C.create_string_buffer(512)
-    if fn(int(max_days), int(Y), int(X), int(chunk_y), int(chunk_x), sz.ctypes.data, buf, 512) != 0:
+    if load().twxmo_sizes(int(max_days), int(Y), int(X), int(chunk_y), int(chunk_x), sz.ctypes.data, buf, 512) != 0:
         raise ValueError(buf.value.decode(errors="replace"))
     return {k: int(v) for k, v in zip(MO_SIZES, sz)}
 
@@ -1769,13 +1587,10 @@ class Mosaic(object):
         self.max_days, self.Y, self.X, self.cy, self.cx = int(max_days), int(Y), int(X), int(chunk_y), int(chunk_x)
         self.Yp, self.Xp, self.nchunk = self.sizes["Yp"], self.sizes["Xp"], self.sizes["nchunk"]
         self.lib = load()
-        fn = _pq_fn("twxmo_create", [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_char_p, C.c_int])
-        self.lib.twxmo_destroy.restype, self.lib.twxmo_destroy.argtypes = None, [C.c_void_p]
-        self.lib.twxmo_last_error.restype, self.lib.twxmo_last_error.argtypes = C.c_char_p, [C.c_void_p]
         h = C.c_void_p()
         buf = C.create_string_buffer(512)
         self.h = None
-        if fn(int(device), self.max_days, self.Y, self.X, self.cy, self.cx, C.byref(h), buf, 512) != 0:
+        if self.lib.twxmo_create(int(device), self.max_days, self.Y, self.X, self.cy, self.cx, C.byref(h), buf, 512) != 0:
             raise QaError(buf.value.decode(errors="replace"))
         self.h = h
         self._keep = None
@@ -1806,15 +1621,13 @@ class Mosaic(object):
         return [(d, r0, c0) for d in range(nlayers) for r0 in range(0, self.Yp, self.cy) for c0 in range(0, self.Xp, self.cx)]
 
     def clear(self, ndays):
-        fn = _pq_fn("twxmo_clear", [C.c_void_p, C.c_int64])
-        self._chk(fn(self.h, int(ndays)), "twxmo_clear")
+        self._chk(self.lib.twxmo_clear(self.h, int(ndays)), "twxmo_clear")
 
     def staging(self, shape):
         """An int16 array of ``shape`` over the pinned buffer the next ``place`` uploads from: fill it, then pass it to ``place``."""
-        fn = _pq_fn("twxmo_staging", [C.c_void_p, C.c_int64, C.c_void_p])
         n = int(np.prod(shape, dtype=np.int64))
         p = C.c_void_p()
-        self._chk(fn(self.h, n * 2, C.byref(p)), "twxmo_staging")
+        self._chk(self.lib.twxmo_staging(self.h, n * 2, C.byref(p)), "twxmo_staging")
         return np.frombuffer((C.c_char * (n * 2)).from_address(p.value), np.int16, n).reshape(shape)
 
     def place(self, slab, y0, x0):
@@ -1823,24 +1636,22 @@ class Mosaic(object):
         if a.dtype != np.int16 or a.ndim != 3:
             raise TypeError("place takes an int16 slab [nd, ty, tx]")
         a = np.ascontiguousarray(a)
-        fn = _pq_fn("twxmo_place", [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32])
         if not (-2 ** 31 <= int(y0) < 2 ** 31 and -2 ** 31 <= int(x0) < 2 ** 31):
             raise QaError("twxmo_place failed: the slab lies outside the mosaic")
-        self._chk(fn(self.h, a.ctypes.data, a.shape[0], a.shape[1], a.shape[2], int(y0), int(x0)), "twxmo_place")
+        self._chk(self.lib.twxmo_place(self.h, a.ctypes.data, a.shape[0], a.shape[1], a.shape[2], int(y0), int(x0)),
+                  "twxmo_place")
 
     def monthly(self, ndays, day_month):
         dm = _c(day_month, np.int32)
         if dm.shape != (int(ndays),):
             raise ValueError("day_month must be [ndays]")
-        fn = _pq_fn("twxmo_monthly", [C.c_void_p, C.c_int64, C.c_void_p])
-        self._chk(fn(self.h, int(ndays), dm.ctypes.data), "twxmo_monthly")
+        self._chk(self.lib.twxmo_monthly(self.h, int(ndays), dm.ctypes.data), "twxmo_monthly")
 
     def deflate(self, nlayers, monthly=False, with_offset=False):
         """List of uint8 views, one zlib stream per (layer, chunk row, chunk column) in that order -- views of the object's pinned
         block, valid until the next ``deflate``.  ``with_offset``: also the int64 offsets [n + 1] of the streams in that block."""
-        fn = _pq_fn("twxmo_deflate", [C.c_void_p, C.c_int, C.c_int64, C.c_void_p])
         s = TwxmoStreams()
-        self._chk(fn(self.h, MO_MONTHLY if monthly else MO_DAILY, int(nlayers), C.byref(s)), "twxmo_deflate")
+        self._chk(self.lib.twxmo_deflate(self.h, MO_MONTHLY if monthly else MO_DAILY, int(nlayers), C.byref(s)), "twxmo_deflate")
         n = int(s.nstreams)
         off = np.ctypeslib.as_array(s.offset, shape=(n + 1,)).copy()
         whole = np.frombuffer((C.c_char * int(off[-1])).from_address(s.data), np.uint8)
@@ -1851,17 +1662,16 @@ class Mosaic(object):
 
     def download(self, nlayers, monthly=False):
         """The padded image int16 [nlayers, Yp, Xp] (debug / tests)."""
-        fn = _pq_fn("twxmo_download", [C.c_void_p, C.c_int, C.c_int64, C.c_void_p])
         out = np.empty((int(nlayers), self.Yp, self.Xp), np.int16)
-        self._chk(fn(self.h, MO_MONTHLY if monthly else MO_DAILY, int(nlayers), out.ctypes.data), "twxmo_download")
+        self._chk(self.lib.twxmo_download(self.h, MO_MONTHLY if monthly else MO_DAILY, int(nlayers), out.ctypes.data),
+                  "twxmo_download")
         return out
 
     def timing(self):
         """{group + '_ms': device time since the last ``clear``} plus ``device_bytes`` / ``pinned_bytes`` held now."""
-        fn = _pq_fn("twxmo_timing", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
         ms = (C.c_float * len(MO_GROUPS))()
         db, pb = C.c_int64(), C.c_int64()
-        self._chk(fn(self.h, C.addressof(ms), C.addressof(db), C.addressof(pb)), "twxmo_timing")
+        self._chk(self.lib.twxmo_timing(self.h, C.addressof(ms), C.addressof(db), C.addressof(pb)), "twxmo_timing")
         out = {g + "_ms": float(ms[k]) for k, g in enumerate(MO_GROUPS)}
         out["device_bytes"], out["pinned_bytes"] = db.value, pb.value
         return out
