@@ -1,4 +1,5 @@
-"""High-precision arbiter of the universal-kriging solve (TEST INFRASTRUCTURE, like the rest of oracle/).
+"""High-precision arbiter of the universal-kriging solve and of the GWR hat row (TEST INFRASTRUCTURE, like the rest of
+oracle/).
 
 The kriging arithmetic of the reference lives in gstat / sp (parity unpinned at that
 boundary).  What CAN be pinned without R is the numerics: this module evaluates the published predictor -- the
@@ -6,6 +7,12 @@ sp / gstat WGS84 great-circle distance (Meeus, Astronomical Algorithms, ch. 11: 
 the exponential covariance, and the augmented (k + 5) universal-kriging system -- in 40-digit arithmetic (mpmath).
 The fp64 oracle (orc_uk: GLS form, centred and scaled trend) and the GPU kernels (fp32 pair distances and
 exponentials, fp64 factorisation, bordered Cholesky) are compared with it; the differences are pure rounding.
+
+The GWR half (gwr_hat) is the reference's own _gwr_series algebra (interp_tair.py:1099-1146), which IS plain numpy: the
+raw, unshifted 6 x 6 normal matrix X'WX of X = [1, lon, lat, elev, tdi, lst], solved in 40 digits.  The fp64 oracle
+(orc_gwr_hat: columns centred and scaled, Cholesky) and the GPU kernels (k_gwr_z / k_gwr_z_cell: columns shifted to the
+cell, unscaled Cholesky with reciprocal pivots) are compared with it (tests/test_oracle_gwr.py,
+tests/test_gpu_gwr_matrix.py): the hat row is invariant to both changes of basis, so again the differences are rounding.
 
 Known-answer distances that do NOT come from this repository's algebra (tests/test_oracle_uk.py):
   * sp's documented example  spDistsN1(cbind(c(5, 6), c(60, 60)), c(5, 60), longlat = TRUE) -> 0.00000 55.79918
@@ -72,3 +79,24 @@ def uk(lon, lat, elev, lst, y, pt, nug, psill, rng):
     mean = sum(sol[i] * mp.mpf(float(y[i])) for i in range(k))
     var = c00 - sum(sol[i] * b[i] for i in range(n))
     return float(mean), float(var)
+
+
+def gwr_hat(X5, w, x5):
+    """The GWR hat row z_j = w_j x0' (X'WX)^-1 x_j of _gwr_series (interp_tair.py:1099-1146) with X = [1, lon, lat, elev,
+    tdi, lst]: the raw, unshifted 6 x 6 normal matrix, solved by lu_solve in 40 digits.  X5 [k, 5] predictors of the
+    neighbours, w [k] their weights, x5 [5] the point's predictors.  Returns z [k] as Python floats."""
+    k = len(w)
+    X = [[mp.mpf(1)] + [mp.mpf(float(v)) for v in X5[i]] for i in range(k)]
+    W = [mp.mpf(float(v)) for v in w]
+    x0 = mp.matrix([mp.mpf(1)] + [mp.mpf(float(v)) for v in x5])
+    M = mp.zeros(6, 6)
+    for i in range(k):
+        for a in range(6):
+            wx = W[i] * X[i][a]
+            for b in range(a + 1):
+                M[a, b] += wx * X[i][b]
+    for a in range(6):
+        for b in range(a):
+            M[b, a] = M[a, b]
+    s = mp.lu_solve(M, x0)                                    # (X'WX is symmetric: x0' M^-1 x_j = (M^-1 x0)' x_j)
+    return [float(W[i] * sum(s[a] * X[i][a] for a in range(6))) for i in range(k)]

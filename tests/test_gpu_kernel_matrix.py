@@ -16,15 +16,21 @@ Measured on gfx950 (max |d| against the oracle over mean and variance, point mod
 1.4e-6 degC; fp64 build of the own size 6.9e-14; PREC = 2 6.9e-14.  Against the arbiter at each fp64 instance's largest k
 (long range): own size 3.2e-14, PREC = 2 3.2e-14, oracle 1.8e-14.  Grid mode: the fp64 builds and the coarse tie-guard
 build give the oracle's f4 bits, status, ninvalid and daily values everywhere."""
+import os
+import sys
+
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__))))
+
+from grid_bars import F64_BAR, FAST_BAR, assert_f4_oracle as _assert_f4_oracle, assert_fast_oracle  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 KMIN, KMAX = 6, 152                                          # TWX_MAX_NNGHS (include/twx.h)
 VARIOS = (None, (0.25, 1.4, 60.0), (0.8, 0.0, 0.0), (0.05, 2.0, 900.0))   # default, mid, pure nugget, long range
 LONG = 3                                                     # the ill-conditioned one
-FAST_BAR, F64_BAR = 1e-5, 1e-10                              # degC (the fp64 builds measure ~7e-14)
 # largest k of each fp64 kernel instance (twx_krig_bucket: 40, 48, .. 96 one-wave; 104 k_uk<7>, 120 <8>, 136 <9>, 152 <10>)
 INSTANCE_KMAX = (40, 48, 56, 64, 72, 80, 88, 96, 104, 120, 136, 152)
 # per-month constant bandwidths: every bucket edge of twx_krig_bucket and of twx_f64_coarse_bucket
@@ -166,16 +172,6 @@ def _grid_run(lib, grid, tmin, tmax, flags):
     return got, t, bw
 
 
-def _assert_f4_oracle(got, want, what):
-    assert np.array_equal(got["status"], want["status"]) and np.all(got["status"] == 0), what
-    assert np.array_equal(got["ninvalid"], want["ninvalid"]), what
-    for k in ("norm_tmin", "norm_tmax", "se_tmin", "se_tmax"):
-        n = int((got[k] != want[k].astype(np.float32)).sum())
-        assert n == 0, (what, k, n)                                             # the same f4 bits
-    for k in ("daily_tmin", "daily_tmax"):
-        assert (got[k] != want[k]).mean() < 2e-6, (what, k, int((got[k] != want[k]).sum()))
-
-
 @pytest.mark.parametrize("K", KSETS, ids=lambda K: "K%d" % K[0])
 def test_grid_mode_constant_bandwidths(golden_case, orc, K):
     """(b) Grid mode (pair distances through k_tile_dist) with every station's optim_nnghs of month m set to K_m: the
@@ -192,13 +188,7 @@ def test_grid_mode_constant_bandwidths(golden_case, orc, K):
         got, t, bw = _grid_run(lib, grid, dbn, dbx, flags)
         assert bw.shape == (144, 12) and np.all(bw == np.array(K)), (name, np.unique(bw))
         if name == "fast":
-            assert np.array_equal(got["status"], want["status"]) and np.all(got["status"] == 0)
-            assert np.array_equal(got["ninvalid"], want["ninvalid"])
-            for k in ("norm_tmin", "norm_tmax", "se_tmin", "se_tmax"):
-                err = float(np.abs(got[k].astype(np.float64) - want[k]).max())
-                assert err <= FAST_BAR, (k, err)
-            for k in ("daily_tmin", "daily_tmax"):
-                assert np.abs(got[k].astype(int) - want[k].astype(int)).max() <= 1, k
+            assert_fast_oracle(got, want)
         else:
             assert t["uk_f64_solves"] == t["uk_solves"] > 0, (name, t)
             _assert_f4_oracle(got, want, name)
