@@ -1122,7 +1122,7 @@ int twxpc_pors_counts(int device, int64_t nstn, int64_t ndays, const float *vals
 /* ---- the GHCN-Daily ingest of step04: InsertGhcn.parse_stn_obs (twx/db/create_db_all_stations.py:1042-1103) for a batch
  * of .dly files, and create_tobs_db (twx/homog/tobs.py:121-157) for a batch of by-year CSV files; twx_ghcn.hip.  Both see
  * one byte buffer of files laid end to end: file_off [nfiles + 1] int64 from 0 to nbytes.  A last line without a newline is
- * a line; lines never span files.  Out of scope: InsertSnotel / InsertRaws, downloading (add_utc_offset: twxtz_*). ---- */
+ * a line; lines never span files.  Out of scope: InsertSnotel, downloading (InsertRaws: include/twx_raws.h; add_utc_offset: twxtz_*). ---- */
 #define TWXGH_NKERNELS 4                /* kernel groups timed: fill; line index; claim pass; write pass */
 #define TWXGH_MAX_BYTES ((int64_t)2147483584)   /* of one call's buffer: a line's position + 1 is a uint32 */
 #define TWXGH_MAX_CELLS ((int64_t)1 << 31)      /* 3 nrows ndays of a .dly call, nstn nwin of a by-year call */

@@ -6,7 +6,11 @@
 buffer on a thread pool and settles what only Python can: a value field that is not ``[+-]?[0-9]+`` goes through
 ``float()`` exactly as the reference's would, a header ``int()`` refuses raises ``ValueError`` naming the file and line.
 
-Out of scope: ``InsertSnotel`` / ``InsertRaws`` (their inputs are scrapes of web services), ``obsio``,
+The RAWS sites, which ``read_ghcn_stations`` drops as the reference does, come from their native source: ``raws.py``
+(``InsertRaws``), through ``create_all_stations_db(..., raws=...)``.
+
+Out of scope: ``InsertSnotel`` (it reads files "cleaned and formatted using the snotel_clean module", which the reference
+does not contain, and parses them with ``pandas.read_csv``, whose number parser is not ``float()``), ``obsio``,
 deflate of the station variables (``zlib=False``: a station's kernel row IS a NetCDF-4 chunk and is written as one), and
 downloading anything.
 """
@@ -457,17 +461,43 @@ def write_all_stations_db(path, stns, days, batches, tobs=None, format=None):
     return path
 
 
+def _with_raws(stns, raws, stats):
+    """The station table of both networks, sorted by id as ``insert_data_netcdf_db`` sorts it (:509), and the RAWS part."""
+    from . import raws as _raws
+    rstns = _raws.read_raws_stations(*raws, stats=stats)
+    width = max(stns.dtype["station_name"].itemsize, rstns.dtype["station_name"].itemsize) // 4
+    dtype = [(n, "U%d" % width) if n == "station_name" else (n, t) for n, t in STN_DTYPE]
+    both = np.concatenate([stns.astype(dtype), rstns.astype(dtype)])
+    both = both[np.argsort(both[sdb.STN_ID], kind="stable")]
+    ids = both[sdb.STN_ID]
+    if np.any(ids[1:] == ids[:-1]):
+        raise ValueError("station id %s is listed twice" % ids[1:][ids[1:] == ids[:-1]][0])
+    # the prefixes make each network a contiguous run of rows: the writer relies on it
+    assert all(s.startswith("GHCN_") for s in ids[:stns.size]) and all(s.startswith("RAWS_") for s in ids[stns.size:])
+    return both, rstns
+
+
 def create_all_stations_db(path, path_stn_file, path_obs_files, start, end, path_by_year=None, check_obs_exist=False,
-                           format=None, batch_bytes=BATCH_BYTES, device=0, timing=None, stats=None):
+                           format=None, batch_bytes=BATCH_BYTES, device=0, timing=None, stats=None, raws=None):
     """The reference's step04: the database every later step takes as ``--db``.  ``tmin`` / ``tmax`` / ``prcp`` and their
     GHCN quality flags of every station of ``read_ghcn_stations`` over the period, and with ``path_by_year`` the times of
-    observation of Tmax as ``tobs_tmax`` (int16, -1 = none).  Every file is looked for before any device work.  Returns
-    the station table."""
+    observation of Tmax as ``tobs_tmax`` (int16, -1 = none).  ``raws`` = (metadata file, id file, directory of the daily
+    listings), the arguments of ``raws.read_raws_stations``, adds the RAWS sites: the table is the union of both networks
+    sorted by id, the RAWS rows have empty flags and no time of observation; ``stats`` receives their counts as
+    ``raws_*``.  Without ``raws`` the file is what it was before the RAWS ingest existed.  Every file is looked for before
+    any device work.  Returns the station table."""
     min_ymd, max_ymd, d0, ndays = _period(start, end)
     stns = read_ghcn_stations(path_stn_file, path_obs_files, check_obs_exist)
     if stns.size < 1:
         raise ValueError("%s lists no station to insert" % path_stn_file)
     paths = _dly_paths(stns[sdb.STN_ID], path_obs_files)
+    nghcn, rpaths, allstns = int(stns.size), [], stns
+    if raws is not None:
+        from . import raws as _raws
+        if len(tuple(raws)) != 3:
+            raise ValueError("raws must be (metadata file, id file, directory of the daily listings)")
+        allstns, rstns = _with_raws(stns, tuple(raws), stats)
+        rpaths = _raws._raws_paths(rstns[sdb.STN_ID], raws[2])
     years = range(d0.year, (d0 + _dt.timedelta(ndays - 1)).year + 1)
     by_year = _by_year_files(path_by_year, years) if path_by_year is not None else None
     days = get_days_metadata(d0, d0 + _dt.timedelta(ndays - 1))
@@ -477,12 +507,25 @@ def create_all_stations_db(path, path_stn_file, path_obs_files, start, end, path
         out = parse_tobs_files(by_year, stns[sdb.STN_ID], start, end, device=device, timing=timing, stats=tstats)
         if stats is not None:
             stats.update({"tobs_" + k: v for k, v in tstats.items()})
+        if allstns.size > nghcn:                                   # a RAWS site has no time of observation
+            out = np.concatenate([out, np.full((allstns.size - nghcn, ndays), -1, np.int16)])
         return out
 
-    write_all_stations_db(path, stns, days, iter_dly_batches(paths, start, end, batch_bytes=batch_bytes, device=device,
-                                                             timing=timing, stats=stats),
-                          tobs=tobs if by_year is not None else None, format=format)
-    return stns
+    def batches():
+        for b in iter_dly_batches(paths, start, end, batch_bytes=batch_bytes, device=device, timing=timing, stats=stats):
+            yield b
+        if rpaths:
+            rstats = {}
+            try:
+                for i0, i1, val, flag in _raws.iter_raws_batches(rpaths, start, end, batch_bytes=batch_bytes, device=device,
+                                                                 timing=timing, stats=rstats):
+                    yield nghcn + i0, nghcn + i1, val, flag
+            finally:
+                if stats is not None:
+                    stats.update({"raws_" + k: v for k, v in rstats.items()})
+
+    write_all_stations_db(path, allstns, days, batches(), tobs=tobs if by_year is not None else None, format=format)
+    return allstns
 
 
 def create_tobs_db(path_ghcn_yrly, fpath_db, stnids, min_date, max_date, element="TMAX", format=None, device=0):

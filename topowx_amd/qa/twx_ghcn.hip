@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "twx_ghcn_field.h"
+#include "twx_ghcn_index.h"
 #include "twx_qa.h"
 #include "twx_qa_common.h"
 
@@ -61,33 +62,6 @@ __device__ __forceinline__ uint32_t gh_thread_newlines(const uint8_t *__restrict
     const uint4 w = *reinterpret_cast<const uint4 *>(buf + p0);
     const int64_t left = nbytes - 1 - p0;
     return gh_newlines(w, left > 16 ? 16 : (int)left);
-}
-
-// the file that holds byte q (0 <= q < file_off[nfiles]): the last f with file_off[f] <= q
-__device__ __forceinline__ int gh_file_of(const int64_t *__restrict__ file_off, int nfiles, int64_t q)
-{
-    int lo = 0, hi = nfiles;                                     // file_off[lo] <= q < file_off[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (file_off[mid] <= q) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// Line i of the index: entries 0 .. nfiles - 1 are the files' first lines, the rest the candidates.  False: no line.
-__device__ __forceinline__ bool gh_line(int64_t i, int64_t nlines, int nfiles, const int64_t *__restrict__ file_off,
-                                        const uint32_t *__restrict__ cand, int *f, int64_t *start, int64_t *fend)
-{
-    if (i >= nlines) return false;
-    if (i < nfiles) {
-        *f = (int)i;
-        *start = file_off[i];
-    } else {
-        *start = (int64_t)cand[i - nfiles];
-        *f = gh_file_of(file_off, nfiles, *start - 1);           // the file of the newline byte
-    }
-    *fend = file_off[*f + 1];
-    return *start < *fend;
 }
 
 }  // namespace
@@ -371,6 +345,19 @@ int gh_index(const uint8_t *buf, int64_t nbytes, int64_t nfiles, const int64_t *
 }
 
 }  // namespace
+
+// twx_ghcn_index.h: the index for another unit, which owns what comes back in dev
+int gh_index_build(const uint8_t *buf, int64_t nbytes, int64_t nfiles, const int64_t *file_off, void *dev[4], uint32_t *ncand,
+                   float *ms, char *errbuf, int errlen)
+{
+    QaBuf b[4];
+    QaTimer tm;
+    dev[0] = dev[1] = dev[2] = dev[3] = nullptr;
+    QACHK(tm.init());
+    const int rc = gh_index(buf, nbytes, nfiles, file_off, b[0], b[1], b[2], b[3], ncand, tm, ms, errbuf, errlen);
+    for (int k = 0; k < 4; ++k) { dev[k] = b[k].p; b[k].p = nullptr; }
+    return rc;
+}
 
 extern "C" int twxgh_parse_dly(int device, const uint8_t *buf, int64_t nbytes, int64_t nfiles, const int64_t *file_off,
                                const int32_t *file_col, int64_t nrows, int32_t min_ymd, int32_t max_ymd, int64_t ndays,
