@@ -160,6 +160,28 @@ def select(db, lat, lon, k, excl=-1, rm_zero_dist=False):
     return rc, idx, dist, wgt
 
 
+def smooth_nnghs(optim_m, idx, wgt):
+    """(status, bandwidth) of orc_smooth_nnghs (interp_tair.py:821-835 / :245-259): ``optim_m`` is one month's column of the
+    table [n], ``idx`` / ``wgt`` the neighbours and weights of ``select``."""
+    optim_m = np.ascontiguousarray(optim_m, np.float64)
+    idx = np.ascontiguousarray(idx, np.int32)
+    wgt = np.ascontiguousarray(wgt, np.float64)
+    k = C.c_int(0)
+    rc = lib().orc_smooth_nnghs(_ptr(optim_m, _dp), _ptr(idx, _ip), _ptr(wgt, _dp), C.c_int(idx.size), C.byref(k))
+    return rc, k.value
+
+
+def smooth_vario(nug_m, psill_m, rng_m, idx, wgt):
+    """(status, [nug, psill, rng]) of orc_smooth_vario (interp_tair.py:837-851)."""
+    nug_m, psill_m, rng_m = (np.ascontiguousarray(a, np.float64) for a in (nug_m, psill_m, rng_m))
+    idx = np.ascontiguousarray(idx, np.int32)
+    wgt = np.ascontiguousarray(wgt, np.float64)
+    v = np.zeros(3)
+    rc = lib().orc_smooth_vario(_ptr(nug_m, _dp), _ptr(psill_m, _dp), _ptr(rng_m, _dp), _ptr(idx, _ip), _ptr(wgt, _dp),
+                                C.c_int(idx.size), _ptr(v, _dp))
+    return rc, v
+
+
 def uk(lon, lat, elev, lst, y, pt, nug, psill, rng):
     lon, lat, elev, lst, y = (np.ascontiguousarray(a, np.float64) for a in (lon, lat, elev, lst, y))
     mean, var = C.c_double(), C.c_double()

@@ -16,6 +16,32 @@ def assert_f4_oracle(got, want, what):
         assert (got[k] != want[k]).mean() < 2e-6, (what, k, int((got[k] != want[k]).sum()))
 
 
+def assert_fast_oracle_where(got, want, what=""):
+    """assert_fast_oracle for grids with failing cells: the oracle's status on EVERY cell; where it is 0, the oracle's ninvalid
+    (two-variable daily runs), normals / SE within 1e-5 degC and daily values within 1; fill values elsewhere.  Returns the
+    worst normals / SE error and the number of daily values off by one."""
+    assert np.array_equal(got["status"], want["status"]), (what, got["status"].tolist(), want["status"].tolist())
+    ok = want["status"] == 0
+    worst, off = 0.0, 0
+    for k in sorted(got):
+        if k == "status":
+            continue
+        assert np.array_equal(got[k][..., ~ok], want[k][..., ~ok].astype(got[k].dtype)), (what, k, "fill values")
+        if not ok.any():
+            continue
+        if k == "ninvalid":
+            assert np.array_equal(got[k][ok], want[k][ok]), (what, k)
+        elif k.startswith("daily_"):
+            d = np.abs(got[k][:, ok].astype(int) - want[k][:, ok].astype(int))
+            assert d.max() <= 1, (what, k, int(d.max()))
+            off += int((d != 0).sum())
+        else:
+            err = float(np.abs(got[k][:, ok].astype(np.float64) - want[k][:, ok]).max())
+            assert err <= FAST_BAR, (what, k, err)
+            worst = max(worst, err)
+    return worst, off
+
+
 def assert_fast_oracle(got, want):
     """The default (fast) build: the oracle's status and ninvalid, normals / SE within 1e-5 degC, daily values within 1."""
     assert np.array_equal(got["status"], want["status"]) and np.all(got["status"] == 0)
