@@ -24,8 +24,8 @@ show_diagnostics "$LOG"
 python3 tests/tools/isa_resources.py "$LOG" > topowx_amd/libtwxhip.resources.txt
 # libtwxqa.so: the station QA kernels (include/twx_qa.h), a library of their own -- built second, same flags.  Every unit
 # of topowx_amd/qa is named here once (tests/test_emnorm_host.py compares the names with the directory; twxrw_raws.hip is
-# checked by tests/test_raws_host.py); twx_mosaic
-# deflates with the kernels of topowx_amd/csrc/twx_deflate.h.
+# checked by tests/test_raws_host.py); the headers next to them (twx_qa_common.h, twx_qa_series.h, ...) are no units;
+# twx_mosaic deflates with the kernels of topowx_amd/csrc/twx_deflate.h.
 if ! hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared -std=c++17 -Iinclude \
     -Rpass-analysis=kernel-resource-usage "$@" -o topowx_amd/libtwxqa.so topowx_amd/qa/twx_outlier.hip \
     topowx_amd/qa/twx_spatial.hip topowx_amd/qa/twx_corrob.hip topowx_amd/qa/twx_nonspatial.hip \

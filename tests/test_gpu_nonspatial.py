@@ -172,6 +172,25 @@ def test_edge_all_nan_one_value_one_station_and_a_short_month():
     assert np.array_equal(g0[:, 0], f0[:, 2]) and np.array_equal(g1[:, 0], f1[:, 2])
 
 
+def test_streak_walk_at_the_block_seams():
+    """Flag 9 of runs planted where the streak walk's 64-day blocks meet (tests/streak_cases.py), in both variables; the
+    NaN days inside the long run also keep the duplicate-month check, which runs first, from taking its months."""
+    import restate_nonspatial as RN
+    import streak_cases as SC
+    days = SC.days()
+    base = np.arange(SC.NDAYS)[:, None] * 0.07 - 10.0 + np.arange(SC.NSTN)[None, :] * 0.01
+    tmin, planted = SC.build(base, 30.5 + np.arange(len(SC.RUNS)), [np.nan] * len(SC.HOLES))
+    tmax = tmin + np.float32(8.0)
+    assert planted.sum() == 31 + (146 - len(SC.HOLES)) + 4 * 20
+    for s in range(SC.NSTN):                                      # the restatement against the plan, on the CPU
+        assert np.array_equal(RN.streaks(tmin[:, s]), planted[:, s]), s
+    want = RN.run(tmin, tmax, days[YMD])
+    assert np.array_equal(want["flags_tmin"] == 9, planted) and np.array_equal(want["flags_tmax"] == 9, planted)
+    f0, f1 = run_qa_non_spatial(tmin, tmax, days)
+    assert np.array_equal(f0 == 9, want["flags_tmin"] == 9), np.argwhere((f0 == 9) != planted)[:10].tolist()
+    assert np.array_equal(f1 == 9, want["flags_tmax"] == 9), np.argwhere((f1 == 9) != planted)[:10].tolist()
+
+
 def test_two_calls_give_identical_bytes(case):
     tmin, tmax, days = case
     a = run_qa_non_spatial(tmin, tmax, days, details=True)

@@ -212,6 +212,24 @@ def test_record_starting_on_29_february():
                                                                              for k in range(3)]), "the table alone")
 
 
+def test_streak_walk_at_the_block_seams():
+    """Flag 9 of runs planted where the streak walk's 64-day blocks meet (tests/streak_cases.py); the long run has zeros and
+    NaN days inside it, which break no run and count for none."""
+    import streak_cases as SC
+    days = SC.days()
+    base = 1.0 + np.arange(SC.NDAYS)[:, None] * 0.01 + np.arange(SC.NSTN)[None, :] * 0.003
+    p, planted = SC.build(base, 50.5 + np.arange(len(SC.RUNS)), (0.0, np.nan, 0.0, np.nan, 0.0))
+    tv = np.full(p.shape, 5.0, np.float32)
+    assert planted.sum() == 31 + (146 - len(SC.HOLES)) + 4 * 20
+    for s in range(SC.NSTN):                                        # the restatement against the plan, on the CPU
+        assert np.array_equal(RP.streak_mask(p[:, s]), planted[:, s]), s
+    want = RP.run(p, tv, days[YMD], streak=True)["flags"]
+    assert np.array_equal(want == 9, planted)
+    got = qa_prcp.run_qa_non_spatial(p, tv, days, streak=True)
+    assert np.array_equal(got == 9, want == 9), np.argwhere((got == 9) != planted)[:10].tolist()
+    assert not (qa_prcp.run_qa_non_spatial(p, tv, days) == 9).any()     # the default chain leaves the check out
+
+
 def test_record_over_the_window_cap_fails_the_call():
     years = _qalib.PQ_MAX_WINDOW_VALUES // 29 + 1
     days = get_days_metadata(dt.date(1800, 1, 1), dt.date(1800 + years - 1, 12, 31))

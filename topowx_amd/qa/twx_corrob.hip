@@ -39,11 +39,10 @@
 #include <vector>
 
 #include "twx_qa.h"
-#include "twx_qa_common.h"
+#include "twx_qa_series.h"
 
 #define CB_NJOBS 380                         // 365 rows + the 15 leap rows whose window holds Feb 29
 #define CB_LEAP_FIRST 52                     // Feb 22 of the 366-row table
-#define CB_BIWEIGHT_C 7.5                    // qa_temp.py:1173
 #define CB_QA_OK 1                           // qa_temp.py:41-59
 #define CB_QA_MISSING 2
 #define CB_QA_SPATIAL_REGRESS 16
@@ -53,20 +52,6 @@
 namespace {
 
 __device__ __forceinline__ bool cb_finite(double v) { return fabs(v) <= 1.79769313486231570e308; }
-__device__ __forceinline__ bool cb_finitef(float v) { return fabsf(v) <= 3.40282346638528859812e38f; }
-
-// sum over the 256 threads of a workgroup, in a fixed tree order; every thread returns the same value
-__device__ __forceinline__ double block_sum(double v, double *red, int tid)
-{
-    __syncthreads();
-    red[tid] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = red[tid] + red[tid + s];
-        __syncthreads();
-    }
-    return red[0];
-}
 
 }  // namespace
 
@@ -97,13 +82,11 @@ __global__ __launch_bounds__(256) void k_doy_norms(int64_t ndays, int nyears, co
         int t = centre - 7 + j;
         t = t < 0 ? t + period : (t >= period ? t - period : t);
         const int q = (leap_job || t < 59) ? t : t + 1;
-        const int2 y = yr[k];                                    // x: series index of Jan 1, y: leap year
-        if (q == 59 && !y.y) continue;                           // (a 365-row window never holds Feb 29: q != 59 there)
-        const int64_t d = (int64_t)y.x + ((q < 59 || y.y) ? q : q - 1);
-        if (d < 0 || d >= ndays) continue;
+        const int64_t d = qa_date_day(q, yr[k], ndays);          // (a 365-row window never holds Feb 29: q != 59 there)
+        if (d < 0) continue;
         if (msk && msk[d]) continue;
         const float v = src[d];
-        if (!cb_finitef(v)) continue;
+        if (!qa_finitef(v)) continue;
         xs[atomicAdd(&cnt, 1)] = v;                              // <= 15 * nyears <= TWXQA_MAX_NORM_VALUES (host check)
     }
     __syncthreads();
@@ -115,61 +98,8 @@ __global__ __launch_bounds__(256) void k_doy_norms(int64_t ndays, int nyears, co
         while (np2 < n) np2 <<= 1;
         for (int i = n + tid; i < np2; i += 256) xs[i] = __builtin_inff();
         __syncthreads();
-        for (int k = 2; k <= np2; k <<= 1) {
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int i = tid; i < np2; i += 256) {
-                    const int ixj = i ^ j;
-                    if (ixj > i) {
-                        const float a = xs[i], b = xs[ixj];
-                        if ((a > b) == ((i & k) == 0)) { xs[i] = b; xs[ixj] = a; }
-                    }
-                }
-                __syncthreads();
-            }
-        }
-        // ---- M, then the two middle order statistics of |X - M| by counting -------------------------------------
-        const int p = n >> 1;
-        const double M = (n & 1) ? (double)xs[p] : ((double)xs[p - 1] + (double)xs[p]) / 2.0;
-        const int k1 = (n - 1) >> 1, k2 = n >> 1;
-        for (int i = tid; i < n; i += 256) {
-            const double v = i < p ? M - (double)xs[i] : (double)xs[i] - M;
-            // left part [0, p): deviations do not rise; right part [p, n): they do not fall
-            int lo = 0, hi = p;                                  // first a with M - xs[a] <= v
-            while (lo < hi) { const int m = (lo + hi) >> 1; if (M - (double)xs[m] <= v) hi = m; else lo = m + 1; }
-            int c_le = p - lo;
-            lo = 0; hi = p;                                      // first a with M - xs[a] < v
-            while (lo < hi) { const int m = (lo + hi) >> 1; if (M - (double)xs[m] < v) hi = m; else lo = m + 1; }
-            int c_lt = p - lo;
-            lo = p; hi = n;                                      // first b with xs[b] - M > v
-            while (lo < hi) { const int m = (lo + hi) >> 1; if ((double)xs[m] - M > v) hi = m; else lo = m + 1; }
-            c_le += lo - p;
-            lo = p; hi = n;                                      // first b with xs[b] - M >= v
-            while (lo < hi) { const int m = (lo + hi) >> 1; if ((double)xs[m] - M >= v) hi = m; else lo = m + 1; }
-            c_lt += lo - p;
-            if (c_lt <= k1 && k1 < c_le) mad_k[0] = v;           // (equal values may all write: the same bits)
-            if (c_lt <= k2 && k2 < c_le) mad_k[1] = v;
-        }
-        __syncthreads();
-        const double MAD = (n & 1) ? mad_k[0] : (mad_k[0] + mad_k[1]) / 2.0;
-        if (MAD == 0.0) {
-            double sum = 0.0;
-            for (int i = tid; i < n; i += 256) sum = sum + (double)xs[i];
-            result = block_sum(sum, red, tid) / (double)n;
-        } else {
-            const double scale = CB_BIWEIGHT_C * MAD;
-            double num = 0.0, den = 0.0;
-            for (int i = tid; i < n; i += 256) {
-                const double dx = (double)xs[i] - M;
-                double u = dx / scale;
-                if (fabs(u) >= 1.0) u = 1.0;
-                const double h = 1.0 - u * u, w = h * h;
-                num = num + dx * w;
-                den = den + w;
-            }
-            num = block_sum(num, red, tid);
-            den = block_sum(den, red, tid);
-            result = M + num / den;
-        }
+        qa_lds_sort(xs, np2, tid);
+        result = qa_biweight<false>(xs, n, red, mad_k, tid, nullptr);
     }
     if (tid == 0) {
         double *o = out + ((size_t)s * ostride + ooff) * TWXQA_NORM_ROWS;   // table (s, ooff) of [nseries][ostride][731]
@@ -317,8 +247,8 @@ __global__ __launch_bounds__(256) void k_mega_final(int64_t ndays, const float *
     for (int64_t d = tid; d < ndays; d += 256) {                 // (a thread touches its own column of red only)
         const int m = month[d] - 1;
         const float a = tmin[o0 + d], b = tmax[o0 + d];
-        if (cb_finitef(a) && !r_tmin[f0 + d] && !c_tmin[f0 + d]) red[0][m][tid] = fminf(red[0][m][tid], a);
-        if (cb_finitef(b) && !r_tmax[f0 + d] && !c_tmax[f0 + d]) red[1][m][tid] = fmaxf(red[1][m][tid], b);
+        if (qa_finitef(a) && !r_tmin[f0 + d] && !c_tmin[f0 + d]) red[0][m][tid] = fminf(red[0][m][tid], a);
+        if (qa_finitef(b) && !r_tmax[f0 + d] && !c_tmax[f0 + d]) red[1][m][tid] = fmaxf(red[1][m][tid], b);
     }
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
@@ -339,11 +269,11 @@ __global__ __launch_bounds__(256) void k_mega_final(int64_t ndays, const float *
         if (a != a) fa = CB_QA_MISSING;
         else if (r_tmin[f0 + d]) fa = CB_QA_SPATIAL_REGRESS;
         else if (c_tmin[f0 + d]) fa = CB_QA_SPATIAL_CORROB;
-        else if (both && cb_finitef(a) && a > hi) fa = CB_QA_MEGA_INCONSIST;
+        else if (both && qa_finitef(a) && a > hi) fa = CB_QA_MEGA_INCONSIST;
         if (b != b) fb = CB_QA_MISSING;
         else if (r_tmax[f0 + d]) fb = CB_QA_SPATIAL_REGRESS;
         else if (c_tmax[f0 + d]) fb = CB_QA_SPATIAL_CORROB;
-        else if (both && cb_finitef(b) && b < lo) fb = CB_QA_MEGA_INCONSIST;
+        else if (both && qa_finitef(b) && b < lo) fb = CB_QA_MEGA_INCONSIST;
         f_tmin[f0 + d] = fa;
         f_tmax[f0 + d] = fb;
     }
@@ -354,57 +284,12 @@ __global__ __launch_bounds__(256) void k_mega_final(int64_t ndays, const float *
 // ---------------------------------------------------------------------------------
 namespace {
 
-// The calendar tables of a day axis of consecutive days (checked): per year of the series (Jan 1's series index,
-// leap), per day the row of the 731-row normals (365-row table first) and the month.  -1 and a message on failure.
-struct CbCalendar {
-    int nyears = 0;
-    std::vector<int32_t> yr;        // [nyears][2]
-    std::vector<int32_t> normrow;   // [ndays]
-    std::vector<uint8_t> month;     // [ndays]
-};
-
-int cb_calendar(const char *fn, int64_t ndays, const int32_t *ymd, CbCalendar &c, char *errbuf, int errlen)
+// The calendar of a day axis; these entries report a day out of sequence before the cap on the years.
+int cb_cal(const char *who, int64_t ndays, const int32_t *ymd, QaCalendar &c, char *errbuf, int errlen)
 {
-    char msg[224];
-    const int32_t a = ymd[0];
-    const int y0 = a / 10000, m0 = (a / 100) % 100, d0 = a % 100;
-    if (a < 10101 || m0 < 1 || m0 > 12 || d0 < 1 || d0 > 31) {
-        snprintf(msg, sizeof msg, "%s: ymd[0] is not a date", fn);
-        return qa_fail(errbuf, errlen, msg);
-    }
-    const int64_t z0 = qa_days_from_civil(y0, m0, d0);
-    c.normrow.resize((size_t)ndays);
-    c.month.resize((size_t)ndays);
-    int y = y0, mth = m0, day = d0;
-    static const int mlen[12] = {31, 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31};
-    int64_t jan1 = qa_days_from_civil(y0, 1, 1) - z0;
-    c.yr.assign({(int32_t)jan1, qa_leap(y0) ? 1 : 0});
-    for (int64_t i = 0; i < ndays; ++i) {
-        if (ymd[i] != y * 10000 + mth * 100 + day) {
-            snprintf(msg, sizeof msg, "%s: ymd[%lld] = %d: the days are not consecutive calendar days", fn, (long long)i,
-                     (int)ymd[i]);
-            return qa_fail(errbuf, errlen, msg);
-        }
-        c.normrow[(size_t)i] = (int32_t)(i - jan1) + (qa_leap(y) ? 365 : 0);
-        c.month[(size_t)i] = (uint8_t)mth;
-        if (++day > mlen[mth - 1] + ((mth == 2 && qa_leap(y)) ? 1 : 0)) {
-            day = 1;
-            if (++mth > 12) {
-                mth = 1;
-                ++y;
-                jan1 = i + 1;
-                if (i + 1 < ndays) { c.yr.push_back((int32_t)jan1); c.yr.push_back(qa_leap(y) ? 1 : 0); }
-            }
-        }
-    }
-    c.nyears = (int)(c.yr.size() / 2);
-    if ((int64_t)c.nyears * 15 > TWXQA_MAX_NORM_VALUES) {
-        snprintf(msg, sizeof msg, "%s: the series touches %d years; a row of the day-of-year normals holds at most "
-                 "TWXQA_MAX_NORM_VALUES = %d values (15 per year, %d years)", fn, c.nyears, TWXQA_MAX_NORM_VALUES,
-                 TWXQA_MAX_NORM_VALUES / 15);
-        return qa_fail(errbuf, errlen, msg);
-    }
-    return 0;
+    if (qa_cal_years(who, ndays, ymd, c, errbuf, errlen) != 0 || qa_cal_walk(who, ndays, ymd, c, errbuf, errlen) != 0) return -1;
+    return qa_year_cap(who, c, 15, TWXQA_MAX_NORM_VALUES, "a row of the day-of-year normals holds at most TWXQA_MAX_NORM_VALUES",
+                       "", errbuf, errlen);
 }
 
 }  // namespace
@@ -416,8 +301,8 @@ extern "C" int twxqa_doy_norms(int device, int64_t nseries, int64_t ndays, const
     if (nseries < 1 || ndays < 1 || ndays > INT32_MAX - 64 || nseries * CB_NJOBS > INT32_MAX)
         return qa_fail(errbuf, errlen, "twxqa_doy_norms: need nseries >= 1, ndays >= 1 and nseries * 380 < 2^31");
     if (!series || !ymd || !norms) return qa_fail(errbuf, errlen, "twxqa_doy_norms: null buffer");
-    CbCalendar cal;
-    if (cb_calendar("twxqa_doy_norms", ndays, ymd, cal, errbuf, errlen) != 0) return -1;
+    QaCalendar cal;
+    if (cb_cal("twxqa_doy_norms", ndays, ymd, cal, errbuf, errlen) != 0) return -1;
     const size_t ns = (size_t)nseries, nd = (size_t)ndays;
     QACHK(hipSetDevice(device));
     QaBuf b_obs, b_yr, b_rows, b_out;
@@ -454,8 +339,8 @@ extern "C" int twxqa_spatial_only(int device, int64_t nstn, int64_t ndays, const
         return qa_fail(errbuf, errlen, "twxqa_spatial_only: need nstn >= 1, ndays >= 1 and ntarget >= 1");
     if (!lon || !lat || !tmin || !tmax || !ymd || !target_idx || !flag_tmin || !flag_tmax)
         return qa_fail(errbuf, errlen, "twxqa_spatial_only: null buffer");
-    CbCalendar cal;
-    if (cb_calendar("twxqa_spatial_only", ndays, ymd, cal, errbuf, errlen) != 0) return -1;
+    QaCalendar cal;
+    if (cb_cal("twxqa_spatial_only", ndays, ymd, cal, errbuf, errlen) != 0) return -1;
     const size_t nt = (size_t)ntarget, ns = (size_t)nstn, nd = (size_t)ndays;
     const int nblk = (int)((ndays + 63) / 64);
     if ((int64_t)nblk * 2 * ntarget > INT32_MAX || (2 * nstn + 2 * ntarget) * CB_NJOBS > INT32_MAX)

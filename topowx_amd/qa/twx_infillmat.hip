@@ -48,19 +48,13 @@
 #include <vector>
 
 #include "twx_qa.h"
-#include "twx_qa_common.h"
+#include "twx_qa_series.h"
 
 #define IF_CAP TWXQA_MAX_RADIUS_NGH
 #define IF_IOA_DENOM0 (-2.0)                 // pair marker: the d1 denominator is 0 (d1 itself lies in [0, 1])
 #define IF_RING_EXHAUSTED (-1)
 #define IF_RING_OVERFLOW (-2)
 #define IF_NOT_REACHED 0x7fffffff
-
-namespace {
-
-__device__ __forceinline__ bool if_finitef(float v) { return fabsf(v) <= 3.40282346638528859812e38f; }
-
-}  // namespace
 
 __global__ __launch_bounds__(64) void k_if_ring(int64_t nstn, const double *__restrict__ lon,
                                                 const double *__restrict__ lat, const uint8_t *__restrict__ elig,
@@ -154,7 +148,7 @@ __global__ __launch_bounds__(256) void k_if_pair(int64_t ndays, const float *__r
         for (int i = a + lane; i < b; i += 64) {
             const int d = perm[i];
             const float o = o_row[d], p = p_row[d];
-            const bool fp = if_finitef(p), fb = fp && if_finitef(o);
+            const bool fp = qa_finitef(p), fb = fp && qa_finitef(o);
             nlap += fp ? 1 : 0;
             nst += fb ? 1 : 0;
             if (fb) so = so + (double)o;
@@ -168,7 +162,7 @@ __global__ __launch_bounds__(256) void k_if_pair(int64_t ndays, const float *__r
             for (int i = a + lane; i < b; i += 64) {
                 const int d = perm[i];
                 const float of = o_row[d], pf = p_row[d];
-                if (if_finitef(pf) && if_finitef(of)) {
+                if (qa_finitef(pf) && qa_finitef(of)) {
                     const double o = (double)of, p = (double)pf;
                     num = num + fabs(p - o);
                     den = den + (fabs(p - mean) + fabs(o - mean));
@@ -289,7 +283,7 @@ __global__ __launch_bounds__(256) void k_if_item(int64_t ndays, const float *__r
     for (int i = a + tid; i < b; i += 256) {
         const int64_t d = perm[i];
         int cnt = 0, c = 0;
-        for (; c < n && cnt < min_nnghs; ++c) cnt += if_finitef(obs[(int64_t)s_sorted[c] * ndays + d]) ? 1 : 0;
+        for (; c < n && cnt < min_nnghs; ++c) cnt += qa_finitef(obs[(int64_t)s_sorted[c] * ndays + d]) ? 1 : 0;
         const int pos = cnt >= min_nnghs ? c : IF_NOT_REACHED;
         m = pos > m ? pos : m;
     }
@@ -314,7 +308,7 @@ __global__ __launch_bounds__(256) void k_if_item(int64_t ndays, const float *__r
             int adds = 0;
             for (int i = a + tid; i < b; i += 256) {
                 const int d = perm[i];
-                adds |= (if_finitef(col[d]) && cnt_row[d] < min_nnghs) ? 1 : 0;
+                adds |= (qa_finitef(col[d]) && cnt_row[d] < min_nnghs) ? 1 : 0;
             }
             keep = __syncthreads_or(adds);
         }
@@ -322,7 +316,7 @@ __global__ __launch_bounds__(256) void k_if_item(int64_t ndays, const float *__r
             for (int i = a + tid; i < b; i += 256) {
                 const int d = perm[i];
                 const int prev = c == 0 ? 0 : cnt_row[d];
-                cnt_row[d] = (uint8_t)(prev + ((if_finitef(col[d]) && prev < min_nnghs) ? 1 : 0));
+                cnt_row[d] = (uint8_t)(prev + ((qa_finitef(col[d]) && prev < min_nnghs) ? 1 : 0));
             }
         }
         if (tid == 0) l_keep[base + c] = (uint8_t)keep;

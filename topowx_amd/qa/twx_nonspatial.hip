@@ -42,11 +42,10 @@
 #include <vector>
 
 #include "twx_qa.h"
-#include "twx_qa_common.h"
+#include "twx_qa_series.h"
 
 #define NS_NJOBS 380                         // 365 rows + the 15 leap rows whose window holds Feb 29
 #define NS_LEAP_FIRST 52                     // Feb 22 of the 366-row table
-#define NS_BIWEIGHT_C 7.5                    // qa_temp.py:1194
 #define NS_MAX_YEARS (TWXQA_MAX_GAP_VALUES / 31)
 #define NS_OK 1                              // qa_temp.py:41-59
 #define NS_MISSING 2
@@ -72,50 +71,6 @@
 #define NS_CLIM_Z 6.0                        // qa_temp.py:1160
 #define NS_DUP_DAYS 10                       // qa_temp.py:323
 
-namespace {
-
-__device__ __forceinline__ bool ns_finitef(float v) { return fabsf(v) <= 3.40282346638528859812e38f; }
-
-// sum over the 256 threads of a workgroup, in a fixed tree order; every thread returns the same value
-__device__ __forceinline__ double ns_block_sum(double v, double *red, int tid)
-{
-    __syncthreads();
-    red[tid] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = red[tid] + red[tid + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
-// the calendar of a day axis on the device
-struct NsCal {
-    const uint8_t *month;      // [ndays] 1..12
-    const uint8_t *yidx;       // [ndays] index of the day's year among the years the axis touches
-    const int32_t *normrow;    // [ndays] row of the 731
-    const int32_t *ystart;     // [nyears] first day of the year that is on the axis
-    const int32_t *ylen;       // [nyears] days of the year on the axis
-    const int32_t *mstart;     // [nyears][12] first day of the month on the axis
-    const int32_t *mlen;       // [nyears][12] days of the month on the axis (0: none)
-    const int2 *yr;            // [nyears] (series index of Jan 1 -- may lie before the axis --, leap)
-    int nyears;
-    int skip_month;            // the month NUMBER never taken as the first of a pair by check 6 (:360)
-};
-
-// two stretches of one series compared by position over the shorter one: all == (a NaN or a removed value: no)
-__device__ __forceinline__ bool ns_same(const float *__restrict__ x, const uint8_t *f, int a, int la, int b, int lb)
-{
-    const int n = la < lb ? la : lb;
-    for (int j = 0; j < n; ++j) {
-        if (f[a + j] != NS_OK || f[b + j] != NS_OK) return false;
-        if (!(x[a + j] == x[b + j])) return false;
-    }
-    return true;
-}
-
-}  // namespace
-
 __global__ __launch_bounds__(256) void k_ns_init(int64_t total, const float *__restrict__ tmin,
                                                  const float *__restrict__ tmax, uint8_t *__restrict__ f_tmin,
                                                  uint8_t *__restrict__ f_tmax)
@@ -132,7 +87,7 @@ __global__ __launch_bounds__(256) void k_ns_init(int64_t total, const float *__r
     f_tmax[i] = fb;
 }
 
-__global__ __launch_bounds__(256) void k_ns_dups(int64_t ndays, NsCal cal, const float *__restrict__ tmin,
+__global__ __launch_bounds__(256) void k_ns_dups(int64_t ndays, QaCal cal, const float *__restrict__ tmin,
                                                  const float *__restrict__ tmax, uint8_t *f_tmin, uint8_t *f_tmax)
 {
     __shared__ uint8_t has_y[NS_MAX_YEARS], dup_y[NS_MAX_YEARS];
@@ -153,7 +108,7 @@ __global__ __launch_bounds__(256) void k_ns_dups(int64_t ndays, NsCal cal, const
         for (int p = tid; p < ny * ny; p += 256) {
             const int a = p / ny, b = p % ny;
             if (b <= a || !has_y[a] || !has_y[b]) continue;
-            if (ns_same(x, f, cal.ystart[a], cal.ylen[a], cal.ystart[b], cal.ylen[b])) { dup_y[a] = 1; dup_y[b] = 1; }
+            if (qa_same(x, f, cal.ystart[a], cal.ylen[a], cal.ystart[b], cal.ylen[b])) { dup_y[a] = 1; dup_y[b] = 1; }
         }
         __syncthreads();
         for (int d = tid; d < nd; d += 256)
@@ -171,7 +126,7 @@ __global__ __launch_bounds__(256) void k_ns_dups(int64_t ndays, NsCal cal, const
                     const int k = p / 144, m1 = (p % 144) / 12, m2 = p % 12;
                     const int a = k * 12 + m1, b = k * 12 + m2;
                     if (m2 <= m1 || m1 + 1 == cal.skip_month || !has_m[a] || !has_m[b]) continue;
-                    if (ns_same(x, f, cal.mstart[a], cal.mlen[a], cal.mstart[b], cal.mlen[b])) { dup_m[a] = 1; dup_m[b] = 1; }
+                    if (qa_same(x, f, cal.mstart[a], cal.mlen[a], cal.mstart[b], cal.mlen[b])) { dup_m[a] = 1; dup_m[b] = 1; }
                 }
             } else {
                 for (int p = tid; p < ny * ny * 12; p += 256) {
@@ -179,7 +134,7 @@ __global__ __launch_bounds__(256) void k_ns_dups(int64_t ndays, NsCal cal, const
                     const int ka = q / ny, kb = q % ny;
                     const int a = ka * 12 + m, b = kb * 12 + m;
                     if (kb <= ka || !has_m[a] || !has_m[b]) continue;
-                    if (ns_same(x, f, cal.mstart[a], cal.mlen[a], cal.mstart[b], cal.mlen[b])) { dup_m[a] = 1; dup_m[b] = 1; }
+                    if (qa_same(x, f, cal.mstart[a], cal.mlen[a], cal.mstart[b], cal.mlen[b])) { dup_m[a] = 1; dup_m[b] = 1; }
                 }
             }
             __syncthreads();
@@ -210,48 +165,11 @@ __global__ __launch_bounds__(256) void k_ns_dups(int64_t ndays, NsCal cal, const
 
 __global__ __launch_bounds__(64) void k_ns_streak(int64_t ndays, const float *__restrict__ obs, uint8_t *flag)
 {
-    const int lane = threadIdx.x;
     const size_t o = (size_t)blockIdx.x * (size_t)ndays;                 // series (variable, station) of [2][nstn][ndays]
-    const float *x = obs + o;
-    uint8_t *f = flag + o;
-    const uint64_t lt = ((uint64_t)1 << lane) - 1;                       // lanes below
-    const uint64_t le = ((uint64_t)2 << lane) - 1;                       // lanes below and this one (lane 63: all)
-    bool carry_has = false;                                              // a run is open from the blocks before
-    float carry_val = 0.0f;
-    int carry_rank = 0, rank_base = 0;                                   // rank (among the live values) and day of the
-    int64_t carry_day = 0;                                               // open run's first value; ndays < 2^31
-    for (int64_t b0 = 0; b0 < ndays; b0 += 64) {                         // uniform
-        const int64_t d = b0 + lane;
-        const bool live = d < ndays && f[d] == NS_OK;
-        const float v = live ? x[d] : 0.0f;
-        const uint64_t lm = __ballot(live);
-        if (lm == 0) continue;
-        const uint64_t below = lm & lt;
-        const float pv = __shfl(v, below ? 63 - __clzll(below) : lane);
-        const bool start = live && (below ? !(v == pv) : (!carry_has || !(v == carry_val)));
-        const uint64_t sm = __ballot(start);
-        const int rank = rank_base + __popcll(below);
-        const uint64_t s_le = sm & le, s_gt = sm & ~le;
-        const int g = s_le ? 63 - __clzll(s_le) : -1;                    // the start of this lane's run, -1: the open run
-        const int nx = s_gt ? __ffsll((unsigned long long)s_gt) - 1 : -1;  // the next start, -1: none in this block
-        const int rank_g = __shfl(rank, g >= 0 ? g : lane), rank_nx = __shfl(rank, nx >= 0 ? nx : lane);
-        if (live && nx >= 0 && rank_nx - (g >= 0 ? rank_g : carry_rank) >= NS_STREAK_LEN) f[d] = NS_STREAK;
-        if (sm != 0) {
-            const int first = __ffsll((unsigned long long)sm) - 1, last = 63 - __clzll(sm);
-            const int rank_first = rank_base + __popcll(lm & (((uint64_t)1 << first) - 1));
-            if (carry_has && rank_first - carry_rank >= NS_STREAK_LEN)   // the open run ended here: its earlier blocks
-                for (int64_t e = carry_day + lane; e < b0; e += 64)
-                    if (f[e] == NS_OK) f[e] = NS_STREAK;
-            carry_rank = rank_base + __popcll(lm & (((uint64_t)1 << last) - 1));
-            carry_day = b0 + last;
-        }
-        carry_has = true;
-        carry_val = __shfl(v, 63 - __clzll(lm));
-        rank_base += __popcll(lm);
-    }
+    qa_streak_walk<NS_OK, NS_STREAK, NS_STREAK_LEN>(ndays, obs + o, flag + o, [](float) { return true; });
 }
 
-__global__ __launch_bounds__(256) void k_ns_gap(int64_t ndays, NsCal cal, const float *__restrict__ obs, uint8_t *flag)
+__global__ __launch_bounds__(256) void k_ns_gap(int64_t ndays, QaCal cal, const float *__restrict__ obs, uint8_t *flag)
 {
     __shared__ float xs[TWXQA_MAX_GAP_VALUES];
     __shared__ int cnt, itop, ibot;
@@ -281,18 +199,7 @@ __global__ __launch_bounds__(256) void k_ns_gap(int64_t ndays, NsCal cal, const 
     __syncthreads();
     const int n = cnt;
     if (n == 0) return;                                                  // uniform
-    for (int k = 2; k <= np2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < np2; i += 256) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const float a = xs[i], b = xs[ixj];
-                    if ((a > b) == ((i & k) == 0)) { xs[i] = b; xs[ixj] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    qa_lds_sort(xs, np2, tid);
     const int p = n >> 1;
     const float med = (n & 1) ? xs[p] : (xs[p - 1] + xs[p]) / 2.0f;      // numpy's float32 mean of the two
     for (int i = 1 + tid; i < n; i += 256) {
@@ -340,13 +247,11 @@ __global__ __launch_bounds__(256) void k_ns_norms(int64_t ndays, int64_t nstn, i
         int t = centre - 7 + j;
         t = t < 0 ? t + period : (t >= period ? t - period : t);
         const int q = (leap_job || t < 59) ? t : t + 1;
-        const int2 y = yr[k];                                    // x: series index of Jan 1, y: leap year
-        if (q == 59 && !y.y) continue;                           // (a 365-row window never holds Feb 29: q != 59 there)
-        const int64_t d = (int64_t)y.x + ((q < 59 || y.y) ? q : q - 1);
-        if (d < 0 || d >= ndays) continue;
+        const int64_t d = qa_date_day(q, yr[k], ndays);          // (a 365-row window never holds Feb 29: q != 59 there)
+        if (d < 0) continue;
         if (flag[so + d] != NS_OK) continue;
         const float v = obs[so + d];
-        if (!ns_finitef(v)) continue;
+        if (!qa_finitef(v)) continue;
         xs[atomicAdd(&cnt, 1)] = v;                              // <= 15 * nyears <= TWXQA_MAX_NORM_VALUES (host check)
     }
     __syncthreads();
@@ -357,69 +262,8 @@ __global__ __launch_bounds__(256) void k_ns_norms(int64_t ndays, int64_t nstn, i
         while (np2 < n) np2 <<= 1;
         for (int i = n + tid; i < np2; i += 256) xs[i] = __builtin_inff();
         __syncthreads();
-        for (int k = 2; k <= np2; k <<= 1) {
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int i = tid; i < np2; i += 256) {
-                    const int ixj = i ^ j;
-                    if (ixj > i) {
-                        const float a = xs[i], b = xs[ixj];
-                        if ((a > b) == ((i & k) == 0)) { xs[i] = b; xs[ixj] = a; }
-                    }
-                }
-                __syncthreads();
-            }
-        }
-        // ---- M, then the two middle order statistics of |X - M| by counting -------------------------------------
-        const int p = n >> 1;
-        const double M = (n & 1) ? (double)xs[p] : ((double)xs[p - 1] + (double)xs[p]) / 2.0;
-        const int k1 = (n - 1) >> 1, k2 = n >> 1;
-        for (int i = tid; i < n; i += 256) {
-            const double v = i < p ? M - (double)xs[i] : (double)xs[i] - M;
-            // left part [0, p): deviations do not rise; right part [p, n): they do not fall
-            int lo = 0, hi = p;                                  // first a with M - xs[a] <= v
-            while (lo < hi) { const int mm = (lo + hi) >> 1; if (M - (double)xs[mm] <= v) hi = mm; else lo = mm + 1; }
-            int c_le = p - lo;
-            lo = 0; hi = p;                                      // first a with M - xs[a] < v
-            while (lo < hi) { const int mm = (lo + hi) >> 1; if (M - (double)xs[mm] < v) hi = mm; else lo = mm + 1; }
-            int c_lt = p - lo;
-            lo = p; hi = n;                                      // first b with xs[b] - M > v
-            while (lo < hi) { const int mm = (lo + hi) >> 1; if ((double)xs[mm] - M > v) hi = mm; else lo = mm + 1; }
-            c_le += lo - p;
-            lo = p; hi = n;                                      // first b with xs[b] - M >= v
-            while (lo < hi) { const int mm = (lo + hi) >> 1; if ((double)xs[mm] - M >= v) hi = mm; else lo = mm + 1; }
-            c_lt += lo - p;
-            if (c_lt <= k1 && k1 < c_le) mad_k[0] = v;           // (equal values may all write: the same bits)
-            if (c_lt <= k2 && k2 < c_le) mad_k[1] = v;
-        }
-        __syncthreads();
-        const double MAD = (n & 1) ? mad_k[0] : (mad_k[0] + mad_k[1]) / 2.0;
-        if (MAD == 0.0) {                                        // the plain mean and std(ddof = 1)
-            double sum = 0.0;
-            for (int i = tid; i < n; i += 256) sum = sum + (double)xs[i];
-            mean = ns_block_sum(sum, red, tid) / (double)n;
-            double ss = 0.0;
-            for (int i = tid; i < n; i += 256) { const double dx = (double)xs[i] - mean; ss = ss + dx * dx; }
-            sd = sqrt(ns_block_sum(ss, red, tid) / (double)(n - 1));
-        } else {
-            const double scale = NS_BIWEIGHT_C * MAD;
-            double num = 0.0, den = 0.0, s1 = 0.0, s2 = 0.0;
-            for (int i = tid; i < n; i += 256) {
-                const double dx = (double)xs[i] - M;
-                double u = dx / scale;
-                if (fabs(u) >= 1.0) u = 1.0;
-                const double u2 = u * u, h = 1.0 - u2, w = h * h;
-                num = num + dx * w;
-                den = den + w;
-                s1 = s1 + (dx * dx) * (w * w);
-                s2 = s2 + h * (1.0 - 5.0 * u2);
-            }
-            num = ns_block_sum(num, red, tid);
-            den = ns_block_sum(den, red, tid);
-            s1 = ns_block_sum(s1, red, tid);
-            s2 = ns_block_sum(s2, red, tid);
-            mean = M + num / den;
-            sd = sqrt((double)n * s1) / fabs(s2);
-        }
+        qa_lds_sort(xs, np2, tid);
+        mean = qa_biweight<true>(xs, n, red, mad_k, tid, &sd);
     }
     if (tid == 0) {
         double *o = out + (size_t)((s % nstn) * 2 + s / nstn) * TWXQA_NORM_ROWS * 2;   // [nstn][2][731][mean, std]
@@ -521,8 +365,8 @@ __global__ __launch_bounds__(256) void k_ns_mega(int64_t ndays, const uint8_t *_
     for (int64_t d = tid; d < ndays; d += 256) {                 // (a thread touches its own column of red only)
         const int m = month[d] - 1;
         const float a = tmin[o + d], b = tmax[o + d];
-        if (f_tmin[o + d] == NS_OK && ns_finitef(a)) red[0][m][tid] = fminf(red[0][m][tid], a);
-        if (f_tmax[o + d] == NS_OK && ns_finitef(b)) red[1][m][tid] = fmaxf(red[1][m][tid], b);
+        if (f_tmin[o + d] == NS_OK && qa_finitef(a)) red[0][m][tid] = fminf(red[0][m][tid], a);
+        if (f_tmax[o + d] == NS_OK && qa_finitef(b)) red[1][m][tid] = fmaxf(red[1][m][tid], b);
     }
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
@@ -539,92 +383,14 @@ __global__ __launch_bounds__(256) void k_ns_mega(int64_t ndays, const uint8_t *_
         const float lo = red[0][m][0], hi = red[1][m][0];
         if (lo == inf || hi == -inf) continue;                   // a month with no finite value on either side is skipped
         const float a = tmin[o + d], b = tmax[o + d];
-        if (f_tmin[o + d] == NS_OK && ns_finitef(a) && a > hi) f_tmin[o + d] = NS_MEGA_INCONSIST;
-        if (f_tmax[o + d] == NS_OK && ns_finitef(b) && b < lo) f_tmax[o + d] = NS_MEGA_INCONSIST;
+        if (f_tmin[o + d] == NS_OK && qa_finitef(a) && a > hi) f_tmin[o + d] = NS_MEGA_INCONSIST;
+        if (f_tmax[o + d] == NS_OK && qa_finitef(b) && b < lo) f_tmax[o + d] = NS_MEGA_INCONSIST;
     }
 }
 
 // ---------------------------------------------------------------------------------
 // host entry
 // ---------------------------------------------------------------------------------
-namespace {
-
-// The calendar tables of a day axis of consecutive days (checked).  -1 and a message on failure.
-struct NsCalendar {
-    int nyears = 0, ndistinct = 0;
-    std::vector<int32_t> yr;        // [nyears][2]: Jan 1's series index, leap
-    std::vector<int32_t> normrow;   // [ndays]
-    std::vector<uint8_t> month;     // [ndays]
-    std::vector<uint8_t> yidx;      // [ndays]
-    std::vector<int32_t> ystart, ylen, mstart, mlen;
-};
-
-int ns_calendar(int64_t ndays, const int32_t *ymd, NsCalendar &c, char *errbuf, int errlen)
-{
-    char msg[256];
-    const int32_t a = ymd[0];
-    const int y0 = a / 10000, m0 = (a / 100) % 100, d0 = a % 100;
-    if (a < 10101 || m0 < 1 || m0 > 12 || d0 < 1 || d0 > 31) return qa_fail(errbuf, errlen, "twxqa_non_spatial: ymd[0] is not a date");
-    // the years the axis touches, before anything is sized by them
-    const int64_t zlast = qa_days_from_civil(y0, m0, d0) + ndays - 1;
-    int64_t ylast = y0 + (ndays - 1) / 366;
-    while (qa_days_from_civil(ylast + 1, 1, 1) <= zlast) ++ylast;
-    const int64_t nyears = ylast - y0 + 1;
-    if (nyears * 31 > TWXQA_MAX_GAP_VALUES) {
-        snprintf(msg, sizeof msg, "twxqa_non_spatial: the series touches %lld years; the gap check sorts at most "
-                 "TWXQA_MAX_GAP_VALUES = %d values of a calendar month (31 per year, %d years)", (long long)nyears,
-                 TWXQA_MAX_GAP_VALUES, TWXQA_MAX_GAP_VALUES / 31);
-        return qa_fail(errbuf, errlen, msg);
-    }
-    if (nyears * 15 > TWXQA_MAX_NORM_VALUES) {
-        snprintf(msg, sizeof msg, "twxqa_non_spatial: the series touches %lld years; a row of the day-of-year normals "
-                 "holds at most TWXQA_MAX_NORM_VALUES = %d values (15 per year, %d years)", (long long)nyears,
-                 TWXQA_MAX_NORM_VALUES, TWXQA_MAX_NORM_VALUES / 15);
-        return qa_fail(errbuf, errlen, msg);
-    }
-    c.nyears = (int)nyears;
-    c.normrow.resize((size_t)ndays);
-    c.month.resize((size_t)ndays);
-    c.yidx.resize((size_t)ndays);
-    c.ystart.assign((size_t)nyears, 0);
-    c.ylen.assign((size_t)nyears, 0);
-    c.mstart.assign((size_t)nyears * 12, 0);
-    c.mlen.assign((size_t)nyears * 12, 0);
-    static const int mlen[12] = {31, 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31};
-    int y = y0, mth = m0, day = d0, k = 0;
-    bool seen[12] = {false, false, false, false, false, false, false, false, false, false, false, false};
-    int64_t jan1 = qa_days_from_civil(y0, 1, 1) - qa_days_from_civil(y0, m0, d0);
-    c.yr.assign({(int32_t)jan1, qa_leap(y0) ? 1 : 0});
-    for (int64_t i = 0; i < ndays; ++i) {
-        if (ymd[i] != y * 10000 + mth * 100 + day) {
-            snprintf(msg, sizeof msg, "twxqa_non_spatial: ymd[%lld] = %d: the days are not consecutive calendar days",
-                     (long long)i, (int)ymd[i]);
-            return qa_fail(errbuf, errlen, msg);
-        }
-        c.normrow[(size_t)i] = (int32_t)(i - jan1) + (qa_leap(y) ? 365 : 0);
-        c.month[(size_t)i] = (uint8_t)mth;
-        c.yidx[(size_t)i] = (uint8_t)k;
-        seen[mth - 1] = true;
-        if (c.ylen[(size_t)k]++ == 0) c.ystart[(size_t)k] = (int32_t)i;
-        const size_t seg = (size_t)k * 12 + (size_t)(mth - 1);
-        if (c.mlen[seg]++ == 0) c.mstart[seg] = (int32_t)i;
-        if (++day > mlen[mth - 1] + ((mth == 2 && qa_leap(y)) ? 1 : 0)) {
-            day = 1;
-            if (++mth > 12) {
-                mth = 1;
-                ++y;
-                jan1 = i + 1;
-                if (i + 1 < ndays) { ++k; c.yr.push_back((int32_t)jan1); c.yr.push_back(qa_leap(y) ? 1 : 0); }
-            }
-        }
-    }
-    for (int m = 0; m < 12; ++m) c.ndistinct += seen[m] ? 1 : 0;
-    if ((int)(c.yr.size() / 2) != c.nyears) return qa_fail(errbuf, errlen, "twxqa_non_spatial: calendar count mismatch");
-    return 0;
-}
-
-}  // namespace
-
 extern "C" int twxqa_non_spatial(int device, int64_t nstn, int64_t ndays, const float *tmin, const float *tmax,
                                  const int32_t *ymd, uint8_t *flag_tmin, uint8_t *flag_tmax, double *norms,
                                  float *kernel_ms, char *errbuf, int errlen)
@@ -634,9 +400,16 @@ extern "C" int twxqa_non_spatial(int device, int64_t nstn, int64_t ndays, const 
         (nstn * ndays + 255) / 256 * 2 > INT32_MAX)
         return qa_fail(errbuf, errlen, "twxqa_non_spatial: need nstn >= 1, ndays >= 1 and fewer than 2^31 work items in one call");
     if (!tmin || !tmax || !ymd || !flag_tmin || !flag_tmax) return qa_fail(errbuf, errlen, "twxqa_non_spatial: null buffer");
-    NsCalendar cal;
-    if (ns_calendar(ndays, ymd, cal, errbuf, errlen) != 0) return -1;
-    const size_t ns = (size_t)nstn, nd = (size_t)ndays, ny = (size_t)cal.nyears;
+    const char *who = "twxqa_non_spatial";
+    QaCalendar cal;
+    if (qa_cal_years(who, ndays, ymd, cal, errbuf, errlen) != 0 ||
+        qa_year_cap(who, cal, 31, TWXQA_MAX_GAP_VALUES, "the gap check sorts at most TWXQA_MAX_GAP_VALUES", " of a calendar month",
+                    errbuf, errlen) != 0 ||
+        qa_year_cap(who, cal, 15, TWXQA_MAX_NORM_VALUES, "a row of the day-of-year normals holds at most TWXQA_MAX_NORM_VALUES",
+                    "", errbuf, errlen) != 0 ||
+        qa_cal_walk(who, ndays, ymd, cal, errbuf, errlen) != 0)
+        return -1;
+    const size_t ns = (size_t)nstn, nd = (size_t)ndays;
     QACHK(hipSetDevice(device));
     QaBuf b_obs, b_flag, b_cal, b_norm;
     QaTimer tm;
@@ -647,30 +420,8 @@ extern "C" int twxqa_non_spatial(int device, int64_t nstn, int64_t ndays, const 
     QACHK(hipMemcpy(d_tmax, tmax, ns * nd * 4, hipMemcpyHostToDevice));
     QACHK(hipMalloc(&b_flag.p, 2 * ns * nd));
     uint8_t *d_f0 = static_cast<uint8_t *>(b_flag.p), *d_f1 = d_f0 + ns * nd;
-    // calendar: int32 tables first (yr, normrow, ystart, ylen, mstart, mlen), then the bytes (month, yidx)
-    const size_t o_yr = 0, o_row = o_yr + ny * 8, o_ys = o_row + nd * 4, o_yl = o_ys + ny * 4, o_ms = o_yl + ny * 4,
-                 o_ml = o_ms + ny * 48, o_mth = o_ml + ny * 48, o_yi = o_mth + nd;
-    QACHK(hipMalloc(&b_cal.p, o_yi + nd));
-    char *dc = static_cast<char *>(b_cal.p);
-    QACHK(hipMemcpy(dc + o_yr, cal.yr.data(), ny * 8, hipMemcpyHostToDevice));
-    QACHK(hipMemcpy(dc + o_row, cal.normrow.data(), nd * 4, hipMemcpyHostToDevice));
-    QACHK(hipMemcpy(dc + o_ys, cal.ystart.data(), ny * 4, hipMemcpyHostToDevice));
-    QACHK(hipMemcpy(dc + o_yl, cal.ylen.data(), ny * 4, hipMemcpyHostToDevice));
-    QACHK(hipMemcpy(dc + o_ms, cal.mstart.data(), ny * 48, hipMemcpyHostToDevice));
-    QACHK(hipMemcpy(dc + o_ml, cal.mlen.data(), ny * 48, hipMemcpyHostToDevice));
-    QACHK(hipMemcpy(dc + o_mth, cal.month.data(), nd, hipMemcpyHostToDevice));
-    QACHK(hipMemcpy(dc + o_yi, cal.yidx.data(), nd, hipMemcpyHostToDevice));
-    NsCal k;
-    k.month = (const uint8_t *)(dc + o_mth);
-    k.yidx = (const uint8_t *)(dc + o_yi);
-    k.normrow = (const int32_t *)(dc + o_row);
-    k.ystart = (const int32_t *)(dc + o_ys);
-    k.ylen = (const int32_t *)(dc + o_yl);
-    k.mstart = (const int32_t *)(dc + o_ms);
-    k.mlen = (const int32_t *)(dc + o_ml);
-    k.yr = (const int2 *)(dc + o_yr);
-    k.nyears = cal.nyears;
-    k.skip_month = cal.ndistinct - 1;
+    QaCal k;
+    if (qa_upload_calendar(cal, cal.normrow, b_cal, k, errbuf, errlen) != 0) return -1;
     QACHK(hipMalloc(&b_norm.p, ns * 2 * TWXQA_NORM_ROWS * 2 * 8)); // [nstn][2][731][2]
     double *d_norm = static_cast<double *>(b_norm.p);
 
@@ -706,7 +457,7 @@ extern "C" int twxqa_non_spatial(int device, int64_t nstn, int64_t ndays, const 
     QACHK(tm.stop_set(&ms[4]));
     if (norms) QACHK(hipMemcpy(norms, d_norm, ns * 2 * TWXQA_NORM_ROWS * 2 * 8, hipMemcpyDeviceToHost));
     QACHK(tm.start());
-    hipLaunchKernelGGL(k_ns_clim, dim3(g_day), dim3(256), 0, nullptr, ndays, nstn, k.normrow, (const float *)d_tmin,
+    hipLaunchKernelGGL(k_ns_clim, dim3(g_day), dim3(256), 0, nullptr, ndays, nstn, k.row, (const float *)d_tmin,
                        (const float *)d_tmax, (const double *)d_norm, d_f0, d_f1);
     QACHK(hipGetLastError());
     QACHK(tm.stop_set(&ms[5]));

@@ -47,7 +47,7 @@
 #include <vector>
 
 #include "twx_qa.h"
-#include "twx_qa_common.h"
+#include "twx_qa_series.h"
 
 #define PC_OK 1                              // qa_prcp.py:37-57
 #define PC_SPATIAL_CORROB 17
@@ -62,8 +62,7 @@
 
 namespace {
 
-__device__ __forceinline__ bool pc_finitef(float v) { return fabsf(v) <= 3.40282346638528859812e38f; }
-__device__ __forceinline__ bool pc_wet(float v) { return v > 0.0f && pc_finitef(v); }
+__device__ __forceinline__ bool pc_wet(float v) { return v > 0.0f && qa_finitef(v); }
 
 }  // namespace
 
@@ -182,7 +181,7 @@ __global__ __launch_bounds__(64) void k_pc_walk(int64_t ndays, int nblk, const f
         const uint16_t *c = cnt_pool + (size_t)slot[j] * PC_ROWS;
         const float a0 = o[-1], a1 = o[0], a2 = o[1];
 #define PC_DAY(a, nf, nb, r)                                                                   \
-        if (pc_finitef(a)) {                                                                   \
+        if (qa_finitef(a)) {                                                                   \
             if (nf < PC_MAX_NGHS) { mn7 = fminf(mn7, a); mx7 = fmaxf(mx7, a); ++nf; }          \
             mnA = fminf(mnA, a); mxA = fmaxf(mxA, a);                                          \
             if (nb < PC_MIN_NGHS && c[r] > TWXPQ_MIN_PERCENTILE_VALUES) ++nb;                  \
@@ -240,10 +239,8 @@ __global__ __launch_bounds__(256) void k_pc_rank(int64_t ndays, int nyears, cons
         if (j >= 29) continue;
         int q = row - 14 + j;
         q = q < 0 ? q + PC_ROWS : (q >= PC_ROWS ? q - PC_ROWS : q);
-        const int2 y = yr[k];                                    // x: series index of Jan 1, y: leap year
-        if (q == 59 && !y.y) continue;
-        const int64_t d = (int64_t)y.x + ((q < 59 || y.y) ? q : q - 1);
-        if (d < 0 || d >= ndays) continue;
+        const int64_t d = qa_date_day(q, yr[k], ndays);
+        if (d < 0) continue;
         if (flag[to + d] != PC_OK) continue;
         const float v = x[d];
         if (!pc_wet(v)) continue;
@@ -287,64 +284,14 @@ __global__ __launch_bounds__(256) void k_pc_apply(int64_t total, const uint8_t *
 // ---------------------------------------------------------------------------------
 namespace {
 
-struct PcCalendar {
-    int nyears = 0;
-    std::vector<int32_t> yr;        // [nyears][2]: Jan 1's series index (may lie before the axis), leap
-    std::vector<uint16_t> row;      // [ndays] yday - 1 of the day's own year: the row of the 366-row table (the quirk)
-    std::vector<uint16_t> mday;     // [ndays] the month-day's index in a leap year's calendar: the date of 2004
-};
-
-// The calendar tables of a day axis of consecutive days (checked).  -1 and a message on failure.
-int pc_calendar(const char *who, int64_t ndays, const int32_t *ymd, PcCalendar &c, char *errbuf, int errlen)
+// The calendar of a day axis, the years capped for the rows of the percentile basis.
+int pc_cal(const char *who, int64_t ndays, const int32_t *ymd, QaCalendar &c, char *errbuf, int errlen)
 {
-    char msg[320];
-    const int32_t a = ymd[0];
-    const int y0 = a / 10000, m0 = (a / 100) % 100, d0 = a % 100;
-    if (a < 10101 || m0 < 1 || m0 > 12 || d0 < 1 || d0 > 31) {
-        snprintf(msg, sizeof msg, "%s: ymd[0] is not a date", who);
-        return qa_fail(errbuf, errlen, msg);
-    }
-    const int64_t zlast = qa_days_from_civil(y0, m0, d0) + ndays - 1;
-    int64_t ylast = y0 + (ndays - 1) / 366;
-    while (qa_days_from_civil(ylast + 1, 1, 1) <= zlast) ++ylast;
-    const int64_t nyears = ylast - y0 + 1;
-    if (nyears * 29 > TWXPQ_MAX_WINDOW_VALUES) {
-        snprintf(msg, sizeof msg, "%s: the series touches %lld years; a row of the percentile basis holds at most "
-                 "TWXPQ_MAX_WINDOW_VALUES = %d values (29 per year, %d years)", who, (long long)nyears,
-                 TWXPQ_MAX_WINDOW_VALUES, TWXPQ_MAX_WINDOW_VALUES / 29);
-        return qa_fail(errbuf, errlen, msg);
-    }
-    c.nyears = (int)nyears;
-    c.row.resize((size_t)ndays);
-    c.mday.resize((size_t)ndays);
-    static const int mlen[12] = {31, 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31};
-    static const int cum[12] = {0, 31, 60, 91, 121, 152, 182, 213, 244, 274, 305, 335};    // a leap year's
-    int y = y0, mth = m0, day = d0;
-    int64_t jan1 = qa_days_from_civil(y0, 1, 1) - qa_days_from_civil(y0, m0, d0);
-    c.yr.assign({(int32_t)jan1, qa_leap(y0) ? 1 : 0});
-    for (int64_t i = 0; i < ndays; ++i) {
-        if (ymd[i] != y * 10000 + mth * 100 + day) {
-            snprintf(msg, sizeof msg, "%s: ymd[%lld] = %d: the days are not consecutive calendar days", who, (long long)i,
-                     (int)ymd[i]);
-            return qa_fail(errbuf, errlen, msg);
-        }
-        c.row[(size_t)i] = (uint16_t)(i - jan1);                  // 0 .. 365
-        c.mday[(size_t)i] = (uint16_t)(cum[mth - 1] + day - 1);   // 0 .. 365
-        if (++day > mlen[mth - 1] + ((mth == 2 && qa_leap(y)) ? 1 : 0)) {
-            day = 1;
-            if (++mth > 12) {
-                mth = 1;
-                ++y;
-                jan1 = i + 1;
-                if (i + 1 < ndays) { c.yr.push_back((int32_t)jan1); c.yr.push_back(qa_leap(y) ? 1 : 0); }
-            }
-        }
-    }
-    if ((int)(c.yr.size() / 2) != c.nyears) {
-        snprintf(msg, sizeof msg, "%s: calendar count mismatch", who);
-        return qa_fail(errbuf, errlen, msg);
-    }
-    return 0;
+    if (qa_cal_years(who, ndays, ymd, c, errbuf, errlen) != 0 ||
+        qa_year_cap(who, c, 29, TWXPQ_MAX_WINDOW_VALUES, "a row of the percentile basis holds at most TWXPQ_MAX_WINDOW_VALUES", "",
+                    errbuf, errlen) != 0)
+        return -1;
+    return qa_cal_walk(who, ndays, ymd, c, errbuf, errlen);
 }
 
 }  // namespace
@@ -361,8 +308,8 @@ extern "C" int twxpc_spatial_corrob(int device, int64_t nstn, int64_t ndays, con
     const int64_t nblk64 = (ndays + 63) / 64;
     if (nblk64 * ntarget > INT32_MAX || (ntarget * ndays + 255) / 256 > INT32_MAX || (nstn + ntarget) > INT32_MAX)
         return qa_fail(errbuf, errlen, "twxpc_spatial_corrob: more than 2^31 - 1 work items in one call");
-    PcCalendar cal;
-    if (pc_calendar("twxpc_spatial_corrob", ndays, ymd, cal, errbuf, errlen) != 0) return -1;
+    QaCalendar cal;
+    if (pc_cal("twxpc_spatial_corrob", ndays, ymd, cal, errbuf, errlen) != 0) return -1;
     for (int64_t i = 0; i < ntarget; ++i) {
         if (target_idx[i] < 0 || target_idx[i] >= nstn) {
             char msg[160];
@@ -440,7 +387,8 @@ extern "C" int twxpc_spatial_corrob(int device, int64_t nstn, int64_t ndays, con
     int2 *d_yr = static_cast<int2 *>(b_cal.p);
     uint16_t *d_row = (uint16_t *)(d_yr + ny), *d_mday = d_row + nd;
     QACHK(hipMemcpy(d_yr, cal.yr.data(), ny * 8, hipMemcpyHostToDevice));
-    QACHK(hipMemcpy(d_row, cal.row.data(), nd * 2, hipMemcpyHostToDevice));
+    const std::vector<uint16_t> row16(cal.row.begin(), cal.row.end());       // yday - 1: 0 .. 365 (k_pc_walk, k_pc_rank take 16 bits)
+    QACHK(hipMemcpy(d_row, row16.data(), nd * 2, hipMemcpyHostToDevice));
     QACHK(hipMemcpy(d_mday, cal.mday.data(), nd * 2, hipMemcpyHostToDevice));
     QACHK(hipMalloc(&b_slot.p, ns * 4));
     QACHK(hipMemcpy(b_slot.p, slot.data(), ns * 4, hipMemcpyHostToDevice));
@@ -505,8 +453,8 @@ extern "C" int twxpc_pors_counts(int device, int64_t nstn, int64_t ndays, const 
     if (nstn < 1 || ndays < 1 || nstn > INT32_MAX || ndays > INT32_MAX - 256)
         return qa_fail(errbuf, errlen, "twxpc_pors_counts: need nstn >= 1 and ndays >= 1");
     if (!vals || !ymd || !counts) return qa_fail(errbuf, errlen, "twxpc_pors_counts: null buffer");
-    PcCalendar cal;
-    if (pc_calendar("twxpc_pors_counts", ndays, ymd, cal, errbuf, errlen) != 0) return -1;
+    QaCalendar cal;
+    if (pc_cal("twxpc_pors_counts", ndays, ymd, cal, errbuf, errlen) != 0) return -1;
     const size_t ns = (size_t)nstn, nd = (size_t)ndays;
     QACHK(hipSetDevice(device));
     QaBuf b_obs, b_cal, b_cnt;

@@ -38,7 +38,7 @@
 #include <vector>
 
 #include "twx_qa.h"
-#include "twx_qa_common.h"
+#include "twx_qa_series.h"
 
 #define PQ_OK 1                              // qa_prcp.py:37-57
 #define PQ_MISSING 2
@@ -61,34 +61,8 @@
 
 namespace {
 
-__device__ __forceinline__ bool pq_finitef(float v) { return fabsf(v) <= 3.40282346638528859812e38f; }
-
 // a value the percentile table, the streak, frequent-value, gap and outlier checks look at
-__device__ __forceinline__ bool pq_wet(float v) { return v > 0.0f && pq_finitef(v); }
-
-struct PqCal {
-    const uint8_t *month;      // [ndays] 1..12
-    const uint8_t *yidx;       // [ndays] index of the day's year among the years the axis touches
-    const int32_t *row;        // [ndays] yday - 1 of the day's own year: the row of the 366-row table (:600, the quirk)
-    const int32_t *ystart;     // [nyears] first day of the year that is on the axis
-    const int32_t *ylen;       // [nyears] days of the year on the axis
-    const int32_t *mstart;     // [nyears][12] first day of the month on the axis
-    const int32_t *mlen;       // [nyears][12] days of the month on the axis (0: none)
-    const int2 *yr;            // [nyears] (series index of Jan 1 -- may lie before the axis --, leap)
-    int nyears;
-    int skip_month;            // the month NUMBER never taken as the first of a pair by check 6 (:266)
-};
-
-// two stretches of one series compared by position over the shorter one: all == (a NaN or a removed value: no)
-__device__ __forceinline__ bool pq_same(const float *__restrict__ x, const uint8_t *f, int a, int la, int b, int lb)
-{
-    const int n = la < lb ? la : lb;
-    for (int j = 0; j < n; ++j) {
-        if (f[a + j] != PQ_OK || f[b + j] != PQ_OK) return false;
-        if (!(x[a + j] == x[b + j])) return false;
-    }
-    return true;
-}
+__device__ __forceinline__ bool pq_wet(float v) { return v > 0.0f && qa_finitef(v); }
 
 }  // namespace
 
@@ -100,7 +74,7 @@ __global__ __launch_bounds__(256) void k_pq_init(int64_t total, const float *__r
     flag[i] = v != v ? PQ_MISSING : PQ_OK;
 }
 
-__global__ __launch_bounds__(256) void k_pq_dups(int64_t ndays, PqCal cal, const float *__restrict__ prcp, uint8_t *flag)
+__global__ __launch_bounds__(256) void k_pq_dups(int64_t ndays, QaCal cal, const float *__restrict__ prcp, uint8_t *flag)
 {
     __shared__ int cnt_y[PQ_MAX_YEARS];
     __shared__ uint8_t dup_y[PQ_MAX_YEARS];
@@ -119,7 +93,7 @@ __global__ __launch_bounds__(256) void k_pq_dups(int64_t ndays, PqCal cal, const
     for (int p = tid; p < ny * ny; p += 256) {
         const int a = p / ny, b = p % ny;
         if (b <= a || cnt_y[a] < PQ_MIN_DUP_VALUES || cnt_y[b] < PQ_MIN_DUP_VALUES) continue;
-        if (pq_same(x, f, cal.ystart[a], cal.ylen[a], cal.ystart[b], cal.ylen[b])) { dup_y[a] = 1; dup_y[b] = 1; }
+        if (qa_same(x, f, cal.ystart[a], cal.ylen[a], cal.ystart[b], cal.ylen[b])) { dup_y[a] = 1; dup_y[b] = 1; }
     }
     __syncthreads();
     for (int d = tid; d < nd; d += 256)
@@ -142,7 +116,7 @@ __global__ __launch_bounds__(256) void k_pq_dups(int64_t ndays, PqCal cal, const
                 const int k = p / 144, m1 = (p % 144) / 12, m2 = p % 12;
                 const int a = k * 12 + m1, b = k * 12 + m2;
                 if (m2 <= m1 || m1 + 1 == cal.skip_month || cnt_m[a] < PQ_MIN_DUP_VALUES || cnt_m[b] < PQ_MIN_DUP_VALUES) continue;
-                if (pq_same(x, f, cal.mstart[a], cal.mlen[a], cal.mstart[b], cal.mlen[b])) { dup_m[a] = 1; dup_m[b] = 1; }
+                if (qa_same(x, f, cal.mstart[a], cal.mlen[a], cal.mstart[b], cal.mlen[b])) { dup_m[a] = 1; dup_m[b] = 1; }
             }
         } else {
             for (int p = tid; p < ny * ny * 12; p += 256) {
@@ -150,7 +124,7 @@ __global__ __launch_bounds__(256) void k_pq_dups(int64_t ndays, PqCal cal, const
                 const int ka = q / ny, kb = q % ny;
                 const int a = ka * 12 + m, b = kb * 12 + m;
                 if (kb <= ka || cnt_m[a] < PQ_MIN_DUP_VALUES || cnt_m[b] < PQ_MIN_DUP_VALUES) continue;
-                if (pq_same(x, f, cal.mstart[a], cal.mlen[a], cal.mstart[b], cal.mlen[b])) { dup_m[a] = 1; dup_m[b] = 1; }
+                if (qa_same(x, f, cal.mstart[a], cal.mlen[a], cal.mstart[b], cal.mlen[b])) { dup_m[a] = 1; dup_m[b] = 1; }
             }
         }
         __syncthreads();
@@ -169,46 +143,9 @@ __global__ __launch_bounds__(256) void k_pq_dups(int64_t ndays, PqCal cal, const
 
 __global__ __launch_bounds__(64) void k_pq_streak(int64_t ndays, const float *__restrict__ prcp, uint8_t *flag)
 {
-    const int lane = threadIdx.x;
     const size_t o = (size_t)blockIdx.x * (size_t)ndays;
-    const float *x = prcp + o;
-    uint8_t *f = flag + o;
-    const uint64_t lt = ((uint64_t)1 << lane) - 1;                       // lanes below
-    const uint64_t le = ((uint64_t)2 << lane) - 1;                       // lanes below and this one (lane 63: all)
-    bool carry_has = false;                                              // a run is open from the blocks before
-    float carry_val = 0.0f;
-    int carry_rank = 0, rank_base = 0;                                   // rank (among the values walked) and day of the
-    int64_t carry_day = 0;                                               // open run's first value; ndays < 2^31
-    for (int64_t b0 = 0; b0 < ndays; b0 += 64) {                         // uniform
-        const int64_t d = b0 + lane;
-        float v = 0.0f;
-        bool live = d < ndays && f[d] == PQ_OK;
-        if (live) { v = x[d]; live = pq_wet(v); }                        // zeros and NaN are skipped and break no run (:392)
-        const uint64_t lm = __ballot(live);
-        if (lm == 0) continue;
-        const uint64_t below = lm & lt;
-        const float pv = __shfl(v, below ? 63 - __clzll(below) : lane);
-        const bool start = live && (below ? !(v == pv) : (!carry_has || !(v == carry_val)));
-        const uint64_t sm = __ballot(start);
-        const int rank = rank_base + __popcll(below);
-        const uint64_t s_le = sm & le, s_gt = sm & ~le;
-        const int g = s_le ? 63 - __clzll(s_le) : -1;                    // the start of this lane's run, -1: the open run
-        const int nx = s_gt ? __ffsll((unsigned long long)s_gt) - 1 : -1;  // the next start, -1: none in this block
-        const int rank_g = __shfl(rank, g >= 0 ? g : lane), rank_nx = __shfl(rank, nx >= 0 ? nx : lane);
-        if (live && nx >= 0 && rank_nx - (g >= 0 ? rank_g : carry_rank) >= PQ_STREAK_LEN) f[d] = PQ_STREAK;
-        if (sm != 0) {
-            const int first = __ffsll((unsigned long long)sm) - 1, last = 63 - __clzll(sm);
-            const int rank_first = rank_base + __popcll(lm & (((uint64_t)1 << first) - 1));
-            if (carry_has && rank_first - carry_rank >= PQ_STREAK_LEN)   // the open run ended here: its earlier blocks
-                for (int64_t e = carry_day + lane; e < b0; e += 64)
-                    if (f[e] == PQ_OK && pq_wet(x[e])) f[e] = PQ_STREAK;
-            carry_rank = rank_base + __popcll(lm & (((uint64_t)1 << last) - 1));
-            carry_day = b0 + last;
-        }
-        carry_has = true;
-        carry_val = __shfl(v, 63 - __clzll(lm));
-        rank_base += __popcll(lm);
-    }
+    // zeros and NaN are skipped and break no run (:392)
+    qa_streak_walk<PQ_OK, PQ_STREAK, PQ_STREAK_LEN>(ndays, prcp + o, flag + o, [](float v) { return pq_wet(v); });
 }
 
 // the day indices of the live values > 0 of a station, in day order: cidx [nstn][ndays], ccnt [nstn]
@@ -287,7 +224,7 @@ __global__ __launch_bounds__(256) void k_pq_apply(int64_t total, const uint8_t *
     if (mark[i] && flag[i] == PQ_OK) flag[i] = PQ_FREQUENT;
 }
 
-__global__ __launch_bounds__(256) void k_pq_gap(int64_t ndays, PqCal cal, const float *__restrict__ prcp, uint8_t *flag)
+__global__ __launch_bounds__(256) void k_pq_gap(int64_t ndays, QaCal cal, const float *__restrict__ prcp, uint8_t *flag)
 {
     __shared__ float xs[TWXQA_MAX_GAP_VALUES];
     __shared__ int cnt, itop;
@@ -317,18 +254,7 @@ __global__ __launch_bounds__(256) void k_pq_gap(int64_t ndays, PqCal cal, const 
     __syncthreads();
     const int n = cnt;
     if (n < 2) return;                                                   // uniform
-    for (int k = 2; k <= np2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < np2; i += 256) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const float a = xs[i], b = xs[ixj];
-                    if ((a > b) == ((i & k) == 0)) { xs[i] = b; xs[ixj] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    qa_lds_sort(xs, np2, tid);
     for (int i = 1 + tid; i < n; i += 256)
         if (xs[i] - xs[i - 1] >= PQ_GAP_THRES) atomicMin(&itop, i);      // the first step (:467-470); float32 difference
     __syncthreads();
@@ -364,10 +290,8 @@ __global__ __launch_bounds__(256) void k_pq_pctiles(int64_t ndays, int nyears, c
         if (j >= 29) continue;
         int q = row - 14 + j;
         q = q < 0 ? q + PQ_ROWS : (q >= PQ_ROWS ? q - PQ_ROWS : q);
-        const int2 y = yr[k];                                            // x: series index of Jan 1, y: leap year
-        if (q == 59 && !y.y) continue;
-        const int64_t d = (int64_t)y.x + ((q < 59 || y.y) ? q : q - 1);
-        if (d < 0 || d >= ndays) continue;
+        const int64_t d = qa_date_day(q, yr[k], ndays);
+        if (d < 0) continue;
         if (flag[so + d] != PQ_OK) continue;
         const float v = prcp[so + d];
         if (!pq_wet(v)) continue;
@@ -384,18 +308,7 @@ __global__ __launch_bounds__(256) void k_pq_pctiles(int64_t ndays, int nyears, c
     while (np2 < n) np2 <<= 1;
     for (int i = n + tid; i < np2; i += 256) xs[i] = __builtin_inff();
     __syncthreads();
-    for (int k = 2; k <= np2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < np2; i += 256) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const float a = xs[i], b = xs[ixj];
-                    if ((a > b) == ((i & k) == 0)) { xs[i] = b; xs[ixj] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    qa_lds_sort(xs, np2, tid);
     if (tid < PQ_COLS) {
         // numpy's 'linear': virtual index (n - 1) q, gamma its fraction, a + (b - a) gamma below 0.5, b - (b - a)(1 - gamma)
         // from 0.5 on; q = 30 / 100 ... as np.true_divide forms them
@@ -431,115 +344,16 @@ __global__ __launch_bounds__(256) void k_pq_clim(int64_t ndays, int64_t nstn, co
 // ---------------------------------------------------------------------------------
 namespace {
 
-struct PqCalendar {
-    int nyears = 0, ndistinct = 0;
-    std::vector<int32_t> yr;        // [nyears][2]: Jan 1's series index, leap
-    std::vector<int32_t> row;       // [ndays]
-    std::vector<uint8_t> month;     // [ndays]
-    std::vector<uint8_t> yidx;      // [ndays]
-    std::vector<int32_t> ystart, ylen, mstart, mlen;
-};
-
-// The calendar tables of a day axis of consecutive days (checked).  -1 and a message on failure.  gap_cap: the chain's gap
-// check bounds the years as well.
-int pq_calendar(const char *who, int64_t ndays, const int32_t *ymd, bool gap_cap, PqCalendar &c, char *errbuf, int errlen)
+// The calendar of a day axis, the years capped for the percentile table and, with gap_cap, for the chain's gap check.
+int pq_cal(const char *who, int64_t ndays, const int32_t *ymd, bool gap_cap, QaCalendar &c, char *errbuf, int errlen)
 {
-    char msg[320];
-    const int32_t a = ymd[0];
-    const int y0 = a / 10000, m0 = (a / 100) % 100, d0 = a % 100;
-    if (a < 10101 || m0 < 1 || m0 > 12 || d0 < 1 || d0 > 31) {
-        snprintf(msg, sizeof msg, "%s: ymd[0] is not a date", who);
-        return qa_fail(errbuf, errlen, msg);
-    }
-    // the years the axis touches, before anything is sized by them
-    const int64_t zlast = qa_days_from_civil(y0, m0, d0) + ndays - 1;
-    int64_t ylast = y0 + (ndays - 1) / 366;
-    while (qa_days_from_civil(ylast + 1, 1, 1) <= zlast) ++ylast;
-    const int64_t nyears = ylast - y0 + 1;
-    if (nyears * 29 > TWXPQ_MAX_WINDOW_VALUES) {
-        snprintf(msg, sizeof msg, "%s: the series touches %lld years; a row of the percentile table holds at most "
-                 "TWXPQ_MAX_WINDOW_VALUES = %d values (29 per year, %d years)", who, (long long)nyears,
-                 TWXPQ_MAX_WINDOW_VALUES, TWXPQ_MAX_WINDOW_VALUES / 29);
-        return qa_fail(errbuf, errlen, msg);
-    }
-    if (gap_cap && nyears * 31 > TWXQA_MAX_GAP_VALUES) {
-        snprintf(msg, sizeof msg, "%s: the series touches %lld years; the gap check sorts at most TWXQA_MAX_GAP_VALUES = %d "
-                 "values of a calendar month (31 per year, %d years)", who, (long long)nyears, TWXQA_MAX_GAP_VALUES,
-                 TWXQA_MAX_GAP_VALUES / 31);
-        return qa_fail(errbuf, errlen, msg);
-    }
-    c.nyears = (int)nyears;
-    c.row.resize((size_t)ndays);
-    c.month.resize((size_t)ndays);
-    c.yidx.resize((size_t)ndays);
-    c.ystart.assign((size_t)nyears, 0);
-    c.ylen.assign((size_t)nyears, 0);
-    c.mstart.assign((size_t)nyears * 12, 0);
-    c.mlen.assign((size_t)nyears * 12, 0);
-    static const int mlen[12] = {31, 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31};
-    int y = y0, mth = m0, day = d0, k = 0;
-    bool seen[12] = {false, false, false, false, false, false, false, false, false, false, false, false};
-    int64_t jan1 = qa_days_from_civil(y0, 1, 1) - qa_days_from_civil(y0, m0, d0);
-    c.yr.assign({(int32_t)jan1, qa_leap(y0) ? 1 : 0});
-    for (int64_t i = 0; i < ndays; ++i) {
-        if (ymd[i] != y * 10000 + mth * 100 + day) {
-            snprintf(msg, sizeof msg, "%s: ymd[%lld] = %d: the days are not consecutive calendar days", who, (long long)i,
-                     (int)ymd[i]);
-            return qa_fail(errbuf, errlen, msg);
-        }
-        c.row[(size_t)i] = (int32_t)(i - jan1);                  // yday - 1 of the day's own year: 0 .. 365
-        c.month[(size_t)i] = (uint8_t)mth;
-        c.yidx[(size_t)i] = (uint8_t)k;
-        seen[mth - 1] = true;
-        if (c.ylen[(size_t)k]++ == 0) c.ystart[(size_t)k] = (int32_t)i;
-        const size_t seg = (size_t)k * 12 + (size_t)(mth - 1);
-        if (c.mlen[seg]++ == 0) c.mstart[seg] = (int32_t)i;
-        if (++day > mlen[mth - 1] + ((mth == 2 && qa_leap(y)) ? 1 : 0)) {
-            day = 1;
-            if (++mth > 12) {
-                mth = 1;
-                ++y;
-                jan1 = i + 1;
-                if (i + 1 < ndays) { ++k; c.yr.push_back((int32_t)jan1); c.yr.push_back(qa_leap(y) ? 1 : 0); }
-            }
-        }
-    }
-    for (int m = 0; m < 12; ++m) c.ndistinct += seen[m] ? 1 : 0;
-    if ((int)(c.yr.size() / 2) != c.nyears) {
-        snprintf(msg, sizeof msg, "%s: calendar count mismatch", who);
-        return qa_fail(errbuf, errlen, msg);
-    }
-    return 0;
-}
-
-// the device copy of the calendar; k's pointers point into b.p
-int pq_upload_calendar(const PqCalendar &cal, int64_t ndays, QaBuf &b, PqCal &k, char *errbuf, int errlen)
-{
-    const size_t nd = (size_t)ndays, ny = (size_t)cal.nyears;
-    // int32 tables first (yr, row, ystart, ylen, mstart, mlen), then the bytes (month, yidx)
-    const size_t o_yr = 0, o_row = o_yr + ny * 8, o_ys = o_row + nd * 4, o_yl = o_ys + ny * 4, o_ms = o_yl + ny * 4,
-                 o_ml = o_ms + ny * 48, o_mth = o_ml + ny * 48, o_yi = o_mth + nd;
-    QACHK(hipMalloc(&b.p, o_yi + nd));
-    char *dc = static_cast<char *>(b.p);
-    QACHK(hipMemcpy(dc + o_yr, cal.yr.data(), ny * 8, hipMemcpyHostToDevice));
-    QACHK(hipMemcpy(dc + o_row, cal.row.data(), nd * 4, hipMemcpyHostToDevice));
-    QACHK(hipMemcpy(dc + o_ys, cal.ystart.data(), ny * 4, hipMemcpyHostToDevice));
-    QACHK(hipMemcpy(dc + o_yl, cal.ylen.data(), ny * 4, hipMemcpyHostToDevice));
-    QACHK(hipMemcpy(dc + o_ms, cal.mstart.data(), ny * 48, hipMemcpyHostToDevice));
-    QACHK(hipMemcpy(dc + o_ml, cal.mlen.data(), ny * 48, hipMemcpyHostToDevice));
-    QACHK(hipMemcpy(dc + o_mth, cal.month.data(), nd, hipMemcpyHostToDevice));
-    QACHK(hipMemcpy(dc + o_yi, cal.yidx.data(), nd, hipMemcpyHostToDevice));
-    k.month = (const uint8_t *)(dc + o_mth);
-    k.yidx = (const uint8_t *)(dc + o_yi);
-    k.row = (const int32_t *)(dc + o_row);
-    k.ystart = (const int32_t *)(dc + o_ys);
-    k.ylen = (const int32_t *)(dc + o_yl);
-    k.mstart = (const int32_t *)(dc + o_ms);
-    k.mlen = (const int32_t *)(dc + o_ml);
-    k.yr = (const int2 *)(dc + o_yr);
-    k.nyears = cal.nyears;
-    k.skip_month = cal.ndistinct - 1;
-    return 0;
+    if (qa_cal_years(who, ndays, ymd, c, errbuf, errlen) != 0 ||
+        qa_year_cap(who, c, 29, TWXPQ_MAX_WINDOW_VALUES, "a row of the percentile table holds at most TWXPQ_MAX_WINDOW_VALUES", "",
+                    errbuf, errlen) != 0 ||
+        (gap_cap && qa_year_cap(who, c, 31, TWXQA_MAX_GAP_VALUES, "the gap check sorts at most TWXQA_MAX_GAP_VALUES",
+                                " of a calendar month", errbuf, errlen) != 0))
+        return -1;
+    return qa_cal_walk(who, ndays, ymd, c, errbuf, errlen);
 }
 
 bool pq_sizes_ok(int64_t nstn, int64_t ndays)
@@ -558,8 +372,8 @@ extern "C" int twxpq_non_spatial(int device, int64_t nstn, int64_t ndays, const 
     if (!pq_sizes_ok(nstn, ndays))
         return qa_fail(errbuf, errlen, "twxpq_non_spatial: need nstn >= 1, ndays >= 1 and fewer than 2^31 work items in one call");
     if (!prcp || !tavg || !ymd || !flag) return qa_fail(errbuf, errlen, "twxpq_non_spatial: null buffer");
-    PqCalendar cal;
-    if (pq_calendar("twxpq_non_spatial", ndays, ymd, true, cal, errbuf, errlen) != 0) return -1;
+    QaCalendar cal;
+    if (pq_cal("twxpq_non_spatial", ndays, ymd, true, cal, errbuf, errlen) != 0) return -1;
     const size_t ns = (size_t)nstn, nd = (size_t)ndays;
     QACHK(hipSetDevice(device));
     QaBuf b_obs, b_flag, b_cal, b_pct, b_idx, b_cnt, b_mark;
@@ -571,8 +385,8 @@ extern "C" int twxpq_non_spatial(int device, int64_t nstn, int64_t ndays, const 
     QACHK(hipMemcpy(d_tavg, tavg, ns * nd * 4, hipMemcpyHostToDevice));
     QACHK(hipMalloc(&b_flag.p, ns * nd));
     uint8_t *d_f = static_cast<uint8_t *>(b_flag.p);
-    PqCal k;
-    if (pq_upload_calendar(cal, ndays, b_cal, k, errbuf, errlen) != 0) return -1;
+    QaCal k;
+    if (qa_upload_calendar(cal, cal.row, b_cal, k, errbuf, errlen) != 0) return -1;
     const size_t pct_bytes = ns * PQ_ROWS * PQ_COLS * 8;
     QACHK(hipMalloc(&b_pct.p, pct_bytes));                        // [nstn][366][5]
     double *d_pct = static_cast<double *>(b_pct.p);
@@ -648,8 +462,8 @@ extern "C" int twxpq_percentiles(int device, int64_t nstn, int64_t ndays, const 
     if (!pq_sizes_ok(nstn, ndays))
         return qa_fail(errbuf, errlen, "twxpq_percentiles: need nstn >= 1, ndays >= 1 and fewer than 2^31 work items in one call");
     if (!vals || !ymd || !pctiles) return qa_fail(errbuf, errlen, "twxpq_percentiles: null buffer");
-    PqCalendar cal;
-    if (pq_calendar("twxpq_percentiles", ndays, ymd, false, cal, errbuf, errlen) != 0) return -1;
+    QaCalendar cal;
+    if (pq_cal("twxpq_percentiles", ndays, ymd, false, cal, errbuf, errlen) != 0) return -1;
     const size_t ns = (size_t)nstn, nd = (size_t)ndays;
     QACHK(hipSetDevice(device));
     QaBuf b_obs, b_flag, b_cal, b_pct;
@@ -658,8 +472,8 @@ extern "C" int twxpq_percentiles(int device, int64_t nstn, int64_t ndays, const 
     QACHK(hipMalloc(&b_obs.p, ns * nd * 4));
     QACHK(hipMemcpy(b_obs.p, vals, ns * nd * 4, hipMemcpyHostToDevice));
     QACHK(hipMalloc(&b_flag.p, ns * nd));
-    PqCal k;
-    if (pq_upload_calendar(cal, ndays, b_cal, k, errbuf, errlen) != 0) return -1;
+    QaCal k;
+    if (qa_upload_calendar(cal, cal.row, b_cal, k, errbuf, errlen) != 0) return -1;
     const size_t pct_bytes = ns * PQ_ROWS * PQ_COLS * 8;
     QACHK(hipMalloc(&b_pct.p, pct_bytes));
     float ms = 0.0f;
