@@ -24,7 +24,7 @@ show_diagnostics "$LOG"
 python3 tests/tools/isa_resources.py "$LOG" > topowx_amd/libtwxhip.resources.txt
 # libtwxqa.so: the station QA kernels (include/twx_qa.h), a library of their own -- built second, same flags.  Every unit
 # of topowx_amd/qa is named here once (tests/test_emnorm_host.py compares the names with the directory; twxrw_raws.hip is
-# checked by tests/test_raws_host.py); the headers next to them (twx_qa_common.h, twx_qa_series.h, ...) are no units;
+# checked by tests/test_raws_host.py and stays last, twxsd_serdeflate.hip by tests/test_series_deflate_host.py); the headers next to them (twx_qa_common.h, twx_qa_series.h, ...) are no units;
 # twx_mosaic deflates with the kernels of topowx_amd/csrc/twx_deflate.h.
 if ! hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared -std=c++17 -Iinclude \
     -Rpass-analysis=kernel-resource-usage "$@" -o topowx_amd/libtwxqa.so topowx_amd/qa/twx_outlier.hip \
@@ -34,7 +34,7 @@ if ! hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared -std=c++17 
     topowx_amd/qa/twx_nnr.hip topowx_amd/qa/twx_homog.hip topowx_amd/qa/twx_stnrast.hip \
     topowx_amd/qa/twx_prcpqa.hip topowx_amd/qa/twx_prcpcorrob.hip \
     topowx_amd/qa/twx_ghcn.hip topowx_amd/qa/twx_nnrsub.hip topowx_amd/qa/twx_tzpoly.hip \
-    topowx_amd/qa/twx_mosaic.hip topowx_amd/qa/twxrw_raws.hip 2> "$LOG"; then
+    topowx_amd/qa/twx_mosaic.hip topowx_amd/qa/twxsd_serdeflate.hip topowx_amd/qa/twxrw_raws.hip 2> "$LOG"; then
     show_diagnostics "$LOG"
     rm -f "$LOG"
     exit 1

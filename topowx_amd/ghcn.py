@@ -10,9 +10,13 @@ The RAWS sites, which ``read_ghcn_stations`` drops as the reference does, come f
 (``InsertRaws``), through ``create_all_stations_db(..., raws=...)``.
 
 Out of scope: ``InsertSnotel`` (it reads files "cleaned and formatted using the snotel_clean module", which the reference
-does not contain, and parses them with ``pandas.read_csv``, whose number parser is not ``float()``), ``obsio``,
-deflate of the station variables (``zlib=False``: a station's kernel row IS a NetCDF-4 chunk and is written as one), and
+does not contain, and parses them with ``pandas.read_csv``, whose number parser is not ``float()``), ``obsio``, and
 downloading anything.
+
+Deflate of the station variables is opt-in.  By default they are not compressed (``zlib=False``: a station's kernel row IS
+a NetCDF-4 chunk and is written as one).  With ``deflate="gpu"`` the seven ``(time, station_id)`` variables are created
+with ``zlib=True`` as the reference creates them, and every batch's kernel rows are shuffled and deflated on the GPU
+(``series_deflate``, ``ncio.write_series_chunks``); ``deflate="host"`` leaves that to libhdf5.
 """
 import datetime as _dt
 import gzip
@@ -380,9 +384,9 @@ _VARS = (("tmin", "f4", MISSING, "minimum air temperature", "C", "minimum_air_te
          ("qflag_prcp", "S1", "", "quality assurance flag prcp", None, "quality assurance flag prcp"))
 
 
-def _create_db(path, stns, days, format, with_tobs):
+def _create_db(path, stns, days, format, with_tobs, zlib=False):
     """``create_netcdf_db`` (:320-456) plus ``prcp`` / ``qflag_prcp`` (parsed and left out of the file by the reference) and,
-    on request, ``tobs_tmax``: dimensions ``time`` and ``station_id``, chunks ``(ndays, 1)``, not compressed."""
+    on request, ``tobs_tmax``: dimensions ``time`` and ``station_id``, chunks ``(ndays, 1)``, compressed only with ``zlib``."""
     ds = ncio.open_dataset(path, "w", format)
     ds.title = "Weather Station Database"
     ds.institution = "University of Montana Numerical Terradynamics Simulation Group"
@@ -409,7 +413,7 @@ def _create_db(path, stns, days, format, with_tobs):
         v = ds.createVariable(name, "f8", (sdb.STN_ID,), fill_value=MISSING)
         v.long_name, v.units, v.standard_name = name, units, name
         v[:] = stns[name]
-    kw = dict(chunksizes=(nd, 1), zlib=False) if ncio._is_nc4(ds) and n else {}
+    kw = dict(chunksizes=(nd, 1), zlib=bool(zlib)) if ncio._is_nc4(ds) and n else {}
     for name, dtype, fill, long_name, units, std in _VARS:
         v = ds.createVariable(name, dtype, ("time", sdb.STN_ID), fill_value=fill, **kw)
         v.long_name, v.standard_name = long_name, std
@@ -421,15 +425,20 @@ def _create_db(path, stns, days, format, with_tobs):
     return ds
 
 
-def write_all_stations_db(path, stns, days, batches, tobs=None, format=None):
+def write_all_stations_db(path, stns, days, batches, tobs=None, format=None, deflate=None, device=0, timing=None):
     """Write the database: ``batches`` yields ``(i0, i1, val [3, i1 - i0, ndays], flag [3, i1 - i0, ndays])`` station-major
     rows of the stations i0 .. i1 - 1 of ``stns`` (``iter_dly_batches``); ``tobs`` [nstn, ndays] int16 (or a callable that
     returns it, called after the observations are in) becomes ``tobs_tmax``.  In NetCDF-4 a station's row is written as
-    the chunk it is (``write_chunk_raw``, no transpose); the classic container is filled from transposed arrays."""
+    the chunk it is (``write_chunk_raw``, no transpose); the classic container is filled from transposed arrays.
+    ``deflate`` = ``"gpu"`` / ``"host"``: the variables are created with ``zlib=True`` and every batch goes through
+    ``ncio.write_series_chunks``; ``None``: not compressed, the file as it always was."""
+    if deflate not in (None, "gpu", "host"):
+        raise ValueError("deflate must be None, 'gpu' or 'host', not %r" % (deflate,))
     n, ndays = int(stns.size), int(days.size)
-    ds = _create_db(path, stns, days, format, tobs is not None)
+    ds = _create_db(path, stns, days, format, tobs is not None, zlib=deflate is not None)
     try:
         raw = ncio._is_nc4(ds)
+        packed = raw and deflate is not None and n > 0
         hold = None if raw else {name: (np.full((ndays, n), MISSING, "f4") if k < 3 else np.zeros((ndays, n), "S1"))
                                  for k, (name, *_) in enumerate(_VARS)}
         for i0, i1, val, flag in batches:
@@ -437,6 +446,10 @@ def write_all_stations_db(path, stns, days, batches, tobs=None, format=None):
             if val.shape != (3, i1 - i0, ndays) or flag.shape != val.shape or not 0 <= i0 <= i1 <= n:
                 raise ValueError("a batch must be (i0, i1, val [3, i1 - i0, ndays], flag [3, i1 - i0, ndays])")
             for e in range(3):
+                if packed:
+                    ncio.write_series_chunks(ds.variables[_VARS[e][0]], val[e], i0, deflate, device=device, timing=timing)
+                    ncio.write_series_chunks(ds.variables[_VARS[3 + e][0]], flag[e], i0, deflate, device=device, timing=timing)
+                    continue
                 for j in range(i0, i1):
                     if raw:
                         ds.variables[_VARS[e][0]].write_chunk_raw((0, j), val[e, j - i0])
@@ -451,7 +464,9 @@ def write_all_stations_db(path, stns, days, batches, tobs=None, format=None):
             tobs = np.ascontiguousarray(tobs() if callable(tobs) else tobs, np.int16)
             if tobs.shape != (n, ndays):
                 raise ValueError("tobs must be [nstn, ndays]")
-            if raw:
+            if packed:
+                ncio.write_series_chunks(ds.variables["tobs_tmax"], tobs, 0, deflate, device=device, timing=timing)
+            elif raw:
                 for j in range(n):
                     ds.variables["tobs_tmax"].write_chunk_raw((0, j), tobs[j])
             else:
@@ -478,14 +493,18 @@ def _with_raws(stns, raws, stats):
 
 
 def create_all_stations_db(path, path_stn_file, path_obs_files, start, end, path_by_year=None, check_obs_exist=False,
-                           format=None, batch_bytes=BATCH_BYTES, device=0, timing=None, stats=None, raws=None):
+                           format=None, batch_bytes=BATCH_BYTES, device=0, timing=None, stats=None, raws=None, deflate=None):
     """The reference's step04: the database every later step takes as ``--db``.  ``tmin`` / ``tmax`` / ``prcp`` and their
     GHCN quality flags of every station of ``read_ghcn_stations`` over the period, and with ``path_by_year`` the times of
     observation of Tmax as ``tobs_tmax`` (int16, -1 = none).  ``raws`` = (metadata file, id file, directory of the daily
     listings), the arguments of ``raws.read_raws_stations``, adds the RAWS sites: the table is the union of both networks
     sorted by id, the RAWS rows have empty flags and no time of observation; ``stats`` receives their counts as
-    ``raws_*``.  Without ``raws`` the file is what it was before the RAWS ingest existed.  Every file is looked for before
-    any device work.  Returns the station table."""
+    ``raws_*``.  Without ``raws`` the file is what it was before the RAWS ingest existed.  ``deflate`` = ``"gpu"``: the seven
+    ``(time, station_id)`` variables are created with ``zlib=True`` and their rows deflated on the GPU batch by batch
+    (``"host"``: by libhdf5); ``None``: not compressed, as before.  Every file is looked for before any device work.
+    Returns the station table."""
+    if deflate not in (None, "gpu", "host"):
+        raise ValueError("deflate must be None, 'gpu' or 'host', not %r" % (deflate,))
     min_ymd, max_ymd, d0, ndays = _period(start, end)
     stns = read_ghcn_stations(path_stn_file, path_obs_files, check_obs_exist)
     if stns.size < 1:
@@ -524,7 +543,8 @@ def create_all_stations_db(path, path_stn_file, path_obs_files, start, end, path
                 if stats is not None:
                     stats.update({"raws_" + k: v for k, v in rstats.items()})
 
-    write_all_stations_db(path, allstns, days, batches(), tobs=tobs if by_year is not None else None, format=format)
+    write_all_stations_db(path, allstns, days, batches(), tobs=tobs if by_year is not None else None, format=format,
+                          deflate=deflate, device=device, timing=timing)
     return allstns
 
 

@@ -46,13 +46,18 @@ def _field(result, name, *alt):
     raise KeyError("the infill result has no %r" % name)
 
 
-def write_infill_db(path, stns, days, tair_var, result, format=None):
+def write_infill_db(path, stns, days, tair_var, result, format=None, deflate=None, device=0, timing=None):
     """The infilled station database of step16's writer (``proc_write``:141-169): ``<var>`` f4, ``flag_infilled`` i1 and
     ``<var>_infilled`` f4 on ``(time, station_id)`` through ``ncio.create_quick_db``, and the station variables ``mae`` and
     ``bias`` f8.  ``result``: what ``infill_daily`` returned, or a loaded step16 report (``ids``, ``fnl_tair``,
     ``mask_infill``, ``infill_tair``, ``mae``, ``bias``); ``stns``: a station table (sorted by id) that holds its stations.
     The database has the result's stations in the table's order.  NaN in the series is written as the fill value.
+    ``deflate`` = ``"gpu"``: the three series go station-major, as the result has them, through
+    ``ncio.write_series_chunks`` -- their chunks are shuffled and deflated on the GPU, nothing is transposed (``"host"``:
+    the same call, libhdf5 deflates); ``None``: the assignment of the transposed arrays, the file as it always was.
     Refuses to overwrite an existing file."""
+    if deflate not in (None, "gpu", "host"):
+        raise ValueError("deflate must be None, 'gpu' or 'host', not %r" % (deflate,))
     if tair_var not in SERIAL_DB_VARIABLES:
         raise ValueError("tair_var must be 'tmin' or 'tmax'")
     path = os.fspath(path)
@@ -82,12 +87,19 @@ def write_infill_db(path, stns, days, tair_var, result, format=None):
     ncio.create_quick_db(path, sub, days, variables, format=format)
     ds = ncio.open_dataset(path, "a")
     try:
-        def f4(a):
-            a = np.asarray(a[order], np.float32).T
+        def f4(a, rows=False):
+            a = np.asarray(a[order], np.float32)
+            a = a if rows else a.T
             return np.ascontiguousarray(np.where(np.isnan(a), np.float32(fill), a))
-        ds.variables[tair_var][:] = f4(fnl)
-        ds.variables[tair_var + "_infilled"][:] = f4(model)
-        ds.variables["flag_infilled"][:] = np.ascontiguousarray((mask[order] != 0).astype(np.int8).T)
+        if deflate is None:
+            ds.variables[tair_var][:] = f4(fnl)
+            ds.variables[tair_var + "_infilled"][:] = f4(model)
+            ds.variables["flag_infilled"][:] = np.ascontiguousarray((mask[order] != 0).astype(np.int8).T)
+        else:
+            kw = dict(deflate=deflate, device=device, timing=timing)
+            ncio.write_series_chunks(ds.variables[tair_var], f4(fnl, rows=True), **kw)
+            ncio.write_series_chunks(ds.variables[tair_var + "_infilled"], f4(model, rows=True), **kw)
+            ncio.write_series_chunks(ds.variables["flag_infilled"], np.ascontiguousarray((mask[order] != 0).astype(np.int8)), **kw)
         for name, long_name, a in (("mae", "mean absolute error", mae), ("bias", "bias", bias)):
             v = ds.createVariable(name, "f8", (STN_ID,), fill_value=ncio.FILL_F8)
             v.long_name, v.units = long_name, "C"
@@ -200,13 +212,17 @@ class SerialComplete(object):
 
 
 def create_serially_complete_db(fpath_infill_db, tair_var, fpath_out_serial_db, device=0, format=None, timing=None,
-                                norm_yrs=None, max_miss=_qalib.SC_MAX_MISS):
+                                norm_yrs=None, max_miss=_qalib.SC_MAX_MISS, deflate=None):
     """``create_serially_complete_db`` (post_infill.py:79-156): the serial database with ``SERIAL_DB_VARIABLES`` over the
     infilled database's station table and day axis; per station "observations + infill", or "all model" if its longest run
     of infilled days reaches ``USE_ALL_INFILL_THRESHOLD``; values still missing become the fill value.  One
     ``twxsc_serial_complete`` call over all stations.  ``norm_yrs`` = (start, end): the same call also computes the monthly
     normals, returned in the record (they are written by ``add_monthly_normals``).  Prints the reference's warning per
-    station with missing values and its "% of stns with all infilled values" line."""
+    station with missing values and its "% of stns with all infilled values" line.  ``deflate`` = ``"gpu"``: the kernel's
+    station-major rows go through ``ncio.write_series_chunks``, their chunks shuffled and deflated on the GPU and nothing
+    transposed (``"host"``: libhdf5 deflates); ``None``: the assignment of the transposed arrays, the file as it always was."""
+    if deflate not in (None, "gpu", "host"):
+        raise ValueError("deflate must be None, 'gpu' or 'host', not %r" % (deflate,))
     if tair_var not in SERIAL_DB_VARIABLES:
         raise ValueError("tair_var must be 'tmin' or 'tmax'")
     stns, _, days, _ = ncio.read_station_db_arrays(fpath_infill_db, tair_var)
@@ -230,8 +246,13 @@ def create_serially_complete_db(fpath_infill_db, tair_var, fpath_out_serial_db, 
                                group_first=gf, group_ndays=gn, max_miss=max_miss, device=device, timing=timing)
     out = ncio.open_dataset(fpath_out_serial_db, "a")
     try:
-        out.variables[tair_var][:] = np.ascontiguousarray(r["serial"].T)
-        out.variables["flag_infilled"][:] = np.ascontiguousarray(r["flag_infilled"].T)
+        if deflate is None:
+            out.variables[tair_var][:] = np.ascontiguousarray(r["serial"].T)
+            out.variables["flag_infilled"][:] = np.ascontiguousarray(r["flag_infilled"].T)
+        else:
+            kw = dict(deflate=deflate, device=device, timing=timing)
+            ncio.write_series_chunks(out.variables[tair_var], np.ascontiguousarray(r["serial"], np.float32), **kw)
+            ncio.write_series_chunks(out.variables["flag_infilled"], np.ascontiguousarray(r["flag_infilled"], np.int8), **kw)
     finally:
         out.close()
     for x in np.nonzero(r["nmissing"] > 0)[0]:

@@ -27,7 +27,7 @@ from .dates import DAY, MONTH, YEAR, get_days_metadata
 
 __all__ = ["TileWriter", "read_tile", "write_station_db", "read_station_db", "read_station_db_arrays", "read_tile_stores",
            "CONVERT_HELP", "climdiv_optim_nstns_path", "create_climdiv_optim_nstns_db", "write_climdiv_optim_nstns_db",
-           "read_climdiv_optim_nstns_db", "create_quick_db", "open_dataset", "default_format", "file_format", "convert_station_db", "FORMATS",
+           "read_climdiv_optim_nstns_db", "create_quick_db", "write_series_chunks", "open_dataset", "default_format", "file_format", "convert_station_db", "FORMATS",
            "create_dly_mosaic_ds", "create_normals_mosaic_ds", "create_ds_mthly", "TWX_SOURCE"]
 
 FILL_I2 = np.int16(-32767)
@@ -1028,6 +1028,41 @@ def create_quick_db(path, stns, days, variables, format=None):
     finally:
         ds.close()
     return path
+
+
+def write_series_chunks(var, rows, i0=0, deflate="gpu", device=0, batch_bytes=None, timing=None):
+    """Write the station-major ``rows`` [k, ndays] as the stations i0 .. i0 + k - 1 of ``var``, a variable on ``(time,
+    station_id)`` as ``create_quick_db`` makes them: NetCDF-4, chunked ``(ndays, 1)``, shuffle + deflate.  ``deflate="gpu"``:
+    the rows' chunk bytes are formed on the GPU (``series_deflate.deflate_series``) and appended with ``write_chunk_raw`` --
+    no transpose, no deflate in libhdf5; ``deflate="host"``: ``var[:, i0:i0 + k] = rows.T``, libhdf5 shuffles and deflates.
+    Raises ``ValueError``, naming what it found, when the variable's chunks or filters are not those.  In the classic
+    container there is no filter: the plain assignment, whatever ``deflate`` says."""
+    if deflate not in ("gpu", "host"):
+        raise ValueError("deflate must be 'gpu' or 'host', not %r" % (deflate,))
+    rows = np.asarray(rows)
+    if len(var.shape) != 2 or rows.ndim != 2 or rows.shape[1] != var.shape[0] or not 0 <= int(i0) <= var.shape[1] - rows.shape[0]:
+        raise ValueError("rows must be [k, ndays] for stations i0 .. i0 + k - 1 of a variable on (time, station_id): rows %s, "
+                         "i0 = %d, variable %s" % (rows.shape, int(i0), tuple(var.shape)))
+    i0, k = int(i0), rows.shape[0]
+    dt = np.dtype(var.dtype)
+    if rows.dtype.itemsize != dt.itemsize:
+        raise ValueError("rows of %s do not fit the variable's %s" % (rows.dtype, dt))
+    if not isinstance(var, _ClassicVar):
+        chunks, filt = var.chunking(), var.filters()
+        want_shuffle = dt.itemsize > 1                             # (the shuffle of one-byte elements is the identity and not set)
+        if chunks != [int(var.shape[0]), 1] or not filt.get("zlib") or bool(filt.get("shuffle")) != want_shuffle:
+            raise ValueError("variable %s must be chunked (%d, 1) with shuffle + deflate; found chunks %s, filters %s"
+                             % (getattr(var, "name", "?"), var.shape[0], chunks, filt))
+    if k == 0:
+        return
+    if isinstance(var, _ClassicVar) or deflate == "host":
+        var[:, i0:i0 + k] = np.ascontiguousarray(rows.T) if dt.kind != "S" else np.ascontiguousarray(rows.view("S1").T)
+        return
+    from . import series_deflate
+    kw = {} if batch_bytes is None else dict(batch_bytes=batch_bytes)
+    packed, off = series_deflate.deflate_series(np.ascontiguousarray(rows), device=device, timing=timing, **kw)
+    for j in range(k):
+        var.write_chunk_raw((0, i0 + j), packed[off[j]:off[j + 1]], filter_mask=0)
 
 
 def read_station_db(path, var_name, cls=None):

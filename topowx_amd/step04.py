@@ -6,12 +6,13 @@ daily listings (``twxrw_parse``).
 
     python -m topowx_amd.step04 --stations ghcnd-stations.txt --dly-dir DIR --out all.nc --start YMD --end YMD
                                 [--by-year DIR] [--check-obs-exist] [--format NETCDF4|NETCDF3_64BIT] [--device N]
-                                [--raws-stations FILE --raws-ids FILE --raws-obs DIR]
+                                [--raws-stations FILE --raws-ids FILE --raws-obs DIR] [--deflate gpu|host]
 
 ``--start`` / ``--end``: ``yyyymmdd`` or ``yyyy-mm-dd``, inclusive.  US / CA / MX stations outside HI and AK that are not
 SNOTEL or RAWS sites are inserted; a station without a ``.dly`` file is an error unless ``--check-obs-exist`` drops it.
 ``--by-year DIR`` holds ``<year>.csv.gz`` (or ``<year>.csv``) for every year of the period.  The station variables are not
-compressed.  ``--raws-stations`` (the metadata file), ``--raws-ids`` (the id file with the states) and ``--raws-obs`` (the
+compressed unless ``--deflate`` asks for it: ``gpu`` creates them with ``zlib=True`` as the reference does and shuffles and
+deflates every batch's rows on the GPU (``twxsd_deflate``), ``host`` leaves that to libhdf5.  ``--raws-stations`` (the metadata file), ``--raws-ids`` (the id file with the states) and ``--raws-obs`` (the
 directory of the ``<id>.txt`` daily listings) go together, all three or none: the RAWS sites with a listing join the table,
 with empty flags and no time of observation.  Where several lines of a listing give one day the last one wins (the
 reference fails there) and the report counts them; a station name keeps its ASCII bytes; ``prcp`` is written.  Out of
@@ -45,6 +46,7 @@ def main(argv=None):
     ap.add_argument("--raws-stations", help="the RAWS station metadata file")
     ap.add_argument("--raws-ids", help="the RAWS station id file (state and id)")
     ap.add_argument("--raws-obs", help="directory of the RAWS daily listings <id>.txt")
+    ap.add_argument("--deflate", choices=("gpu", "host"), help="compress the station variables (default: not compressed)")
     a = ap.parse_args(argv)
     raws = (a.raws_stations, a.raws_ids, a.raws_obs)
     if any(r is not None for r in raws) and not all(r is not None for r in raws):
@@ -54,7 +56,7 @@ def main(argv=None):
     try:
         stns = ghcn.create_all_stations_db(a.out, a.stations, a.dly_dir, a.start, a.end, path_by_year=a.by_year,
                                            check_obs_exist=a.check_obs_exist, format=a.format, device=a.device, timing=tm,
-                                           stats=st, raws=raws if raws[0] is not None else None)
+                                           stats=st, raws=raws if raws[0] is not None else None, deflate=a.deflate)
     except (IOError, OSError, ValueError, KeyError, IndexError) as e:
         print("step04: %s" % e, file=sys.stderr)
         return 1

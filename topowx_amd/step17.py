@@ -4,7 +4,7 @@ test and a world-record test over their WHOLE series (``topowx_amd.infill.find_b
 
     python -m topowx_amd.step17 --infill-tmin A.nc --infill-tmax B.nc --out flagged_bad.csv
                                 (--stnids ids.txt | --log infill.log | --db all.nc --report-tmin R.npz --report-tmax R.npz)
-                                [--cpt-sig X] [--device N]
+                                [--cpt-sig X] [--device N] [--deflate gpu|host]
 
 The suspects come from a text file of ids (``--stnids``, one per line), from a log of the reference's step16 (``--log``:
 its ``Could not infill`` and ``ERROR|`` lines, ``get_bad_infill_stnids``), or from two step16 reports (``--report-*``:
@@ -57,6 +57,9 @@ def main(argv=None):
     ap.add_argument("--report-tmax", help="step16 report of Tmax (.npz)")
     ap.add_argument("--cpt-sig", type=float, default=_qalib.CK_SIG, help="level of the variance change-point check")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--deflate", choices=("gpu", "host"),
+                    help="with --report-*: write the databases' series station-major, their chunks deflated on the GPU (gpu) or by "
+                         "libhdf5 (host); default: the transposed assignment")
     a = ap.parse_args(argv)
     reports = bool(a.report_tmin or a.report_tmax or a.db)
     if sum([bool(a.stnids), bool(a.log), reports]) != 1 or (reports and not (a.report_tmin and a.report_tmax and a.db)):
@@ -79,7 +82,7 @@ def main(argv=None):
                 ids.update(str(s) for s in suspect_infill_stnids(rep))
                 cur = opath
                 try:
-                    write_infill_db(opath, stns, days, var, rep)
+                    write_infill_db(opath, stns, days, var, rep, deflate=a.deflate, device=a.device)
                 except KeyError as e:
                     raise _Unknown(str(e.args[0]))
             ids = sorted(ids)

@@ -7,6 +7,7 @@ stations through netCDF.
 
     python -m topowx_amd.step18 --infill-tmin A.nc --infill-tmax B.nc --serial-tmin C.nc --serial-tmax D.nc
                                 [--start-norm-yr 1981] [--end-norm-yr 2010] [--format NETCDF4|NETCDF3_64BIT] [--device N]
+                                [--deflate gpu|host]
 
 The infilled databases are what ``python -m topowx_amd.step17 --report-*`` (``write_infill_db``) or the reference's step16
 wrote.  An existing output file is not overwritten.  The outputs are what ``python -m topowx_amd.step20``,
@@ -43,6 +44,9 @@ def main(argv=None):
     ap.add_argument("--end-norm-yr", type=int, default=2010)
     ap.add_argument("--format", choices=ncio.FORMATS, help="container of the outputs (default: ncio.default_format())")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--deflate", choices=("gpu", "host"),
+                    help="write the series station-major, their chunks deflated on the GPU (gpu) or by libhdf5 (host); default: the "
+                         "transposed assignment")
     a = ap.parse_args(argv)
     tm, line = {}, {}
     t0 = time.perf_counter()
@@ -52,7 +56,7 @@ def main(argv=None):
             cur = src
             ncio.file_format(src)
             with contextlib.redirect_stdout(sys.stderr):             # the reference's warnings: not on the JSON line's stream
-                rec = create_serially_complete_db(src, var, dst, device=a.device, format=a.format, timing=tm)
+                rec = create_serially_complete_db(src, var, dst, device=a.device, format=a.format, timing=tm, deflate=a.deflate)
             cur = dst
             stnda = StationSerialDataDb(dst, var, mode="r+")
             try:
